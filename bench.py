@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py — headline benchmark of the MI355X hot paths (contract: see the round brief).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--detail]]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up (--warmup ticks, then two untimed blocks of the timed length: PRIME_MAX_STEPS), times ONE block of
+exactly --steps ticks and prints the headline line (roofline and cpu_baseline null); --dump-outputs DIR also writes what the last
+timed tick returned (dump_outputs).  Everything else below — the kernel profile behind `roofline`, the synchronous tick, the CPU
+baselines, the RBPF object, the N > 1 legs, bench_detail.json, and the --steps block timed 31 times with `ms_per_step` their
+median — runs with --full only.
 
 A "step" is one MPPI control tick (controller::MPPI::newControls, mppi.cpp:72-140) INCLUDING its Gaussian control-noise
 sampling (mppi.cpp:173-184), which is part of the path: the perturbations of every tick are drawn on the device inside
@@ -204,9 +210,9 @@ def _roof_obj(r):
     return o
 
 
-def compact_line(full):
+def compact_line(full, detail_file=True):
     """The record the driver parses: the contract's keys, one roofline and one cpu_baseline object, a small RBPF summary — numbers and
-    names, no prose.  Everything else the run measured is in bench_detail.json (`detail`)."""
+    names, no prose.  Everything else the run measured is in bench_detail.json (`detail`; null when a plain run wrote none)."""
     keys = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "ms_per_step_min", "ms_per_step_max", "repeats",
             "higher_is_better", "scaling", "vs_baseline", "dtype", "data")
     out = {k: full.get(k) for k in keys}
@@ -232,25 +238,42 @@ def compact_line(full):
     for k in ("strong_scaling_configs3", "rbpf_sharded", "weak_tick_via_comm_all_gather"):   # N > 1 legs: the figures only
         if full.get(k) is not None:
             out[k] = _pick(full[k], ("rollouts_per_s", "particle_updates_per_s", "ms_per_step", "ms_per_scan", "exchange_kind", "exchange", "resamples", "scaling"))
-    out["detail"] = os.path.basename(DETAIL_PATH)
+    out["detail"] = os.path.basename(DETAIL_PATH) if detail_file else None
     return out
 
 
-def emit(full):
-    """bench_detail.json <- everything measured; stdout's LAST line <- the compact record (asserted under LINE_LIMIT bytes)."""
-    try:
-        with open(DETAIL_PATH, "w") as f:
-            json.dump(full, f, indent=1)
-            f.write("\n")
-    except OSError as e:   # (a read-only checkout: the line still goes out)
-        print(f"[bench] could not write {DETAIL_PATH}: {e}", file=sys.stderr, flush=True)
-    text = json.dumps(compact_line(full), separators=(",", ":"))
+def emit(full, detail_file=True):
+    """bench_detail.json <- everything measured (--full); stdout's LAST line <- the compact record (asserted under LINE_LIMIT bytes)."""
+    if detail_file:
+        try:
+            with open(DETAIL_PATH, "w") as f:
+                json.dump(full, f, indent=1)
+                f.write("\n")
+        except OSError as e:   # (a read-only checkout: the line still goes out)
+            print(f"[bench] could not write {DETAIL_PATH}: {e}", file=sys.stderr, flush=True)
+    text = json.dumps(compact_line(full, detail_file), separators=(",", ":"))
     if len(text) >= LINE_LIMIT:   # never print a line the driver cannot read: drop the secondary object first
-        c = compact_line(full)
+        c = compact_line(full, detail_file)
         c.pop("rbpf", None)
         text = json.dumps(c, separators=(",", ":"))
     sys.stdout.flush()
     print(text, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+PRIME_MAX_STEPS = 2000   # a plain run's two untimed blocks of the timed length (warm-up), up to this length: beyond it the <= 99
+                         # remainder ticks outside the 100-tick graphs weigh < 5 %
+
+
+def dump_outputs(path, m, controls):
+    """--dump-outputs: what a caller of the timed tick receives from its last call — the controls (ul, ur) to apply and the 2 x T
+    control sequence the tick left as the next one's warm start — as float64 .npy files.  The inputs are fixed by the arguments
+    (seed 42, tick numbers from 0), so two builds given the same arguments can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"controls": np.asarray(controls, dtype=np.float64), "control_sequence": np.ascontiguousarray(m.getControls(), dtype=np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 LEGS_BUDGET_S = 240.0  # the N > 1 legs take seconds (60 ticks, 14 scans, RCCL's first point-to-point connections)
@@ -289,13 +312,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--full", action="store_true", help="everything beside the headline as well: roofline and kernel profile, synchronous "
+                    "tick, CPU baselines, the RBPF object, the N > 1 legs, bench_detail.json (a plain run times the headline ticks only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large", action="store_true")
     ap.add_argument("--no-rbpf", action="store_true", help="skip the secondary RBPF object (development)")
-    ap.add_argument("--detail", action="store_true", help="every optional leg as well (per-shape roofline objects, options, noise forms, "
-                    "reference-field variants, configs[4] as written); all of it goes to bench_detail.json, never into the last line")
-    ap.add_argument("--repeats", type=int, default=31, help="the --steps block is timed this many times; ms_per_step is the median")
+    ap.add_argument("--detail", action="store_true", help="implies --full; every optional leg as well (per-shape roofline objects, options, "
+                    "noise forms, reference-field variants, configs[4] as written); all of it goes to bench_detail.json, never into the last line")
+    ap.add_argument("--repeats", type=int, default=None, help="the --steps block is timed this many times; ms_per_step is the median "
+                    "(default: 1, with --full 31)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed tick returned "
+                    "(controls.npy: (ul, ur); control_sequence.npy: the 2 x T warm start it left) as float64 .npy files into DIR")
     args = ap.parse_args()
+    args.full = args.full or args.detail
+    if args.repeats is None:
+        args.repeats = 31 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -347,7 +378,7 @@ def main():
     m = make_mppi(K, horizon, local_rank)
     m.setRngShard(rank * K, world * K)
     T = m.steps
-    a, b = synth_noise(T, K, device, 1234 + rank)
+    a, b = synth_noise(T, K, device, 1234 + rank) if args.full else (None, None)   # (resident noise: the --full kernel profile only)
     # a stream of its own (not the legacy default stream): tbnav_mppi_enqueue_rng_batch replays captured hipGraphs of ticks, and a
     # capture cannot be taken on the null stream; every launch, event and synchronisation below is on / of this stream
     torch.cuda.set_stream(torch.cuda.Stream(device))
@@ -395,6 +426,12 @@ def main():
     els = None
     if world == 1:
         ticks(args.warmup)
+        if args.repeats == 1 and args.steps <= PRIME_MAX_STEPS:
+            # part of the warm-up: a batch shorter than a 100-tick chunk (or a chunked batch's remainder) is replayed from a graph of
+            # its own length, built by the SECOND batch that asks for it — two untimed blocks of the timed length put the one timed
+            # block where blocks 3.. of --full's 31 are (their median)
+            ticks(args.steps)
+            ticks(args.steps)
         sync()  # (one rank: the barrier of the bracket is empty)
         g0 = m.graphReplayedTicks()
         # the block of EXACTLY --steps ticks, timed --repeats times back to back (state carried): 20 ticks are 0.2 ms of work, one
@@ -451,14 +488,13 @@ def main():
         el = float(t.item())
     out_controls = m.lastControls(stream)
     assert all(np.isfinite(out_controls)), out_controls
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m, out_controls)
 
     line = None
     if rank == 0:
         ms_step = el / args.steps * 1e3
         value = world * K * args.steps / el
-        # (local launches of this rank's kernels — no exchange — also on a handle with a communicator attached)
-        # the production tick's own kernels: the in-kernel-noise instantiation the timed region ran
-        ms_k = kernel_profile(m, a, b, stream, min(args.steps, 500), rng=(SEED, 20_000_000))
         k_rollout, k_combine = m.lastKernelNames()
         sampler = "fp64 Box-Muller on 52-bit uniforms" if k_rollout.endswith(", 2>") else "fp32 Box-Muller on 24-bit uniforms"
         line = {
@@ -484,11 +520,22 @@ def main():
                                                  + ", issued by libtbnav_hip.so on the tick's stream (tbnav_mppi_attach_comm)"
                                                  if comm is not None else f"torch.distributed {dist.get_backend()} all-gather from Python (rtn_amd.sharded)"),
             "ms_per_step_one_python_call_per_tick": None if el_py is None else round(el_py / args.steps * 1e3, 6),
-            "roofline": dict(roofline_obj(K, T, ms_k, ms_step, k_rollout, None, "mppi_K1024_T50" if (K, T) == (1024, 50) else None, "mppi_K1024_T50", "mppi_K1024_T50_device_noise"),
-                             combine_kernel=k_combine),
-            # the tick is two dependent launches: what the guide prices for that alone (MI355X_MICROARCH.md, "boundary" row)
-            "latency_floor": {"dependent_launches_per_tick": 2, "boundary_us_each": [1.45, 1.9]},
+            "roofline": None,   # (--full)
         }
+        if args.full:
+            # (local launches of this rank's kernels — no exchange — also on a handle with a communicator attached)
+            # the production tick's own kernels: the in-kernel-noise instantiation the timed region ran
+            ms_k = kernel_profile(m, a, b, stream, min(args.steps, 500), rng=(SEED, 20_000_000))
+            line["roofline"] = dict(roofline_obj(K, T, ms_k, ms_step, k_rollout, None, "mppi_K1024_T50" if (K, T) == (1024, 50) else None,
+                                                 "mppi_K1024_T50", "mppi_K1024_T50_device_noise"), combine_kernel=k_combine)
+            # the tick is two dependent launches: what the guide prices for that alone (MI355X_MICROARCH.md, "boundary" row)
+            line["latency_floor"] = {"dependent_launches_per_tick": 2, "boundary_us_each": [1.45, 1.9]}
+    if not args.full:   # a plain run: the headline line and nothing else
+        if rank == 0:
+            emit(line, detail_file=False)
+        if world > 1:
+            teardown(m, comm)
+        return
 
     # ---- N > 1: everything after the headline runs under a watchdog: the headline above is complete, and a collective that does
     #      not come back (an exchange that hangs on this node) must not take it along — on expiry rank 0 prints the line without
@@ -598,19 +645,23 @@ def main():
             line["rbpf"] = bench_rbpf.run(device, args, with_cpu=not args.no_cpu_baseline, detail=args.detail)
         emit(line)
     if world > 1:
-        # (the line is out: a teardown that does not come back — a peer already gone, a communicator that waits — must not keep the
-        #  job alive: after a minute every rank leaves)
-        import threading
-        bye = threading.Timer(60.0, lambda: os._exit(0))
-        bye.daemon = True
-        bye.start()
-        # handles before the communicator they exchange through, the communicator before the job's own process group
-        m.close()
-        if comm is not None:
-            comm.close()
-        dist.barrier()
-        dist.destroy_process_group()
-        bye.cancel()
+        teardown(m, comm)
+
+
+def teardown(m, comm):
+    """N > 1: the line is out.  A teardown that does not come back — a peer already gone, a communicator that waits — must not keep
+    the job alive: after a minute every rank leaves."""
+    import threading
+    bye = threading.Timer(60.0, lambda: os._exit(0))
+    bye.daemon = True
+    bye.start()
+    # handles before the communicator they exchange through, the communicator before the job's own process group
+    m.close()
+    if comm is not None:
+        comm.close()
+    dist.barrier()
+    dist.destroy_process_group()
+    bye.cancel()
 
 
 def multi_gpu_legs(world, rank, local_rank, device, one_gpu_test, stream, sync, barrier, comm=None):

@@ -104,7 +104,7 @@ def test_a_failure_on_one_rank_stops_every_rank_at_the_same_scan(gpu_pkg, world,
 
 
 def test_bench_two_ranks_on_one_gpu_through_the_library_communicator(gpu_pkg):
-    """bench.py exactly as the driver launches it for N = 2 (torch.distributed.run, --steps 20 --warmup 5), with its one-GPU dev
+    """bench.py as the driver launches it for N = 2 (torch.distributed.run, --steps 20 --warmup 5) with --full, and its one-GPU dev
     switch: the timed ticks, the synchronous-tick measurement and both multi-GPU legs go through tbnav_mppi_attach_comm /
     tbnav_rbpf_attach_comm in two processes.  (Round 3: the synchronous-tick loop ran on rank 0 alone — with a communicator
     attached that is a collective the other rank never joins.)"""
@@ -112,7 +112,7 @@ def test_bench_two_ranks_on_one_gpu_through_the_library_communicator(gpu_pkg):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, TBNAV_BENCH_ONE_GPU_GLOO="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

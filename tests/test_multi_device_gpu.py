@@ -237,7 +237,7 @@ def test_class_shims_with_n_gpus_on_two_devices(gpu_pkg, devices):
 
 
 def test_bench_two_gpus_as_the_driver_launches_it(gpu_pkg, devices):
-    """bench.py --gpus 2 under torch.distributed.run, one rank per device over RCCL — no dev switch: the line must say which
+    """bench.py --gpus 2 --full under torch.distributed.run, one rank per device over RCCL — no dev switch: the line must say which
     exchange carried the headline (`exchange`: DIRECT, or the all-gather if the direct exchange's self-test failed on this node —
     visibly, not silently), time the same tick through the all-gather beside it, and carry both multi-GPU legs."""
     import socket
@@ -246,7 +246,7 @@ def test_bench_two_gpus_as_the_driver_launches_it(gpu_pkg, devices):
     if not _distinct(devices):
         env["TBNAV_BENCH_ONE_GPU_GLOO"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

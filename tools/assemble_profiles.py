@@ -49,5 +49,6 @@ for key, tag in SQ_KEYS.items():
         sq[key] = json.load(open(G(f"sq_summary_{tag}.json")))
 json.dump(sq, open(P(f"{R}_sq_counters.json"), "w"), indent=1)
 shutil.copy(G(f"{R}_kernel_stats.md"), P(f"{R}_kernel_stats.md"))
-shutil.copy(G(f"{R}_bench_under_rocprof.json"), P(f"{R}_bench_under_rocprof.json"))
+if os.path.exists(G(f"{R}_bench_under_rocprof.json")):   # (tools/profile_round.sh now writes it to profiles/ itself)
+    shutil.copy(G(f"{R}_bench_under_rocprof.json"), P(f"{R}_bench_under_rocprof.json"))
 print("profiles/ refreshed")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything profiles/ is built from, in one go on the GPU box (run from the repo root):
-#   1. rocprofv3 --kernel-trace --stats of `python bench.py` (the command the driver times)          -> gpurun_out/${R}_trace/
+#   1. rocprofv3 --kernel-trace --stats of `python bench.py --full`       -> profiles/${R}_bench_under_rocprof.json + the kernel table
 #   2. per workload (one driver each): a --kernel-trace --stats pass (its OWN table: the bench run mixes the legs' launches),
 #      PMC passes (FETCH_SIZE, WRITE_SIZE separately; no other tracing) and an SQ counter pass        -> gpurun_out/{kstats,pmc,sq}_*
 # Workloads (round 5: one per BASELINE shape a roofline object is quoted for):
@@ -12,7 +12,8 @@ root=$(pwd)
 mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/${R}_trace
-timeout -k 5 900 rocprofv3 --kernel-trace --stats -d /tmp/${R}_trace -o run -- python "$root/bench.py" --steps 500 --warmup 50 --no-cpu-baseline > "$root/gpurun_out/${R}_bench_under_rocprof.json" 2> /tmp/${R}_trace.log
+# (bench.py --full: the RBPF leg and the kernel profile are part of what this table is read for; its line goes straight to profiles/)
+timeout -k 5 900 rocprofv3 --kernel-trace --stats -d "$TMPDIR/${R}_trace" -o run -- python "$root/bench.py" --full --steps 500 --warmup 50 --no-cpu-baseline > "$root/profiles/${R}_bench_under_rocprof.json" 2> "$TMPDIR/${R}_trace.log"
 db=$(find /tmp/${R}_trace -name "*.db" | head -1)
 if [ -n "$db" ]; then python "$root/profiles/summarize_rocpd.py" "$db" > "$root/gpurun_out/${R}_kernel_stats.md"; else echo "no rocpd db"; tail -5 /tmp/${R}_trace.log; find /tmp/${R}_trace | head; fi
 cd "$root"
