@@ -102,7 +102,12 @@ enum { TBNAV_MPPI_OPT_KERNEL = 1, TBNAV_MPPI_OPT_TRIG = 2, TBNAV_MPPI_OPT_NO_LDS
                                      0: fp32 Box-Muller on 24-bit uniforms — normals on a 2^-24 grid out to 5.9 sigma (about 2 % faster at K = 1024) */,
        TBNAV_MPPI_OPT_WIDE_COMBINE = 11 /* 1 (default): a single-GPU tick whose time steps have more than 256 soft-min records (the fused kernel at K = 4097 ... 8192) combines
                                             them with four waves per step (mppi_combine_wide); 0: always one wave per step (A-B measurements) */,
-       TBNAV_MPPI_OPT_FAULT_INJECT = 10 /* tests: 1 = the local half of this handle's next sharded tick reports a failure (its rollouts are not launched) */ };
+       TBNAV_MPPI_OPT_FAULT_INJECT = 10 /* tests: 1 = the local half of this handle's next sharded tick reports a failure (its rollouts are not launched) */,
+       TBNAV_MPPI_OPT_NOISE_AHEAD = 12 /* 1 (default): a single-GPU device-noise tick on the fused kernel with 8 rollouts per workgroup (K <= 2048 at 256 CUs)
+                                          draws the NEXT tick's perturbations in extra workgroups of its combine launch, and the next fused kernel takes them
+                                          from there instead of drawing them on its critical path — when they are its own (same seed, counters, sampler and
+                                          options; otherwise it draws them itself: results never depend on the order of the ticks); 0: every fused kernel draws
+                                          its own (the launches of round 6).  Same perturbations, same results, bit for bit. */ };
 int tbnav_mppi_set_option(tbnav_mppi* h, int32_t option, int32_t value);
 
 /* Rollout dynamics.  TBNAV_MPPI_DYN_RK4 (default) is the reference MPPI: CartModel + RK4 (controller/include/

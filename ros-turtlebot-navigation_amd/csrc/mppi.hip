@@ -159,18 +159,24 @@ int launch_partials(tbnav_mppi* h, const double* d_duL, const double* d_duR, dou
 }
 
 }  // namespace
-int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S, const DirectSrc* direct) {
+int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S, const DirectSrc* direct,
+                             const RngArgs* next) {
   if (S < 0) S = h->S;
   int tpr = 1;
   while (tpr < G * S && tpr < kWave) tpr <<= 1;
   const int wpb = TBNAV_COMBINE_WAVES;  // waves per workgroup
   const int steps_per_block = wpb * (kWave / tpr);
   const int blocks = (h->T + steps_per_block - 1) / steps_per_block;
+  // noise ahead (the one-group form only): sampler blocks behind the time steps' blocks, TBNAV_AHEAD_PAIRS pairs per lane
+  const RngArgs nx = next ? *next : RngArgs{0, 0, 0.0, 0.0};
+  const int pairs_per_block = wpb * kWave * TBNAV_AHEAD_PAIRS;
+  const int ahead_blocks = nx.ahead ? (h->K * h->T + pairs_per_block - 1) / pairs_per_block : 0;
+  const RngArgs off{0, 0, 0.0, 0.0};
   const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
   // (records that came through an all-gather: only the error words — a poisoned record raises them, see mppi_combine)
   const DirectSrc ds = direct ? *direct : DirectSrc{nullptr, 0ull, (G > 1 && h->comm) ? h->d_dx_err : nullptr, (G > 1 && h->comm) ? h->d_dx_dead : nullptr, 0u};
-#define TBNAV_COMBINE(KEEP, MODE) do { h->lk_combine[0] = KEEP; h->lk_combine[1] = MODE; hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(blocks), dim3(wpb * kWave), 0, st, h->T, G, S, lam_of(h), h->p.max_wheel_vel, usrc, \
-                                                    d_records, h->d_u[1 - h->ucur], h->d_out, h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1), ds); } while (0)
+#define TBNAV_COMBINE(KEEP, MODE) do { h->lk_combine[0] = KEEP; h->lk_combine[1] = MODE; hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(blocks + (MODE == 0 ? ahead_blocks : 0)), dim3(wpb * kWave), 0, st, h->T, G, S, lam_of(h), h->p.max_wheel_vel, usrc, \
+                                                    d_records, h->d_u[1 - h->ucur], h->d_out, h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1), ds, MODE == 0 ? nx : off); } while (0)
 #define TBNAV_COMBINE_KEEP(MODE) do { if (G * S > 4 * kWave && G * S <= 8 * kWave) TBNAV_COMBINE(8, MODE); else if (G * S > 2 * kWave && G * S <= 4 * kWave) TBNAV_COMBINE(4, MODE); \
                                       else TBNAV_COMBINE(2, MODE); } while (0)
   // (which form: the direct exchange polls; records that came through an all-gather may carry a failed rank's poison; one group has neither —
@@ -223,6 +229,33 @@ bool pick_noise(tbnav_mppi* h, const double*& d_duL, const double*& d_duR) {
 // the perturbations can be drawn inside the fused kernel: its in-kernel form exists for 8 and 16 rollouts per workgroup (either sampler)
 bool rng_in_kernel(const tbnav_mppi* h) {
   return h->fused_rng && (h->fused_r == 8 || h->fused_r == 16);
+}
+
+// Noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD) where the tick is latency-bound: 8 rollouts per workgroup (K <= 2048 at 256 CUs), the
+// single-GPU combine (one group of K / 8 records per step: never the four-wave form) with most of the chip idle beside it.
+bool ahead_wanted(const tbnav_mppi* h) { return h->fused_rng && h->fused_r == 8; }
+bool ahead_on(const tbnav_mppi* h) { return h->noise_ahead && h->d_ahead && ahead_wanted(h) && !h->comm; }
+// (re)allocate the pair buffer and its tag for the handle's kernel choice; a fresh tag matches no tick
+hipError_t ahead_alloc(tbnav_mppi* h) {
+  (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag);
+  h->d_ahead = nullptr; h->d_ahead_tag = nullptr;
+  if (!ahead_wanted(h)) return hipSuccess;
+  hipError_t e = hipMalloc((void**)&h->d_ahead, (size_t)2 * h->T * h->K * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&h->d_ahead_tag, kTagWords * sizeof(uint64_t));
+  if (e == hipSuccess) e = hipMemset(h->d_ahead_tag, 0xFF, kTagWords * sizeof(uint64_t));
+  return e;
+}
+
+// One device-noise tick on the fused kernel: with noise ahead, the fused kernel takes its pairs from the buffer when the tag is
+// its own and the combine draws the next tick's (the tick after `g`: the counters of one tick further on, same tick0 word)
+int rng_tick(tbnav_mppi* h, const double x0[3], RngArgs g, hipStream_t st) {
+  const bool ahead = ahead_on(h);
+  if (ahead) { g.ahead = h->d_ahead; g.ahead_tag = h->d_ahead_tag; g.epoch = h->cfg_epoch; g.kind = h->sampler == 1 ? 2 : 1; g.K = h->K; }
+  const int rc = launch_fused(h, x0, h->d_duL, h->d_duR, st, &g);
+  if (rc != TBNAV_OK) return rc;
+  RngArgs nx = g;
+  nx.base += (uint64_t)h->T * h->k_global;
+  return launch_combine(h, h->d_records_f, 1, st, h->fused_S, nullptr, ahead ? &nx : nullptr);
 }
 
 }  // namespace
@@ -330,6 +363,7 @@ int tbnav_mppi_create(const tbnav_mppi_params* params, tbnav_mppi** out) {
   alloc(&h->d_records, (size_t)T * h->S * TBNAV_MPPI_REC);
   if (h->prefix_rg) alloc(&h->d_total, (size_t)h->K);
   if (h->fused_r) alloc(&h->d_records_f, (size_t)T * h->fused_S * TBNAV_MPPI_REC);
+  if (e == hipSuccess) e = ahead_alloc(h);
   alloc(&h->d_out, 2);
   if (e == hipSuccess) e = hipMemset(h->d_out, 0, 2 * sizeof(double));
   if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_out, 4 * sizeof(double), hipHostMallocMapped);
@@ -373,6 +407,7 @@ void tbnav_mppi_destroy(tbnav_mppi* h) {
   direct_teardown(h);
   exchange_words_free(h);
   (void)hipFree(h->d_raw); (void)hipFree(h->d_records); (void)hipFree(h->d_records_f); (void)hipFree(h->d_out);
+  (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag);
   if (h->h_out) (void)hipHostFree(h->h_out);
   for (auto* g : {&h->tg, &h->tgs}) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); }
   (void)hipFree(h->d_tick0);
@@ -424,6 +459,10 @@ int tbnav_mppi_set_option(tbnav_mppi* h, int32_t option, int32_t value) {
       if (value != 0 && value != 1) return TBNAV_ERR_INVALID_ARG;
       h->sampler = value;
       return TBNAV_OK;
+    case TBNAV_MPPI_OPT_NOISE_AHEAD:    // 1 (default): a device-noise tick's combine draws the next tick's perturbations; 0: the fused kernel draws its own
+      if (value != 0 && value != 1) return TBNAV_ERR_INVALID_ARG;
+      h->noise_ahead = value != 0;
+      return TBNAV_OK;
     case TBNAV_MPPI_OPT_KERNEL: {
       // 0: mppi_rollout_cost (sequential); n > 0: mppi_rollout_scan with n steps per thread; -4 / -8 / -16: fused, that many rollouts per workgroup
       int fused = 0, tc = 0;
@@ -445,6 +484,8 @@ int tbnav_mppi_set_option(tbnav_mppi* h, int32_t option, int32_t value) {
       (void)hipFree(h->d_records_f);
       h->d_records_f = nullptr;
       if (fused) TBNAV_HIP(hipMalloc((void**)&h->d_records_f, sizeof(double) * (size_t)T * h->fused_S * TBNAV_MPPI_REC));
+      TBNAV_HIP(hipDeviceSynchronize());   // (a queued tick may still read the old pair buffer)
+      TBNAV_HIP(ahead_alloc(h));
       return TBNAV_OK;
     }
     default: return TBNAV_ERR_INVALID_ARG;
@@ -655,12 +696,25 @@ int tbnav_mppi_profile_kernels_rng(tbnav_mppi* h, const double x0[3], uint64_t s
     ms[which] = t / (float)reps;
   };
   for (int i = 0; i < TBNAV_MPPI_NKERNELS; ++i) ms[i] = 0.f;
-  // the launches of tbnav_mppi_enqueue_rng, kernel by kernel: the RNG = true instantiation of the fused kernel
+  // the launches of tbnav_mppi_enqueue_rng, kernel by kernel, in the form the steady-state tick runs them: the in-kernel-noise
+  // instantiation of the fused kernel and, with noise ahead, that kernel finding its pairs drawn (one untimed tick `tick` draws
+  // tick + 1's; every timed launch is tick + 1 and hits) and the combine with its sampler blocks (drawing tick + 2 + r)
+  const bool ahead = ahead_on(h);
+  RngArgs g{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
+  if (ahead) {
+    rc = rng_tick(h, x0, g, st);
+    g.ahead = h->d_ahead; g.ahead_tag = h->d_ahead_tag; g.epoch = h->cfg_epoch; g.kind = h->sampler == 1 ? 2 : 1; g.K = h->K;
+  }
   timed(0, [&](int r) {
-    const RngArgs g{seed, rng_base(h, tick + (uint64_t)r), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
-    return launch_fused(h, x0, h->d_duL, h->d_duR, st, &g);
+    RngArgs gr = g;
+    gr.base = rng_base(h, ahead ? tick + 1 : tick + (uint64_t)r);
+    return launch_fused(h, x0, h->d_duL, h->d_duR, st, &gr);
   });
-  timed(2, [&](int) { return launch_combine(h, h->d_records_f, 1, st, h->fused_S); });
+  timed(2, [&](int r) {
+    RngArgs nx = g;
+    nx.base = rng_base(h, tick + 2 + (uint64_t)r);
+    return launch_combine(h, h->d_records_f, 1, st, h->fused_S, nullptr, ahead ? &nx : nullptr);
+  });
   for (auto& e : ev) (void)hipEventDestroy(e);
   return rc;
 }
@@ -760,9 +814,7 @@ int tbnav_mppi_enqueue_rng(tbnav_mppi* h, const double x0[3], uint64_t seed, uin
   }
   DeviceGuard guard(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const RngArgs g{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
-  const int rc = launch_fused(h, x0, h->d_duL, h->d_duR, st, &g);
-  return rc != TBNAV_OK ? rc : launch_combine(h, h->d_records_f, 1, st, h->fused_S);
+  return rng_tick(h, x0, RngArgs{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)}, st);
 }
 
 namespace {
@@ -788,8 +840,7 @@ void build_graph(tbnav_mppi* h, TickGraph& g, int len, const double* x0, uint64_
   for (int t = 0; t < len && rc == TBNAV_OK; ++t) {
     RngArgs ra{seed, rng_base(h, (uint64_t)t), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
     ra.tick0 = h->d_tick0; ra.per_tick = (uint64_t)h->T * h->k_global;
-    rc = launch_fused(h, x0, h->d_duL, h->d_duR, st, &ra);
-    if (rc == TBNAV_OK) rc = launch_combine(h, h->d_records_f, 1, st, h->fused_S);
+    rc = rng_tick(h, x0, ra, st);   // (the last tick's combine draws the first tick of the next replay: the tag holds the resolved counters)
   }
   if (rc == TBNAV_OK) { hipLaunchKernelGGL(mppi_tick_advance, dim3(1), dim3(1), 0, st, h->d_tick0, (uint64_t)len); if (hipGetLastError() != hipSuccess) rc = TBNAV_ERR_HIP; }
   hipGraph_t gr = nullptr;

@@ -24,6 +24,9 @@ constexpr int kSlice = kSliceThreads * kSliceItems;  // rollouts per K-slice rec
 constexpr int kMaxLdsBytes = 160 * 1024;
 constexpr int kGroup = 4;        // steps per group of the one-lane-per-rollout kernels (independent trig chains)
 constexpr int kRoundGroups = 3;  // groups per round of mppi_rollout_prefix
+#ifndef TBNAV_AHEAD_PAIRS
+#define TBNAV_AHEAD_PAIRS 1  // noise pairs per lane of the combine's sampler blocks (TBNAV_MPPI_OPT_NOISE_AHEAD; 1, 2, 4 measured: docs/lab_notebook.md)
+#endif
 #ifndef TBNAV_COMBINE_WAVES
 #define TBNAV_COMBINE_WAVES 1  // one wave per workgroup: the groups spread over as many CUs as there are time steps (K = 1024 tick 8.9 -> 8.4 us against four waves)
 #endif
@@ -296,7 +299,16 @@ struct RngArgs {  // base = tick * T * K_global + k0 * T
   // replayed graphs of ticks (tbnav_mppi_enqueue_rng_batch): `base` is baked for the tick's position in the chunk and the chunk's
   // first tick is read from device memory, times the counters one tick uses
   const uint64_t* tick0 = nullptr; uint64_t per_tick = 0;
+  // noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD; null: off): the single-GPU combine of tick j draws tick j+1's pairs into `ahead`
+  // ([K][T] (dl, dr) pairs, pair k*T + i = counter base + k*T + i) and describes them in `ahead_tag` (NoiseTag); the fused
+  // kernel of the next launch takes its pairs from there when the tag is the one it would draw, and draws them itself otherwise
+  double* ahead = nullptr; uint64_t* ahead_tag = nullptr;
+  uint64_t epoch = 0;  // the handle's cfg_epoch at launch (an option change in between is a miss)
+  int kind = 0;        // the sampler of the combine's draw: 2 = fp64, 1 = fp32 (the fused kernel's RNG argument; that kernel has it as a template argument)
+  int K = 0;           // the handle's rollouts: the combine's draw covers K * T pairs
 };
+// what a block of drawn-ahead pairs is: seed, the RESOLVED counter base (tick, k0 and K_global in it), sampler kind, cfg_epoch
+enum { kTagSeed = 0, kTagBase = 1, kTagKind = 2, kTagEpoch = 3, kTagWords = 4 };
 // WIDE = false (the narrow sampler, TBNAV_MPPI_OPT_SAMPLER = 0; the default up to round 5): Box-Muller on the fp32 transcendental units (v_log_f32,
 // v_sin_f32 / v_cos_f32 take their argument in turns): a handful of instructions instead of ~130 fp64 ones for log +
 // sincospi + sqrt.  The perturbations are random numbers, not parity quantities: 24-bit uniforms give normals on a 2^-24 grid
@@ -361,7 +373,7 @@ __global__ __launch_bounds__(kWave) void mppi_merge_records(int T, int Sf, int p
 template <int kKeep, int MODE>   // MODE 0: one group of records (every single-GPU tick); 1: records of several ranks through an all-gather; 2: the direct exchange
 __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam, double umax, USrc u, const double* __restrict__ records,
                                                     double* __restrict__ u_out, double* __restrict__ out, double* __restrict__ out_host, double seq,
-                                                    DirectSrc ds);
+                                                    DirectSrc ds, RngArgs nx /* MODE 0, nx.ahead set: blocks past the time steps' draw the next tick's noise */);
 __global__ __launch_bounds__(256) void mppi_combine_wide(int T, int R, Lam lam, double umax, USrc u, const double* __restrict__ records, double* __restrict__ u_out,
                                                          double* __restrict__ out, double* __restrict__ out_host, double seq);
 __global__ __launch_bounds__(256) void mppi_direct_publish(const double* __restrict__ mine, int n, unsigned long long* const* __restrict__ peers, int me, int P,

@@ -89,6 +89,12 @@ struct tbnav_mppi {
   bool fail_next = false;                            // fault injection (TBNAV_MPPI_OPT_FAULT_INJECT, tests): the next sharded tick's local half fails
   bool wide_combine = true;                          // TBNAV_MPPI_OPT_WIDE_COMBINE: four waves per time step when a step has more than 256 records
   int sampler = 1;                                   // TBNAV_MPPI_OPT_SAMPLER: 1 (default) = fp64 Box-Muller on 52-bit uniforms, 0 = fp32 on 24-bit uniforms
+  // noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD): the combine of a device-noise tick draws the next tick's perturbations in blocks of its
+  // own, into d_ahead; the next fused kernel takes them from there when d_ahead_tag says they are its own (RngArgs).  Kept apart from
+  // d_duL / d_duR (tbnav_mppi_get_noise, the sample-then-tick path).  Allocated where it is used: 8 rollouts per workgroup, noise drawn inside
+  bool noise_ahead = true;
+  double* d_ahead = nullptr;       // [K][T] (dl, dr) pairs
+  uint64_t* d_ahead_tag = nullptr; // [kTagWords]
   unsigned long long dx_budget = 200000000ull;       // 2 s of the 100 MHz clock (host-side skew between ranks is legitimate — a control loop's is milliseconds; longer: the peer has failed)
   bool dx_withhold = false;                          // fault injection (TBNAV_MPPI_OPT_DIRECT_EXCHANGE = 2, tests): this rank's records never reach its peers
   unsigned int dx_seq = 0;
@@ -123,7 +129,9 @@ struct DeviceGuard {
 // (mppi.hip)
 Lam lam_of(double lambda);
 inline Lam lam_of(const tbnav_mppi* h) { return lam_of(h->p.lambda); }
-int launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S = -1, const DirectSrc* direct = nullptr);
+// next: a single-GPU combine also draws these perturbations (noise ahead; ignored by the other forms)
+int launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S = -1, const DirectSrc* direct = nullptr,
+                   const RngArgs* next = nullptr);
 // (mppi_sharded.hip)
 int sharded_tick(tbnav_mppi* h, const double x0[3], const double* d_duL, const double* d_duR, const uint64_t* seed, uint64_t tick, void* stream);
 void direct_teardown(tbnav_mppi* h);

@@ -469,14 +469,50 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(RolloutArgs a, c
     // row is one or two cache lines, fetched once and served to the other waves from L1); the values also go to
     // the LDS tile for the partials below
     double dl[TL], dr[TL], uL[TL], uR[TL];
-    if constexpr (RNG != 0) { if (rng.tick0) rng.base += *rng.tick0 * rng.per_tick; }  // (a scalar load, under the warm-start loads)
 #pragma unroll
     for (int q = 0; q < TL; ++q) {
       const int i = lane * TL + q, ii = i < T ? i : T - 1;
-      if constexpr (RNG != 0) device_noise<RNG == 2>(rng, T, ii, kk, dl[q], dr[q]);  // production mode: the perturbations never touch HBM
-      else { dl[q] = duL[(size_t)ii * K + kk]; dr[q] = duR[(size_t)ii * K + kk]; }
       uL[q] = u.get(0, ii, T);
       uR[q] = u.get(1, ii, T);
+    }
+    // noise ahead: the previous launch's combine may have drawn this tick's pairs already.  The pairs (16 B per lane and step:
+    // wave r reads its rollout's 16*T contiguous bytes) and the tag are requested together with the warm-start controls and the
+    // tick word, before the tag is looked at; a tag that is not this launch's (first tick, a gap, another seed / sampler / option)
+    // draws as before
+    double2 pre[TL];
+    uint64_t tag[kTagWords];
+    if constexpr (RNG != 0) {
+      if (rng.ahead) {   // (launch-uniform)
+        const double2* ap = reinterpret_cast<const double2*>(rng.ahead) + (size_t)kk * T;
+#pragma unroll
+        for (int q = 0; q < TL; ++q) { const int i = lane * TL + q; pre[q] = ap[i < T ? i : T - 1]; }
+#pragma unroll
+        for (int w = 0; w < kTagWords; ++w) tag[w] = rng.ahead_tag[w];
+      }
+    }
+    if constexpr (RNG != 0) { if (rng.tick0) rng.base += *rng.tick0 * rng.per_tick; }  // (a scalar load, under the warm-start loads)
+    bool hit = false;
+    if constexpr (RNG != 0) {
+      if (rng.ahead)
+        hit = (tag[kTagSeed] == rng.seed) & (tag[kTagBase] == rng.base) & (tag[kTagKind] == (uint64_t)RNG) & (tag[kTagEpoch] == rng.epoch);
+    }
+    if constexpr (RNG != 0) {
+      if (hit) {
+#pragma unroll
+        for (int q = 0; q < TL; ++q) { dl[q] = pre[q].x; dr[q] = pre[q].y; }
+      } else {
+#pragma unroll
+        for (int q = 0; q < TL; ++q) {
+          const int i = lane * TL + q, ii = i < T ? i : T - 1;
+          device_noise<RNG == 2>(rng, T, ii, kk, dl[q], dr[q]);  // production mode: the perturbations never touch HBM
+        }
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < TL; ++q) {
+        const int i = lane * TL + q, ii = i < T ? i : T - 1;
+        dl[q] = duL[(size_t)ii * K + kk]; dr[q] = duR[(size_t)ii * K + kk];
+      }
     }
     double v[TL], w[TL], ctrl[TL], pth[TL];
     double run = 0.0;

@@ -215,10 +215,39 @@ __device__ __forceinline__ bool direct_load_records(const DirectSrc& d, const si
   return true;
 }
 
+// Noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD): sampler block b of the single-GPU combine draws pairs [b * P, (b + 1) * P) of the NEXT
+// tick, P = TBNAV_AHEAD_PAIRS * blockDim.x, with the device_noise the fused kernel would call (same counters, same code: the
+// same bits), into nx.ahead[k * T + i]; block 0 also writes the tag.  The next launch on the stream sees both whole through the
+// kernel boundary.  The pairs do not depend on the controls, so this work sits in the combine's shadow: its time-step blocks
+// occupy one wave on T CUs, the sampler blocks spread over the rest.
+template <bool WIDE>
+__device__ __forceinline__ void draw_ahead(RngArgs g, int T, int K, int b) {
+  if (g.tick0) g.base += *g.tick0 * g.per_tick;   // (a replayed graph: resolved as the fused kernel of that tick will resolve it)
+  const int n = K * T;
+  double dl[TBNAV_AHEAD_PAIRS], dr[TBNAV_AHEAD_PAIRS];
+#pragma unroll
+  for (int q = 0; q < TBNAV_AHEAD_PAIRS; ++q) {   // (independent chains: the last block's tail recomputes pair n - 1)
+    const int p = (b * TBNAV_AHEAD_PAIRS + q) * (int)blockDim.x + (int)threadIdx.x, pc = p < n ? p : n - 1;
+    const int k = pc / T, i = pc - k * T;
+    device_noise<WIDE>(g, T, i, k, dl[q], dr[q]);
+  }
+  double2* out = reinterpret_cast<double2*>(g.ahead);
+#pragma unroll
+  for (int q = 0; q < TBNAV_AHEAD_PAIRS; ++q) {
+    const int p = (b * TBNAV_AHEAD_PAIRS + q) * (int)blockDim.x + (int)threadIdx.x;
+    if (p < n) out[p] = make_double2(dl[q], dr[q]);
+  }
+  if (b == 0 && threadIdx.x == 0) {   // (vector stores from one lane)
+    uint64_t* tg = g.ahead_tag;
+    tg[kTagSeed] = g.seed; tg[kTagBase] = g.base; tg[kTagKind] = (uint64_t)g.kind; tg[kTagEpoch] = g.epoch;
+  }
+}
+
 template <int kKeep, int MODE>
 __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam, double umax, USrc u,
                                                     const double* __restrict__ records, double* __restrict__ u_out,
-                                                    double* __restrict__ out, double* __restrict__ out_host, double seq, DirectSrc ds) {
+                                                    double* __restrict__ out, double* __restrict__ out_host, double seq, DirectSrc ds,
+                                                    RngArgs nx) {
   // MODE 0 — one group of records, the single-GPU tick — carries none of the exchange's failure handling: a template argument, not a
   // launch-time test (as one body the headline tick ran 0.2 us slower than round 4's: 7.95 against 7.75 us).
   constexpr bool DIRECT = MODE == 2, GATHERED = MODE == 1;
@@ -238,6 +267,15 @@ __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam
   int tpr = 1;
   while (tpr < R && tpr < kWave) tpr <<= 1;
   const int spw = kWave / tpr, sub = lane / tpr, l = lane - sub * tpr;
+  if constexpr (MODE == 0) {
+    // the time-step blocks come first (the lowest block indices dispatch first); the blocks after them draw the next tick's noise
+    const int step_blocks = (T + nw * spw - 1) / (nw * spw);
+    if (nx.ahead && (int)blockIdx.x >= step_blocks) {   // (launch-uniform / block-uniform)
+      const int b = (int)blockIdx.x - step_blocks;
+      if (nx.kind == 2) draw_ahead<true>(nx, T, nx.K, b); else draw_ahead<false>(nx, T, nx.K, b);
+      return;
+    }
+  }
   const int i = (blockIdx.x * nw + wid) * spw + sub;
   const bool valid = i < T;
   // the warm-start controls do not depend on the records: fetch them first, under the record loads
@@ -505,7 +543,7 @@ __global__ void mppi_sample_noise(int T, int K, uint64_t seed, uint64_t base, do
   }
 }
 
-#define TBNAV_INST_COMBINE(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(int, int, int, Lam, double, USrc, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc);
+#define TBNAV_INST_COMBINE(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(int, int, int, Lam, double, USrc, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc, RngArgs);
 TBNAV_INST_COMBINE(2, 0) TBNAV_INST_COMBINE(4, 0) TBNAV_INST_COMBINE(8, 0)
 TBNAV_INST_COMBINE(2, 1) TBNAV_INST_COMBINE(4, 1) TBNAV_INST_COMBINE(8, 1)
 TBNAV_INST_COMBINE(2, 2) TBNAV_INST_COMBINE(4, 2) TBNAV_INST_COMBINE(8, 2)
