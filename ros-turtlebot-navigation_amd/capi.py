@@ -79,6 +79,26 @@ class RbpfStats(C.Structure):
                 ("status", C.c_int32), ("n_valid_beams", C.c_int32)]
 
 
+class IcpParams(C.Structure):
+    """tbnav_icp_params (include/tbnav_icp.h)."""
+    _fields_ = [
+        ("beam_min", C.c_float), ("beam_max", C.c_float), ("beam_delta", C.c_float),
+        ("range_min", C.c_float), ("range_max", C.c_float), ("max_iter", C.c_int32),
+        ("Trs", C.c_double * 3), ("max_corr_dist", C.c_double), ("transform_eps", C.c_double),
+        ("fitness_eps", C.c_double), ("device", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class IcpInfo(C.Structure):
+    """tbnav_icp_info."""
+    _fields_ = [("iterations", C.c_int32), ("correspondences", C.c_int32), ("mse", C.c_double), ("criterion", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+# tbnav_icp_criterion
+ICP_NOT_RUN, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES, ICP_DEGENERATE = range(7)
+
+
 _lib = None
 
 
@@ -244,6 +264,16 @@ def lib() -> C.CDLL:
         "tbnav_rbpf_set_timing": (C.c_int, [vp, i32]),
         "tbnav_rbpf_set_scan_matching": (C.c_int, [vp, i32, C.c_double, C.c_double, i32]),
         "tbnav_rbpf_get_scan_match": (C.c_int, [vp, vp, vp]),
+        # ICP (include/tbnav_icp.h)
+        "tbnav_icp_default_params": (None, [C.POINTER(IcpParams)]),
+        "tbnav_icp_create": (C.c_int, [C.POINTER(IcpParams), C.POINTER(vp)]),
+        "tbnav_icp_destroy": (None, [vp]),
+        "tbnav_icp_reset": (C.c_int, [vp]),
+        "tbnav_icp_match": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpInfo)]),
+        "tbnav_icp_step": (C.c_int, [vp, vp, i32, dp, dp, C.POINTER(i32), C.POINTER(IcpInfo)]),
+        "tbnav_icp_step_batch": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
+        "tbnav_icp_cloud": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
+        "tbnav_icp_last_batch_launches": (C.c_int, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1,0 +1,581 @@
+// icp.hip — point-to-point ICP between laser scans (include/tbnav_icp.h): the reference's ScanAlignment::pclICP /
+// pclICPWrapper (bmapping/src/bmapping/cloud_alignment.cpp:37-223) restated on the device.
+//
+// One workgroup of kThreads threads aligns one (target, source) pair; the whole iteration loop runs inside the launch.
+//   - the target cloud lives in LDS as float2, one slot per BEAM (an invalid beam holds NaN, which never wins the strict
+//     '<' of the nearest-neighbour scan, so the scan order over the valid points is the compacted cloud's order); the
+//     scan runs as C independent chains per point (latency: one wave per SIMD), merged in (distance, index) order;
+//   - thread t keeps the source beams t, t + B, ... (P of them, a template parameter) in registers, untransformed;
+//   - per iteration: transform, nearest neighbour against every target, the ten fp64 sums in the header's fixed order
+//     (per thread in increasing beam, then the tree t += t + s: s = 128 and 64 through LDS, 32..1 by shuffles in wave 0),
+//     and wave 0 leaves the totals in LDS; after ONE barrier every thread computes R_inc and the stopping criteria from
+//     them redundantly (wave-uniform), so the loop needs no further barrier and no global memory.
+// Compiled with -ffp-contract=off (csrc/Makefile): every fp64 / fp32 expression keeps the restatement's rounding.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <new>
+#include <vector>
+
+#include "common.hpp"
+#include "tbnav_icp.h"
+
+namespace {
+
+constexpr int kThreads = 256;   // B of the header's reduction order
+constexpr int kWave = 64;
+constexpr int kSums = 9;        // Sax, Say, Sbx, Sby, Sxx, Syy, Sxy, Syx, Sd (n is counted apart, as an int)
+
+struct IcpConst {
+  float range_min, range_max;
+  double trs_c, trs_s, trs_x, trs_y;   // Trs as Transform2D holds it
+  double max_corr2;                    // max_corr_dist^2
+  double rot_thresh, trans_thresh;     // 1 - transform_eps, transform_eps
+  double fitness_eps;
+  int max_iter;
+};
+
+// one alignment: scan indices (-1: the handle's stored scan) and the float-rounded initial guess
+struct IcpPair {
+  int32_t tgt, src;
+  double c, s, x, y;
+};
+
+struct IcpOut {
+  double R00, R10, tx, ty, mse;
+  int32_t iterations, correspondences, criterion, pad;
+};
+
+__device__ __forceinline__ bool cloud_point(float r, float2 cs, const IcpConst& k, float2& p) {
+  if (!(r >= k.range_min && r < k.range_max)) return false;
+  const double px = (double)r * (double)cs.x, py = (double)r * (double)cs.y;
+  p.x = (float)(((k.trs_c * px) - (k.trs_s * py)) + k.trs_x);
+  p.y = (float)(((k.trs_s * px) + (k.trs_c * py)) + k.trs_y);
+  return true;
+}
+
+template <int P, int C = (P <= 2 ? 4 : P <= 4 ? 2 : 1)>
+__global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ scans, const float* __restrict__ stored,
+                                                        const float2* __restrict__ table, int n_beams,
+                                                        const IcpPair* __restrict__ pairs, IcpOut* __restrict__ out, IcpConst k) {
+  extern __shared__ float4 lds_dyn[];          // 16-byte aligned: the nearest-neighbour scan reads it as float4
+  float2* tgt = reinterpret_cast<float2*>(lds_dyn);  // [n_beams rounded up to 4]
+  __shared__ double red_a[kSums][kThreads / 2];  // s = 128 partials
+  __shared__ double red_b[kSums][kThreads / 4];  // s = 64 partials
+  __shared__ int cnt_a[kThreads / 2], cnt_b[kThreads / 4];
+  __shared__ double tot[kSums];
+  __shared__ int tot_n;
+
+  const int t = threadIdx.x;
+  const IcpPair pr = pairs[blockIdx.x];
+  const float* ts = pr.tgt < 0 ? stored : scans + (size_t)pr.tgt * n_beams;
+  const float* ss = pr.src < 0 ? stored : scans + (size_t)pr.src * n_beams;
+  const float qnan = __builtin_nanf("");
+  const int n4 = (n_beams + 3) & ~3;  // the LDS cloud is padded to whole float4 pairs of points with NaN
+  for (int i = t; i < n4; i += kThreads) {
+    float2 p = make_float2(qnan, qnan);
+    if (i < n_beams && !cloud_point(ts[i], table[i], k, p)) p = make_float2(qnan, qnan);
+    tgt[i] = p;
+  }
+  float2 src[P];
+  bool valid[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const int i = t + j * kThreads;
+    valid[j] = i < n_beams && cloud_point(ss[i], table[i], k, src[j]);
+    if (!valid[j]) src[j] = make_float2(0.0f, 0.0f);
+  }
+  __syncthreads();
+
+  double R00 = pr.c, R01 = -pr.s, R10 = pr.s, R11 = pr.c, tx = pr.x, ty = pr.y;
+  double prev = DBL_MAX, mse = 0.0;
+  int iter = 0, n = 0, crit = TBNAV_ICP_NOT_RUN;
+  while (true) {
+    ++iter;
+    double sum[kSums];
+#pragma unroll
+    for (int q = 0; q < kSums; ++q) sum[q] = 0.0;
+    int cnt = 0;
+    float2 a[P];
+    float best[P][C];
+    int bi[P][C];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      a[j].x = (float)(((R00 * (double)src[j].x) + (R01 * (double)src[j].y)) + tx);
+      a[j].y = (float)(((R10 * (double)src[j].x) + (R11 * (double)src[j].y)) + ty);
+#pragma unroll
+      for (int c = 0; c < C; ++c) { best[j][c] = __builtin_huge_valf(); bi[j][c] = 0x7fffffff; }
+    }
+    // nearest neighbour: C independent chains per point (chain c: targets m = c mod C, in increasing m, strict '<'), four
+    // targets per two 16-byte LDS reads (a broadcast: every lane reads the same address)
+    for (int m = 0; m < n4; m += 4) {
+      const float4 t01 = *reinterpret_cast<const float4*>(&tgt[m]);
+      const float4 t23 = *reinterpret_cast<const float4*>(&tgt[m + 2]);
+      const float bx[4] = {t01.x, t01.z, t23.x, t23.z}, by[4] = {t01.y, t01.w, t23.y, t23.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const float dx = a[j].x - bx[r], dy = a[j].y - by[r];
+          const float d = dx * dx + dy * dy;
+          if (d < best[j][r % C]) { best[j][r % C] = d; bi[j][r % C] = m + r; }
+        }
+      }
+    }
+    // the chains' minima in (distance, index) order: the lowest index among equal distances, as one scan in beam order
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+#pragma unroll
+      for (int c = 1; c < C; ++c) {
+        if (best[j][c] < best[j][0] || (best[j][c] == best[j][0] && bi[j][c] < bi[j][0])) { best[j][0] = best[j][c]; bi[j][0] = bi[j][c]; }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      if (valid[j] && (double)best[j][0] <= k.max_corr2) {
+        const float2 b = tgt[bi[j][0]];
+        const double ax = a[j].x, ay = a[j].y, bx = b.x, by = b.y;
+        ++cnt;
+        sum[0] += ax; sum[1] += ay; sum[2] += bx; sum[3] += by;
+        sum[4] += ax * bx; sum[5] += ay * by; sum[6] += ax * by; sum[7] += ay * bx;
+        sum[8] += (double)best[j][0];
+      }
+    }
+    // tree: t += t + s for s = 128, 64 (LDS), 32 .. 1 (wave 0, shuffles)
+    if (t >= kThreads / 2) {
+#pragma unroll
+      for (int q = 0; q < kSums; ++q) red_a[q][t - kThreads / 2] = sum[q];
+      cnt_a[t - kThreads / 2] = cnt;
+    }
+    __syncthreads();
+    if (t < kThreads / 2) {
+#pragma unroll
+      for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + red_a[q][t];
+      cnt += cnt_a[t];
+      if (t >= kThreads / 4) {
+#pragma unroll
+        for (int q = 0; q < kSums; ++q) red_b[q][t - kThreads / 4] = sum[q];
+        cnt_b[t - kThreads / 4] = cnt;
+      }
+    }
+    __syncthreads();
+    if (t < kWave) {
+#pragma unroll
+      for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + red_b[q][t];
+      cnt += cnt_b[t];
+#pragma unroll
+      for (int s = kWave / 2; s > 0; s >>= 1) {
+#pragma unroll
+        for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + __shfl_down(sum[q], s, kWave);
+        cnt += __shfl_down(cnt, s, kWave);
+      }
+      if (t == 0) {
+#pragma unroll
+        for (int q = 0; q < kSums; ++q) tot[q] = sum[q];
+        tot_n = cnt;
+      }
+    }
+    __syncthreads();
+    // every thread: R_inc and the criteria from the totals (wave-uniform from here to the loop's end).  The next writes of
+    // red_a / red_b / tot come after the next iteration's first / second barrier, which every thread reaches only after it
+    // has read what it needs here.
+    n = tot_n;
+    if (n < 3) { crit = TBNAV_ICP_NO_CORRESPONDENCES; mse = 0.0; break; }
+    const double dn = (double)n;
+    const double Sax = tot[0], Say = tot[1], Sbx = tot[2], Sby = tot[3];
+    const double A = (tot[4] + tot[5]) - ((Sax * Sbx) + (Say * Sby)) / dn;
+    const double S = (tot[6] - tot[7]) - ((Sax * Sby) - (Say * Sbx)) / dn;
+    const double r = sqrt((A * A) + (S * S));
+    mse = tot[8] / dn;
+    if (r == 0.0) { crit = TBNAV_ICP_DEGENERATE; break; }
+    const double c = A / r, s = S / r;
+    const double amx = Sax / dn, amy = Say / dn, bmx = Sbx / dn, bmy = Sby / dn;
+    const double tix = bmx - ((c * amx) - (s * amy));
+    const double tiy = bmy - ((s * amx) + (c * amy));
+    const double n00 = (c * R00) - (s * R10), n01 = (c * R01) - (s * R11);
+    const double n10 = (s * R00) + (c * R10), n11 = (s * R01) + (c * R11);
+    const double ntx = ((c * tx) - (s * ty)) + tix, nty = ((s * tx) + (c * ty)) + tiy;
+    R00 = n00; R01 = n01; R10 = n10; R11 = n11; tx = ntx; ty = nty;
+    if (iter >= k.max_iter) { crit = TBNAV_ICP_ITERATIONS; break; }
+    if (c >= k.rot_thresh && ((tix * tix) + (tiy * tiy)) <= k.trans_thresh) { crit = TBNAV_ICP_TRANSFORM; break; }
+    const double dm = fabs(mse - prev);
+    if (dm < 1e-12) { crit = TBNAV_ICP_ABS_MSE; break; }
+    if (dm / prev < k.fitness_eps) { crit = TBNAV_ICP_REL_MSE; break; }
+    prev = mse;
+  }
+  if (t == 0) {
+    IcpOut o;
+    o.R00 = R00; o.R10 = R10; o.tx = tx; o.ty = ty; o.mse = mse;
+    o.iterations = iter; o.correspondences = n; o.criterion = crit; o.pad = 0;
+    out[blockIdx.x] = o;
+  }
+}
+
+// the cloud of one scan, per beam (test hook; the same cloud_point as the alignment)
+__global__ __launch_bounds__(kThreads) void icp_cloud(const float* __restrict__ scan, const float2* __restrict__ table, int n_beams,
+                                                      float2* __restrict__ xy, int* __restrict__ valid, IcpConst k) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n_beams) return;
+  float2 p = make_float2(0.0f, 0.0f);
+  valid[i] = cloud_point(scan[i], table[i], k, p) ? 1 : 0;
+  xy[i] = p;
+}
+
+bool converged(int crit) { return crit >= TBNAV_ICP_ITERATIONS && crit <= TBNAV_ICP_REL_MSE; }
+
+struct DevGuard {
+  int prev = -1;
+  bool ok = false;
+  explicit DevGuard(int d) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(d) == hipSuccess) ok = true; }
+  ~DevGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
+};
+
+}  // namespace
+
+struct tbnav_icp {
+  tbnav_icp_params p{};
+  IcpConst k{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int table_beams = 0;                 // beam count the device table was built for
+  float2* d_table = nullptr;           // cosf / sinf per beam [table_beams]
+  float* d_stored = nullptr;           // the stored scan (pclICPWrapper's old_scan) [stored_cap]
+  int stored_cap = 0, stored_beams = 0;
+  bool have_stored = false;
+  float* d_scans = nullptr;            // batch scans / match inputs
+  size_t scans_cap = 0;
+  IcpPair* d_pairs = nullptr;
+  IcpOut* d_out = nullptr;
+  int pairs_cap = 0;
+  int last_launches = 0;
+  std::vector<IcpPair> h_pairs;
+  std::vector<IcpOut> h_out;
+};
+
+namespace {
+
+int ensure_table(tbnav_icp* h, int n_beams) {
+  if (h->table_beams == n_beams) return TBNAV_OK;
+  // createPointCloud's beam angles (cloud_alignment.cpp:120-154): float angle, std::cos(float) = glibc cosf
+  std::vector<float2> tab((size_t)n_beams);
+  const float bmin = h->p.beam_min, bmax = h->p.beam_max, bd = h->p.beam_delta;
+  float ang = bmin;
+  for (int i = 0; i < n_beams; ++i) {
+    tab[(size_t)i] = make_float2(std::cos(ang), std::sin(ang));
+    ang += bd;
+    if (bmax < 0.0 && ang <= bmax) ang = bmin;
+    else if (bmax >= 0.0 && ang >= bmax) ang = bmin;
+  }
+  if (h->d_table) TBNAV_HIP(hipFree(h->d_table));
+  h->d_table = nullptr;
+  h->table_beams = 0;
+  TBNAV_HIP(hipMalloc(&h->d_table, sizeof(float2) * (size_t)n_beams));
+  TBNAV_HIP(hipMemcpyAsync(h->d_table, tab.data(), sizeof(float2) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipStreamSynchronize(h->stream));  // tab is about to go out of scope
+  h->table_beams = n_beams;
+  return TBNAV_OK;
+}
+
+int ensure_scans(tbnav_icp* h, size_t floats) {
+  if (floats <= h->scans_cap) return TBNAV_OK;
+  if (h->d_scans) TBNAV_HIP(hipFree(h->d_scans));
+  h->d_scans = nullptr;
+  h->scans_cap = 0;
+  TBNAV_HIP(hipMalloc(&h->d_scans, sizeof(float) * floats));
+  h->scans_cap = floats;
+  return TBNAV_OK;
+}
+
+int ensure_pairs(tbnav_icp* h, int n) {
+  if (n <= h->pairs_cap) return TBNAV_OK;
+  if (h->d_pairs) TBNAV_HIP(hipFree(h->d_pairs));
+  if (h->d_out) TBNAV_HIP(hipFree(h->d_out));
+  h->d_pairs = nullptr; h->d_out = nullptr; h->pairs_cap = 0;
+  TBNAV_HIP(hipMalloc(&h->d_pairs, sizeof(IcpPair) * (size_t)n));
+  TBNAV_HIP(hipMalloc(&h->d_out, sizeof(IcpOut) * (size_t)n));
+  h->pairs_cap = n;
+  return TBNAV_OK;
+}
+
+IcpPair make_pair(int tgt, int src, const double T[3]) {
+  // pclICP's guess (cloud_alignment.cpp:171-183): float cos / sin / x / y
+  IcpPair p;
+  p.tgt = tgt; p.src = src;
+  p.c = (double)(float)std::cos(T[0]);
+  p.s = (double)(float)std::sin(T[0]);
+  p.x = (double)(float)T[1];
+  p.y = (double)(float)T[2];
+  return p;
+}
+
+template <int P>
+int launch_p(tbnav_icp* h, int n_pairs, int n_beams) {
+  const size_t lds = sizeof(float2) * (size_t)((n_beams + 3) & ~3);
+  hipLaunchKernelGGL(icp_align<P>, dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
+                     h->d_pairs, h->d_out, h->k);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// aligns h->h_pairs[0, n_pairs) (scans already in d_scans / d_stored) -> h->h_out
+int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
+  if (int rc = ensure_pairs(h, n_pairs)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_pairs, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
+  const int per = (n_beams + kThreads - 1) / kThreads;  // source beams per thread
+  int rc;
+  if (per <= 1) rc = launch_p<1>(h, n_pairs, n_beams);
+  else if (per <= 2) rc = launch_p<2>(h, n_pairs, n_beams);
+  else if (per <= 3) rc = launch_p<3>(h, n_pairs, n_beams);
+  else if (per <= 4) rc = launch_p<4>(h, n_pairs, n_beams);
+  else if (per <= 6) rc = launch_p<6>(h, n_pairs, n_beams);
+  else if (per <= 8) rc = launch_p<8>(h, n_pairs, n_beams);
+  else if (per <= 12) rc = launch_p<12>(h, n_pairs, n_beams);
+  else rc = launch_p<16>(h, n_pairs, n_beams);
+  if (rc) return rc;
+  h->h_out.resize((size_t)n_pairs);
+  TBNAV_HIP(hipMemcpyAsync(h->h_out.data(), h->d_out, sizeof(IcpOut) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  ++h->last_launches;
+  return TBNAV_OK;
+}
+
+void result(const IcpOut& o, double T_out[3], tbnav_icp_info* info) {
+  if (converged(o.criterion)) {
+    T_out[0] = std::atan2(o.R10, o.R00);  // pclICP :209 (on the fp64 state, header note)
+    T_out[1] = o.tx;
+    T_out[2] = o.ty;
+  } else {
+    T_out[0] = T_out[1] = T_out[2] = 0.0;
+  }
+  if (info) {
+    info->iterations = o.iterations;
+    info->correspondences = o.correspondences;
+    info->mse = o.mse;
+    info->criterion = o.criterion;
+    info->reserved = 0;
+  }
+}
+
+void first_call(double T_out[3], int32_t* ok, tbnav_icp_info* info) {
+  T_out[0] = T_out[1] = T_out[2] = 0.0;
+  if (ok) *ok = 1;
+  if (info) *info = tbnav_icp_info{0, 0, 0.0, TBNAV_ICP_NOT_RUN, 0};
+}
+
+int store_scan(tbnav_icp* h, const float* dev_src, const float* host_src, int n_beams) {
+  if (n_beams > h->stored_cap) {
+    if (h->d_stored) TBNAV_HIP(hipFree(h->d_stored));
+    h->d_stored = nullptr; h->stored_cap = 0;
+    TBNAV_HIP(hipMalloc(&h->d_stored, sizeof(float) * (size_t)n_beams));
+    h->stored_cap = n_beams;
+  }
+  if (dev_src) TBNAV_HIP(hipMemcpyAsync(h->d_stored, dev_src, sizeof(float) * (size_t)n_beams, hipMemcpyDeviceToDevice, h->stream));
+  else TBNAV_HIP(hipMemcpyAsync(h->d_stored, host_src, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  h->stored_beams = n_beams;
+  h->have_stored = true;
+  return TBNAV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void tbnav_icp_default_params(tbnav_icp_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->max_iter = 100;
+  p->max_corr_dist = 0.5;
+  p->transform_eps = 1e-8;
+  p->fitness_eps = 1e-6;
+  p->device = -1;
+}
+
+int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
+  if (!params || !out) return TBNAV_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (params->max_iter < 1 || params->max_iter > TBNAV_ICP_MAX_ITER || !(params->max_corr_dist > 0.0) ||
+      !(params->transform_eps >= 0.0) || !(params->fitness_eps >= 0.0))
+    return TBNAV_ERR_INVALID_ARG;
+  int ndev = 0;
+  {
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__);
+  }
+  int dev = params->device;
+  if (dev < 0) TBNAV_HIP(hipGetDevice(&dev));
+  if (dev >= ndev) return TBNAV_ERR_INVALID_ARG;
+  DevGuard guard(dev);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  tbnav_icp* h = new (std::nothrow) tbnav_icp();
+  if (!h) return TBNAV_ERR_INVALID_ARG;
+  h->p = *params;
+  h->device = dev;
+  IcpConst& k = h->k;
+  k.range_min = params->range_min;
+  k.range_max = params->range_max;
+  k.trs_c = std::cos(params->Trs[0]);  // Transform2D(Vector2D, theta) (rigid2d.hpp)
+  k.trs_s = std::sin(params->Trs[0]);
+  k.trs_x = params->Trs[1];
+  k.trs_y = params->Trs[2];
+  k.max_corr2 = params->max_corr_dist * params->max_corr_dist;
+  k.rot_thresh = 1.0 - params->transform_eps;
+  k.trans_thresh = params->transform_eps;
+  k.fitness_eps = params->fitness_eps;
+  k.max_iter = params->max_iter;
+  const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    delete h;
+    return tbnav::hip_fail(e, "hipStreamCreateWithFlags", __FILE__, __LINE__);
+  }
+  *out = h;
+  return TBNAV_OK;
+}
+
+void tbnav_icp_destroy(tbnav_icp* h) {
+  if (!h) return;
+  {
+    DevGuard guard(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(h->d_table);
+    (void)hipFree(h->d_stored);
+    (void)hipFree(h->d_scans);
+    (void)hipFree(h->d_pairs);
+    (void)hipFree(h->d_out);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+  }
+  delete h;
+}
+
+int tbnav_icp_reset(tbnav_icp* h) {
+  if (!h) return TBNAV_ERR_INVALID_ARG;
+  h->have_stored = false;
+  h->stored_beams = 0;
+  return TBNAV_OK;
+}
+
+int tbnav_icp_last_batch_launches(const tbnav_icp* h) { return h ? h->last_launches : 0; }
+
+int tbnav_icp_cloud(tbnav_icp* h, const float* scan, int32_t n_beams, float* xy, int32_t* n_points) {
+  if (!h || !scan || !xy || !n_points || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
+  DevGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  if (int rc = ensure_table(h, n_beams)) return rc;
+  // scratch: the scan, then the points [n_beams] float2 and the flags [n_beams] int (4 floats per beam in all)
+  if (int rc = ensure_scans(h, 4 * (size_t)n_beams)) return rc;
+  float* d_scan = h->d_scans;
+  float2* d_xy = reinterpret_cast<float2*>(h->d_scans + 2 * (size_t)n_beams);  // 8-byte aligned
+  int* d_valid = reinterpret_cast<int*>(h->d_scans + n_beams);
+  TBNAV_HIP(hipMemcpyAsync(d_scan, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(icp_cloud, dim3((n_beams + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, d_scan, h->d_table,
+                     (int)n_beams, d_xy, d_valid, h->k);
+  TBNAV_HIP(hipGetLastError());
+  std::vector<float2> pts((size_t)n_beams);
+  std::vector<int> valid((size_t)n_beams);
+  TBNAV_HIP(hipMemcpyAsync(pts.data(), d_xy, sizeof(float2) * (size_t)n_beams, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(valid.data(), d_valid, sizeof(int) * (size_t)n_beams, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  int m = 0;
+  for (int i = 0; i < n_beams; ++i)
+    if (valid[(size_t)i]) { xy[2 * m] = pts[(size_t)i].x; xy[2 * m + 1] = pts[(size_t)i].y; ++m; }
+  *n_points = m;
+  return TBNAV_OK;
+}
+
+int tbnav_icp_match(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3],
+                    double T_out[3], tbnav_icp_info* info) {
+  if (!h || !target_scan || !source_scan || !T_init || !T_out || !info || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS)
+    return TBNAV_ERR_INVALID_ARG;
+  DevGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  if (int rc = ensure_table(h, n_beams)) return rc;
+  if (int rc = ensure_scans(h, 2 * (size_t)n_beams)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  h->h_pairs.assign(1, make_pair(0, 1, T_init));
+  h->last_launches = 0;
+  if (int rc = run_pairs(h, 1, n_beams)) return rc;
+  result(h->h_out[0], T_out, info);
+  return TBNAV_OK;
+}
+
+int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const double T_init[3], double T_out[3], int32_t* ok,
+                   tbnav_icp_info* info) {
+  if (!h || !scan || !T_init || !T_out || !ok || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
+  if (h->have_stored && n_beams != h->stored_beams) return TBNAV_ERR_INVALID_ARG;
+  DevGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  if (!h->have_stored) {  // cloud_alignment.cpp:64-68
+    if (int rc = store_scan(h, nullptr, scan, n_beams)) return rc;
+    first_call(T_out, ok, info);
+    return TBNAV_OK;
+  }
+  if (int rc = ensure_table(h, n_beams)) return rc;
+  if (int rc = ensure_scans(h, (size_t)n_beams)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  h->h_pairs.assign(1, make_pair(-1, 0, T_init));
+  h->last_launches = 0;
+  if (int rc = run_pairs(h, 1, n_beams)) return rc;
+  const IcpOut o = h->h_out[0];
+  result(o, T_out, info);
+  *ok = converged(o.criterion) ? 1 : 0;
+  if (*ok) return store_scan(h, h->d_scans, nullptr, n_beams);  // :59 — a failure keeps the old scan (:53-56)
+  return TBNAV_OK;
+}
+
+int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int32_t n_scans, const double* T_init, int32_t* ok,
+                         double* T_out, tbnav_icp_info* info) {
+  if (!h || !scans || !T_init || !ok || !T_out || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS || n_scans <= 0)
+    return TBNAV_ERR_INVALID_ARG;
+  if (h->have_stored && n_beams != h->stored_beams) return TBNAV_ERR_INVALID_ARG;
+  DevGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  if (int rc = ensure_table(h, n_beams)) return rc;
+  if (int rc = ensure_scans(h, (size_t)n_beams * (size_t)n_scans)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scans, sizeof(float) * (size_t)n_beams * (size_t)n_scans, hipMemcpyHostToDevice, h->stream));
+  h->last_launches = 0;
+  int s = 0;
+  int target = -1;  // -1: the stored scan
+  if (!h->have_stored) {
+    first_call(T_out, ok, info);
+    target = 0;
+    s = 1;
+  }
+  // launch 1: every scan against its predecessor (the stored scan for the first), speculatively.  Then walk in order: the
+  // result for (actual target, scan) is taken from what has been aligned so far; when it is missing (a scan before
+  // failed, so the target stayed an earlier scan), the scans from there are aligned against the actual target in another
+  // launch — through the first one whose speculative alignment converged (the scans before it will probably fail against
+  // any target, and the walk would need each of them next).
+  std::map<std::pair<int, int>, IcpOut> done;  // (target, source) -> result
+  if (s < n_scans) {
+    h->h_pairs.clear();
+    for (int q = s; q < n_scans; ++q) h->h_pairs.push_back(make_pair(q - 1, q, T_init + 3 * (size_t)q));
+    if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
+    for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = h->h_out[j];
+  }
+  for (; s < n_scans; ++s) {
+    auto it = done.find({target, s});
+    if (it == done.end()) {
+      h->h_pairs.clear();
+      for (int q = s; q < n_scans; ++q) {
+        h->h_pairs.push_back(make_pair(target, q, T_init + 3 * (size_t)q));
+        const auto spec = done.find({q - 1, q});
+        if (spec != done.end() && converged(spec->second.criterion)) break;
+      }
+      if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
+      for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = h->h_out[j];
+      it = done.find({target, s});
+    }
+    const IcpOut& o = it->second;
+    result(o, T_out + 3 * (size_t)s, info ? info + s : nullptr);
+    ok[s] = converged(o.criterion) ? 1 : 0;
+    if (ok[s]) target = s;
+  }
+  if (target >= 0) return store_scan(h, h->d_scans + (size_t)target * n_beams, nullptr, n_beams);
+  return TBNAV_OK;
+}
+
+}  // extern "C"

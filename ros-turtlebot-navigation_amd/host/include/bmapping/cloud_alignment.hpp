@@ -1,13 +1,19 @@
 // bmapping/cloud_alignment.hpp — ScanAlignment with the reference's surface
 // (reference bmapping/include/bmapping/cloud_alignment.hpp:28-80, cloud_alignment.cpp:37-72).
 //
-// The reference wraps pcl::IterativeClosestPoint (PCL, third party, version unpinned, not in this
-// image).  ICP is serial, runs once per scan BEFORE the particle loop (particle_filter.cpp:146-153)
-// and is out of the hot path: here the matcher is a pluggable host
-// callable.  The default reproduces what the reference does when PCL converges onto the initial
-// guess: it returns the guess.  The reference's bookkeeping is kept: the first call returns
-// (true, identity) and stores the scan (cloud_alignment.cpp:43-50); a failed match does not
-// refresh the stored scan (:62-71).
+// The reference wraps pcl::IterativeClosestPoint (PCL, third party, version unpinned, not part of this project).  Here the
+// matcher is a pluggable host callable, and the reference's bookkeeping is kept: the first call returns (true, identity)
+// and stores the scan (cloud_alignment.cpp:43-50); a failed match does not refresh the stored scan (:62-71).
+//
+// useDeviceICP() installs the GPU point-to-point ICP (include/tbnav_icp.h, csrc/icp.hip): a restatement of PCL's
+// IterativeClosestPoint with the reference's settings, whose arithmetic is fixed in that header.  Parity with PCL itself is
+// unpinned.  A failed alignment prints "ICP FAILED TO CONVERGED!" on stdout as pclICP does (:202).  Copies of a
+// ScanAlignment (ParticleFilter keeps one, particle_filter.hpp) share the device handle.
+//
+// Without a matcher the shim returns the initial guess (what a PCL ICP that converges onto its guess returns) and says so
+// once on stderr.  Compiling with -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor call useDeviceICP(), so a node
+// built unchanged against this header runs with the device ICP.  The define only changes a default
+// argument, which is evaluated where the constructor is called: objects compiled with and without it link together.
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -18,6 +24,12 @@
 #include "bmapping/sensor_model.hpp"
 #include "rigid2d/rigid2d.hpp"
 
+#ifdef TBNAV_SCAN_ALIGNMENT_DEVICE_ICP
+#define TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT true
+#else
+#define TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT false
+#endif
+
 namespace bmapping {
 
 using rigid2d::Transform2D;
@@ -27,10 +39,15 @@ class ScanAlignment {
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
   using Matcher = std::function<bool(Transform2D&, const Transform2D&, const std::vector<float>&, const std::vector<float>&)>;
 
-  ScanAlignment(const LaserProperties& props, const Transform2D& Trs) : props_(props), Trs_(Trs) {}
+  ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT)
+      : props_(props), Trs_(Trs) {
+    if (device_icp) useDeviceICP();
+  }
 
   /// plug in a real scan matcher (e.g. a PCL ICP wrapper in a catkin workspace that has PCL)
   void setMatcher(Matcher m) { matcher_ = std::move(m); }
+  /// (addition) the GPU ICP as the matcher, on `device` (-1: the current one); throws std::runtime_error without a GPU
+  void useDeviceICP(int device = -1);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

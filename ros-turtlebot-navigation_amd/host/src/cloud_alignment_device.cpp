@@ -1,0 +1,53 @@
+// cloud_alignment_device.cpp — ScanAlignment::useDeviceICP: the device ICP of include/tbnav_icp.h as the shim's matcher.
+#include <iostream>
+#include <memory>
+#include <stdexcept>
+#include <string>
+
+#include "bmapping/cloud_alignment.hpp"
+#include "tbnav_icp.h"
+
+namespace bmapping {
+
+void ScanAlignment::useDeviceICP(int device) {
+  tbnav_icp_params p;
+  tbnav_icp_default_params(&p);  // the reference's settings (cloud_alignment.cpp:21-34)
+  p.beam_min = props_.beam_min; p.beam_max = props_.beam_max; p.beam_delta = props_.beam_delta;
+  p.range_min = props_.range_min; p.range_max = props_.range_max;
+  const auto trs = Trs_.displacement();
+  p.Trs[0] = trs.theta; p.Trs[1] = trs.x; p.Trs[2] = trs.y;
+  p.device = device;
+  tbnav_icp* raw = nullptr;
+  const int rc = tbnav_icp_create(&p, &raw);
+  if (rc != TBNAV_OK) {
+    std::string msg = std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(rc);
+    const char* hip = tbnav_last_hip_error();
+    if (hip && *hip) msg += std::string(" [") + hip + "]";
+    throw std::runtime_error(msg);
+  }
+  // the matcher holds the handle: copies of this object (and of the std::function) share it
+  std::shared_ptr<tbnav_icp> h(raw, tbnav_icp_destroy);
+  matcher_ = [h](Transform2D& T, const Transform2D& T_init, const std::vector<float>& target, const std::vector<float>& source) {
+    if (target.size() != source.size()) throw std::invalid_argument("bmapping::ScanAlignment: scans of different lengths");
+    const auto g = T_init.displacement();
+    const double tinit[3] = {g.theta, g.x, g.y};
+    double out[3];
+    tbnav_icp_info info{};
+    const int rc = tbnav_icp_match(h.get(), target.data(), source.data(), (int32_t)source.size(), tinit, out, &info);
+    if (rc != TBNAV_OK) {
+      std::string msg = std::string("bmapping::ScanAlignment::pclICP: ") + tbnav_status_string(rc);
+      const char* hip = tbnav_last_hip_error();
+      if (hip && *hip) msg += std::string(" [") + hip + "]";
+      if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+      throw std::runtime_error(msg);
+    }
+    if (info.criterion < TBNAV_ICP_ITERATIONS || info.criterion > TBNAV_ICP_REL_MSE) {
+      std::cout << "ICP FAILED TO CONVERGED!" << std::endl;  // cloud_alignment.cpp:202
+      return false;
+    }
+    T = Transform2D(rigid2d::Vector2D(out[1], out[2]), out[0]);  // :206-217
+    return true;
+  };
+}
+
+}  // namespace bmapping

@@ -1,0 +1,126 @@
+"""Python mirror of bmapping::ScanAlignment with the device ICP (include/tbnav_icp.h, csrc/icp.hip).
+
+Same method names and meaning as the reference's class (bmapping/include/bmapping/cloud_alignment.hpp:28-80):
+pclICPWrapper(T_init, scan) keeps the previous scan in the handle (cloud_alignment.cpp:37-72), pclICP aligns two scans
+statelessly (:160-223).  wrapperBatch replays a logged run: its (ok, T) arrays are tbnav_rbpf_slam_batch's icp_ok / T_icp.
+init_guess is ParticleFilter::icpInitGuess (particle_filter.cpp:602-612).  The algorithm is a restatement of PCL's
+IterativeClosestPoint; parity with PCL itself is unpinned (see the header).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import capi
+
+
+def default_params(beam_delta_deg=1.0, Trs=(0.0, 0.0, 0.0), device=-1, **kw) -> "capi.IcpParams":
+    """The shipped LDS-01 laser (config/LDS_01_lidar.yaml, narrowed to float like LaserProperties) and the reference's ICP
+    settings (cloud_alignment.cpp:21-34)."""
+    L = capi.lib()
+    p = capi.IcpParams()
+    L.tbnav_icp_default_params(C.byref(p))
+    d2r = math.pi / 180.0
+    p.beam_min, p.beam_max, p.beam_delta = 0.0, float(np.float32(360.0 * d2r)), float(np.float32(beam_delta_deg * d2r))
+    p.range_min, p.range_max = 0.12, 3.5
+    p.Trs[:] = [float(v) for v in Trs]
+    p.device = device
+    for key, v in kw.items():
+        setattr(p, key, v)
+    return p
+
+
+def _d3(v):
+    return (C.c_double * 3)(*[float(x) for x in v])
+
+
+def _info(i: "capi.IcpInfo") -> dict:
+    return dict(iterations=i.iterations, correspondences=i.correspondences, mse=i.mse, criterion=i.criterion)
+
+
+def converged(criterion: int) -> bool:
+    return capi.ICP_ITERATIONS <= criterion <= capi.ICP_REL_MSE
+
+
+def normalize_angle_PI(rad: float) -> float:
+    """rigid2d::normalize_angle_PI (host/include/rigid2d/rigid2d.hpp)."""
+    PI = 3.14159265358979323846
+    turns = math.floor((rad + PI) / (2.0 * PI))
+    rad = (rad + PI) - turns * 2.0 * PI
+    if rad < 0:
+        rad += 2.0 * PI
+    return rad - PI
+
+
+def init_guess(cur, prev):
+    """icpInitGuess: (dtheta, dx, dy) of two odometry poses (theta, x, y) — world-frame dx, dy, as the reference writes it."""
+    dth = normalize_angle_PI(normalize_angle_PI(float(cur[0])) - normalize_angle_PI(float(prev[0])))
+    return (dth, float(cur[1]) - float(prev[1]), float(cur[2]) - float(prev[2]))
+
+
+class ScanAlignment:
+    """bmapping::ScanAlignment on one MI355X."""
+
+    def __init__(self, params: "capi.IcpParams | None" = None):
+        self._L = capi.lib()
+        self.params = params if params is not None else default_params()
+        self._h = C.c_void_p()
+        capi.check(self._L.tbnav_icp_create(C.byref(self.params), C.byref(self._h)), "tbnav_icp_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.tbnav_icp_destroy(self._h)
+        self._h = C.c_void_p()
+
+    __del__ = close
+
+    def reset(self):
+        capi.check(self._L.tbnav_icp_reset(self._h), "tbnav_icp_reset")
+
+    def pclICPWrapper(self, T_init, scan):
+        """-> (ok, T = (theta, x, y), info dict)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        out = (C.c_double * 3)()
+        ok = C.c_int32()
+        info = capi.IcpInfo()
+        capi.check(self._L.tbnav_icp_step(self._h, scan.ctypes.data, scan.size, _d3(T_init), out, C.byref(ok), C.byref(info)),
+                   "tbnav_icp_step")
+        return bool(ok.value), tuple(out), _info(info)
+
+    def pclICP(self, T_init, target_scan, source_scan):
+        """-> (ok, T, info dict); stateless"""
+        tgt = np.ascontiguousarray(target_scan, dtype=np.float32)
+        src = np.ascontiguousarray(source_scan, dtype=np.float32)
+        if tgt.size != src.size:
+            raise ValueError("target and source scans must have the same number of beams")
+        out = (C.c_double * 3)()
+        info = capi.IcpInfo()
+        capi.check(self._L.tbnav_icp_match(self._h, tgt.ctypes.data, src.ctypes.data, src.size, _d3(T_init), out, C.byref(info)),
+                   "tbnav_icp_match")
+        return converged(info.criterion), tuple(out), _info(info)
+
+    def wrapperBatch(self, T_init, scans):
+        """n successive pclICPWrapper calls in one call: T_init [n][3], scans [n][n_beams] -> (ok int32 [n], T [n][3],
+        info list)"""
+        scans = np.ascontiguousarray(scans, dtype=np.float32)
+        n, nb = scans.shape
+        T_init = np.ascontiguousarray(T_init, dtype=np.float64).reshape(n, 3)
+        ok = np.zeros(n, dtype=np.int32)
+        T = np.zeros((n, 3), dtype=np.float64)
+        info = (capi.IcpInfo * n)()
+        capi.check(self._L.tbnav_icp_step_batch(self._h, scans.ctypes.data, nb, n, T_init.ctypes.data, ok.ctypes.data,
+                                                T.ctypes.data, C.cast(info, C.c_void_p)), "tbnav_icp_step_batch")
+        return ok, T, [_info(i) for i in info]
+
+    def lastBatchLaunches(self) -> int:
+        return int(self._L.tbnav_icp_last_batch_launches(self._h))
+
+    def cloud(self, scan):
+        """the cloud the kernel builds from one scan: float32 [m][2] in beam order"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        xy = np.empty((scan.size, 2), dtype=np.float32)
+        m = C.c_int32()
+        capi.check(self._L.tbnav_icp_cloud(self._h, scan.ctypes.data, scan.size, xy.ctypes.data, C.byref(m)), "tbnav_icp_cloud")
+        return xy[:m.value].copy()

@@ -1,0 +1,95 @@
+"""Timing of the device ICP (include/tbnav_icp.h) on the GPU:
+python tools/icp_time.py [--out FILE] [--quick]
+  - latency of one synchronous tbnav_icp_step (host clock around the call, which ends in a stream synchronise) at 360 beams
+    (1 deg) and 1080 beams (1/3 deg): median / p10 / p90 of 500 scans after 20 of warm-up, a robot driving round a room;
+  - tbnav_icp_step_batch over 2000 scans of the same kind of run: median of 5 calls (after one of warm-up), per call and
+    per scan, with the launches it made;
+  --quick: a few scans only (what a `rocprofv3 --kernel-trace --stats` run of this script needs).
+Kernel times come from a separate rocprofv3 run, not from this script."""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as g  # noqa: E402
+
+g.load_package()
+import oracle_api as orc  # noqa: E402  (the synthetic room only: room_scan is numpy)
+import rbpf_cases as rc  # noqa: E402
+from rtn_amd import icp  # noqa: E402
+
+
+def loop_run(n, n_beams, beam_delta_deg, seed=1):
+    """a robot driving an ellipse in ROOM_BENCH, 500 scans per lap: poses (theta, x, y) and LDS-01-like scans"""
+    phi = 2 * math.pi * np.arange(n) / 500.0
+    poses = np.stack([phi + math.pi / 2, 1.0 * np.cos(phi), 0.8 * np.sin(phi)], axis=1)
+    rng = np.random.default_rng(seed)
+    scans = np.stack([orc.room_scan(p, n_beams=n_beams, beam_delta_deg=beam_delta_deg, walls=rc.ROOM_BENCH, rng=rng) for p in poses])
+    T_init = np.array([icp.init_guess(poses[s], poses[s - 1] if s else poses[0]) for s in range(n)])
+    return scans, T_init
+
+
+def step_latency(n_beams, beam_delta_deg, n_warm, n_time):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+    scans, T_init = loop_run(n_warm + n_time, n_beams, beam_delta_deg)
+    ts, iters, fails = [], [], 0
+    for s in range(n_warm + n_time):
+        t0 = time.perf_counter()
+        ok, T, info = a.pclICPWrapper(T_init[s], scans[s])
+        t1 = time.perf_counter()
+        if s >= n_warm:
+            ts.append((t1 - t0) * 1e6)
+            iters.append(info["iterations"])
+            fails += 0 if ok else 1
+    a.close()
+    ts = np.array(ts)
+    return dict(n_beams=n_beams, scans=n_time, median_us=float(np.median(ts)), p10_us=float(np.percentile(ts, 10)),
+                p90_us=float(np.percentile(ts, 90)), mean_iterations=float(np.mean(iters)), max_iterations=int(np.max(iters)),
+                failures=fails)
+
+
+def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+    scans, T_init = loop_run(n_scans, n_beams, beam_delta_deg, seed=2)
+    ts = []
+    for r in range(reps + 1):
+        a.reset()
+        t0 = time.perf_counter()
+        ok, T, info = a.wrapperBatch(T_init, scans)
+        t1 = time.perf_counter()
+        if r > 0:
+            ts.append((t1 - t0) * 1e3)
+    launches = a.lastBatchLaunches()
+    a.close()
+    med = float(np.median(ts))
+    return dict(n_beams=n_beams, scans=n_scans, median_ms=med, min_ms=float(np.min(ts)), per_scan_us=med * 1e3 / n_scans,
+                launches=launches, failures=int(n_scans - ok.sum()), mean_iterations=float(np.mean([i["iterations"] for i in info[1:]])))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--quick", action="store_true")
+    a = ap.parse_args()
+    if a.quick:
+        res = dict(step_360=step_latency(360, 1.0, 2, 10), step_1080=step_latency(1080, 1.0 / 3.0, 2, 10),
+                   batch_2000=batch_time(2000, 1))
+    else:
+        res = dict(step_360=step_latency(360, 1.0, 20, 500), step_1080=step_latency(1080, 1.0 / 3.0, 20, 500),
+                   batch_2000=batch_time(2000, 5))
+    print(json.dumps(res, indent=1))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
