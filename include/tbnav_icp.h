@@ -1,4 +1,4 @@
-/* tbnav_icp.h — point-to-point ICP between two laser scans on the GPU: the scan matcher that the reference's
+/* tbnav_icp.h — ICP between two laser scans on the GPU (point-to-point, and point-to-line as an option): the scan matcher that the reference's
  * bmapping::ScanAlignment::pclICPWrapper (bmapping/src/bmapping/cloud_alignment.cpp:37-223) runs once per scan through
  * pcl::IterativeClosestPoint<PointXYZ, PointXYZ>.  PCL is a third-party library that is not part of this project, so
  * what is implemented here is a RESTATEMENT of PCL 1.8's algorithm with the reference's settings (max_iter 100,
@@ -46,9 +46,53 @@
  *    correspondence rejector installed (an assumption: PCL's text is not part of this project).
  *  - The reference's result is read from a float matrix; here from the fp64 state.
  *
+ * POINT-TO-LINE METRIC (an addition, TBNAV_ICP_METRIC_LINE through tbnav_icp_set_metric; the default stays the point metric
+ * above).  It has NO COUNTERPART IN THE REFERENCE, which only ever runs PCL's point-to-point ICP: this section is its whole
+ * specification, restated in tests/icp_line_restatement.py and reproduced by the kernel bit for bit.  A source point is held
+ * to the LINE through its nearest target point along the target cloud's tangent there, so it may slide along a wall: the
+ * iteration converges in a few steps where the point metric converges linearly, it is not pulled along the wall towards
+ * zero translation by the two scans sampling different points of it, and a direction the scan cannot see stays at the
+ * initial guess or makes the alignment fail (DEGENERATE) instead of returning a confident wrong answer.
+ * Unchanged from the point metric: the clouds (item 1), the initial guess (item 2), how a source point is transformed, the
+ * nearest-neighbour search and its ties, the max_corr_dist gate, the summation order, the composition R <- R_inc * R,
+ * t <- R_inc * t + t_inc, the stopping rules and their order (item 4), the result (item 5).  New, fp64 unless said, every
+ * product and sum as parenthesised, no contraction:
+ *  L1. Target normals, once per target cloud, with normal_window w (beams, 1..TBNAV_ICP_LINE_MAX_WINDOW, default 1) and
+ *      normal_max_gap g (metres, > 0, default 0.25).  For a valid target beam i with point p_i: beam j is NEAR when it is
+ *      valid and the fp32 d = dx*dx + dy*dy (dx = p_j.x - p_i.x, dy likewise, as in the search) has (double)d <= g*g.
+ *      lo = the LOWEST near j in [max(0, i-w), i), or i when there is none; hi = the HIGHEST near j in
+ *      (i, min(n_beams-1, i+w)], or i.  lo == hi: no normal.  Else tx = (double)p_hi.x - (double)p_lo.x, ty likewise,
+ *      l = sqrt((tx*tx) + (ty*ty)); l == 0: no normal; else n_i = ((float)(-ty / l), (float)(tx / l)).  The gap keeps a
+ *      normal from being drawn across a depth discontinuity (the beams on either side of it get one-sided normals).
+ *  L2. Pairs: a source point is kept when its nearest target (the nearest of ALL target points, as in item 3) passes the
+ *      distance gate AND has a normal.  Fewer than 3 kept: FAILED (TBNAV_ICP_NO_CORRESPONDENCES).
+ *  L3. Sums per kept pair, a = the transformed source point (float, widened), b = the target, n = its normal (widened):
+ *      ex = ax - bx, ey = ay - by, r = (nx*ex) + (ny*ey), j = (ax*ny) - (ay*nx); the count and, in the fixed order of item
+ *      3, H00 += j*j, H01 += j*nx, H02 += j*ny, H11 += nx*nx, H12 += nx*ny, H22 += ny*ny, g0 += j*r, g1 += nx*r,
+ *      g2 += ny*r, Sr += r*r.
+ *  L4. Step: Gauss-Newton on sum (n . (R_inc a + t_inc - b))^2 linearised in the angle, unknowns (th, t_x, t_y), the
+ *      translation eliminated first.  mse = Sr / n (it feeds the ABS / REL rules and info.mse, and is reported on DEGENERATE).
+ *      tr = H11 + H22, det = (H11*H22) - (H12*H12); not det > K*(tr*tr): FAILED (TBNAV_ICP_DEGENERATE), K =
+ *      TBNAV_ICP_LINE_MIN_COND.  v1 = ((H22*H01) - (H12*H02)) / det, v2 = ((H11*H02) - (H12*H01)) / det,
+ *      dth = H00 - ((H01*v1) + (H02*v2)); not dth > K*H00: FAILED (TBNAV_ICP_DEGENERATE).
+ *      th = -(g0 - ((v1*g1) + (v2*g2))) / dth; w1 = g1 + (H01*th), w2 = g2 + (H02*th);
+ *      t_x = -((H22*w1) - (H12*w2)) / det, t_y = -((H11*w2) - (H12*w1)) / det.
+ *      Rotation without a transcendental: u = 0.5*th, q = 1 + (u*u), c = (1 - (u*u)) / q, s = th / q: an exact rotation
+ *      (c*c + s*s = 1) that agrees with th to third order and has the same fixed point th = 0.  The TRANSFORM rule uses this
+ *      c and |t_inc|^2 = (t_x*t_x) + (t_y*t_y).
+ *  K = 1e-6 is a design constant, not a measurement.  Where it sits: det / tr^2 (1/4 when the normals are spread evenly over
+ *  all directions, 0 when they are all parallel) is 0.24-0.25 for the two rooms of tests/rbpf_cases.py, 0.048 for a 2 m wide
+ *  corridor with 1 cm range noise, and 6.5e-11 for the same corridor without noise, where only the float rounding of the
+ *  normals is left: a step taken on that throws the clouds apart.
+ *  Divergences to know: the index window does not wrap from the last beam to beam 0 (the first and last w beams of a full
+ *  turn get one-sided normals); normals are taken on the target cloud only; no robust weighting and no outlier rejection
+ *  beyond the distance gate.
+ *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
- * max_iter <= 1000; anything larger is TBNAV_ERR_INVALID_ARG.
+ * max_iter <= 1000; anything larger is TBNAV_ERR_INVALID_ARG.  The line metric is a kernel of its own (icp_align_line) that
+ * shares the cloud, the search and the tree with the point kernel and keeps the normals as float2 in LDS beside the cloud
+ * (16 bytes per beam): with it n_beams <= TBNAV_ICP_LINE_MAX_BEAMS = 2048 (32 KB of dynamic LDS beside 16 KB for the tree).
  */
 #ifndef TBNAV_ICP_H
 #define TBNAV_ICP_H
@@ -63,6 +107,15 @@ extern "C" {
 
 #define TBNAV_ICP_MAX_BEAMS 4096
 #define TBNAV_ICP_MAX_ITER 1000
+
+/* the error an alignment minimises (tbnav_icp_set_metric); POINT is the reference's and the default */
+#define TBNAV_ICP_METRIC_POINT 0
+#define TBNAV_ICP_METRIC_LINE 1
+#define TBNAV_ICP_LINE_MAX_BEAMS 2048         /* n_beams limit of the line metric */
+#define TBNAV_ICP_LINE_MAX_WINDOW 16
+#define TBNAV_ICP_LINE_NORMAL_WINDOW 1        /* default normal_window (beams) */
+#define TBNAV_ICP_LINE_NORMAL_MAX_GAP 0.25    /* default normal_max_gap (metres) */
+#define TBNAV_ICP_LINE_MIN_COND 1e-6          /* K of item L4 */
 
 typedef struct tbnav_icp_params {
   float beam_min, beam_max, beam_delta, range_min, range_max;  /* LaserProperties (sensor_model.hpp) */
@@ -127,6 +180,21 @@ int tbnav_icp_cloud(tbnav_icp* h, const float* scan, int32_t n_beams, float* xy,
 
 /* number of kernel launches the last tbnav_icp_step_batch made (1 when no scan failed) */
 int tbnav_icp_last_batch_launches(const tbnav_icp* h);
+
+/* (addition, no counterpart in the reference) the metric of every later tbnav_icp_match / tbnav_icp_step /
+ * tbnav_icp_step_batch of this handle, realignment launches included.  A new handle is TBNAV_ICP_METRIC_POINT.
+ * normal_window <= 0 / normal_max_gap <= 0 select the defaults; they are stored with either metric and used by the line
+ * metric only.  An unknown metric, a window above TBNAV_ICP_LINE_MAX_WINDOW, or METRIC_LINE on a handle whose stored scan has
+ * more than TBNAV_ICP_LINE_MAX_BEAMS beams is TBNAV_ERR_INVALID_ARG and changes nothing.  The stored scan is kept.  With
+ * METRIC_LINE the calls above return TBNAV_ERR_INVALID_ARG for n_beams > TBNAV_ICP_LINE_MAX_BEAMS. */
+int tbnav_icp_set_metric(tbnav_icp* h, int32_t metric, int32_t normal_window, double normal_max_gap);
+/* any of the three outputs may be null */
+int tbnav_icp_get_metric(const tbnav_icp* h, int32_t* metric, int32_t* normal_window, double* normal_max_gap);
+
+/* test hook: the normals of one scan taken as a target (item L1, with the handle's window and gap), per BEAM:
+ * nxy [n_beams][2], has [n_beams]; a beam without a normal (an invalid beam included) holds (0, 0) and 0.
+ * n_beams <= TBNAV_ICP_LINE_MAX_BEAMS. */
+int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* nxy, int32_t* has);
 
 #ifdef __cplusplus
 }

@@ -97,6 +97,9 @@ class IcpInfo(C.Structure):
 
 # tbnav_icp_criterion
 ICP_NOT_RUN, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES, ICP_DEGENERATE = range(7)
+# tbnav_icp_set_metric
+ICP_METRIC_POINT, ICP_METRIC_LINE = 0, 1
+ICP_LINE_MAX_BEAMS, ICP_LINE_MAX_WINDOW = 2048, 16
 
 
 _lib = None
@@ -274,6 +277,9 @@ def lib() -> C.CDLL:
         "tbnav_icp_step_batch": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp]),
         "tbnav_icp_cloud": (C.c_int, [vp, vp, i32, vp, C.POINTER(i32)]),
         "tbnav_icp_last_batch_launches": (C.c_int, [vp]),
+        "tbnav_icp_set_metric": (C.c_int, [vp, i32, i32, C.c_double]),
+        "tbnav_icp_get_metric": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]),
+        "tbnav_icp_normals": (C.c_int, [vp, vp, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

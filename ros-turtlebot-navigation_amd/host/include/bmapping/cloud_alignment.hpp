@@ -14,6 +14,12 @@
 // once on stderr.  Compiling with -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor call useDeviceICP(), so a node
 // built unchanged against this header runs with the device ICP.  The define only changes a default
 // argument, which is evaluated where the constructor is called: objects compiled with and without it link together.
+//
+// useDeviceICP(device, ICPMetric::PointToLine) installs the same device ICP with its point-to-line metric (tbnav_icp.h,
+// POINT-TO-LINE METRIC): an addition with NO counterpart in the reference, which only ever runs PCL's point-to-point ICP.
+// useDeviceICP(device) stays point-to-point.  Compiling with -DTBNAV_SCAN_ALIGNMENT_POINT_TO_LINE beside
+// -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor choose the line metric; it too only changes a default argument
+// (alone, without the first define, it has no effect).
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -30,24 +36,36 @@
 #define TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT false
 #endif
 
+#ifdef TBNAV_SCAN_ALIGNMENT_POINT_TO_LINE
+#define TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT ::bmapping::ICPMetric::PointToLine
+#else
+#define TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT ::bmapping::ICPMetric::PointToPoint
+#endif
+
 namespace bmapping {
 
 using rigid2d::Transform2D;
+
+/// (addition) what the device ICP minimises: PointToPoint is the reference's (PCL's) metric and the default
+enum class ICPMetric { PointToPoint, PointToLine };
 
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
   using Matcher = std::function<bool(Transform2D&, const Transform2D&, const std::vector<float>&, const std::vector<float>&)>;
 
-  ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT)
+  ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT,
+                ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT)
       : props_(props), Trs_(Trs) {
-    if (device_icp) useDeviceICP();
+    if (device_icp) useDeviceICP(-1, device_metric);
   }
 
   /// plug in a real scan matcher (e.g. a PCL ICP wrapper in a catkin workspace that has PCL)
   void setMatcher(Matcher m) { matcher_ = std::move(m); }
   /// (addition) the GPU ICP as the matcher, on `device` (-1: the current one); throws std::runtime_error without a GPU
-  void useDeviceICP(int device = -1);
+  void useDeviceICP(int device = -1) { useDeviceICP(device, ICPMetric::PointToPoint); }
+  /// (addition) the same with the metric named: PointToLine has no counterpart in the reference (default window and gap)
+  void useDeviceICP(int device, ICPMetric metric);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

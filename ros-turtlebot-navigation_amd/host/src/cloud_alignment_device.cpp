@@ -1,4 +1,5 @@
-// cloud_alignment_device.cpp — ScanAlignment::useDeviceICP: the device ICP of include/tbnav_icp.h as the shim's matcher.
+// cloud_alignment_device.cpp — ScanAlignment::useDeviceICP: the device ICP of include/tbnav_icp.h as the shim's matcher, with
+// its point-to-point metric (the reference's) or its point-to-line metric (an addition).
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -9,7 +10,7 @@
 
 namespace bmapping {
 
-void ScanAlignment::useDeviceICP(int device) {
+void ScanAlignment::useDeviceICP(int device, ICPMetric metric) {
   tbnav_icp_params p;
   tbnav_icp_default_params(&p);  // the reference's settings (cloud_alignment.cpp:21-34)
   p.beam_min = props_.beam_min; p.beam_max = props_.beam_max; p.beam_delta = props_.beam_delta;
@@ -27,6 +28,10 @@ void ScanAlignment::useDeviceICP(int device) {
   }
   // the matcher holds the handle: copies of this object (and of the std::function) share it
   std::shared_ptr<tbnav_icp> h(raw, tbnav_icp_destroy);
+  if (metric == ICPMetric::PointToLine) {
+    const int mrc = tbnav_icp_set_metric(raw, TBNAV_ICP_METRIC_LINE, 0, 0.0);  // the default window and gap
+    if (mrc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(mrc));
+  }
   matcher_ = [h](Transform2D& T, const Transform2D& T_init, const std::vector<float>& target, const std::vector<float>& source) {
     if (target.size() != source.size()) throw std::invalid_argument("bmapping::ScanAlignment: scans of different lengths");
     const auto g = T_init.displacement();

@@ -5,6 +5,9 @@ pclICPWrapper(T_init, scan) keeps the previous scan in the handle (cloud_alignme
 statelessly (:160-223).  wrapperBatch replays a logged run: its (ok, T) arrays are tbnav_rbpf_slam_batch's icp_ok / T_icp.
 init_guess is ParticleFilter::icpInitGuess (particle_filter.cpp:602-612).  The algorithm is a restatement of PCL's
 IterativeClosestPoint; parity with PCL itself is unpinned (see the header).
+
+metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
+point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
 from __future__ import annotations
 
@@ -60,14 +63,49 @@ def init_guess(cur, prev):
     return (dth, float(cur[1]) - float(prev[1]), float(cur[2]) - float(prev[2]))
 
 
+_METRICS = {"point": capi.ICP_METRIC_POINT, "line": capi.ICP_METRIC_LINE}
+
+
 class ScanAlignment:
     """bmapping::ScanAlignment on one MI355X."""
 
-    def __init__(self, params: "capi.IcpParams | None" = None):
+    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0):
         self._L = capi.lib()
         self.params = params if params is not None else default_params()
+        if metric not in _METRICS:
+            raise ValueError(f"metric must be one of {sorted(_METRICS)}, not {metric!r}")
         self._h = C.c_void_p()
         capi.check(self._L.tbnav_icp_create(C.byref(self.params), C.byref(self._h)), "tbnav_icp_create")
+        if metric != "point" or normal_window or normal_max_gap:
+            try:
+                self.setMetric(metric, normal_window, normal_max_gap)
+            except Exception:
+                self.close()
+                raise
+
+    def setMetric(self, metric="point", normal_window=0, normal_max_gap=0.0):
+        """tbnav_icp_set_metric: "point" | "line" for every later call; normal_window (beams, 0: the default 1) and
+        normal_max_gap (metres, 0: the default 0.25) are the line metric's.  The stored scan is kept."""
+        if metric not in _METRICS:
+            raise ValueError(f"metric must be one of {sorted(_METRICS)}, not {metric!r}")
+        capi.check(self._L.tbnav_icp_set_metric(self._h, _METRICS[metric], int(normal_window), float(normal_max_gap)),
+                   "tbnav_icp_set_metric")
+
+    def metric(self):
+        """-> (metric name, normal_window, normal_max_gap) as the handle holds them"""
+        m, w, g = C.c_int32(), C.c_int32(), C.c_double()
+        capi.check(self._L.tbnav_icp_get_metric(self._h, C.byref(m), C.byref(w), C.byref(g)), "tbnav_icp_get_metric")
+        return {v: k for k, v in _METRICS.items()}[m.value], w.value, g.value
+
+    def normals(self, scan):
+        """the normals the line metric gives one scan taken as a target, per beam: (float32 [n_beams][2], int32 [n_beams]
+        flags); a beam without a normal holds (0, 0) and 0"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        nxy = np.zeros((scan.size, 2), dtype=np.float32)
+        has = np.zeros(scan.size, dtype=np.int32)
+        capi.check(self._L.tbnav_icp_normals(self._h, scan.ctypes.data, scan.size, nxy.ctypes.data, has.ctypes.data),
+                   "tbnav_icp_normals")
+        return nxy, has
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

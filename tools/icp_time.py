@@ -1,9 +1,14 @@
 """Timing of the device ICP (include/tbnav_icp.h) on the GPU:
-python tools/icp_time.py [--out FILE] [--quick]
+python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N]
   - latency of one synchronous tbnav_icp_step (host clock around the call, which ends in a stream synchronise) at 360 beams
     (1 deg) and 1080 beams (1/3 deg): median / p10 / p90 of 500 scans after 20 of warm-up, a robot driving round a room;
   - tbnav_icp_step_batch over 2000 scans of the same kind of run: median of 5 calls (after one of warm-up), per call and
     per scan, with the launches it made;
+  --metric: the point metric (default), the line metric (tbnav_icp_set_metric, default window and gap), or both: the two are then
+    timed in the same process on the same scans, each record under its metric's name with its mean iteration count, and
+    "line_over_point" holds the ratios of the medians and of the iteration counts;
+  --max-iter: tbnav_icp_params.max_iter (default 100, the reference's): a launch of step_batch lasts as long as its slowest
+    pair, so a pair that runs to the cap sets the batch's time;
   --quick: a few scans only (what a `rocprofv3 --kernel-trace --stats` run of this script needs).
 Kernel times come from a separate rocprofv3 run, not from this script."""
 import argparse
@@ -36,8 +41,8 @@ def loop_run(n, n_beams, beam_delta_deg, seed=1):
     return scans, T_init
 
 
-def step_latency(n_beams, beam_delta_deg, n_warm, n_time):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric)
     scans, T_init = loop_run(n_warm + n_time, n_beams, beam_delta_deg)
     ts, iters, fails = [], [], 0
     for s in range(n_warm + n_time):
@@ -52,11 +57,11 @@ def step_latency(n_beams, beam_delta_deg, n_warm, n_time):
     ts = np.array(ts)
     return dict(n_beams=n_beams, scans=n_time, median_us=float(np.median(ts)), p10_us=float(np.percentile(ts, 10)),
                 p90_us=float(np.percentile(ts, 90)), mean_iterations=float(np.mean(iters)), max_iterations=int(np.max(iters)),
-                failures=fails)
+                at_max_iter=int(np.sum(np.array(iters) >= max_iter)), failures=fails)
 
 
-def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric)
     scans, T_init = loop_run(n_scans, n_beams, beam_delta_deg, seed=2)
     ts = []
     for r in range(reps + 1):
@@ -70,20 +75,33 @@ def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0):
     a.close()
     med = float(np.median(ts))
     return dict(n_beams=n_beams, scans=n_scans, median_ms=med, min_ms=float(np.min(ts)), per_scan_us=med * 1e3 / n_scans,
-                launches=launches, failures=int(n_scans - ok.sum()), mean_iterations=float(np.mean([i["iterations"] for i in info[1:]])))
+                launches=launches, failures=int(n_scans - ok.sum()), mean_iterations=float(np.mean([i["iterations"] for i in info[1:]])),
+                max_iterations=int(np.max([i["iterations"] for i in info[1:]])),
+                at_max_iter=int(np.sum([i["criterion"] == 1 for i in info[1:]])))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--metric", choices=("point", "line", "both"), default="point")
+    ap.add_argument("--max-iter", type=int, default=100)
     a = ap.parse_args()
-    if a.quick:
-        res = dict(step_360=step_latency(360, 1.0, 2, 10), step_1080=step_latency(1080, 1.0 / 3.0, 2, 10),
-                   batch_2000=batch_time(2000, 1))
+    n_warm, n_time, reps = (2, 10, 1) if a.quick else (20, 500, 5)
+
+    def run(metric):
+        return dict(step_360=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter),
+                    step_1080=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter),
+                    batch_2000=batch_time(2000, reps, metric=metric, max_iter=a.max_iter))
+
+    if a.metric == "both":
+        res = dict(point=run("point"), line=run("line"))
+        res["line_over_point"] = {
+            key: dict(time=res["line"][key][t] / res["point"][key][t],
+                      iterations=res["line"][key]["mean_iterations"] / res["point"][key]["mean_iterations"])
+            for key, t in (("step_360", "median_us"), ("step_1080", "median_us"), ("batch_2000", "median_ms"))}
     else:
-        res = dict(step_360=step_latency(360, 1.0, 20, 500), step_1080=step_latency(1080, 1.0 / 3.0, 20, 500),
-                   batch_2000=batch_time(2000, 5))
+        res = run(a.metric)
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
