@@ -149,7 +149,10 @@ typedef struct tbnav_icp_info {
 
 typedef struct tbnav_icp tbnav_icp;
 
-/* The defaults above are the reference's (cloud_alignment.cpp:21-34): callers set the laser fields and Trs. */
+/* The defaults above are the reference's (cloud_alignment.cpp:21-34): callers set the laser fields and Trs.
+ * tbnav_icp_create refuses (TBNAV_ERR_INVALID_ARG, before it touches a device) max_iter outside 1..TBNAV_ICP_MAX_ITER, a
+ * negative or NaN epsilon, and a max_corr_dist that is not positive or whose square is not finite (the gate of item 3 must be
+ * able to drop a point that has no nearest target at all). */
 void tbnav_icp_default_params(tbnav_icp_params* p);
 int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out);
 void tbnav_icp_destroy(tbnav_icp* h);

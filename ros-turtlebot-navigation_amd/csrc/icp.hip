@@ -704,8 +704,11 @@ void tbnav_icp_default_params(tbnav_icp_params* p) {
 int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
   if (!params || !out) return TBNAV_ERR_INVALID_ARG;
   *out = nullptr;
+  // max_corr_dist^2 must be finite: a point with no nearest target (an empty target cloud, a guess that is not a number) is
+  // left at distance +inf with no index, and only a finite gate keeps it from being taken for a pair
   if (params->max_iter < 1 || params->max_iter > TBNAV_ICP_MAX_ITER || !(params->max_corr_dist > 0.0) ||
-      !(params->transform_eps >= 0.0) || !(params->fitness_eps >= 0.0))
+      !std::isfinite(params->max_corr_dist * params->max_corr_dist) || !(params->transform_eps >= 0.0) ||
+      !(params->fitness_eps >= 0.0))
     return TBNAV_ERR_INVALID_ARG;
   int ndev = 0;
   {
