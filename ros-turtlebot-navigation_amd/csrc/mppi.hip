@@ -127,8 +127,9 @@ int launch_fused(tbnav_mppi* h, const double x0[3], const double* d_duL, const d
   const size_t lds = fused_lds_bytes(h->T, R);
   const RngArgs g = rng ? *rng : RngArgs{0, 0, 0.0, 0.0};
 #define TBNAV_FUSED(TR, RR, TLL, RG) do { h->lk_rollout[0] = 1; h->lk_rollout[1] = TR; h->lk_rollout[2] = RR; h->lk_rollout[3] = TLL; h->lk_rollout[4] = RG;     \
-                                     hipLaunchKernelGGL((mppi_rollout_fused<TR, RR, TLL, RG>), grid, block, lds, st, a, d_duL, d_duR, usrc, \
-                                                        lam_of(h), h->keep_j ? h->d_J : nullptr, h->d_records_f, h->fused_S, g); } while (0)
+                                     hipLaunchKernelGGL((mppi_rollout_fused<TR, RR, TLL, RG>), grid, block, lds, st, usrc.p, (const double*)g.ahead, (const uint64_t*)g.ahead_tag, g.tick0, \
+                                                        usrc.shift, h->T, h->K, h->fused_S, h->d_records_f, h->keep_j ? h->d_J : nullptr, a, usrc.init_l, usrc.init_r, \
+                                                        lam_of(h), d_duL, d_duR, rng_rest(g)); } while (0)
 #define TBNAV_FUSED_R(TR)                                                                                \
   if (R == 8) { if (TL == 1) TBNAV_FUSED(TR, 8, 1, 0); else TBNAV_FUSED(TR, 8, 2, 0); }          \
   else if (R == 4) { if (TL == 1) TBNAV_FUSED(TR, 4, 1, 0); else TBNAV_FUSED(TR, 4, 2, 0); }     \
@@ -162,8 +163,11 @@ int launch_partials(tbnav_mppi* h, const double* d_duL, const double* d_duR, dou
 int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S, const DirectSrc* direct,
                              const RngArgs* next) {
   if (S < 0) S = h->S;
-  int tpr = 1;
-  while (tpr < G * S && tpr < kWave) tpr <<= 1;
+  // lanes per time step (the power of two >= the record count, at most a wave) and the time steps' blocks are formed here, once,
+  // and handed to the kernel: they are launch-uniform, and used to head its chain as a loop and an integer division
+  int tpr_log2 = 0;
+  while ((1 << tpr_log2) < G * S && (1 << tpr_log2) < kWave) ++tpr_log2;
+  const int tpr = 1 << tpr_log2;
   const int wpb = TBNAV_COMBINE_WAVES;  // waves per workgroup
   const int steps_per_block = wpb * (kWave / tpr);
   const int blocks = (h->T + steps_per_block - 1) / steps_per_block;
@@ -175,8 +179,9 @@ int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipS
   const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
   // (records that came through an all-gather: only the error words — a poisoned record raises them, see mppi_combine)
   const DirectSrc ds = direct ? *direct : DirectSrc{nullptr, 0ull, (G > 1 && h->comm) ? h->d_dx_err : nullptr, (G > 1 && h->comm) ? h->d_dx_dead : nullptr, 0u};
-#define TBNAV_COMBINE(KEEP, MODE) do { h->lk_combine[0] = KEEP; h->lk_combine[1] = MODE; hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(blocks + (MODE == 0 ? ahead_blocks : 0)), dim3(wpb * kWave), 0, st, h->T, G, S, lam_of(h), h->p.max_wheel_vel, usrc, \
-                                                    d_records, h->d_u[1 - h->ucur], h->d_out, h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1), ds, MODE == 0 ? nx : off); } while (0)
+#define TBNAV_COMBINE(KEEP, MODE) do { h->lk_combine[0] = KEEP; h->lk_combine[1] = MODE; hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(blocks + (MODE == 0 ? ahead_blocks : 0)), dim3(wpb * kWave), 0, st, d_records, usrc.p, MODE == 0 ? nx.ahead : nullptr, MODE == 0 ? nx.tick0 : nullptr, \
+                                                    h->T, S, usrc.shift, blocks, G, tpr_log2, MODE == 0 ? nx.ahead_tag : nullptr, lam_of(h), h->p.max_wheel_vel, usrc.init_l, usrc.init_r, \
+                                                    h->d_u[1 - h->ucur], h->d_out, h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1), ds, rng_rest(MODE == 0 ? nx : off)); } while (0)
 #define TBNAV_COMBINE_KEEP(MODE) do { if (G * S > 4 * kWave && G * S <= 8 * kWave) TBNAV_COMBINE(8, MODE); else if (G * S > 2 * kWave && G * S <= 4 * kWave) TBNAV_COMBINE(4, MODE); \
                                       else TBNAV_COMBINE(2, MODE); } while (0)
   // (which form: the direct exchange polls; records that came through an all-gather may carry a failed rank's poison; one group has neither —

@@ -43,6 +43,16 @@ struct USrc {
     return (i + 1 < T) ? p[row * T + i + 1] : (row ? init_r : init_l);
   }
 };
+// The same value without a branch, for the two kernels of the latency-bound tick (mppi_rollout_fused, mppi_combine): the load is
+// requested from a clamped index with nothing but `p`, `shift` and T — which those kernels get preloaded into SGPRs — and
+// uinit, which arrives with the other kernel arguments, is selected afterwards.  0 <= i < T.
+__device__ __forceinline__ double usrc_load(const double* __restrict__ p, int shift, int row, int i, int T) {
+  const int j = shift ? (i + 1 < T ? i + 1 : T - 1) : i;
+  return p[row * T + j];
+}
+__device__ __forceinline__ double usrc_select(double loaded, int shift, int i, int T, double init) {
+  return (shift && i + 1 >= T) ? init : loaded;
+}
 
 // lambda and fl(1 / lambda) (formed on the host by the correctly rounded division; 0: use the division).  x / lambda is needed
 // once per soft-min weight and sits on the K = 1024 tick's latency chain; the quotient below is the correctly rounded one — the
@@ -307,6 +317,11 @@ struct RngArgs {  // base = tick * T * K_global + k0 * T
   int kind = 0;        // the sampler of the combine's draw: 2 = fp64, 1 = fp32 (the fused kernel's RNG argument; that kernel has it as a template argument)
   int K = 0;           // the handle's rollouts: the combine's draw covers K * T pairs
 };
+// RngArgs as the two kernels of the latency-bound tick take it: the three pointers that address a wave's first loads (`ahead`,
+// `ahead_tag`, `tick0`) travel as leading kernel parameters of their own, so that they are preloaded into SGPRs with the other
+// addresses (csrc/Makefile: PRELOAD); the rest comes in one struct behind them.
+struct RngRest { uint64_t seed, base; double sig_l, sig_r; uint64_t per_tick, epoch; int kind, K; };
+inline RngRest rng_rest(const RngArgs& g) { return RngRest{g.seed, g.base, g.sig_l, g.sig_r, g.per_tick, g.epoch, g.kind, g.K}; }
 // what a block of drawn-ahead pairs is: seed, the RESOLVED counter base (tick, k0 and K_global in it), sampler kind, cfg_epoch
 enum { kTagSeed = 0, kTagBase = 1, kTagKind = 2, kTagEpoch = 3, kTagWords = 4 };
 // WIDE = false (the narrow sampler, TBNAV_MPPI_OPT_SAMPLER = 0; the default up to round 5): Box-Muller on the fp32 transcendental units (v_log_f32,
@@ -318,8 +333,8 @@ enum { kTagSeed = 0, kTagBase = 1, kTagKind = 2, kTagEpoch = 3, kTagWords = 4 };
 // (utilities.cpp:20-24): the same Philox counter, all 128 bits of it — two uniforms of 52 random bits + the half-ulp centring
 // ((n + 0.5) * 2^-52 is exact in a double: 53 significant bits, never 0 or 1), fp64 log / sqrt / sincospi: normals out to
 // sqrt(2 * 53 * ln 2) = 8.57 sigma on a grid finer than 2^-52.
-template <bool WIDE>
-__device__ __forceinline__ void device_noise(const RngArgs& g, int T, int i, int k, double& dl, double& dr) {
+template <bool WIDE, class Rng /* RngArgs or RngRest: seed, base, sig_l, sig_r */>
+__device__ __forceinline__ void device_noise(const Rng& g, int T, int i, int k, double& dl, double& dr) {
   uint32_t r[4];
   philox4x32_10(g.base + (uint64_t)k * T + i, g.seed, r);
   if constexpr (WIDE) {
@@ -360,10 +375,14 @@ __global__ __launch_bounds__(kWave) void mppi_rollout_prefix(RolloutArgs a_in, c
 template <int TRIG, int TC, int MAXW>
 __global__ __launch_bounds__(kWave * MAXW) void mppi_rollout_scan(RolloutArgs a, const double* __restrict__ duL, const double* __restrict__ duR, USrc u,
                                                                   double* __restrict__ J);
+// (mppi_rollout_fused and mppi_combine: what addresses a wave's first loads comes first, as plain pointers and ints — the leading
+//  14 dwords of a kernel's arguments are preloaded into SGPRs, up to the first by-value struct — and USrc / RngArgs arrive unpacked:
+//  u_p, u_shift, init_l, init_r and ahead, ahead_tag, tick0, RngRest)
 template <int TRIG, int R, int TL, int RNG>
-__global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(RolloutArgs a, const double* __restrict__ duL, const double* __restrict__ duR, USrc u, Lam lam,
-                                                                double* __restrict__ J /* NULL: not kept */, double* __restrict__ records, int S,
-                                                                RngArgs rng);
+__global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __restrict__ u_p, const double* __restrict__ ahead, const uint64_t* __restrict__ ahead_tag,
+                                                                const uint64_t* __restrict__ tick0, int u_shift, int T, int K, int S, double* __restrict__ records,
+                                                                double* __restrict__ J /* NULL: not kept */, RolloutArgs a /* its T, K: not read */, double init_l,
+                                                                double init_r, Lam lam, const double* __restrict__ duL, const double* __restrict__ duR, RngRest rng);
 // soft-min, exchange words, noise (mppi_softmin.hip)
 __global__ __launch_bounds__(kSliceThreads) void mppi_partials(int T, int K, int S, Lam lam, const double* __restrict__ J, const double* __restrict__ duL,
                                                                const double* __restrict__ duR, double* __restrict__ records, int prefix_rows,
@@ -371,9 +390,13 @@ __global__ __launch_bounds__(kSliceThreads) void mppi_partials(int T, int K, int
 __global__ __launch_bounds__(kWave) void mppi_merge_records(int T, int Sf, int per_slice, int S, Lam lam, const double* __restrict__ fine,
                                                             double* __restrict__ records, DirectPub pub);
 template <int kKeep, int MODE>   // MODE 0: one group of records (every single-GPU tick); 1: records of several ranks through an all-gather; 2: the direct exchange
-__global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam, double umax, USrc u, const double* __restrict__ records,
-                                                    double* __restrict__ u_out, double* __restrict__ out, double* __restrict__ out_host, double seq,
-                                                    DirectSrc ds, RngArgs nx /* MODE 0, nx.ahead set: blocks past the time steps' draw the next tick's noise */);
+__global__ __launch_bounds__(256) void mppi_combine(const double* __restrict__ records, const double* __restrict__ u_p,
+                                                    double* __restrict__ ahead /* MODE 0, set: blocks past the time steps' draw the next tick's noise */,
+                                                    const uint64_t* __restrict__ tick0, int T, int S, int u_shift,
+                                                    int step_blocks /* launch_combine's: blocks that serve time steps */, int G,
+                                                    int tpr_log2 /* lanes per time step = 1 << tpr_log2 */, uint64_t* __restrict__ ahead_tag, Lam lam, double umax,
+                                                    double init_l, double init_r, double* __restrict__ u_out, double* __restrict__ out,
+                                                    double* __restrict__ out_host, double seq, DirectSrc ds, RngRest nx);
 __global__ __launch_bounds__(256) void mppi_combine_wide(int T, int R, Lam lam, double umax, USrc u, const double* __restrict__ records, double* __restrict__ u_out,
                                                          double* __restrict__ out, double* __restrict__ out_host, double seq);
 __global__ __launch_bounds__(256) void mppi_direct_publish(const double* __restrict__ mine, int n, unsigned long long* const* __restrict__ peers, int me, int P,

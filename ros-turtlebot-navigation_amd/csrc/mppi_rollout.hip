@@ -451,13 +451,13 @@ __global__ __launch_bounds__(kWave * MAXW) void mppi_rollout_scan(RolloutArgs a,
 // The combine then merges K/R records per step instead of K/2048.  Numerics: the sums are wave-scan trees
 // instead of sequential chains (a few 1e-16 relative on x, y, theta, J — inside the 1e-11 J assertion).
 template <int TRIG, int R, int TL, int RNG>
-__global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(RolloutArgs a, const double* __restrict__ duL,
-                                                                const double* __restrict__ duR, USrc u, Lam lam,
-                                                                double* __restrict__ J /* NULL: not kept */, double* __restrict__ records, int S,
-                                                                RngArgs rng) {
+__global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __restrict__ u_p, const double* __restrict__ ahead,
+                                                                const uint64_t* __restrict__ ahead_tag, const uint64_t* __restrict__ tick0,
+                                                                int u_shift, int T, int K, int S, double* __restrict__ records,
+                                                                double* __restrict__ J /* NULL: not kept */, RolloutArgs a, double init_l, double init_r,
+                                                                Lam lam, const double* __restrict__ duL, const double* __restrict__ duR, RngRest rng) {
   extern __shared__ __attribute__((aligned(16))) double lds_all[];
   constexpr int RP = R + 1;  // padded tile rows: the transposed reads of a wave hit distinct banks
-  const int T = a.T, K = a.K;
   double* nL = lds_all;           // [T][RP]
   double* nR = nL + T * RP;       // [T][RP]
   double* Jl = nR + T * RP;       // [T][RP]
@@ -472,29 +472,43 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(RolloutArgs a, c
 #pragma unroll
     for (int q = 0; q < TL; ++q) {
       const int i = lane * TL + q, ii = i < T ? i : T - 1;
-      uL[q] = u.get(0, ii, T);
-      uR[q] = u.get(1, ii, T);
+      uL[q] = usrc_load(u_p, u_shift, 0, ii, T);   // (the address needs preloaded arguments only; uinit is selected below)
+      uR[q] = usrc_load(u_p, u_shift, 1, ii, T);
     }
     // noise ahead: the previous launch's combine may have drawn this tick's pairs already.  The pairs (16 B per lane and step:
-    // wave r reads its rollout's 16*T contiguous bytes) and the tag are requested together with the warm-start controls and the
-    // tick word, before the tag is looked at; a tag that is not this launch's (first tick, a gap, another seed / sampler / option)
-    // draws as before
+    // wave r reads its rollout's 16*T contiguous bytes), the tag and the tick word are requested together with the warm-start
+    // controls, from preloaded addresses and without a branch in between (the tick word of a launch that has none is read from the
+    // tag's address and multiplied by zero), so that one wait covers them and every kernel argument that is not preloaded; a tag that
+    // is not this launch's (first tick, a gap, another seed / sampler / option) draws as before
     double2 pre[TL];
-    uint64_t tag[kTagWords];
-    if constexpr (RNG != 0) {
-      if (rng.ahead) {   // (launch-uniform)
-        const double2* ap = reinterpret_cast<const double2*>(rng.ahead) + (size_t)kk * T;
-#pragma unroll
-        for (int q = 0; q < TL; ++q) { const int i = lane * TL + q; pre[q] = ap[i < T ? i : T - 1]; }
-#pragma unroll
-        for (int w = 0; w < kTagWords; ++w) tag[w] = rng.ahead_tag[w];
-      }
-    }
-    if constexpr (RNG != 0) { if (rng.tick0) rng.base += *rng.tick0 * rng.per_tick; }  // (a scalar load, under the warm-start loads)
     bool hit = false;
     if constexpr (RNG != 0) {
-      if (rng.ahead)
+      if (ahead) {   // (launch-uniform, a preloaded word)
+        const double2* ap = reinterpret_cast<const double2*>(ahead) + (size_t)kk * T;
+#pragma unroll
+        for (int q = 0; q < TL; ++q) { const int i = lane * TL + q; pre[q] = ap[i < T ? i : T - 1]; }
+        uint64_t tag[kTagWords];
+#pragma unroll
+        for (int w = 0; w < kTagWords; ++w) tag[w] = ahead_tag[w];
+        uint64_t t0 = *(tick0 ? tick0 : ahead_tag);
+        // Every entry load is requested above this line and the one scalar wait of the entry falls here: the empty statements
+        // want the tag, the tick word and every kernel argument in registers.  Left to itself the compiler sinks the tag load
+        // below the wait for per_tick (a second, far scalar round trip) and fetches the other argument lines where they are
+        // first used, each behind a wait of its own (tests/test_mppi_entry_isa.py).
+        asm volatile("" : "+s"(tag[0]), "+s"(tag[1]), "+s"(tag[2]), "+s"(tag[3]), "+s"(t0)
+                     : "s"(rng.seed), "s"(rng.base), "s"(rng.per_tick), "s"(rng.epoch), "s"(rng.sig_l), "s"(rng.sig_r), "s"(init_l), "s"(init_r),
+                       "s"(lam.lambda), "s"(lam.inv), "s"(J), "s"(a.x0[0]), "s"(a.x0[1]), "s"(a.x0[2]));
+        asm volatile("" :: "s"(a.half_r), "s"(a.r_over_b), "s"(a.r_d), "s"(a.h), "s"(a.h6), "s"(a.xd[0]), "s"(a.xd[1]), "s"(a.xd[2]), "s"(a.Q[0]),
+                     "s"(a.Q[1]), "s"(a.Q[2]), "s"(a.R[0]), "s"(a.R[1]), "s"(a.P1[0]), "s"(a.P1[1]), "s"(a.P1[2]));
+        rng.base += t0 * (tick0 ? rng.per_tick : 0ull);
         hit = (tag[kTagSeed] == rng.seed) & (tag[kTagBase] == rng.base) & (tag[kTagKind] == (uint64_t)RNG) & (tag[kTagEpoch] == rng.epoch);
+      } else if (tick0) rng.base += *tick0 * rng.per_tick;
+    }
+#pragma unroll
+    for (int q = 0; q < TL; ++q) {
+      const int i = lane * TL + q, ii = i < T ? i : T - 1;
+      uL[q] = usrc_select(uL[q], u_shift, ii, T, init_l);
+      uR[q] = usrc_select(uR[q], u_shift, ii, T, init_r);
     }
     if constexpr (RNG != 0) {
       if (hit) {
@@ -642,7 +656,8 @@ template __global__ void mppi_rollout_prefix<3>(TBNAV_ARGS_ROLLOUT, double* __re
 TBNAV_INST_SCAN(1)
 TBNAV_INST_SCAN(3)
 #undef TBNAV_INST_SCAN
-#define TBNAV_ARGS_FUSED RolloutArgs, const double* __restrict__, const double* __restrict__, USrc, Lam, double* __restrict__, double* __restrict__, int, RngArgs
+#define TBNAV_ARGS_FUSED const double* __restrict__, const double* __restrict__, const uint64_t* __restrict__, const uint64_t* __restrict__, int, int, int, int, \
+                         double* __restrict__, double* __restrict__, RolloutArgs, double, double, Lam, const double* __restrict__, const double* __restrict__, RngRest
 #define TBNAV_INST_FUSED(TR, RR, RG) \
   template __global__ void mppi_rollout_fused<TR, RR, 1, RG>(TBNAV_ARGS_FUSED); template __global__ void mppi_rollout_fused<TR, RR, 2, RG>(TBNAV_ARGS_FUSED);
 #define TBNAV_INST_FUSED_TR(TR) \

@@ -221,36 +221,45 @@ __device__ __forceinline__ bool direct_load_records(const DirectSrc& d, const si
 // kernel boundary.  The pairs do not depend on the controls, so this work sits in the combine's shadow: its time-step blocks
 // occupy one wave on T CUs, the sampler blocks spread over the rest.
 template <bool WIDE>
-__device__ __forceinline__ void draw_ahead(RngArgs g, int T, int K, int b) {
-  if (g.tick0) g.base += *g.tick0 * g.per_tick;   // (a replayed graph: resolved as the fused kernel of that tick will resolve it)
-  const int n = K * T;
+__device__ __forceinline__ void draw_ahead(RngRest g, double* __restrict__ ahead, uint64_t* __restrict__ ahead_tag, const uint64_t* __restrict__ tick0, int T, int b) {
+  constexpr int nthr = TBNAV_COMBINE_WAVES * kWave;   // (launch_combine's workgroup: a constant, not the hidden block-size argument)
+  // (a replayed graph: resolved as the fused kernel of that tick will resolve it.  This is a second scalar round trip behind the
+  //  kernel arguments', as before: the sampler workgroups were not measured to end the launch — docs/lab_notebook.md, Round 8)
+  if (tick0) g.base += *tick0 * g.per_tick;
+  const int n = g.K * T;
   double dl[TBNAV_AHEAD_PAIRS], dr[TBNAV_AHEAD_PAIRS];
 #pragma unroll
   for (int q = 0; q < TBNAV_AHEAD_PAIRS; ++q) {   // (independent chains: the last block's tail recomputes pair n - 1)
-    const int p = (b * TBNAV_AHEAD_PAIRS + q) * (int)blockDim.x + (int)threadIdx.x, pc = p < n ? p : n - 1;
+    const int p = (b * TBNAV_AHEAD_PAIRS + q) * nthr + (int)threadIdx.x, pc = p < n ? p : n - 1;
     const int k = pc / T, i = pc - k * T;
     device_noise<WIDE>(g, T, i, k, dl[q], dr[q]);
   }
-  double2* out = reinterpret_cast<double2*>(g.ahead);
+  double2* out = reinterpret_cast<double2*>(ahead);
 #pragma unroll
   for (int q = 0; q < TBNAV_AHEAD_PAIRS; ++q) {
-    const int p = (b * TBNAV_AHEAD_PAIRS + q) * (int)blockDim.x + (int)threadIdx.x;
+    const int p = (b * TBNAV_AHEAD_PAIRS + q) * nthr + (int)threadIdx.x;
     if (p < n) out[p] = make_double2(dl[q], dr[q]);
   }
   if (b == 0 && threadIdx.x == 0) {   // (vector stores from one lane)
-    uint64_t* tg = g.ahead_tag;
-    tg[kTagSeed] = g.seed; tg[kTagBase] = g.base; tg[kTagKind] = (uint64_t)g.kind; tg[kTagEpoch] = g.epoch;
+    ahead_tag[kTagSeed] = g.seed; ahead_tag[kTagBase] = g.base; ahead_tag[kTagKind] = (uint64_t)g.kind; ahead_tag[kTagEpoch] = g.epoch;
   }
 }
 
-template <int kKeep, int MODE>
-__global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam, double umax, USrc u,
-                                                    const double* __restrict__ records, double* __restrict__ u_out,
-                                                    double* __restrict__ out, double* __restrict__ out_host, double seq, DirectSrc ds,
-                                                    RngArgs nx) {
-  // MODE 0 — one group of records, the single-GPU tick — carries none of the exchange's failure handling: a template argument, not a
-  // launch-time test (as one body the headline tick ran 0.2 us slower than round 4's: 7.95 against 7.75 us).
+// The time steps' half of mppi_combine.  The launch-uniform arithmetic is the host's (launch_combine): lanes per time step as
+// tpr_log2, and the workgroup is TBNAV_COMBINE_WAVES waves by construction.  The warm-start controls and the records are requested
+// from addresses that need the kernel's preloaded arguments only; what arrives with the other arguments (uinit, lambda, umax) is
+// used after them.
+// STRAIGHT (MODE 0): one group of records, a whole wave per time step and exactly kKeep records per lane (S == kKeep * kWave: K = 1024
+// and 2048 with eight rollouts per workgroup).  tpr, keep and G are compile-time, no record load needs a predicate or a division,
+// and a record (64 aligned bytes) is read as 16-byte loads.  The lane-to-record assignment (r = l + q * tpr), the order of every
+// sum and the epilogue are the general form's: the same bits.
+template <int kKeep, int MODE, bool STRAIGHT>
+__device__ __forceinline__ void combine_steps(const double* __restrict__ records, const double* __restrict__ u_p, int T, int S, int u_shift, int G_in, int tpr_log2,
+                                              const Lam& lam, double umax, double init_l, double init_r, double* __restrict__ u_out, double* __restrict__ out,
+                                              double* __restrict__ out_host, double seq, const DirectSrc& ds) {
+  static_assert(TBNAV_MPPI_REC == 8, "a record is four 16-byte loads");
   constexpr bool DIRECT = MODE == 2, GATHERED = MODE == 1;
+  constexpr int nw = TBNAV_COMBINE_WAVES;
   // (DIRECT: `records` is not read — field f of record (g, i, sl) is polled for in the exchange buffer, same index)
   // (an exchange that has timed out once stays dead: the ticks queued behind it must not each wait the whole bound again)
   const bool dead = DIRECT && __hip_atomic_load(ds.err_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
@@ -262,30 +271,35 @@ __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam
   //  u = -max_wheel_vel on every healthy rank.)
   bool failed = dead;
   auto field = [&](const double* rec, int f) { return DIRECT ? (dead ? 0.0 : direct_load(ds, (size_t)(rec - records) + f, failed)) : rec[f]; };
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave, nw = blockDim.x / kWave;
-  const int R = G * S;
-  int tpr = 1;
-  while (tpr < R && tpr < kWave) tpr <<= 1;
-  const int spw = kWave / tpr, sub = lane / tpr, l = lane - sub * tpr;
-  if constexpr (MODE == 0) {
-    // the time-step blocks come first (the lowest block indices dispatch first); the blocks after them draw the next tick's noise
-    const int step_blocks = (T + nw * spw - 1) / (nw * spw);
-    if (nx.ahead && (int)blockIdx.x >= step_blocks) {   // (launch-uniform / block-uniform)
-      const int b = (int)blockIdx.x - step_blocks;
-      if (nx.kind == 2) draw_ahead<true>(nx, T, nx.K, b); else draw_ahead<false>(nx, T, nx.K, b);
-      return;
-    }
-  }
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  const int G = STRAIGHT ? 1 : G_in, R = G * S;
+  const int tpr = STRAIGHT ? kWave : 1 << tpr_log2;
+  const int spw = STRAIGHT ? 1 : kWave >> tpr_log2, sub = STRAIGHT ? 0 : lane >> tpr_log2, l = lane - sub * tpr;
   const int i = (blockIdx.x * nw + wid) * spw + sub;
   const bool valid = i < T;
-  // the warm-start controls do not depend on the records: fetch them first, under the record loads
-  const double u_l = valid ? u.get(0, i, T) : 0.0, u_r = valid ? u.get(1, i, T) : 0.0;
+  const int ic = valid ? i : 0;
+  // the warm-start controls do not depend on the records: fetch them first, under the record loads (uinit is selected below)
+  const double u_l0 = usrc_load(u_p, u_shift, 0, ic, T), u_r0 = usrc_load(u_p, u_shift, 1, ic, T);
   // Up to kKeep records per lane stay in registers (2: at most 128 records per step — the K = 1024 tick, whose critical
   // path should not carry idle slots; 4 / 8: up to 256 / 512 — the fused kernel with 16 rollouts per workgroup up to K = 4096 / 8192);
   // beyond that the second pass re-reads them (L1/L2 hits).
-  const bool keep = R <= kKeep * tpr;
+  const bool keep = STRAIGHT ? true : R <= kKeep * tpr;
   double rk[kKeep][7];
-  if constexpr (DIRECT) {
+  if constexpr (STRAIGHT) {
+    const double2* rp = reinterpret_cast<const double2*>(records) + ((size_t)ic * S + l) * (TBNAV_MPPI_REC / 2);
+#pragma unroll
+    for (int q = 0; q < kKeep; ++q) {
+      const double2* p = rp + (size_t)q * kWave * (TBNAV_MPPI_REC / 2);
+      // (field 6 is asked for alone — the eighth word is not used; the compiler reads the aligned 16 bytes all the same.  What
+      //  keeps all ten entry loads in front of the first wait is the fence below: without it the warm-start loads and half of
+      //  the record loads were issued behind a wait for the first half, a second memory round trip)
+      const double2 v0 = p[0], v1 = p[1], v2 = p[2];
+      rk[q][0] = v0.x; rk[q][1] = v0.y; rk[q][2] = v1.x; rk[q][3] = v1.y; rk[q][4] = v2.x; rk[q][5] = v2.y;
+      rk[q][6] = reinterpret_cast<const double*>(p)[6];
+    }
+    // (a wave past the last time step — TBNAV_COMBINE_WAVES > 1 only — reads step 0's records and discards its result below)
+    __builtin_amdgcn_sched_barrier(0);   // every entry load is requested above this line (tests/test_mppi_entry_isa.py)
+  } else if constexpr (DIRECT) {
     size_t idx[kKeep];
     bool hv[kKeep];
 #pragma unroll
@@ -318,6 +332,7 @@ __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam
       for (int f = 0; f < 7; ++f) rk[q][f] = have ? rec[f] : 0.0;  // n == 0 marks "no record"
     }
   }
+  const double u_l = valid ? usrc_select(u_l0, u_shift, ic, T, init_l) : 0.0, u_r = valid ? usrc_select(u_r0, u_shift, ic, T, init_r) : 0.0;
   double M = __builtin_huge_val();
   if (keep) {
 #pragma unroll
@@ -397,6 +412,33 @@ __global__ __launch_bounds__(256) void mppi_combine(int T, int G, int S, Lam lam
       }
     }
   }
+}
+
+template <int kKeep, int MODE>
+__global__ __launch_bounds__(256) void mppi_combine(const double* __restrict__ records, const double* __restrict__ u_p, double* __restrict__ ahead,
+                                                    const uint64_t* __restrict__ tick0, int T, int S, int u_shift, int step_blocks, int G, int tpr_log2,
+                                                    uint64_t* __restrict__ ahead_tag, Lam lam, double umax, double init_l, double init_r,
+                                                    double* __restrict__ u_out, double* __restrict__ out, double* __restrict__ out_host, double seq,
+                                                    DirectSrc ds, RngRest nx) {
+  static_assert(TBNAV_COMBINE_WAVES * kWave <= 256, "launch bounds");
+  // MODE 0 — one group of records, the single-GPU tick — carries none of the exchange's failure handling: a template argument, not a
+  // launch-time test (as one body the headline tick ran 0.2 us slower than round 4's: 7.95 against 7.75 us).
+  if constexpr (MODE == 0) {
+    // the time-step blocks come first (the lowest block indices dispatch first); the blocks after them draw the next tick's noise
+    // (the expectations only order the code: the straight-line form follows the entry, nothing of the other forms lies before it)
+    if (__builtin_expect((int)blockIdx.x >= step_blocks, 0)) {   // (block-uniform, a preloaded word; the grid is longer than step_blocks only with `ahead` set)
+      const int b = (int)blockIdx.x - step_blocks;
+      if (!ahead) return;
+      if (nx.kind == 2) draw_ahead<true>(nx, ahead, ahead_tag, tick0, T, b); else draw_ahead<false>(nx, ahead, ahead_tag, tick0, T, b);
+      return;
+    }
+    // the straight-line form of the latency-bound ticks, inside the same instantiation (launch-uniform, preloaded words)
+    if (__builtin_expect(G == 1 && S == kKeep * kWave, 1)) {
+      combine_steps<kKeep, 0, true>(records, u_p, T, S, u_shift, G, tpr_log2, lam, umax, init_l, init_r, u_out, out, out_host, seq, ds);
+      return;
+    }
+  }
+  combine_steps<kKeep, MODE, false>(records, u_p, T, S, u_shift, G, tpr_log2, lam, umax, init_l, init_r, u_out, out, out_host, seq, ds);
 }
 
 // The single-GPU combine for MANY records per time step (256 < records <= 1024: the fused kernel's 16-rollout records at K = 4097 ...
@@ -543,7 +585,7 @@ __global__ void mppi_sample_noise(int T, int K, uint64_t seed, uint64_t base, do
   }
 }
 
-#define TBNAV_INST_COMBINE(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(int, int, int, Lam, double, USrc, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc, RngArgs);
+#define TBNAV_INST_COMBINE(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(const double* __restrict__, const double* __restrict__, double* __restrict__, const uint64_t* __restrict__, int, int, int, int, int, int, uint64_t* __restrict__, Lam, double, double, double, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc, RngRest);
 TBNAV_INST_COMBINE(2, 0) TBNAV_INST_COMBINE(4, 0) TBNAV_INST_COMBINE(8, 0)
 TBNAV_INST_COMBINE(2, 1) TBNAV_INST_COMBINE(4, 1) TBNAV_INST_COMBINE(8, 1)
 TBNAV_INST_COMBINE(2, 2) TBNAV_INST_COMBINE(4, 2) TBNAV_INST_COMBINE(8, 2)

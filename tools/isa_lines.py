@@ -7,9 +7,10 @@ lo = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 hi = int(sys.argv[4]) if len(sys.argv) > 4 else 10**9
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = os.path.join(tempfile.gettempdir(), "isa_lines.s")
-contract = "-ffp-contract=off" if "rbpf" in src else "-ffp-contract=fast-honor-pragmas"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from makefile_flags import per_file_flags   # the file's own flags in csrc/Makefile (contraction, kernel-argument preload)
 subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-fast-math", f"-I{root}/include",
-                f"-I{os.path.dirname(os.path.abspath(src))}", contract, "-gline-tables-only", "-S", "--cuda-device-only", src, "-o", out],
+                f"-I{os.path.dirname(os.path.abspath(src))}", *per_file_flags(src), "-gline-tables-only", "-S", "--cuda-device-only", src, "-o", out],
                check=True, stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 start = [i for i, l in enumerate(lines) if re.match(r"^\S*" + key + r"\S*:", l)][0]

@@ -12,9 +12,10 @@ CSRC = os.path.join(ROOT, "ros-turtlebot-navigation_amd", "csrc")
 which = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 extra = sys.argv[3:]
-contract = "-ffp-contract=fast-honor-pragmas" if which.startswith("mppi") else "-ffp-contract=off"
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from makefile_flags import per_file_flags   # the file's own flags in csrc/Makefile (contraction, kernel-argument preload)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", f"-I{ROOT}/include", f"-I{CSRC}",
-       contract, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, which + ".hip"), "-o", "/tmp/_kr.o"] + extra
+       *per_file_flags(which), "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, which + ".hip"), "-o", "/tmp/_kr.o"] + extra
 err = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True).stderr
 demangle = subprocess.run(["c++filt"], input=err, stdout=subprocess.PIPE, text=True).stdout
 cur = None
