@@ -90,8 +90,8 @@
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
- * max_iter <= 1000; anything larger is TBNAV_ERR_INVALID_ARG.  The line metric is a kernel of its own (icp_align_line) that
- * shares the cloud, the search and the tree with the point kernel and keeps the normals as float2 in LDS beside the cloud
+ * max_iter <= 1000; anything larger is TBNAV_ERR_INVALID_ARG.  Both metrics are instantiations of one kernel (icp_align) and
+ * share the cloud, the search and the tree; the line metric keeps the normals as float2 in LDS beside the cloud
  * (16 bytes per beam): with it n_beams <= TBNAV_ICP_LINE_MAX_BEAMS = 2048 (32 KB of dynamic LDS beside 16 KB for the tree).
  */
 #ifndef TBNAV_ICP_H

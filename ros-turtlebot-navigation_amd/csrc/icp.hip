@@ -1,18 +1,21 @@
 // icp.hip — ICP between laser scans, point-to-point and (as an option) point-to-line (include/tbnav_icp.h): the reference's
 // ScanAlignment::pclICP / pclICPWrapper (bmapping/src/bmapping/cloud_alignment.cpp:37-223) restated on the device.
 //
-// One workgroup of kThreads threads aligns one (target, source) pair; the whole iteration loop runs inside the launch.
+// One kernel, icp_align<Metric, P, C>, and two metrics.  One workgroup of kThreads threads aligns one (target, source) pair;
+// the whole iteration loop runs inside the launch.
 //   - the target cloud lives in LDS as float2, one slot per BEAM (an invalid beam holds NaN, which never wins the strict
 //     '<' of the nearest-neighbour scan, so the scan order over the valid points is the compacted cloud's order); the
 //     scan runs as C independent chains per point (latency: one wave per SIMD), merged in (distance, index) order;
 //   - thread t keeps the source beams t, t + B, ... (P of them, a template parameter) in registers, untransformed;
-//   - per iteration: transform, nearest neighbour against every target, the ten fp64 sums in the header's fixed order
+//   - per iteration: transform, nearest neighbour against every target, the metric's fp64 sums in the header's fixed order
 //     (per thread in increasing beam, then the tree t += t + s: s = 128 and 64 through LDS, 32..1 by shuffles in wave 0),
 //     and wave 0 leaves the totals in LDS; after ONE barrier every thread computes R_inc and the stopping criteria from
 //     them redundantly (wave-uniform), so the loop needs no further barrier and no global memory.
-// icp_align_line is the same shape for the header's POINT-TO-LINE METRIC (an addition; the reference has no such metric): the
-// target's normals as a second float2 array in LDS beside the cloud, computed by the workgroup before the loop, ten sums
-// through the same tree, and a 3x3 Gauss-Newton step solved by every thread from the totals.
+// A metric (PointMetric, LineMetric) supplies what differs: how many sums there are, what a kept pair adds to them, and how
+// the increment (c, s, tix, tiy) and mse come out of the totals.  PointMetric is the reference's: nine sums and a closed-form
+// rotation.  LineMetric is the header's POINT-TO-LINE METRIC (an addition; the reference has no such metric): the target's
+// normals as a second float2 array in LDS beside the cloud, computed by the workgroup before the loop, ten sums, and a 3x3
+// Gauss-Newton step solved by every thread from the totals.
 // Compiled with -ffp-contract=off (csrc/Makefile): every fp64 / fp32 expression keeps the restatement's rounding.
 #include <hip/hip_runtime.h>
 
@@ -30,8 +33,6 @@ namespace {
 
 constexpr int kThreads = 256;   // B of the header's reduction order
 constexpr int kWave = 64;
-constexpr int kSums = 9;        // Sax, Say, Sbx, Sby, Sxx, Syy, Sxy, Syx, Sd (n is counted apart, as an int)
-constexpr int kLineSums = 10;   // line metric: H00, H01, H02, H11, H12, H22, g0, g1, g2, Sr
 
 struct IcpConst {
   float range_min, range_max;
@@ -68,257 +69,6 @@ __device__ __forceinline__ bool cloud_point(float r, float2 cs, const IcpConst& 
   return true;
 }
 
-template <int P, int C = (P <= 2 ? 4 : P <= 4 ? 2 : 1)>
-__global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ scans, const float* __restrict__ stored,
-                                                        const float2* __restrict__ table, int n_beams,
-                                                        const IcpPair* __restrict__ pairs, IcpOut* __restrict__ out, IcpConst k) {
-  extern __shared__ float4 lds_dyn[];          // 16-byte aligned: the nearest-neighbour scan reads it as float4
-  float2* tgt = reinterpret_cast<float2*>(lds_dyn);  // [n_beams rounded up to 4]
-  __shared__ double red_a[kSums][kThreads / 2];  // s = 128 partials
-  __shared__ double red_b[kSums][kThreads / 4];  // s = 64 partials
-  __shared__ int cnt_a[kThreads / 2], cnt_b[kThreads / 4];
-  __shared__ double tot[kSums];
-  __shared__ int tot_n;
-
-  const int t = threadIdx.x;
-  const IcpPair pr = pairs[blockIdx.x];
-  const float* ts = pr.tgt < 0 ? stored : scans + (size_t)pr.tgt * n_beams;
-  const float* ss = pr.src < 0 ? stored : scans + (size_t)pr.src * n_beams;
-  const float qnan = __builtin_nanf("");
-  const int n4 = (n_beams + 3) & ~3;  // the LDS cloud is padded to whole float4 pairs of points with NaN
-  for (int i = t; i < n4; i += kThreads) {
-    float2 p = make_float2(qnan, qnan);
-    if (i < n_beams && !cloud_point(ts[i], table[i], k, p)) p = make_float2(qnan, qnan);
-    tgt[i] = p;
-  }
-  float2 src[P];
-  bool valid[P];
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const int i = t + j * kThreads;
-    valid[j] = i < n_beams && cloud_point(ss[i], table[i], k, src[j]);
-    if (!valid[j]) src[j] = make_float2(0.0f, 0.0f);
-  }
-  __syncthreads();
-
-  double R00 = pr.c, R01 = -pr.s, R10 = pr.s, R11 = pr.c, tx = pr.x, ty = pr.y;
-  double prev = DBL_MAX, mse = 0.0;
-  int iter = 0, n = 0, crit = TBNAV_ICP_NOT_RUN;
-  while (true) {
-    ++iter;
-    double sum[kSums];
-#pragma unroll
-    for (int q = 0; q < kSums; ++q) sum[q] = 0.0;
-    int cnt = 0;
-    float2 a[P];
-    float best[P][C];
-    int bi[P][C];
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      a[j].x = (float)(((R00 * (double)src[j].x) + (R01 * (double)src[j].y)) + tx);
-      a[j].y = (float)(((R10 * (double)src[j].x) + (R11 * (double)src[j].y)) + ty);
-#pragma unroll
-      for (int c = 0; c < C; ++c) { best[j][c] = __builtin_huge_valf(); bi[j][c] = 0x7fffffff; }
-    }
-    // nearest neighbour: C independent chains per point (chain c: targets m = c mod C, in increasing m, strict '<'), four
-    // targets per two 16-byte LDS reads (a broadcast: every lane reads the same address)
-    for (int m = 0; m < n4; m += 4) {
-      const float4 t01 = *reinterpret_cast<const float4*>(&tgt[m]);
-      const float4 t23 = *reinterpret_cast<const float4*>(&tgt[m + 2]);
-      const float bx[4] = {t01.x, t01.z, t23.x, t23.z}, by[4] = {t01.y, t01.w, t23.y, t23.w};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const float dx = a[j].x - bx[r], dy = a[j].y - by[r];
-          const float d = dx * dx + dy * dy;
-          if (d < best[j][r % C]) { best[j][r % C] = d; bi[j][r % C] = m + r; }
-        }
-      }
-    }
-    // the chains' minima in (distance, index) order: the lowest index among equal distances, as one scan in beam order
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-#pragma unroll
-      for (int c = 1; c < C; ++c) {
-        if (best[j][c] < best[j][0] || (best[j][c] == best[j][0] && bi[j][c] < bi[j][0])) { best[j][0] = best[j][c]; bi[j][0] = bi[j][c]; }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < P; ++j) {
-      if (valid[j] && (double)best[j][0] <= k.max_corr2) {
-        const float2 b = tgt[bi[j][0]];
-        const double ax = a[j].x, ay = a[j].y, bx = b.x, by = b.y;
-        ++cnt;
-        sum[0] += ax; sum[1] += ay; sum[2] += bx; sum[3] += by;
-        sum[4] += ax * bx; sum[5] += ay * by; sum[6] += ax * by; sum[7] += ay * bx;
-        sum[8] += (double)best[j][0];
-      }
-    }
-    // tree: t += t + s for s = 128, 64 (LDS), 32 .. 1 (wave 0, shuffles)
-    if (t >= kThreads / 2) {
-#pragma unroll
-      for (int q = 0; q < kSums; ++q) red_a[q][t - kThreads / 2] = sum[q];
-      cnt_a[t - kThreads / 2] = cnt;
-    }
-    __syncthreads();
-    if (t < kThreads / 2) {
-#pragma unroll
-      for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + red_a[q][t];
-      cnt += cnt_a[t];
-      if (t >= kThreads / 4) {
-#pragma unroll
-        for (int q = 0; q < kSums; ++q) red_b[q][t - kThreads / 4] = sum[q];
-        cnt_b[t - kThreads / 4] = cnt;
-      }
-    }
-    __syncthreads();
-    if (t < kWave) {
-#pragma unroll
-      for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + red_b[q][t];
-      cnt += cnt_b[t];
-#pragma unroll
-      for (int s = kWave / 2; s > 0; s >>= 1) {
-#pragma unroll
-        for (int q = 0; q < kSums; ++q) sum[q] = sum[q] + __shfl_down(sum[q], s, kWave);
-        cnt += __shfl_down(cnt, s, kWave);
-      }
-      if (t == 0) {
-#pragma unroll
-        for (int q = 0; q < kSums; ++q) tot[q] = sum[q];
-        tot_n = cnt;
-      }
-    }
-    __syncthreads();
-    // every thread: R_inc and the criteria from the totals (wave-uniform from here to the loop's end).  The next writes of
-    // red_a / red_b / tot come after the next iteration's first / second barrier, which every thread reaches only after it
-    // has read what it needs here.
-    n = tot_n;
-    if (n < 3) { crit = TBNAV_ICP_NO_CORRESPONDENCES; mse = 0.0; break; }
-    const double dn = (double)n;
-    const double Sax = tot[0], Say = tot[1], Sbx = tot[2], Sby = tot[3];
-    const double A = (tot[4] + tot[5]) - ((Sax * Sbx) + (Say * Sby)) / dn;
-    const double S = (tot[6] - tot[7]) - ((Sax * Sby) - (Say * Sbx)) / dn;
-    const double r = sqrt((A * A) + (S * S));
-    mse = tot[8] / dn;
-    if (r == 0.0) { crit = TBNAV_ICP_DEGENERATE; break; }
-    const double c = A / r, s = S / r;
-    const double amx = Sax / dn, amy = Say / dn, bmx = Sbx / dn, bmy = Sby / dn;
-    const double tix = bmx - ((c * amx) - (s * amy));
-    const double tiy = bmy - ((s * amx) + (c * amy));
-    const double n00 = (c * R00) - (s * R10), n01 = (c * R01) - (s * R11);
-    const double n10 = (s * R00) + (c * R10), n11 = (s * R01) + (c * R11);
-    const double ntx = ((c * tx) - (s * ty)) + tix, nty = ((s * tx) + (c * ty)) + tiy;
-    R00 = n00; R01 = n01; R10 = n10; R11 = n11; tx = ntx; ty = nty;
-    if (iter >= k.max_iter) { crit = TBNAV_ICP_ITERATIONS; break; }
-    if (c >= k.rot_thresh && ((tix * tix) + (tiy * tiy)) <= k.trans_thresh) { crit = TBNAV_ICP_TRANSFORM; break; }
-    const double dm = fabs(mse - prev);
-    if (dm < 1e-12) { crit = TBNAV_ICP_ABS_MSE; break; }
-    if (dm / prev < k.fitness_eps) { crit = TBNAV_ICP_REL_MSE; break; }
-    prev = mse;
-  }
-  if (t == 0) {
-    IcpOut o;
-    o.R00 = R00; o.R10 = R10; o.tx = tx; o.ty = ty; o.mse = mse;
-    o.iterations = iter; o.correspondences = n; o.criterion = crit; o.pad = 0;
-    out[blockIdx.x] = o;
-  }
-}
-
-// ---- the point-to-line metric (tbnav_icp.h, POINT-TO-LINE METRIC; no counterpart in the reference) ----
-// icp_align's stages as templates.  icp_align itself keeps its own inline text above: moving it onto these changed the code
-// the compiler makes for its nearest-neighbour loop (branches in place of selects at P = 2), and its timings are the measured
-// ones.  What the two kernels compute in these stages is the same contract, item by item.
-
-// the accumulated fp64 transform applied to the thread's source points (contract item 3), rounded to float
-template <int P>
-__device__ __forceinline__ void transform_sources(const float2 (&src)[P], float2 (&a)[P], double R00, double R01, double R10,
-                                                  double R11, double tx, double ty) {
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    a[j].x = (float)(((R00 * (double)src[j].x) + (R01 * (double)src[j].y)) + tx);
-    a[j].y = (float)(((R10 * (double)src[j].x) + (R11 * (double)src[j].y)) + ty);
-  }
-}
-
-// nearest neighbour of each a[j] in the LDS cloud -> best[j][0] (fp32 squared distance), bi[j][0] (beam index): C independent
-// chains per point (chain c: targets m = c mod C, in increasing m, strict '<'), four targets per two 16-byte LDS reads (a
-// broadcast: every lane reads the same address); then the chains' minima in (distance, index) order: the lowest index
-// among equal distances, as one scan in beam order
-template <int P, int C>
-__device__ __forceinline__ void nearest_targets(const float2* tgt, int n4, const float2 (&a)[P], float (&best)[P][C], int (&bi)[P][C]) {
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) { best[j][c] = __builtin_huge_valf(); bi[j][c] = 0x7fffffff; }
-  }
-  for (int m = 0; m < n4; m += 4) {
-    const float4 t01 = *reinterpret_cast<const float4*>(&tgt[m]);
-    const float4 t23 = *reinterpret_cast<const float4*>(&tgt[m + 2]);
-    const float bx[4] = {t01.x, t01.z, t23.x, t23.z}, by[4] = {t01.y, t01.w, t23.y, t23.w};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        const float dx = a[j].x - bx[r], dy = a[j].y - by[r];
-        const float d = dx * dx + dy * dy;
-        const bool lt = d < best[j][r % C];   // selects, not branches: the loop body stays one block
-        best[j][r % C] = lt ? d : best[j][r % C];
-        bi[j][r % C] = lt ? m + r : bi[j][r % C];
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-#pragma unroll
-    for (int c = 1; c < C; ++c) {
-      if (best[j][c] < best[j][0] || (best[j][c] == best[j][0] && bi[j][c] < bi[j][0])) { best[j][0] = best[j][c]; bi[j][0] = bi[j][c]; }
-    }
-  }
-}
-
-// tree: t += t + s for s = 128, 64 (LDS), 32 .. 1 (wave 0, shuffles); wave 0 leaves the totals in tot / *tot_n, which every
-// thread may read after the closing barrier.  The next writes of red_a / red_b / tot come after the next call's first /
-// second barrier, which every thread reaches only after it has read what it needs of this one.
-template <int NS>
-__device__ __forceinline__ void tree_sums(double (&sum)[NS], int cnt, double (*red_a)[kThreads / 2], double (*red_b)[kThreads / 4],
-                                          int* cnt_a, int* cnt_b, double* tot, int* tot_n, int t) {
-  if (t >= kThreads / 2) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) red_a[q][t - kThreads / 2] = sum[q];
-    cnt_a[t - kThreads / 2] = cnt;
-  }
-  __syncthreads();
-  if (t < kThreads / 2) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_a[q][t];
-    cnt += cnt_a[t];
-    if (t >= kThreads / 4) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) red_b[q][t - kThreads / 4] = sum[q];
-      cnt_b[t - kThreads / 4] = cnt;
-    }
-  }
-  __syncthreads();
-  if (t < kWave) {
-#pragma unroll
-    for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_b[q][t];
-    cnt += cnt_b[t];
-#pragma unroll
-    for (int s = kWave / 2; s > 0; s >>= 1) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) sum[q] = sum[q] + __shfl_down(sum[q], s, kWave);
-      cnt += __shfl_down(cnt, s, kWave);
-    }
-    if (t == 0) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) tot[q] = sum[q];
-      *tot_n = cnt;
-    }
-  }
-  __syncthreads();
-}
-
 // the target cloud of scan ts into LDS, one slot per beam, padded to whole float4 pairs of points; NaN for what is not a point
 __device__ __forceinline__ void load_target(float2* tgt, const float* __restrict__ ts, const float2* __restrict__ table, int n_beams,
                                             int n4, const IcpConst& k, int t) {
@@ -327,18 +77,6 @@ __device__ __forceinline__ void load_target(float2* tgt, const float* __restrict
     float2 p = make_float2(qnan, qnan);
     if (i < n_beams && !cloud_point(ts[i], table[i], k, p)) p = make_float2(qnan, qnan);
     tgt[i] = p;
-  }
-}
-
-// the thread's source beams t, t + B, ... of scan ss
-template <int P>
-__device__ __forceinline__ void load_sources(float2 (&src)[P], bool (&valid)[P], const float* __restrict__ ss,
-                                             const float2* __restrict__ table, int n_beams, const IcpConst& k, int t) {
-#pragma unroll
-  for (int j = 0; j < P; ++j) {
-    const int i = t + j * kThreads;
-    valid[j] = i < n_beams && cloud_point(ss[i], table[i], k, src[j]);
-    if (!valid[j]) src[j] = make_float2(0.0f, 0.0f);
   }
 }
 
@@ -372,21 +110,100 @@ __device__ __forceinline__ bool target_normal(const float2* tgt, int i, int n_be
   return true;
 }
 
-// One workgroup per pair like icp_align, with the normals of the target cloud in LDS beside it (NaN: no normal), computed
-// once before the loop; per iteration each kept pair fetches its target and its normal, and the tree adds ten sums.
-template <int P, int C = (P <= 2 ? 4 : P <= 4 ? 2 : 1)>
-__global__ __launch_bounds__(kThreads) void icp_align_line(const float* __restrict__ scans, const float* __restrict__ stored,
-                                                             const float2* __restrict__ table, int n_beams,
-                                                             const IcpPair* __restrict__ pairs, IcpOut* __restrict__ out, IcpConst k,
-                                                             IcpLine ln) {
-  extern __shared__ float4 lds_dyn[];
-  const int n4 = (n_beams + 3) & ~3;
+// ---- the two metrics: what icp_align does not share ----
+// kSums: the fp64 sums of the header (the pair count n is counted apart, as an int).  kNormals: the kernel keeps the target's
+// normals in LDS beside the cloud and hands add() the nearest target's.  kMaxBeams: what fits in LDS.  Params: the metric's
+// by-value kernel parameters.
+//   add(sum, a, b, nf, d): a kept pair (transformed source a, nearest target b with normal nf at fp32 squared distance d)
+//     into the thread's sums; false: the pair does not count.
+//   step(tot, n, mp, c, s, tix, tiy, mse): the increment from the totals of n >= 3 pairs; mse is assigned first; false: degenerate.
+
+// the reference's point-to-point metric: Sax, Say, Sbx, Sby, Sxx, Syy, Sxy, Syx, Sd and the closed-form 2-D rotation
+struct PointMetric {
+  static constexpr int kSums = 9;
+  static constexpr bool kNormals = false;
+  static constexpr int kMaxBeams = TBNAV_ICP_MAX_BEAMS;
+  struct Params {};
+  static __device__ __forceinline__ bool add(double (&sum)[kSums], float2 a, float2 b, float2, float d) {
+    const double ax = a.x, ay = a.y, bx = b.x, by = b.y;
+    sum[0] += ax; sum[1] += ay; sum[2] += bx; sum[3] += by;
+    sum[4] += ax * bx; sum[5] += ay * by; sum[6] += ax * by; sum[7] += ay * bx;
+    sum[8] += (double)d;
+    return true;
+  }
+  static __device__ __forceinline__ bool step(const double* tot, int n, const Params&, double& c, double& s, double& tix,
+                                              double& tiy, double& mse) {
+    const double dn = (double)n;
+    const double Sax = tot[0], Say = tot[1], Sbx = tot[2], Sby = tot[3];
+    const double A = (tot[4] + tot[5]) - ((Sax * Sbx) + (Say * Sby)) / dn;
+    const double S = (tot[6] - tot[7]) - ((Sax * Sby) - (Say * Sbx)) / dn;
+    const double r = sqrt((A * A) + (S * S));
+    mse = tot[8] / dn;
+    if (r == 0.0) return false;
+    c = A / r; s = S / r;
+    const double amx = Sax / dn, amy = Say / dn, bmx = Sbx / dn, bmy = Sby / dn;
+    tix = bmx - ((c * amx) - (s * amy));
+    tiy = bmy - ((s * amx) + (c * amy));
+    return true;
+  }
+};
+
+// the point-to-line metric (tbnav_icp.h, POINT-TO-LINE METRIC; no counterpart in the reference): H00, H01, H02, H11, H12,
+// H22, g0, g1, g2, Sr and the 3x3 Gauss-Newton step (theta eliminated last)
+struct LineMetric {
+  static constexpr int kSums = 10;
+  static constexpr bool kNormals = true;
+  static constexpr int kMaxBeams = TBNAV_ICP_LINE_MAX_BEAMS;
+  using Params = IcpLine;
+  static __device__ __forceinline__ bool add(double (&sum)[kSums], float2 a, float2 b, float2 nf, float) {
+    if (!(nf.x == nf.x)) return false;  // the nearest target has no normal
+    const double ax = a.x, ay = a.y, nx = nf.x, ny = nf.y;
+    const double ex = ax - (double)b.x, ey = ay - (double)b.y;
+    const double r = (nx * ex) + (ny * ey);
+    const double jj = (ax * ny) - (ay * nx);
+    sum[0] += jj * jj; sum[1] += jj * nx; sum[2] += jj * ny;
+    sum[3] += nx * nx; sum[4] += nx * ny; sum[5] += ny * ny;
+    sum[6] += jj * r; sum[7] += nx * r; sum[8] += ny * r;
+    sum[9] += r * r;
+    return true;
+  }
+  static __device__ __forceinline__ bool step(const double* tot, int n, const Params& ln, double& c, double& s, double& tix,
+                                              double& tiy, double& mse) {
+    const double H00 = tot[0], H01 = tot[1], H02 = tot[2], H11 = tot[3], H12 = tot[4], H22 = tot[5];
+    const double g0 = tot[6], g1 = tot[7], g2 = tot[8];
+    mse = tot[9] / (double)n;
+    const double tr = H11 + H22;
+    const double det = (H11 * H22) - (H12 * H12);
+    if (!(det > ln.min_cond * (tr * tr))) return false;
+    const double v1 = ((H22 * H01) - (H12 * H02)) / det;
+    const double v2 = ((H11 * H02) - (H12 * H01)) / det;
+    const double dth = H00 - ((H01 * v1) + (H02 * v2));
+    if (!(dth > ln.min_cond * H00)) return false;
+    const double th = -(g0 - ((v1 * g1) + (v2 * g2))) / dth;
+    const double w1 = g1 + (H01 * th), w2 = g2 + (H02 * th);
+    tix = -((H22 * w1) - (H12 * w2)) / det;
+    tiy = -((H11 * w2) - (H12 * w1)) / det;
+    const double u = 0.5 * th;
+    const double q = 1.0 + (u * u);
+    c = (1.0 - (u * u)) / q; s = th / q;
+    return true;
+  }
+};
+
+template <class M, int P, int C = (P <= 2 ? 4 : P <= 4 ? 2 : 1)>
+__global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ scans, const float* __restrict__ stored,
+                                                        const float2* __restrict__ table, int n_beams,
+                                                        const IcpPair* __restrict__ pairs, IcpOut* __restrict__ out, IcpConst k,
+                                                        typename M::Params mp) {
+  constexpr int NS = M::kSums;
+  extern __shared__ float4 lds_dyn[];          // 16-byte aligned: the nearest-neighbour scan reads it as float4
+  const int n4 = (n_beams + 3) & ~3;           // the LDS cloud is padded to whole float4 pairs of points with NaN
   float2* tgt = reinterpret_cast<float2*>(lds_dyn);  // [n4]
-  float2* nrm = tgt + n4;                            // [n4]
-  __shared__ double red_a[kLineSums][kThreads / 2];  // s = 128 partials
-  __shared__ double red_b[kLineSums][kThreads / 4];  // s = 64 partials
+  float2* nrm = tgt + n4;                            // [n4], M::kNormals only (NaN: no normal)
+  __shared__ double red_a[NS][kThreads / 2];  // s = 128 partials
+  __shared__ double red_b[NS][kThreads / 4];  // s = 64 partials
   __shared__ int cnt_a[kThreads / 2], cnt_b[kThreads / 4];
-  __shared__ double tot[kLineSums];
+  __shared__ double tot[NS];
   __shared__ int tot_n;
 
   const int t = threadIdx.x;
@@ -396,69 +213,122 @@ __global__ __launch_bounds__(kThreads) void icp_align_line(const float* __restri
   load_target(tgt, ts, table, n_beams, n4, k, t);
   float2 src[P];
   bool valid[P];
-  load_sources<P>(src, valid, ss, table, n_beams, k, t);
-  __syncthreads();
-  for (int i = t; i < n4; i += kThreads) {
-    float2 v;
-    if (!(i < n_beams && target_normal(tgt, i, n_beams, ln, v))) v = make_float2(__builtin_nanf(""), __builtin_nanf(""));
-    nrm[i] = v;
+#pragma unroll
+  for (int j = 0; j < P; ++j) {
+    const int i = t + j * kThreads;
+    valid[j] = i < n_beams && cloud_point(ss[i], table[i], k, src[j]);
+    if (!valid[j]) src[j] = make_float2(0.0f, 0.0f);
   }
   __syncthreads();
+  if constexpr (M::kNormals) {
+    for (int i = t; i < n4; i += kThreads) {
+      float2 v;
+      if (!(i < n_beams && target_normal(tgt, i, n_beams, mp, v))) v = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+      nrm[i] = v;
+    }
+    __syncthreads();
+  }
 
   double R00 = pr.c, R01 = -pr.s, R10 = pr.s, R11 = pr.c, tx = pr.x, ty = pr.y;
   double prev = DBL_MAX, mse = 0.0;
   int iter = 0, n = 0, crit = TBNAV_ICP_NOT_RUN;
   while (true) {
     ++iter;
-    double sum[kLineSums];
+    double sum[NS];
 #pragma unroll
-    for (int q = 0; q < kLineSums; ++q) sum[q] = 0.0;
+    for (int q = 0; q < NS; ++q) sum[q] = 0.0;
     int cnt = 0;
-    {
-      float2 a[P];
-      float best[P][C];
-      int bi[P][C];
-      transform_sources<P>(src, a, R00, R01, R10, R11, tx, ty);
-      nearest_targets<P, C>(tgt, n4, a, best, bi);
+    float2 a[P];
+    float best[P][C];
+    int bi[P][C];
 #pragma unroll
-      for (int j = 0; j < P; ++j) {
-        if (valid[j] && (double)best[j][0] <= k.max_corr2) {
-          const float2 b = tgt[bi[j][0]], nf = nrm[bi[j][0]];
-          if (nf.x == nf.x) {  // the nearest target has a normal
-            const double ax = a[j].x, ay = a[j].y, nx = nf.x, ny = nf.y;
-            const double ex = ax - (double)b.x, ey = ay - (double)b.y;
-            const double r = (nx * ex) + (ny * ey);
-            const double jj = (ax * ny) - (ay * nx);
-            ++cnt;
-            sum[0] += jj * jj; sum[1] += jj * nx; sum[2] += jj * ny;
-            sum[3] += nx * nx; sum[4] += nx * ny; sum[5] += ny * ny;
-            sum[6] += jj * r; sum[7] += nx * r; sum[8] += ny * r;
-            sum[9] += r * r;
-          }
+    for (int j = 0; j < P; ++j) {
+      a[j].x = (float)(((R00 * (double)src[j].x) + (R01 * (double)src[j].y)) + tx);
+      a[j].y = (float)(((R10 * (double)src[j].x) + (R11 * (double)src[j].y)) + ty);
+#pragma unroll
+      for (int c = 0; c < C; ++c) { best[j][c] = __builtin_huge_valf(); bi[j][c] = 0x7fffffff; }
+    }
+    // nearest neighbour: C independent chains per point (chain c: targets m = c mod C, in increasing m, strict '<'), four
+    // targets per two 16-byte LDS reads (a broadcast: every lane reads the same address).  The loop stays in the kernel's
+    // body, not in a helper, and compares by selects, not branches: so its body is one basic block in every instantiation.
+    for (int m = 0; m < n4; m += 4) {
+      const float4 t01 = *reinterpret_cast<const float4*>(&tgt[m]);
+      const float4 t23 = *reinterpret_cast<const float4*>(&tgt[m + 2]);
+      const float bx[4] = {t01.x, t01.z, t23.x, t23.z}, by[4] = {t01.y, t01.w, t23.y, t23.w};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const float dx = a[j].x - bx[r], dy = a[j].y - by[r];
+          const float d = dx * dx + dy * dy;
+          const bool lt = d < best[j][r % C];
+          best[j][r % C] = lt ? d : best[j][r % C];
+          bi[j][r % C] = lt ? m + r : bi[j][r % C];
         }
       }
     }
-    tree_sums<kLineSums>(sum, cnt, red_a, red_b, cnt_a, cnt_b, tot, &tot_n, t);
-    // every thread: the 3x3 Gauss-Newton step (theta eliminated last) and the criteria from the totals, wave-uniform
+    // the chains' minima in (distance, index) order: the lowest index among equal distances, as one scan in beam order
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+#pragma unroll
+      for (int c = 1; c < C; ++c) {
+        if (best[j][c] < best[j][0] || (best[j][c] == best[j][0] && bi[j][c] < bi[j][0])) { best[j][0] = best[j][c]; bi[j][0] = bi[j][c]; }
+      }
+    }
+    // the gate, and what the metric makes of a pair inside it
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      if (valid[j] && (double)best[j][0] <= k.max_corr2) {
+        const float2 b = tgt[bi[j][0]];
+        float2 nf = make_float2(0.0f, 0.0f);
+        if constexpr (M::kNormals) nf = nrm[bi[j][0]];
+        if (M::add(sum, a[j], b, nf, best[j][0])) ++cnt;
+      }
+    }
+    // tree: t += t + s for s = 128, 64 (LDS), 32 .. 1 (wave 0, shuffles)
+    if (t >= kThreads / 2) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) red_a[q][t - kThreads / 2] = sum[q];
+      cnt_a[t - kThreads / 2] = cnt;
+    }
+    __syncthreads();
+    if (t < kThreads / 2) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_a[q][t];
+      cnt += cnt_a[t];
+      if (t >= kThreads / 4) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) red_b[q][t - kThreads / 4] = sum[q];
+        cnt_b[t - kThreads / 4] = cnt;
+      }
+    }
+    __syncthreads();
+    if (t < kWave) {
+#pragma unroll
+      for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_b[q][t];
+      cnt += cnt_b[t];
+#pragma unroll
+      for (int s = kWave / 2; s > 0; s >>= 1) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) sum[q] = sum[q] + __shfl_down(sum[q], s, kWave);
+        cnt += __shfl_down(cnt, s, kWave);
+      }
+      if (t == 0) {
+#pragma unroll
+        for (int q = 0; q < NS; ++q) tot[q] = sum[q];
+        tot_n = cnt;
+      }
+    }
+    __syncthreads();
+    // every thread: R_inc and the criteria from the totals (wave-uniform from here to the loop's end).  The next writes of
+    // red_a / red_b / tot come after the next iteration's first / second barrier, which every thread reaches only after it
+    // has read what it needs here.
     n = tot_n;
     if (n < 3) { crit = TBNAV_ICP_NO_CORRESPONDENCES; mse = 0.0; break; }
-    const double H00 = tot[0], H01 = tot[1], H02 = tot[2], H11 = tot[3], H12 = tot[4], H22 = tot[5];
-    const double g0 = tot[6], g1 = tot[7], g2 = tot[8];
-    mse = tot[9] / (double)n;
-    const double tr = H11 + H22;
-    const double det = (H11 * H22) - (H12 * H12);
-    if (!(det > ln.min_cond * (tr * tr))) { crit = TBNAV_ICP_DEGENERATE; break; }
-    const double v1 = ((H22 * H01) - (H12 * H02)) / det;
-    const double v2 = ((H11 * H02) - (H12 * H01)) / det;
-    const double dth = H00 - ((H01 * v1) + (H02 * v2));
-    if (!(dth > ln.min_cond * H00)) { crit = TBNAV_ICP_DEGENERATE; break; }
-    const double th = -(g0 - ((v1 * g1) + (v2 * g2))) / dth;
-    const double w1 = g1 + (H01 * th), w2 = g2 + (H02 * th);
-    const double tix = -((H22 * w1) - (H12 * w2)) / det;
-    const double tiy = -((H11 * w2) - (H12 * w1)) / det;
-    const double u = 0.5 * th;
-    const double q = 1.0 + (u * u);
-    const double c = (1.0 - (u * u)) / q, s = th / q;
+    // step() assigns all four or returns false.  The zeros are never read, but left undefined on the degenerate path they
+    // cost most instantiations registers (8-10 VGPRs at P = 2, which is a workgroup per CU in a batch of the line metric)
+    double c = 0.0, s = 0.0, tix = 0.0, tiy = 0.0;
+    if (!M::step(tot, n, mp, c, s, tix, tiy, mse)) { crit = TBNAV_ICP_DEGENERATE; break; }
     const double n00 = (c * R00) - (s * R10), n01 = (c * R01) - (s * R11);
     const double n10 = (s * R00) + (c * R10), n11 = (s * R01) + (c * R11);
     const double ntx = ((c * tx) - (s * ty)) + tix, nty = ((s * tx) + (c * ty)) + tiy;
@@ -596,56 +466,63 @@ IcpPair make_pair(int tgt, int src, const double T[3]) {
   return p;
 }
 
-template <int P>
-int launch_p(tbnav_icp* h, int n_pairs, int n_beams) {
-  const size_t lds = sizeof(float2) * (size_t)((n_beams + 3) & ~3);
-  hipLaunchKernelGGL(icp_align<P>, dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
-                     h->d_pairs, h->d_out, h->k);
+// one launch of icp_align<M, P> over h->d_pairs.  Dynamic LDS: the cloud, 8 bytes per beam rounded up to 4 beams, and as much
+// again for the normals of a metric that keeps them
+template <class M, int P>
+int launch(tbnav_icp* h, int n_pairs, int n_beams) {
+  const size_t lds = (M::kNormals ? 2 : 1) * sizeof(float2) * (size_t)((n_beams + 3) & ~3);
+  typename M::Params mp{};
+  if constexpr (M::kNormals) mp = h->line;
+  hipLaunchKernelGGL((icp_align<M, P>), dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
+                     h->d_pairs, h->d_out, h->k, mp);
   TBNAV_HIP(hipGetLastError());
   return TBNAV_OK;
 }
 
-// the line metric: cloud and normals in LDS (16 bytes per beam), n_beams <= TBNAV_ICP_LINE_MAX_BEAMS (beams_ok)
-template <int P>
-int launch_line(tbnav_icp* h, int n_pairs, int n_beams) {
-  const size_t lds = 2 * sizeof(float2) * (size_t)((n_beams + 3) & ~3);
-  hipLaunchKernelGGL(icp_align_line<P>, dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
-                     h->d_pairs, h->d_out, h->k, h->line);
-  TBNAV_HIP(hipGetLastError());
-  return TBNAV_OK;
+// source beams per thread -> P; the ladder ends at the P that holds the metric's kMaxBeams (n_beams <= kMaxBeams: beams_ok)
+template <class M>
+int dispatch(tbnav_icp* h, int n_pairs, int n_beams) {
+  static_assert(M::kMaxBeams <= 16 * kThreads, "no instantiation holds kMaxBeams");
+  const int per = (n_beams + kThreads - 1) / kThreads;
+  if (per <= 1) return launch<M, 1>(h, n_pairs, n_beams);
+  if (per <= 2) return launch<M, 2>(h, n_pairs, n_beams);
+  if (per <= 3) return launch<M, 3>(h, n_pairs, n_beams);
+  if (per <= 4) return launch<M, 4>(h, n_pairs, n_beams);
+  if (per <= 6) return launch<M, 6>(h, n_pairs, n_beams);
+  if constexpr (M::kMaxBeams <= 8 * kThreads) {
+    return launch<M, 8>(h, n_pairs, n_beams);
+  } else {
+    if (per <= 8) return launch<M, 8>(h, n_pairs, n_beams);
+    if (per <= 12) return launch<M, 12>(h, n_pairs, n_beams);
+    return launch<M, 16>(h, n_pairs, n_beams);
+  }
 }
 
 // the beam counts the handle's metric can align
 bool beams_ok(const tbnav_icp* h, int n_beams) {
-  return n_beams > 0 && n_beams <= (h->metric == TBNAV_ICP_METRIC_LINE ? TBNAV_ICP_LINE_MAX_BEAMS : TBNAV_ICP_MAX_BEAMS);
+  return n_beams > 0 && n_beams <= (h->metric == TBNAV_ICP_METRIC_LINE ? LineMetric::kMaxBeams : PointMetric::kMaxBeams);
 }
 
 // aligns h->h_pairs[0, n_pairs) (scans already in d_scans / d_stored) -> h->h_out, with the handle's metric
 int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
   if (int rc = ensure_pairs(h, n_pairs)) return rc;
   TBNAV_HIP(hipMemcpyAsync(h->d_pairs, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
-  const int per = (n_beams + kThreads - 1) / kThreads;  // source beams per thread
-  int rc;
-  if (h->metric == TBNAV_ICP_METRIC_LINE) {
-    if (per <= 1) rc = launch_line<1>(h, n_pairs, n_beams);
-    else if (per <= 2) rc = launch_line<2>(h, n_pairs, n_beams);
-    else if (per <= 3) rc = launch_line<3>(h, n_pairs, n_beams);
-    else if (per <= 4) rc = launch_line<4>(h, n_pairs, n_beams);
-    else if (per <= 6) rc = launch_line<6>(h, n_pairs, n_beams);
-    else rc = launch_line<8>(h, n_pairs, n_beams);
-  } else if (per <= 1) rc = launch_p<1>(h, n_pairs, n_beams);
-  else if (per <= 2) rc = launch_p<2>(h, n_pairs, n_beams);
-  else if (per <= 3) rc = launch_p<3>(h, n_pairs, n_beams);
-  else if (per <= 4) rc = launch_p<4>(h, n_pairs, n_beams);
-  else if (per <= 6) rc = launch_p<6>(h, n_pairs, n_beams);
-  else if (per <= 8) rc = launch_p<8>(h, n_pairs, n_beams);
-  else if (per <= 12) rc = launch_p<12>(h, n_pairs, n_beams);
-  else rc = launch_p<16>(h, n_pairs, n_beams);
-  if (rc) return rc;
+  const bool line = h->metric == TBNAV_ICP_METRIC_LINE;
+  if (int rc = line ? dispatch<LineMetric>(h, n_pairs, n_beams) : dispatch<PointMetric>(h, n_pairs, n_beams)) return rc;
   h->h_out.resize((size_t)n_pairs);
   TBNAV_HIP(hipMemcpyAsync(h->h_out.data(), h->d_out, sizeof(IcpOut) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
   TBNAV_HIP(hipStreamSynchronize(h->stream));
   ++h->last_launches;
+  return TBNAV_OK;
+}
+
+// the test hooks' scratch in d_scans, 4 floats per beam: the uploaded scan at its start, then the flags [n_beams] int and the
+// values [n_beams] float2 that the hook's kernel writes
+int hook_scratch(tbnav_icp* h, const float* scan, int n_beams, int*& flags, float2*& xy) {
+  if (int rc = ensure_scans(h, 4 * (size_t)n_beams)) return rc;
+  flags = reinterpret_cast<int*>(h->d_scans + n_beams);
+  xy = reinterpret_cast<float2*>(h->d_scans + 2 * (size_t)n_beams);  // 8-byte aligned
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   return TBNAV_OK;
 }
 
@@ -772,7 +649,7 @@ int tbnav_icp_last_batch_launches(const tbnav_icp* h) { return h ? h->last_launc
 int tbnav_icp_set_metric(tbnav_icp* h, int32_t metric, int32_t normal_window, double normal_max_gap) {
   if (!h || (metric != TBNAV_ICP_METRIC_POINT && metric != TBNAV_ICP_METRIC_LINE) || normal_window > TBNAV_ICP_LINE_MAX_WINDOW)
     return TBNAV_ERR_INVALID_ARG;
-  // a stored scan the line kernel has no LDS for cannot be kept
+  // a stored scan the line metric has no LDS for cannot be kept
   if (metric == TBNAV_ICP_METRIC_LINE && h->have_stored && h->stored_beams > TBNAV_ICP_LINE_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
   h->metric = metric;
   h->line.window = normal_window > 0 ? normal_window : TBNAV_ICP_LINE_NORMAL_WINDOW;
@@ -794,13 +671,10 @@ int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* n
   DevGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
-  // scratch as in tbnav_icp_cloud: the scan, the flags [n_beams] int, the normals [n_beams] float2
-  if (int rc = ensure_scans(h, 4 * (size_t)n_beams)) return rc;
-  float* d_scan = h->d_scans;
-  int* d_has = reinterpret_cast<int*>(h->d_scans + n_beams);
-  float2* d_nxy = reinterpret_cast<float2*>(h->d_scans + 2 * (size_t)n_beams);  // 8-byte aligned
-  TBNAV_HIP(hipMemcpyAsync(d_scan, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(icp_normals, dim3(1), dim3(kThreads), sizeof(float2) * (size_t)((n_beams + 3) & ~3), h->stream, d_scan,
+  int* d_has;
+  float2* d_nxy;
+  if (int rc = hook_scratch(h, scan, n_beams, d_has, d_nxy)) return rc;
+  hipLaunchKernelGGL(icp_normals, dim3(1), dim3(kThreads), sizeof(float2) * (size_t)((n_beams + 3) & ~3), h->stream, h->d_scans,
                      h->d_table, (int)n_beams, d_nxy, d_has, h->k, h->line);
   TBNAV_HIP(hipGetLastError());
   TBNAV_HIP(hipMemcpyAsync(nxy, d_nxy, sizeof(float2) * (size_t)n_beams, hipMemcpyDeviceToHost, h->stream));
@@ -814,13 +688,10 @@ int tbnav_icp_cloud(tbnav_icp* h, const float* scan, int32_t n_beams, float* xy,
   DevGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
-  // scratch: the scan, then the points [n_beams] float2 and the flags [n_beams] int (4 floats per beam in all)
-  if (int rc = ensure_scans(h, 4 * (size_t)n_beams)) return rc;
-  float* d_scan = h->d_scans;
-  float2* d_xy = reinterpret_cast<float2*>(h->d_scans + 2 * (size_t)n_beams);  // 8-byte aligned
-  int* d_valid = reinterpret_cast<int*>(h->d_scans + n_beams);
-  TBNAV_HIP(hipMemcpyAsync(d_scan, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(icp_cloud, dim3((n_beams + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, d_scan, h->d_table,
+  int* d_valid;
+  float2* d_xy;
+  if (int rc = hook_scratch(h, scan, n_beams, d_valid, d_xy)) return rc;
+  hipLaunchKernelGGL(icp_cloud, dim3((n_beams + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->d_scans, h->d_table,
                      (int)n_beams, d_xy, d_valid, h->k);
   TBNAV_HIP(hipGetLastError());
   std::vector<float2> pts((size_t)n_beams);

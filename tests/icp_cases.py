@@ -20,8 +20,8 @@ import rbpf_cases as rc
 Case = namedtuple("Case", "name kw tgt src T")
 
 B = 256                                   # kThreads
-POINT_P = (1, 2, 3, 4, 6, 8, 12, 16)      # icp_align<P>: source beams per thread (run_pairs)
-LINE_P = (1, 2, 3, 4, 6, 8)               # icp_align_line<P>
+POINT_P = (1, 2, 3, 4, 6, 8, 12, 16)      # icp_align<PointMetric, P>: source beams per thread (run_pairs)
+LINE_P = (1, 2, 3, 4, 6, 8)               # icp_align<LineMetric, P>
 MAX_BEAMS = 4096                          # TBNAV_ICP_MAX_BEAMS
 MAX_ITER = 1000                           # TBNAV_ICP_MAX_ITER
 F32 = np.float32
@@ -42,7 +42,7 @@ def beams_per_thread(n_beams: int, metric="point") -> int:
 
 
 def chains(P: int) -> int:
-    """C of icp_align<P, C>: independent chains of the nearest-neighbour scan (target m is in chain m mod C)."""
+    """C of icp_align<Metric, P, C>: independent chains of the nearest-neighbour scan (target m is in chain m mod C)."""
     return 4 if P <= 2 else 2 if P <= 4 else 1
 
 

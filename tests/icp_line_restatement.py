@@ -1,7 +1,7 @@
 """numpy restatement of the device ICP's POINT-TO-LINE METRIC (include/tbnav_icp.h, that section of the contract), beside
 icp_restatement.py, which restates the point metric.  This metric has no counterpart in the reference (which only ever runs
 PCL's point-to-point ICP): the header is the specification, and this file spells it with every rounding so that the GPU
-tests can hold the kernel (csrc/icp.hip, icp_align_line) to it bit for bit.
+tests can hold the kernel (csrc/icp.hip, icp_align<LineMetric>) to it bit for bit.
 
 Shared with the point metric and imported from icp_restatement: the cloud, the initial guess, the transformed source
 points, the nearest-neighbour search, the distance gate, the summation order, the composition, the stopping rules.

@@ -27,7 +27,7 @@ def test_bounded_fuzz_sweep_of_the_icp_against_the_restatements(gpu_pkg):
     assert len(summary) == 1 and summary[0].startswith(f"icp: {N_CASES} cases done, failures so far 0; "), lines
     tot = ast.literal_eval(summary[0].split("; ", 1)[1])
     assert tot["matches"] == N_CASES and tot["batches"] == N_CASES // 4, tot
-    assert set(tot["point_P"]) == {1, 2, 3, 4, 6, 8, 12, 16}, tot      # every instantiation of icp_align
-    assert set(tot["line_P"]) == {1, 2, 3, 4, 6, 8}, tot               # and of icp_align_line
+    assert set(tot["point_P"]) == {1, 2, 3, 4, 6, 8, 12, 16}, tot      # every instantiation of icp_align<PointMetric>
+    assert set(tot["line_P"]) == {1, 2, 3, 4, 6, 8}, tot               # and of icp_align<LineMetric>
     assert set(tot["criterion"]) == {0, 1, 2, 3, 4, 5, 6}, tot         # every way to stop (0: a batch's first scan)
     assert tot["with_ties"] >= 10, tot

@@ -1,4 +1,4 @@
-"""The device ICP's point-to-line metric (include/tbnav_icp.h POINT-TO-LINE METRIC, csrc/icp.hip icp_align_line) against the
+"""The device ICP's point-to-line metric (include/tbnav_icp.h POINT-TO-LINE METRIC, csrc/icp.hip icp_align<LineMetric>) against the
 numpy restatement of that contract (tests/icp_line_restatement.py), bit for bit, through every layer: the C-ABI (set_metric /
 get_metric / normals / match / step / step_batch), the Python mirror (rtn_amd.icp.ScanAlignment(metric="line")) and the C++
 ScanAlignment::useDeviceICP(device, ICPMetric::PointToLine) inside bmapping::ParticleFilter.  The metric has no counterpart in
@@ -193,7 +193,7 @@ def test_step_batch_is_n_steps_and_the_restatement(gpu_pkg):
     failed = [s for s in range(n) if not ok[s]]
     assert failed == bad, failed
     assert launches > 1, "a failure must realign the pairs that depended on it"
-    # the point metric on the same run gives other numbers: the batch did run the line kernel, in every launch
+    # the point metric on the same run gives other numbers: the batch did run the line metric, in every launch
     c, _ = _aligner(gpu_pkg, metric="point")
     okp, Tp, infop = c.wrapperBatch(T_init, scans)
     assert np.array_equal(okp, ok) and not np.array_equal(Tp, T)

@@ -1,6 +1,6 @@
 """The device ICP (include/tbnav_icp.h, csrc/icp.hip) on the cases of tests/icp_cases.py, against the numpy restatements
-(tests/icp_restatement.py, tests/icp_line_restatement.py) bit for bit: every instantiation of icp_align<P> and icp_align_line<P>
-at its edges, exact distance ties across the chains of the nearest-neighbour scan, every stop rule, sparse scans, 2 and 3
+(tests/icp_restatement.py, tests/icp_line_restatement.py) bit for bit: every instantiation of icp_align<Metric, P> for both
+metrics at its edges, exact distance ties across the chains of the nearest-neighbour scan, every stop rule, sparse scans, 2 and 3
 correspondences, the distance gate on its edge, guesses that are not numbers, lasers that take createPointCloud's other
 branches, one handle at changing beam counts, and tbnav_icp_step_batch over mixed runs at 767 and 4096 beams.  No tolerance
 anywhere: ok, T as bit patterns, iterations, criterion, correspondences, mse.  test_icp_cases.py shows on the CPU that the cases
@@ -163,8 +163,8 @@ def test_one_handle_at_changing_beam_counts(gpu_pkg):
 @pytest.mark.parametrize("n,n_scans", [(767, 24), (4096, 64)])
 def test_step_batch_over_a_mixed_run(gpu_pkg, n, n_scans):
     """tbnav_icp_step_batch over a run that holds the tie pair, sparse, degenerate and all-invalid scans between ordinary ones:
-    equal to one tbnav_icp_step per scan and to the restatement's wrapper; at 767 beams icp_align<3> (two chains), at 4096
-    beams icp_align<16>, whose first launch runs 63 workgroups side by side."""
+    equal to one tbnav_icp_step per scan and to the restatement's wrapper; at 767 beams icp_align<PointMetric, 3> (two chains), at 4096
+    beams icp_align<PointMetric, 16>, whose first launch runs 63 workgroups side by side."""
     kw, scans, T_init = ic.batch_run(n, n_scans)
     assert ic.beams_per_thread(n) == {767: 3, 4096: 16}[n]
     a, p = _aligner(gpu_pkg, kw)
@@ -191,7 +191,7 @@ def test_step_batch_over_a_mixed_run(gpu_pkg, n, n_scans):
 
 
 def test_line_step_batch_over_a_mixed_run(gpu_pkg):
-    """The same run at 767 beams through icp_align_line<3>."""
+    """The same run at 767 beams through icp_align<LineMetric, 3>."""
     n, n_scans = 767, 24
     kw, scans, T_init = ic.batch_run(n, n_scans)
     a, p = _aligner(gpu_pkg, kw, "line")
