@@ -1,4 +1,5 @@
-/* tbnav_icp.h — ICP between two laser scans on the GPU (point-to-point, and point-to-line as an option): the scan matcher that the reference's
+/* tbnav_icp.h — ICP between two laser scans on the GPU (point-to-point, and point-to-line as an option; a correlative search
+ * for the initial guess as another): the scan matcher that the reference's
  * bmapping::ScanAlignment::pclICPWrapper (bmapping/src/bmapping/cloud_alignment.cpp:37-223) runs once per scan through
  * pcl::IterativeClosestPoint<PointXYZ, PointXYZ>.  PCL is a third-party library that is not part of this project, so
  * what is implemented here is a RESTATEMENT of PCL 1.8's algorithm with the reference's settings (max_iter 100,
@@ -87,6 +88,64 @@
  *  Divergences to know: the index window does not wrap from the last beam to beam 0 (the first and last w beams of a full
  *  turn get one-sided normals); normals are taken on the target cloud only; no robust weighting and no outlier rejection
  *  beyond the distance gate.
+ *
+ * CORRELATIVE SEARCH (an addition, off by default, tbnav_icp_set_search; csrc/icp_search.hip).  It has NO COUNTERPART IN THE
+ * REFERENCE: this section is its whole specification, restated in tests/icp_search_restatement.py and reproduced by the kernels
+ * EXACTLY (scores are integers: there is no tolerance anywhere).  The ICP above is a local method: from a guess that is wrong
+ * by more than about half the correspondence gate it converges, ok = 1, onto a wrong answer (ROOM_BENCH of tests/rbpf_cases.py,
+ * guess off by (0, 0.65, 0.65) m: ok after 9 iterations, 1.07 m off).  The search scores EVERY pose of a (theta, x, y) window
+ * round the guess against a likelihood table of the target scan (Olson 2009; Cartographer's real-time correlative matcher)
+ * and hands the best one to the ICP; it is exhaustive inside its window, so it has no basin.  All arithmetic is integer, or
+ * fp64 with every product and sum as parenthesised and no contraction.
+ *  S1. Parameters (tbnav_icp_search_params; defaults in brackets): resolution [0.05 m] the table's cell; half_extent E [4.0 m]
+ *      half the table's side; sigma [0.05 m] and stamp_cells k [3, 1..8] the Gaussian stamp's width and half width in cells (k
+ *      is an explicit integer on purpose: ceil(3 * 0.05 / 0.05) evaluates to 4 in doubles); lin_cells wl [6, 0..16] the window
+ *      +-wl cells in x and y; ang_steps wa [20, 0..90] the window +-wa steps of ang_step [pi/180] radians; slack_q10
+ *      [0, 0..1023] the selection slack in 1/1024; min_quality [0.5] the acceptance threshold.  n = 2 * ceil(E / resolution)
+ *      cells per side, inv = 1.0 / resolution.  Required: resolution, E, sigma positive and finite, ang_step and min_quality
+ *      finite, n >= 2 and n + 2*wl <= TBNAV_ICP_SEARCH_MAX_SIDE = 208 (the padded byte table then fits in LDS beside the source
+ *      cells).  Anything else is TBNAV_ERR_INVALID_ARG and changes nothing.
+ *  S2. Clouds: both are exactly item 1 above (the same code and beam table as the ICP's).
+ *  S3. Stamp, on the host with glibc exp, (2k+1)^2 values of uint8, ox, oy in -k..k:
+ *      stamp[oy][ox] = floor(255.0 * exp(-(d2 / (2.0 * (sigma*sigma)))) + 0.5), d2 = (double)(ox*ox + oy*oy) * (resolution*resolution).
+ *  S4. Table, uint8 [n][n] indexed [iy][ix].  The cell of a target point p: ix = floor(((double)p.x + E) * inv), iy likewise.
+ *      table[c] = the MAXIMUM of stamp[c - cell(p)] over the target points whose stamp covers c, 0 where none does (a maximum
+ *      has no order).  A point whose cell is outside the table stamps the part that falls inside.
+ *  S5. Candidates: na = 2*wa + 1 angles, nl = 2*wl + 1 offsets per axis.  theta_a = theta0 + (double)(ia - wa) * ang_step;
+ *      (cos theta_a, sin theta_a) = (c, s) in double on the HOST with glibc, uploaded: no transcendental on the device.  A valid
+ *      source point (sx, sy) (the doubles of its floats) under angle ia: ax = (((c * sx) - (s * sy)) + x0),
+ *      ay = (((s * sx) + (c * sy)) + y0), x0 and y0 the DOUBLES of T_init; its base cell bx = floor((ax + E) * inv), by likewise.
+ *      score[ia][iy][ix] = the sum over the valid source points of table[by + (iy - wl)][bx + (ix - wl)], a cell outside the
+ *      table adding 0 (uint32).
+ *  S6. Selection: best = the maximum score; thr = best - ((uint64)best * slack_q10 >> 10); among the candidates with
+ *      score >= thr the one with the smallest D = (ia-wa)^2 + (iy-wl)^2 + (ix-wl)^2, then the lowest linear index
+ *      (ia*nl + iy)*nl + ix.  slack_q10 = 0: the arg-max, ties going to the candidate nearest the guess.  candidates = the number
+ *      of candidates with score >= thr.
+ *  S7. Result: T = (theta0 + (double)(ia-wa)*ang_step, x0 + (double)(ix-wl)*resolution, y0 + (double)(iy-wl)*resolution), theta
+ *      not wrapped; points = the valid source points; quality = (double)score / (255.0 * (double)points), 0 when points == 0;
+ *      at_edge = 1 when the chosen index sits on the border of an axis whose half width is not zero;
+ *      accepted = quality >= min_quality, and points > 0, and at least one target point.
+ *  S8. In front of the ICP.  With the search on, tbnav_icp_match / _step / _step_batch (its realignment launches included)
+ *      search every pair first, then run the ICP, with either metric, from T when accepted (T goes through item 2 like any
+ *      guess) and from T_init UNCHANGED otherwise: a search that is not accepted gives the search-off result bit for bit.  The
+ *      first tbnav_icp_step, which stores the scan, does not search.  tbnav_icp_step_batch stays n successive steps, bit for
+ *      bit.  The search's result comes back to the host before the alignment is launched (the guess of item 2 is formed on the
+ *      host, with glibc): one more stream synchronisation per launch.
+ *  min_quality = 0.5 is a design constant, not a measurement.  Where it sits (a CPU prototype of this contract, the two rooms
+ *  of tests/rbpf_cases.py, 1 cm range noise): a true match 0.76-0.90; the truth outside the window 0.14; the wrong room 0.42; a
+ *  random cloud 0.09.  On the pairs above the search lands within one cell and 1 degree of the truth, and the ICP started
+ *  from it ends 1.7 mm / 6.6 mrad off after 6 iterations.
+ *  KNOWN LIMITS.  The search cannot tell an unobservable direction from an observable one: two noise-free scans of a corridor
+ *  taken 10 cm apart along it are identical, the search overlays them and so moves the guess BACK by 10 cm.  slack_q10 = 64
+ *  kept the guess on one noisy corridor sample and 32 did not; one sample is not a rule.  A caller who relies on the line
+ *  metric's corridor behaviour leaves the search off there.  Translation accuracy is one cell: the ICP behind the search is
+ *  what refines it.
+ *  KERNELS (csrc/icp_search.hip): icp_search_table, one workgroup per pair, stamps the target into a byte table in LDS (a
+ *  compare-and-swap maximum on the byte's dword) and writes it padded with wl zero cells on every side; icp_search_score, one
+ *  workgroup of 256 threads per (pair, angle), keeps the padded table and its angle's base cells in LDS, each thread owning
+ *  translations and walking the points (base cells outside the table, whose window is only partly inside, take a
+ *  bounds-tested path), and reduces one 64-bit key (score high, inverted rank low) per workgroup; icp_search_select reduces
+ *  the na keys.  slack_q10 > 0 scores a second time against thr.  n_beams <= TBNAV_ICP_MAX_BEAMS with either metric.
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
@@ -198,6 +257,56 @@ int tbnav_icp_get_metric(const tbnav_icp* h, int32_t* metric, int32_t* normal_wi
  * nxy [n_beams][2], has [n_beams]; a beam without a normal (an invalid beam included) holds (0, 0) and 0.
  * n_beams <= TBNAV_ICP_LINE_MAX_BEAMS. */
 int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* nxy, int32_t* has);
+
+/* ---- CORRELATIVE SEARCH (an addition, no counterpart in the reference; the section of that name above) ---- */
+#define TBNAV_ICP_SEARCH_MAX_SIDE 208   /* n + 2*lin_cells */
+#define TBNAV_ICP_SEARCH_MAX_STAMP 8
+#define TBNAV_ICP_SEARCH_MAX_LIN 16
+#define TBNAV_ICP_SEARCH_MAX_ANG 90
+
+typedef struct tbnav_icp_search_params {
+  double resolution;    /* 0.05 m */
+  double half_extent;   /* 4.0 m */
+  double sigma;         /* 0.05 m */
+  double ang_step;      /* pi / 180 */
+  double min_quality;   /* 0.5 */
+  int32_t stamp_cells;  /* 3 */
+  int32_t lin_cells;    /* 6 */
+  int32_t ang_steps;    /* 20 */
+  int32_t slack_q10;    /* 0 */
+} tbnav_icp_search_params;
+
+typedef struct tbnav_icp_search_info {
+  double T[3];          /* S7 */
+  double quality;
+  uint32_t score;
+  int32_t points;       /* valid source points */
+  int32_t candidates;
+  int32_t ia, iy, ix;   /* the chosen candidate */
+  int32_t at_edge;
+  int32_t accepted;
+  int32_t searched;     /* 0: no search ran (the search is off, or tbnav_icp_step stored its first scan); all else is 0 then */
+  int32_t reserved;
+} tbnav_icp_search_info;
+
+void tbnav_icp_default_search_params(tbnav_icp_search_params* p);
+/* turns the search on for every later tbnav_icp_match / _step / _step_batch of this handle (S8); params == NULL turns it off
+ * (and the handle's parameters go back to the defaults).  A new handle has it off.  Parameters outside S1's limits are
+ * TBNAV_ERR_INVALID_ARG and change nothing.  The stored scan is kept. */
+int tbnav_icp_set_search(tbnav_icp* h, const tbnav_icp_search_params* params);
+/* either output may be null; params are the defaults while the search is off */
+int tbnav_icp_get_search(const tbnav_icp* h, int32_t* on, tbnav_icp_search_params* params);
+/* the search record of the last tbnav_icp_match or tbnav_icp_step, for a batch the last scan's (searched = 0 when none ran) */
+int tbnav_icp_last_search(const tbnav_icp* h, tbnav_icp_search_info* info);
+/* the search alone, stateless, with the handle's search parameters (the defaults when the search is off):
+ * T_out = info->T.  n_beams <= TBNAV_ICP_MAX_BEAMS.  info is required. */
+int tbnav_icp_search(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3],
+                     double T_out[3], tbnav_icp_search_info* info);
+/* test hook: the same, and the whole score volume (S5): scores [na][nl][nl] */
+int tbnav_icp_search_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
+                            const double T_init[3], double T_out[3], tbnav_icp_search_info* info, uint32_t* scores);
+/* test hook: the table (S4) of one scan taken as a target: table [n][n] */
+int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uint8_t* table);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,23 @@ ICP_METRIC_POINT, ICP_METRIC_LINE = 0, 1
 ICP_LINE_MAX_BEAMS, ICP_LINE_MAX_WINDOW = 2048, 16
 
 
+class IcpSearchParams(C.Structure):
+    """tbnav_icp_search_params (include/tbnav_icp.h, CORRELATIVE SEARCH)."""
+    _fields_ = [("resolution", C.c_double), ("half_extent", C.c_double), ("sigma", C.c_double), ("ang_step", C.c_double),
+                ("min_quality", C.c_double), ("stamp_cells", C.c_int32), ("lin_cells", C.c_int32), ("ang_steps", C.c_int32),
+                ("slack_q10", C.c_int32)]
+
+
+class IcpSearchInfo(C.Structure):
+    """tbnav_icp_search_info."""
+    _fields_ = [("T", C.c_double * 3), ("quality", C.c_double), ("score", C.c_uint32), ("points", C.c_int32),
+                ("candidates", C.c_int32), ("ia", C.c_int32), ("iy", C.c_int32), ("ix", C.c_int32), ("at_edge", C.c_int32),
+                ("accepted", C.c_int32), ("searched", C.c_int32), ("reserved", C.c_int32)]
+
+
+ICP_SEARCH_MAX_SIDE, ICP_SEARCH_MAX_STAMP, ICP_SEARCH_MAX_LIN, ICP_SEARCH_MAX_ANG = 208, 8, 16, 90
+
+
 _lib = None
 
 
@@ -280,6 +297,13 @@ def lib() -> C.CDLL:
         "tbnav_icp_set_metric": (C.c_int, [vp, i32, i32, C.c_double]),
         "tbnav_icp_get_metric": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_double)]),
         "tbnav_icp_normals": (C.c_int, [vp, vp, i32, vp, vp]),
+        "tbnav_icp_default_search_params": (None, [C.POINTER(IcpSearchParams)]),
+        "tbnav_icp_set_search": (C.c_int, [vp, C.POINTER(IcpSearchParams)]),
+        "tbnav_icp_get_search": (C.c_int, [vp, C.POINTER(i32), C.POINTER(IcpSearchParams)]),
+        "tbnav_icp_last_search": (C.c_int, [vp, C.POINTER(IcpSearchInfo)]),
+        "tbnav_icp_search": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo)]),
+        "tbnav_icp_search_scores": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), vp]),
+        "tbnav_icp_search_table": (C.c_int, [vp, vp, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

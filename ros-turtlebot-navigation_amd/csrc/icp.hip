@@ -27,47 +27,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "icp_device.hpp"
 #include "tbnav_icp.h"
 
 namespace {
 
-constexpr int kThreads = 256;   // B of the header's reduction order
-constexpr int kWave = 64;
-
-struct IcpConst {
-  float range_min, range_max;
-  double trs_c, trs_s, trs_x, trs_y;   // Trs as Transform2D holds it
-  double max_corr2;                    // max_corr_dist^2
-  double rot_thresh, trans_thresh;     // 1 - transform_eps, transform_eps
-  double fitness_eps;
-  int max_iter;
-};
-
-// the line metric's parameters (tbnav_icp_set_metric)
-struct IcpLine {
-  double gap2;       // normal_max_gap^2
-  double min_cond;   // TBNAV_ICP_LINE_MIN_COND
-  int window;        // normal_window
-};
-
-// one alignment: scan indices (-1: the handle's stored scan) and the float-rounded initial guess
-struct IcpPair {
-  int32_t tgt, src;
-  double c, s, x, y;
-};
-
-struct IcpOut {
-  double R00, R10, tx, ty, mse;
-  int32_t iterations, correspondences, criterion, pad;
-};
-
-__device__ __forceinline__ bool cloud_point(float r, float2 cs, const IcpConst& k, float2& p) {
-  if (!(r >= k.range_min && r < k.range_max)) return false;
-  const double px = (double)r * (double)cs.x, py = (double)r * (double)cs.y;
-  p.x = (float)(((k.trs_c * px) - (k.trs_s * py)) + k.trs_x);
-  p.y = (float)(((k.trs_s * px) + (k.trs_c * py)) + k.trs_y);
-  return true;
-}
+using namespace tbnav_icpdev;   // the handle, the kernel constants and cloud_point (icp_device.hpp)
 
 // the target cloud of scan ts into LDS, one slot per beam, padded to whole float4 pairs of points; NaN for what is not a point
 __device__ __forceinline__ void load_target(float2* tgt, const float* __restrict__ ts, const float2* __restrict__ table, int n_beams,
@@ -378,39 +343,9 @@ __global__ __launch_bounds__(kThreads) void icp_cloud(const float* __restrict__ 
 
 bool converged(int crit) { return crit >= TBNAV_ICP_ITERATIONS && crit <= TBNAV_ICP_REL_MSE; }
 
-struct DevGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DevGuard(int d) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(d) == hipSuccess) ok = true; }
-  ~DevGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
-struct tbnav_icp {
-  tbnav_icp_params p{};
-  IcpConst k{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int table_beams = 0;                 // beam count the device table was built for
-  float2* d_table = nullptr;           // cosf / sinf per beam [table_beams]
-  float* d_stored = nullptr;           // the stored scan (pclICPWrapper's old_scan) [stored_cap]
-  int stored_cap = 0, stored_beams = 0;
-  bool have_stored = false;
-  float* d_scans = nullptr;            // batch scans / match inputs
-  size_t scans_cap = 0;
-  IcpPair* d_pairs = nullptr;
-  IcpOut* d_out = nullptr;
-  int pairs_cap = 0;
-  int last_launches = 0;
-  int metric = TBNAV_ICP_METRIC_POINT;  // tbnav_icp_set_metric
-  IcpLine line{TBNAV_ICP_LINE_NORMAL_MAX_GAP * TBNAV_ICP_LINE_NORMAL_MAX_GAP, TBNAV_ICP_LINE_MIN_COND, TBNAV_ICP_LINE_NORMAL_WINDOW};
-  double line_gap = TBNAV_ICP_LINE_NORMAL_MAX_GAP;
-  std::vector<IcpPair> h_pairs;
-  std::vector<IcpOut> h_out;
-};
-
-namespace {
+namespace tbnav_icpdev {
 
 int ensure_table(tbnav_icp* h, int n_beams) {
   if (h->table_beams == n_beams) return TBNAV_OK;
@@ -444,6 +379,10 @@ int ensure_scans(tbnav_icp* h, size_t floats) {
   return TBNAV_OK;
 }
 
+}  // namespace tbnav_icpdev
+
+namespace {
+
 int ensure_pairs(tbnav_icp* h, int n) {
   if (n <= h->pairs_cap) return TBNAV_OK;
   if (h->d_pairs) TBNAV_HIP(hipFree(h->d_pairs));
@@ -464,6 +403,17 @@ IcpPair make_pair(int tgt, int src, const double T[3]) {
   p.x = (double)(float)T[1];
   p.y = (double)(float)T[2];
   return p;
+}
+
+// one more alignment for run_pairs: the pair, and its guess as given (the correlative search starts from the doubles)
+void add_pair(tbnav_icp* h, int tgt, int src, const double T[3]) {
+  h->h_pairs.push_back(make_pair(tgt, src, T));
+  h->h_init.push_back({T[0], T[1], T[2]});
+}
+
+void clear_pairs(tbnav_icp* h) {
+  h->h_pairs.clear();
+  h->h_init.clear();
 }
 
 // one launch of icp_align<M, P> over h->d_pairs.  Dynamic LDS: the cloud, 8 bytes per beam rounded up to 4 beams, and as much
@@ -503,9 +453,20 @@ bool beams_ok(const tbnav_icp* h, int n_beams) {
   return n_beams > 0 && n_beams <= (h->metric == TBNAV_ICP_METRIC_LINE ? LineMetric::kMaxBeams : PointMetric::kMaxBeams);
 }
 
-// aligns h->h_pairs[0, n_pairs) (scans already in d_scans / d_stored) -> h->h_out, with the handle's metric
+// aligns h->h_pairs[0, n_pairs) (scans already in d_scans / d_stored) -> h->h_out, with the handle's metric.  With the
+// correlative search on (tbnav_icp_set_search) every pair is searched first -> h->h_sinfo, and an accepted search's pose
+// replaces the pair's guess: one host round trip between the search and the alignment (the guess is formed here, with glibc).
 int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
   if (int rc = ensure_pairs(h, n_pairs)) return rc;
+  if (h->search.on) {
+    if (int rc = search_pairs(h, n_pairs, n_beams, h->search.p, nullptr)) return rc;
+    for (int i = 0; i < n_pairs; ++i) {
+      const tbnav_icp_search_info& si = h->h_sinfo[(size_t)i];
+      if (si.accepted) h->h_pairs[(size_t)i] = make_pair(h->h_pairs[(size_t)i].tgt, h->h_pairs[(size_t)i].src, si.T);
+    }
+  } else {
+    h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
+  }
   TBNAV_HIP(hipMemcpyAsync(h->d_pairs, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
   const bool line = h->metric == TBNAV_ICP_METRIC_LINE;
   if (int rc = line ? dispatch<LineMetric>(h, n_pairs, n_beams) : dispatch<PointMetric>(h, n_pairs, n_beams)) return rc;
@@ -601,6 +562,7 @@ int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
   h->p = *params;
   h->device = dev;
+  tbnav_icp_default_search_params(&h->search.p);
   IcpConst& k = h->k;
   k.range_min = params->range_min;
   k.range_max = params->range_max;
@@ -632,6 +594,7 @@ void tbnav_icp_destroy(tbnav_icp* h) {
     (void)hipFree(h->d_scans);
     (void)hipFree(h->d_pairs);
     (void)hipFree(h->d_out);
+    search_free(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);
   }
   delete h;
@@ -716,9 +679,11 @@ int tbnav_icp_match(tbnav_icp* h, const float* target_scan, const float* source_
   if (int rc = ensure_scans(h, 2 * (size_t)n_beams)) return rc;
   TBNAV_HIP(hipMemcpyAsync(h->d_scans, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   TBNAV_HIP(hipMemcpyAsync(h->d_scans + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  h->h_pairs.assign(1, make_pair(0, 1, T_init));
+  clear_pairs(h);
+  add_pair(h, 0, 1, T_init);
   h->last_launches = 0;
   if (int rc = run_pairs(h, 1, n_beams)) return rc;
+  h->search.last = h->h_sinfo[0];
   result(h->h_out[0], T_out, info);
   return TBNAV_OK;
 }
@@ -732,14 +697,17 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
   if (!h->have_stored) {  // cloud_alignment.cpp:64-68
     if (int rc = store_scan(h, nullptr, scan, n_beams)) return rc;
     first_call(T_out, ok, info);
+    h->search.last = tbnav_icp_search_info{};
     return TBNAV_OK;
   }
   if (int rc = ensure_table(h, n_beams)) return rc;
   if (int rc = ensure_scans(h, (size_t)n_beams)) return rc;
   TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  h->h_pairs.assign(1, make_pair(-1, 0, T_init));
+  clear_pairs(h);
+  add_pair(h, -1, 0, T_init);
   h->last_launches = 0;
   if (int rc = run_pairs(h, 1, n_beams)) return rc;
+  h->search.last = h->h_sinfo[0];
   const IcpOut o = h->h_out[0];
   result(o, T_out, info);
   *ok = converged(o.criterion) ? 1 : 0;
@@ -770,27 +738,30 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
   // failed, so the target stayed an earlier scan), the scans from there are aligned against the actual target in another
   // launch — through the first one whose speculative alignment converged (the scans before it will probably fail against
   // any target, and the walk would need each of them next).
-  std::map<std::pair<int, int>, IcpOut> done;  // (target, source) -> result
+  struct Done { IcpOut out; tbnav_icp_search_info search; };
+  std::map<std::pair<int, int>, Done> done;  // (target, source) -> result, and the search in front of it
+  h->search.last = tbnav_icp_search_info{};
   if (s < n_scans) {
-    h->h_pairs.clear();
-    for (int q = s; q < n_scans; ++q) h->h_pairs.push_back(make_pair(q - 1, q, T_init + 3 * (size_t)q));
+    clear_pairs(h);
+    for (int q = s; q < n_scans; ++q) add_pair(h, q - 1, q, T_init + 3 * (size_t)q);
     if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
-    for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = h->h_out[j];
+    for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j]};
   }
   for (; s < n_scans; ++s) {
     auto it = done.find({target, s});
     if (it == done.end()) {
-      h->h_pairs.clear();
+      clear_pairs(h);
       for (int q = s; q < n_scans; ++q) {
-        h->h_pairs.push_back(make_pair(target, q, T_init + 3 * (size_t)q));
+        add_pair(h, target, q, T_init + 3 * (size_t)q);
         const auto spec = done.find({q - 1, q});
-        if (spec != done.end() && converged(spec->second.criterion)) break;
+        if (spec != done.end() && converged(spec->second.out.criterion)) break;
       }
       if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
-      for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = h->h_out[j];
+      for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j]};
       it = done.find({target, s});
     }
-    const IcpOut& o = it->second;
+    const IcpOut& o = it->second.out;
+    h->search.last = it->second.search;
     result(o, T_out + 3 * (size_t)s, info ? info + s : nullptr);
     ok[s] = converged(o.criterion) ? 1 : 0;
     if (ok[s]) target = s;

@@ -1,0 +1,123 @@
+// icp_device.hpp — what the device ICP (icp.hip) and the correlative search in front of it (icp_search.hip) share: the handle,
+// the by-value kernel constants, the cloud of contract item 1 (cloud_point with the beam table) and the device buffers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <cstdint>
+#include <vector>
+
+#include "common.hpp"
+#include "tbnav_icp.h"
+
+namespace tbnav_icpdev {
+
+constexpr int kThreads = 256;   // B of the header's reduction order
+constexpr int kWave = 64;
+
+struct IcpConst {
+  float range_min, range_max;
+  double trs_c, trs_s, trs_x, trs_y;   // Trs as Transform2D holds it
+  double max_corr2;                    // max_corr_dist^2
+  double rot_thresh, trans_thresh;     // 1 - transform_eps, transform_eps
+  double fitness_eps;
+  int max_iter;
+};
+
+// the line metric's parameters (tbnav_icp_set_metric)
+struct IcpLine {
+  double gap2;       // normal_max_gap^2
+  double min_cond;   // TBNAV_ICP_LINE_MIN_COND
+  int window;        // normal_window
+};
+
+// one alignment: scan indices (-1: the handle's stored scan) and the float-rounded initial guess
+struct IcpPair {
+  int32_t tgt, src;
+  double c, s, x, y;
+};
+
+struct IcpOut {
+  double R00, R10, tx, ty, mse;
+  int32_t iterations, correspondences, criterion, pad;
+};
+
+__device__ __forceinline__ bool cloud_point(float r, float2 cs, const IcpConst& k, float2& p) {
+  if (!(r >= k.range_min && r < k.range_max)) return false;
+  const double px = (double)r * (double)cs.x, py = (double)r * (double)cs.y;
+  p.x = (float)(((k.trs_c * px) - (k.trs_s * py)) + k.trs_x);
+  p.y = (float)(((k.trs_s * px) + (k.trs_c * py)) + k.trs_y);
+  return true;
+}
+
+struct DevGuard {
+  int prev = -1;
+  bool ok = false;
+  explicit DevGuard(int d) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(d) == hipSuccess) ok = true; }
+  ~DevGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// the correlative search's state in the handle (tbnav_icp.h, CORRELATIVE SEARCH); the buffers are icp_search.hip's
+struct IcpSearch {
+  bool on = false;
+  tbnav_icp_search_params p{};      // the defaults while the search is off
+  tbnav_icp_search_info last{};     // tbnav_icp_last_search
+  tbnav_icp_search_params stamp_of{};  // the parameters d_stamp was built from
+  bool have_stamp = false;
+  uint8_t* d_stamp = nullptr;       // [(2k+1)^2]
+  uint8_t* d_tables = nullptr;      // [chunk][padded table]
+  size_t tables_cap = 0;
+  void* d_in = nullptr;             // per chunk: the pairs, then their rotations
+  size_t in_cap = 0;
+  void* d_rec = nullptr;            // [chunk][na] partial results
+  size_t rec_cap = 0;
+  void* d_sel = nullptr;            // [chunk] results
+  size_t sel_cap = 0;
+  uint32_t* d_tgt_points = nullptr; // [chunk]: the valid target points
+  size_t tgt_cap = 0;
+  uint32_t* d_scores = nullptr;     // the test hook's score volume
+  size_t scores_cap = 0;
+  std::vector<unsigned char> h_in, h_sel;
+};
+
+}  // namespace tbnav_icpdev
+
+struct tbnav_icp {
+  tbnav_icp_params p{};
+  tbnav_icpdev::IcpConst k{};
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int table_beams = 0;                 // beam count the device table was built for
+  float2* d_table = nullptr;           // cosf / sinf per beam [table_beams]
+  float* d_stored = nullptr;           // the stored scan (pclICPWrapper's old_scan) [stored_cap]
+  int stored_cap = 0, stored_beams = 0;
+  bool have_stored = false;
+  float* d_scans = nullptr;            // batch scans / match inputs
+  size_t scans_cap = 0;
+  tbnav_icpdev::IcpPair* d_pairs = nullptr;
+  tbnav_icpdev::IcpOut* d_out = nullptr;
+  int pairs_cap = 0;
+  int last_launches = 0;
+  int metric = TBNAV_ICP_METRIC_POINT;  // tbnav_icp_set_metric
+  tbnav_icpdev::IcpLine line{TBNAV_ICP_LINE_NORMAL_MAX_GAP * TBNAV_ICP_LINE_NORMAL_MAX_GAP, TBNAV_ICP_LINE_MIN_COND,
+                             TBNAV_ICP_LINE_NORMAL_WINDOW};
+  double line_gap = TBNAV_ICP_LINE_NORMAL_MAX_GAP;
+  std::vector<tbnav_icpdev::IcpPair> h_pairs;
+  std::vector<tbnav_icpdev::IcpOut> h_out;
+  tbnav_icpdev::IcpSearch search;
+  std::vector<std::array<double, 3>> h_init;        // T_init of h_pairs, as given (the search starts from the doubles)
+  std::vector<tbnav_icp_search_info> h_sinfo;       // the search record of h_pairs (run_pairs)
+};
+
+namespace tbnav_icpdev {
+
+// icp.hip
+int ensure_table(tbnav_icp* h, int n_beams);
+int ensure_scans(tbnav_icp* h, size_t floats);
+
+// icp_search.hip: the search of h->h_pairs[0, n_pairs) from h->h_init (scans already in d_scans / d_stored, the beam table
+// built) with parameters sp -> h->h_sinfo[0, n_pairs).  scores (n_pairs == 1 only): the whole score volume, or null.
+int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores);
+void search_free(tbnav_icp* h);
+
+}  // namespace tbnav_icpdev

@@ -20,6 +20,14 @@
 // useDeviceICP(device) stays point-to-point.  Compiling with -DTBNAV_SCAN_ALIGNMENT_POINT_TO_LINE beside
 // -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor choose the line metric; it too only changes a default argument
 // (alone, without the first define, it has no effect).
+//
+// useDeviceICP(device, metric, ICPSearch) puts the device ICP's correlative search (tbnav_icp.h, CORRELATIVE SEARCH) in front
+// of every alignment: a window of poses round the guess is scored against a table of the previous scan and the ICP starts from
+// the best one when it is good enough, so a guess that is off by more than the ICP's basin (a wheel slip, a bumped robot)
+// no longer ends in a confident wrong answer.  It too is an addition with NO counterpart in the reference, and off unless
+// asked for: the two overloads above keep their meaning.  -DTBNAV_SCAN_ALIGNMENT_SEARCH beside
+// -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor turn the search on with its default parameters; it only changes a
+// default argument as well (alone it has no effect).
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -42,6 +50,12 @@
 #define TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT ::bmapping::ICPMetric::PointToPoint
 #endif
 
+#ifdef TBNAV_SCAN_ALIGNMENT_SEARCH
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT true
+#else
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT false
+#endif
+
 namespace bmapping {
 
 using rigid2d::Transform2D;
@@ -49,15 +63,29 @@ using rigid2d::Transform2D;
 /// (addition) what the device ICP minimises: PointToPoint is the reference's (PCL's) metric and the default
 enum class ICPMetric { PointToPoint, PointToLine };
 
+/// (addition) the correlative search in front of the device ICP: tbnav_icp_search_params with its defaults
+struct ICPSearch {
+  double resolution = 0.05;    ///< table cell (m)
+  double half_extent = 4.0;    ///< half the table's side (m)
+  double sigma = 0.05;         ///< Gaussian width of the stamp (m)
+  int stamp_cells = 3;         ///< the stamp's half width in cells, 1..8
+  int lin_cells = 6;           ///< window +-lin_cells cells in x and y, 0..16
+  int ang_steps = 20;          ///< window +-ang_steps steps of ang_step, 0..90
+  double ang_step = 3.14159265358979323846 / 180.0;
+  int slack_q10 = 0;           ///< selection slack in 1/1024, 0..1023
+  double min_quality = 0.5;    ///< acceptance threshold
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
   using Matcher = std::function<bool(Transform2D&, const Transform2D&, const std::vector<float>&, const std::vector<float>&)>;
 
   ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT,
-                ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT)
+                ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT, bool device_search = TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT)
       : props_(props), Trs_(Trs) {
-    if (device_icp) useDeviceICP(-1, device_metric);
+    if (device_icp && device_search) useDeviceICP(-1, device_metric, ICPSearch());
+    else if (device_icp) useDeviceICP(-1, device_metric);
   }
 
   /// plug in a real scan matcher (e.g. a PCL ICP wrapper in a catkin workspace that has PCL)
@@ -66,6 +94,9 @@ class ScanAlignment {
   void useDeviceICP(int device = -1) { useDeviceICP(device, ICPMetric::PointToPoint); }
   /// (addition) the same with the metric named: PointToLine has no counterpart in the reference (default window and gap)
   void useDeviceICP(int device, ICPMetric metric);
+  /// (addition) the same with the correlative search in front of every alignment; throws std::invalid_argument for
+  /// parameters outside their limits
+  void useDeviceICP(int device, ICPMetric metric, const ICPSearch& search);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {
@@ -90,6 +121,8 @@ class ScanAlignment {
   }
 
  private:
+  void installDeviceICP(int device, ICPMetric metric, const ICPSearch* search);
+
   LaserProperties props_;
   Transform2D Trs_;
   Matcher matcher_;

@@ -1,5 +1,6 @@
 // cloud_alignment_device.cpp — ScanAlignment::useDeviceICP: the device ICP of include/tbnav_icp.h as the shim's matcher, with
-// its point-to-point metric (the reference's) or its point-to-line metric (an addition).
+// its point-to-point metric (the reference's) or its point-to-line metric (an addition), and optionally its correlative search
+// in front of either (an addition too).
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -10,7 +11,11 @@
 
 namespace bmapping {
 
-void ScanAlignment::useDeviceICP(int device, ICPMetric metric) {
+void ScanAlignment::useDeviceICP(int device, ICPMetric metric) { installDeviceICP(device, metric, nullptr); }
+
+void ScanAlignment::useDeviceICP(int device, ICPMetric metric, const ICPSearch& search) { installDeviceICP(device, metric, &search); }
+
+void ScanAlignment::installDeviceICP(int device, ICPMetric metric, const ICPSearch* search) {
   tbnav_icp_params p;
   tbnav_icp_default_params(&p);  // the reference's settings (cloud_alignment.cpp:21-34)
   p.beam_min = props_.beam_min; p.beam_max = props_.beam_max; p.beam_delta = props_.beam_delta;
@@ -31,6 +36,16 @@ void ScanAlignment::useDeviceICP(int device, ICPMetric metric) {
   if (metric == ICPMetric::PointToLine) {
     const int mrc = tbnav_icp_set_metric(raw, TBNAV_ICP_METRIC_LINE, 0, 0.0);  // the default window and gap
     if (mrc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(mrc));
+  }
+  if (search) {
+    tbnav_icp_search_params sp;
+    tbnav_icp_default_search_params(&sp);
+    sp.resolution = search->resolution; sp.half_extent = search->half_extent; sp.sigma = search->sigma;
+    sp.stamp_cells = search->stamp_cells; sp.lin_cells = search->lin_cells; sp.ang_steps = search->ang_steps;
+    sp.ang_step = search->ang_step; sp.slack_q10 = search->slack_q10; sp.min_quality = search->min_quality;
+    const int src = tbnav_icp_set_search(raw, &sp);
+    if (src == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument("bmapping::ScanAlignment::useDeviceICP: search parameters outside their limits");
+    if (src != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(src));
   }
   matcher_ = [h](Transform2D& T, const Transform2D& T_init, const std::vector<float>& target, const std::vector<float>& source) {
     if (target.size() != source.size()) throw std::invalid_argument("bmapping::ScanAlignment: scans of different lengths");

@@ -30,16 +30,23 @@ const char* hst_icp_last_error() { return g_icp_err.c_str(); }
 // what SLAM feeds its own (icpInitGuess, particle_filter.cpp:602-612): out_ok [n_scans], out_T [n_scans][3] (theta, x, y).
 // out_pose [n_scans][3] = getRobotState, out_neff [n_scans].  Returns 0, or -1 (message in hst_icp_last_error).
 // hst_icp_pf_run_metric: the same with the metric named (0: point-to-point, 1: point-to-line).
-int hst_icp_pf_run_metric(int metric, int N, int k, double map_half, uint64_t seed, const float* scans, int n_beams, int n_scans,
+// hst_icp_pf_run_search: the same with the correlative search in front of the ICP (search != 0; lin_cells as given, all else
+// the defaults).
+int hst_icp_pf_run_search(int metric, int search, int lin_cells, int N, int k, double map_half, uint64_t seed, const float* scans, int n_beams, int n_scans,
                           const double* odom, const double* u, int32_t* out_ok, double* out_T, double* out_pose, int32_t* out_neff) {
   try {
-    if (metric != 0 && metric != 1) throw std::invalid_argument("hst_icp_pf_run_metric: metric must be 0 or 1");
+    if (metric != 0 && metric != 1) throw std::invalid_argument("hst_icp_pf_run_search: metric must be 0 or 1");
     const double d2r = rigid2d::PI / 180.0;
     bmapping::LaserProperties props((float)(0.0 * d2r), (float)(360.0 * d2r), (float)(1.0 * d2r), 0.12f, 3.5f, 0.95, 0.0, 0.04, 0.01, 0.5);
     Transform2D Trs;
     bmapping::GridMapper grid(0.05, -map_half, map_half, -map_half, map_half, props, Trs);
     bmapping::ScanAlignment aligner(props, Trs);
-    if (metric == 1) aligner.useDeviceICP(-1, bmapping::ICPMetric::PointToLine);
+    const bmapping::ICPMetric m = metric == 1 ? bmapping::ICPMetric::PointToLine : bmapping::ICPMetric::PointToPoint;
+    if (search) {
+      bmapping::ICPSearch sp;
+      sp.lin_cells = lin_cells;
+      aligner.useDeviceICP(-1, m, sp);
+    } else if (metric == 1) aligner.useDeviceICP(-1, m);
     else aligner.useDeviceICP();
     bmapping::ScanAlignment observer = aligner;  // shares the handle; keeps its own stored scan
     Transform2D start(Vector2D(odom[1], odom[2]), odom[0]);
@@ -64,6 +71,11 @@ int hst_icp_pf_run_metric(int metric, int N, int k, double map_half, uint64_t se
     }
     return 0;
   } catch (const std::exception& e) { g_icp_err = e.what(); return -1; }
+}
+
+int hst_icp_pf_run_metric(int metric, int N, int k, double map_half, uint64_t seed, const float* scans, int n_beams, int n_scans,
+                          const double* odom, const double* u, int32_t* out_ok, double* out_T, double* out_pose, int32_t* out_neff) {
+  return hst_icp_pf_run_search(metric, 0, 0, N, k, map_half, seed, scans, n_beams, n_scans, odom, u, out_ok, out_T, out_pose, out_neff);
 }
 
 int hst_icp_pf_run(int N, int k, double map_half, uint64_t seed, const float* scans, int n_beams, int n_scans, const double* odom,

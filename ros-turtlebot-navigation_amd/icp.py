@@ -6,6 +6,10 @@ statelessly (:160-223).  wrapperBatch replays a logged run: its (ok, T) arrays a
 init_guess is ParticleFilter::icpInitGuess (particle_filter.cpp:602-612).  The algorithm is a restatement of PCL's
 IterativeClosestPoint; parity with PCL itself is unpinned (see the header).
 
+search=True | dict(...) (an addition with no counterpart in the reference) puts the correlative search of the header's
+CORRELATIVE SEARCH section in front of every alignment: it scores every pose of a window round the guess against a table of
+the target scan and starts the ICP from the best one, when that one is good enough.  The default is off.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -64,12 +68,18 @@ def init_guess(cur, prev):
 
 
 _METRICS = {"point": capi.ICP_METRIC_POINT, "line": capi.ICP_METRIC_LINE}
+_SEARCH_FIELDS = tuple(f for f, _ in capi.IcpSearchParams._fields_)
+
+
+def _search_info(i: "capi.IcpSearchInfo") -> dict:
+    return dict(T=tuple(i.T), quality=i.quality, score=i.score, points=i.points, candidates=i.candidates, ia=i.ia, iy=i.iy,
+                ix=i.ix, at_edge=i.at_edge, accepted=i.accepted, searched=i.searched)
 
 
 class ScanAlignment:
     """bmapping::ScanAlignment on one MI355X."""
 
-    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0):
+    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0, search=None):
         self._L = capi.lib()
         self.params = params if params is not None else default_params()
         if metric not in _METRICS:
@@ -82,6 +92,76 @@ class ScanAlignment:
             except Exception:
                 self.close()
                 raise
+        if search is not None and search is not False:
+            try:
+                self.setSearch(**({} if search is True else dict(search)))
+            except Exception:
+                self.close()
+                raise
+
+    def setSearch(self, *off, **kw):
+        """tbnav_icp_set_search: setSearch(resolution=..., lin_cells=..., ...) turns the correlative search on for every later
+        call, with the defaults (tbnav_icp_default_search_params) for what is not named; setSearch(None) turns it off."""
+        if off:
+            if off != (None,) or kw:
+                raise TypeError("setSearch(None) turns the search off; parameters go by keyword")
+            capi.check(self._L.tbnav_icp_set_search(self._h, None), "tbnav_icp_set_search")
+            return
+        p = capi.IcpSearchParams()
+        self._L.tbnav_icp_default_search_params(C.byref(p))
+        for key, v in kw.items():
+            if key not in _SEARCH_FIELDS:
+                raise TypeError(f"setSearch: no parameter {key!r} (one of {_SEARCH_FIELDS})")
+            setattr(p, key, v)
+        capi.check(self._L.tbnav_icp_set_search(self._h, C.byref(p)), "tbnav_icp_set_search")
+
+    def searchParams(self):
+        """-> (on, dict of tbnav_icp_search_params) as the handle holds them (the defaults while the search is off)"""
+        on, p = C.c_int32(), capi.IcpSearchParams()
+        capi.check(self._L.tbnav_icp_get_search(self._h, C.byref(on), C.byref(p)), "tbnav_icp_get_search")
+        return bool(on.value), {f: getattr(p, f) for f in _SEARCH_FIELDS}
+
+    def _search(self, T_init, target_scan, source_scan, scores):
+        tgt = np.ascontiguousarray(target_scan, dtype=np.float32)
+        src = np.ascontiguousarray(source_scan, dtype=np.float32)
+        if tgt.size != src.size:
+            raise ValueError("target and source scans must have the same number of beams")
+        out = (C.c_double * 3)()
+        info = capi.IcpSearchInfo()
+        if scores is None:
+            capi.check(self._L.tbnav_icp_search(self._h, tgt.ctypes.data, src.ctypes.data, src.size, _d3(T_init), out, C.byref(info)),
+                       "tbnav_icp_search")
+        else:
+            capi.check(self._L.tbnav_icp_search_scores(self._h, tgt.ctypes.data, src.ctypes.data, src.size, _d3(T_init), out,
+                                                       C.byref(info), scores.ctypes.data), "tbnav_icp_search_scores")
+        return bool(info.accepted), tuple(out), _search_info(info)
+
+    def search(self, T_init, target_scan, source_scan):
+        """tbnav_icp_search, stateless: the search alone with the handle's parameters (the defaults while it is off)
+        -> (accepted, T, info dict)"""
+        return self._search(T_init, target_scan, source_scan, None)
+
+    def searchScores(self, T_init, target_scan, source_scan):
+        """test hook: the same and the whole score volume -> (accepted, T, info dict, uint32 [na][nl][nl])"""
+        p = self.searchParams()[1]
+        na, nl = 2 * p["ang_steps"] + 1, 2 * p["lin_cells"] + 1
+        scores = np.zeros((na, nl, nl), dtype=np.uint32)
+        return self._search(T_init, target_scan, source_scan, scores) + (scores,)
+
+    def searchTable(self, scan):
+        """test hook: the likelihood table of one scan taken as a target: uint8 [n][n], indexed [iy][ix]"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        p = self.searchParams()[1]
+        n = 2 * math.ceil(p["half_extent"] / p["resolution"])
+        tab = np.zeros((n, n), dtype=np.uint8)
+        capi.check(self._L.tbnav_icp_search_table(self._h, scan.ctypes.data, scan.size, tab.ctypes.data), "tbnav_icp_search_table")
+        return tab
+
+    def lastSearch(self) -> dict:
+        """the search record of the last pclICP / pclICPWrapper, for a wrapperBatch the last scan's (searched = 0: none ran)"""
+        info = capi.IcpSearchInfo()
+        capi.check(self._L.tbnav_icp_last_search(self._h, C.byref(info)), "tbnav_icp_last_search")
+        return _search_info(info)
 
     def setMetric(self, metric="point", normal_window=0, normal_max_gap=0.0):
         """tbnav_icp_set_metric: "point" | "line" for every later call; normal_window (beams, 0: the default 1) and

@@ -1,5 +1,5 @@
 """Timing of the device ICP (include/tbnav_icp.h) on the GPU:
-python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N]
+python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N] [--search]
   - latency of one synchronous tbnav_icp_step (host clock around the call, which ends in a stream synchronise) at 360 beams
     (1 deg) and 1080 beams (1/3 deg): median / p10 / p90 of 500 scans after 20 of warm-up, a robot driving round a room;
   - tbnav_icp_step_batch over 2000 scans of the same kind of run: median of 5 calls (after one of warm-up), per call and
@@ -9,6 +9,9 @@ python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--ma
     "line_over_point" holds the ratios of the medians and of the iteration counts;
   --max-iter: tbnav_icp_params.max_iter (default 100, the reference's): a launch of step_batch lasts as long as its slowest
     pair, so a pair that runs to the cap sets the batch's time;
+  --search: the correlative search in front of the ICP (tbnav_icp_set_search, default parameters), in the same process on the
+    same scans: every record above with the search off (the parent's rows) and again with it on under "<name>_search", and
+    "search_alone_360" / "_1080": tbnav_icp_search by itself on consecutive scans of the same run;
   --quick: a few scans only (what a `rocprofv3 --kernel-trace --stats` run of this script needs).
 Kernel times come from a separate rocprofv3 run, not from this script."""
 import argparse
@@ -41,10 +44,10 @@ def loop_run(n, n_beams, beam_delta_deg, seed=1):
     return scans, T_init
 
 
-def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric)
+def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100, search=None):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search)
     scans, T_init = loop_run(n_warm + n_time, n_beams, beam_delta_deg)
-    ts, iters, fails = [], [], 0
+    ts, iters, fails, accepted = [], [], 0, 0
     for s in range(n_warm + n_time):
         t0 = time.perf_counter()
         ok, T, info = a.pclICPWrapper(T_init[s], scans[s])
@@ -53,15 +56,38 @@ def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_it
             ts.append((t1 - t0) * 1e6)
             iters.append(info["iterations"])
             fails += 0 if ok else 1
+            accepted += a.lastSearch()["accepted"] if search else 0
+    a.close()
+    ts = np.array(ts)
+    rec = dict(n_beams=n_beams, scans=n_time, median_us=float(np.median(ts)), p10_us=float(np.percentile(ts, 10)),
+               p90_us=float(np.percentile(ts, 90)), mean_iterations=float(np.mean(iters)), max_iterations=int(np.max(iters)),
+               at_max_iter=int(np.sum(np.array(iters) >= max_iter)), failures=fails)
+    if search:
+        rec["searches_accepted"] = accepted
+    return rec
+
+
+def search_latency(n_beams, beam_delta_deg, n_warm, n_time):
+    """tbnav_icp_search alone (default parameters): each scan of the run against the one before it"""
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+    scans, T_init = loop_run(n_warm + n_time + 1, n_beams, beam_delta_deg)
+    ts, acc, qual = [], 0, []
+    for s in range(1, n_warm + n_time + 1):
+        t0 = time.perf_counter()
+        ok, T, info = a.search(T_init[s], scans[s - 1], scans[s])
+        t1 = time.perf_counter()
+        if s > n_warm:
+            ts.append((t1 - t0) * 1e6)
+            acc += int(ok)
+            qual.append(info["quality"])
     a.close()
     ts = np.array(ts)
     return dict(n_beams=n_beams, scans=n_time, median_us=float(np.median(ts)), p10_us=float(np.percentile(ts, 10)),
-                p90_us=float(np.percentile(ts, 90)), mean_iterations=float(np.mean(iters)), max_iterations=int(np.max(iters)),
-                at_max_iter=int(np.sum(np.array(iters) >= max_iter)), failures=fails)
+                p90_us=float(np.percentile(ts, 90)), accepted=acc, mean_quality=float(np.mean(qual)))
 
 
-def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric)
+def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100, search=None):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search)
     scans, T_init = loop_run(n_scans, n_beams, beam_delta_deg, seed=2)
     ts = []
     for r in range(reps + 1):
@@ -86,13 +112,19 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--metric", choices=("point", "line", "both"), default="point")
     ap.add_argument("--max-iter", type=int, default=100)
+    ap.add_argument("--search", action="store_true")
     a = ap.parse_args()
     n_warm, n_time, reps = (2, 10, 1) if a.quick else (20, 500, 5)
 
     def run(metric):
-        return dict(step_360=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter),
-                    step_1080=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter),
-                    batch_2000=batch_time(2000, reps, metric=metric, max_iter=a.max_iter))
+        res = dict(step_360=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter),
+                   step_1080=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter),
+                   batch_2000=batch_time(2000, reps, metric=metric, max_iter=a.max_iter))
+        if a.search:
+            res.update(step_360_search=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter, search=True),
+                       step_1080_search=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter, search=True),
+                       batch_2000_search=batch_time(2000, reps, metric=metric, max_iter=a.max_iter, search=True))
+        return res
 
     if a.metric == "both":
         res = dict(point=run("point"), line=run("line"))
@@ -102,6 +134,9 @@ def main():
             for key, t in (("step_360", "median_us"), ("step_1080", "median_us"), ("batch_2000", "median_ms"))}
     else:
         res = run(a.metric)
+    if a.search:
+        res["search_alone_360"] = search_latency(360, 1.0, n_warm, n_time)
+        res["search_alone_1080"] = search_latency(1080, 1.0 / 3.0, n_warm, n_time)
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
