@@ -52,12 +52,23 @@ __device__ __forceinline__ double dpp_or_zero(double src) {
   const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(src), CTRL, ROW_MASK, BANK_MASK, false);
   return __hiloint2double(hi, lo);
 }
-// inclusive prefix sum over the lanes of a wave (lane i gets v_0 + ... + v_i)
+// The same for a stage whose row and bank masks are full: `old` can then only reach a lane whose source is out of the row or
+// switched off, and bound_ctrl writes the same +0.0 there — no `v_mov_b32 v, 0` in front of each half (mov_dpp leaves `old`
+// undefined, and nothing reads it).
+template <int CTRL>
+__device__ __forceinline__ double dpp_shift_or_zero(double src) {
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(src), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(src), CTRL, 0xf, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
+// inclusive prefix sum over the lanes of a wave (lane i gets v_0 + ... + v_i); LEAN: the full-mask stages without a zeroed `old`
+// (same bits; the kernels of the K = 1024 tick, where every issued VALU instruction counts)
+template <bool LEAN = false>
 __device__ __forceinline__ double wave_scan_incl(double v, int /*lane*/) {
   double out = v;
-  out += dpp_or_zero<0x111, 0xf, 0xf>(v);    // row_shr:1
-  out += dpp_or_zero<0x112, 0xf, 0xf>(v);    // row_shr:2
-  out += dpp_or_zero<0x113, 0xf, 0xf>(v);    // row_shr:3   -> sums of up to four consecutive lanes
+  out += LEAN ? dpp_shift_or_zero<0x111>(v) : dpp_or_zero<0x111, 0xf, 0xf>(v);  // row_shr:1
+  out += LEAN ? dpp_shift_or_zero<0x112>(v) : dpp_or_zero<0x112, 0xf, 0xf>(v);  // row_shr:2
+  out += LEAN ? dpp_shift_or_zero<0x113>(v) : dpp_or_zero<0x113, 0xf, 0xf>(v);  // row_shr:3   -> sums of up to four consecutive lanes
   out += dpp_or_zero<0x114, 0xf, 0xe>(out);  // row_shr:4, banks 1-3
   out += dpp_or_zero<0x118, 0xf, 0xc>(out);  // row_shr:8, banks 2-3 -> inclusive within each row of 16
   out += dpp_or_zero<0x142, 0xa, 0xf>(out);  // row_bcast:15 into rows 1 and 3
@@ -89,12 +100,15 @@ __device__ __forceinline__ double wave_min_dpp(double v) {
 }
 // The partner of a butterfly step inside groups of 2 / 4 / 8 / 16 consecutive lanes, on the DPP network: lane ^ 1 and
 // lane ^ 2 are quad permutations; once a quad's lanes agree, the mirror image within 8 (row_half_mirror) or 16
-// (row_mirror) lanes lies in the other quad / half, which is all a commutative reduction needs.
+// (row_mirror) lanes lies in the other quad / half, which is all a commutative reduction needs.  Every lane has a source inside
+// its group and the masks are full, so `old` is never read and stays undefined (mov_dpp) — the lanes of a group must be
+// switched on or off together, as they are in the one caller of group_reduce_dpp, mppi_rollout_fused's record loop (a group
+// shares its time step).  Changed in place for that reason: no other kernel's code contains it.
 template <int STEP>
 __device__ __forceinline__ double dpp_group_partner(double v) {
   constexpr int ctrl = STEP == 1 ? 0xB1 : STEP == 2 ? 0x4E : STEP == 4 ? 0x141 : 0x140;  // quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, 0xf, 0xf, false);
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), ctrl, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), ctrl, 0xf, 0xf, false);
   return __hiloint2double(hi, lo);
 }
 // all-lanes reduction over groups of R consecutive lanes (R = 2, 4, 8, 16), steps in the order 1, 2, 4, 8
@@ -114,10 +128,11 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
 __device__ __forceinline__ double wave_scan_incl_rev(double v, int lane) {
   // the mirror image of wave_scan_incl inside each row of 16 lanes (row_shl), then the totals of the later rows — read
   // from their first lanes — are added; no LDS permute (two dependent ones before)
+  // (mppi_rollout_fused is the only caller, so the full-mask stages took the bound_ctrl form in place)
   double out = v;
-  out += dpp_or_zero<0x101, 0xf, 0xf>(v);    // row_shl:1
-  out += dpp_or_zero<0x102, 0xf, 0xf>(v);    // row_shl:2
-  out += dpp_or_zero<0x103, 0xf, 0xf>(v);    // row_shl:3
+  out += dpp_shift_or_zero<0x101>(v);        // row_shl:1
+  out += dpp_shift_or_zero<0x102>(v);        // row_shl:2
+  out += dpp_shift_or_zero<0x103>(v);        // row_shl:3
   out += dpp_or_zero<0x104, 0xf, 0x7>(out);  // row_shl:4, banks 0-2
   out += dpp_or_zero<0x108, 0xf, 0x3>(out);  // row_shl:8, banks 0-1 -> inclusive suffix within each row of 16
   const double t1 = readlane_d(out, 16), t2 = readlane_d(out, 32), t3 = readlane_d(out, 48);

@@ -133,6 +133,10 @@ __device__ __forceinline__ void fast_sincos(double x, double& s, double& c) {
   c = ((n + 1) & 2) ? -ca : ca;
 }
 
+// BRANCH: keep the full evaluation behind its branch.  Where the rollout holds one or two steps per lane (mppi_rollout_fused) the
+// compiler otherwise turns the block into selects and every wave issues a fast_sincos per step that nothing reads; the empty
+// statement has to be executed where it stands, and the evaluation hangs on its output.
+template <bool BRANCH = false>
 __device__ __forceinline__ void small_sincos(double d, double& sd, double& cd) {
   // straight-line Taylor pair (truncation < 3e-19 relative for |d| <= 2^-5); the full evaluation is entered only if SOME
   // lane of the wave needs it (wave-uniform branch: no divergence, and never taken for physical wheel speeds)
@@ -149,8 +153,9 @@ __device__ __forceinline__ void small_sincos(double d, double& sd, double& cd) {
   cd = 1.0 - d2 * 0.5 * pc;
   const bool big = !(fabs(d) <= 0.03125);
   if (__any(big)) {
-    double sf, cf;
-    fast_sincos(d, sf, cf);
+    double sf, cf, df = d;
+    if constexpr (BRANCH) asm volatile("" : "+v"(df));
+    fast_sincos(df, sf, cf);
     sd = big ? sf : sd;
     cd = big ? cf : cd;
   }

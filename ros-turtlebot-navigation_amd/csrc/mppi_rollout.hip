@@ -450,6 +450,12 @@ __global__ __launch_bounds__(kWave * MAXW) void mppi_rollout_scan(RolloutArgs a,
 //      records[T][K/R][8], the same record the partials kernel writes for a 2048-rollout slice.
 // The combine then merges K/R records per step instead of K/2048.  Numerics: the sums are wave-scan trees
 // instead of sequential chains (a few 1e-16 relative on x, y, theta, J — inside the 1e-11 J assertion).
+// a + b with b rounded on its own: the product that forms b is not contracted into the sum (mppi*.hip are compiled with
+// -ffp-contract=fast-honor-pragmas).  The lane-local increments below all used to pass through a select, which had the same effect.
+__device__ __forceinline__ double add_unfused(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
 template <int TRIG, int R, int TL, int RNG>
 __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __restrict__ u_p, const double* __restrict__ ahead,
                                                                 const uint64_t* __restrict__ ahead_tag, const uint64_t* __restrict__ tick0,
@@ -530,26 +536,31 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
     }
     double v[TL], w[TL], ctrl[TL], pth[TL];
     double run = 0.0;
+    auto live = [&](int q, double inc) { return (q == 0 || lane * TL + q < T) ? inc : 0.0; };
 #pragma unroll
     for (int q = 0; q < TL; ++q) {
       const int i = lane * TL + q;
       const bool in = i < T;
-      const double ul = in ? uL[q] + dl[q] : 0.0;  // mppi.cpp:93 — rollout controls are not clamped
-      const double ur = in ? uR[q] + dr[q] : 0.0;
+      // (a padding step, i >= T, repeats step T - 1's controls.  A lane whose FIRST step is padding holds no live step, and the
+      //  forward scans carry values to higher lanes only: nothing of it reaches a live step, so its increments are not zeroed.  A
+      //  second step (TL = 2, odd T) can be padding beside a live first one: the lane's start is scan - run, which rounds with run,
+      //  so that increment stays zero — `live`.  Every loss of a padding step is zeroed in front of the backward scan.)
+      const double ul = uL[q] + dl[q];  // mppi.cpp:93 — rollout controls are not clamped
+      const double ur = uR[q] + dr[q];
       if (in) { nL[i * RP + r] = dl[q]; nR[i * RP + r] = dr[q]; }
       ctrl[q] = (ul * a.R[0]) * ul + (ur * a.R[1]) * ur;
       if constexpr (TRIG == 4) {  // exact arc: (v, w) hold the step's body-frame displacement (xn, yn)
         double thn;
         arc_body_step(a, ul, ur, v[q], w[q], thn);
-        run += in ? thn : 0.0;
+        run = add_unfused(run, live(q, thn));
       } else {
         v[q] = a.half_r * (ul + ur);
         w[q] = a.r_over_b * (ur - ul);
-        run += in ? a.h6 * (((w[q] + 2.0 * w[q]) + 2.0 * w[q]) + w[q]) : 0.0;
+        run = add_unfused(run, live(q, a.h6 * (((w[q] + 2.0 * w[q]) + 2.0 * w[q]) + w[q])));
       }
       pth[q] = run;  // lane-local heading change AFTER step q
     }
-    const double th_lane = a.x0[2] + (tbnav::wave_scan_incl(run, lane) - run);  // heading at the start of this lane's steps
+    const double th_lane = a.x0[2] + (tbnav::wave_scan_incl<true>(run, lane) - run);  // heading at the start of this lane's steps
     double runx = 0.0, runy = 0.0, px[TL], py[TL];
 #pragma unroll
     for (int q = 0; q < TL; ++q) {
@@ -559,9 +570,8 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
         // feedforward builds Twb from the CURRENT heading: the raw x0 for the first step, normalised afterwards
         if (lane * TL + q > 0) hth = normalize_angle_pi(hth);
         fast_sincos(hth, s1, c1);
-        const bool in4 = lane * TL + q < T;
-        runx += in4 ? (c1 * v[q] - s1 * w[q]) : 0.0;
-        runy += in4 ? (s1 * v[q] + c1 * w[q]) : 0.0;
+        runx = add_unfused(runx, live(q, c1 * v[q] - s1 * w[q]));
+        runy = add_unfused(runy, live(q, s1 * v[q] + c1 * w[q]));
         px[q] = runx;
         py[q] = runy;
         continue;
@@ -572,7 +582,7 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
         fast_sincos(hth + a.h * w[q], s4, c4);
       } else {
         double sd, cd;
-        small_sincos(a.h * (0.5 * w[q]), sd, cd);
+        small_sincos<true>(a.h * (0.5 * w[q]), sd, cd);
         c2 = c1 * cd - s1 * sd;
         s2 = s1 * cd + c1 * sd;
         const double s2d = 2.0 * sd * cd, c2d = 1.0 - 2.0 * sd * sd;
@@ -580,14 +590,13 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
         s4 = s1 * c2d + c1 * s2d;
       }
       const double k1x = v[q] * c1, k1y = v[q] * s1, k2x = v[q] * c2, k2y = v[q] * s2, k4x = v[q] * c4, k4y = v[q] * s4;
-      const bool in = lane * TL + q < T;
-      runx += in ? a.h6 * (((k1x + 2.0 * k2x) + 2.0 * k2x) + k4x) : 0.0;
-      runy += in ? a.h6 * (((k1y + 2.0 * k2y) + 2.0 * k2y) + k4y) : 0.0;
+      runx = add_unfused(runx, live(q, a.h6 * (((k1x + 2.0 * k2x) + 2.0 * k2x) + k4x)));
+      runy = add_unfused(runy, live(q, a.h6 * (((k1y + 2.0 * k2y) + 2.0 * k2y) + k4y)));
       px[q] = runx;
       py[q] = runy;
     }
-    const double x_lane = a.x0[0] + (tbnav::wave_scan_incl(runx, lane) - runx);
-    const double y_lane = a.x0[1] + (tbnav::wave_scan_incl(runy, lane) - runy);
+    const double x_lane = a.x0[0] + (tbnav::wave_scan_incl<true>(runx, lane) - runx);
+    const double y_lane = a.x0[1] + (tbnav::wave_scan_incl<true>(runy, lane) - runy);
     double suf[TL];
     run = 0.0;
 #pragma unroll
@@ -597,7 +606,7 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
       const double e0 = (x_lane + px[q]) - a.xd[0], e1 = (y_lane + py[q]) - a.xd[1], e2 = th_after - a.xd[2];
       double l = (i == T - 1) ? ((e0 * a.P1[0]) * e0 + (e1 * a.P1[1]) * e1) + (e2 * a.P1[2]) * e2      // mppi.cpp:105 overwrites
                               : (((e0 * a.Q[0]) * e0 + (e1 * a.Q[1]) * e1) + (e2 * a.Q[2]) * e2) + ctrl[q];
-      if (i >= T) l = 0.0;
+      if (i >= T) l = 0.0;  // (the one zero the padding lanes need: this scan runs towards the lower lanes)
       run = l + run;
       suf[q] = run;  // lane-local suffix sum from the lane's last step
     }
@@ -619,6 +628,7 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
   const double inf = __builtin_huge_val();
   const int rr = tid % R;
   const bool ok = k0 + rr < K;
+  const double n = min(R, K - k0);  // rollouts of this workgroup: what summing ok ? 1.0 : 0.0 over the group gives
   for (int t = tid / R; t < T; t += nthr / R) {
     const double j = ok ? Jl[t * RP + rr] : inf;
     const double l = ok ? nL[t * RP + rr] : 0.0, rg = ok ? nR[t * RP + rr] : 0.0;
@@ -629,7 +639,7 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
     // exp(-(J - min)/lambda) with the reference's association: (J - min) * -1.0 / lambda (mppi.cpp:117)
     const double e = ok ? exp(div_lambda((j - mn) * -1.0, lam)) : 0.0;
     const double A = tbnav::group_reduce_dpp<R>(e, gsum), B = tbnav::group_reduce_dpp<R>(e * l, gsum), C = tbnav::group_reduce_dpp<R>(e * rg, gsum);
-    const double D = tbnav::group_reduce_dpp<R>(l, gsum), E = tbnav::group_reduce_dpp<R>(rg, gsum), n = tbnav::group_reduce_dpp<R>(ok ? 1.0 : 0.0, gsum);
+    const double D = tbnav::group_reduce_dpp<R>(l, gsum), E = tbnav::group_reduce_dpp<R>(rg, gsum);
     if (rr == 0) {
       double* rec = records + ((size_t)t * S + blockIdx.x) * TBNAV_MPPI_REC;
       rec[0] = mn; rec[1] = A; rec[2] = B; rec[3] = C; rec[4] = D; rec[5] = E; rec[6] = n; rec[7] = 0.0;
