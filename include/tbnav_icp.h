@@ -135,17 +135,56 @@
  *  of tests/rbpf_cases.py, 1 cm range noise): a true match 0.76-0.90; the truth outside the window 0.14; the wrong room 0.42; a
  *  random cloud 0.09.  On the pairs above the search lands within one cell and 1 degree of the truth, and the ICP started
  *  from it ends 1.7 mm / 6.6 mrad off after 6 iterations.
- *  KNOWN LIMITS.  The search cannot tell an unobservable direction from an observable one: two noise-free scans of a corridor
- *  taken 10 cm apart along it are identical, the search overlays them and so moves the guess BACK by 10 cm.  slack_q10 = 64
- *  kept the guess on one noisy corridor sample and 32 did not; one sample is not a rule.  A caller who relies on the line
- *  metric's corridor behaviour leaves the search off there.  Translation accuracy is one cell: the ICP behind the search is
- *  what refines it.
+ *  THE SHAPE OF THE SCORE VOLUME (an addition to the search, off by default, tbnav_icp_set_search_shape;
+ *  csrc/icp_search_shape.hip; restated in tests/icp_search_shape_restatement.py, the integers reproduced exactly and the doubles
+ *  by the same host arithmetic).  The search alone cannot tell an unobservable direction from an observable one: two noise-free
+ *  scans of a corridor taken 10 cm apart along it are identical, the search overlays them and so moves the guess BACK by 10 cm.
+ *  The score volume holds what is needed to see that: in a corridor the high scores form a ridge along it, in a room a compact
+ *  blob.  With the shape on, the guess is kept along the direction(s) in which the chosen angle's scores are flat.
+ *  F1. Parameters (tbnav_icp_search_shape_params; defaults in brackets): drop_q10 [256, 0..1023] how far below the chosen score
+ *      a candidate still counts, in 1/1024 of it; flat_cells2 [2.0, finite and > 0] the second moment, in cells^2, above which a
+ *      direction is flat.  Anything else is TBNAV_ERR_INVALID_ARG and changes nothing.
+ *  F2. Weights, after S6 has chosen (ia, iy*, ix*) with score best: floor = best - (uint32)(((uint64)best * drop_q10) >> 10); for
+ *      every candidate (iy, ix) of slice ia ONLY, all nl^2 of them: w = score > floor ? score - floor : 0.
+ *  F3. Integer sums, dx = ix - wl, dy = iy - wl: S0 = sum w, Sx = sum w*dx, Sy = sum w*dy, Sxx = sum w*dx^2, Sxy = sum w*dx*dy,
+ *      Syy = sum w*dy^2, cells = the number of candidates with w > 0.  Exact integers (int64 on the device: w < 2^20,
+ *      dx^2 <= 2^8, at most 1089 cells, so every sum is below 2^39); no order is prescribed.
+ *  F4. Moments, on the HOST in fp64, every product and sum as parenthesised, sqrt from glibc (S0 > 0):
+ *      mx = Sx/S0, my = Sy/S0; a = (Sxx/S0) - (mx*mx), b = (Sxy/S0) - (mx*my), c = (Syy/S0) - (my*my);
+ *      hd = 0.5*(a - c), h = sqrt((hd*hd) + (b*b)); l1 = (0.5*(a + c)) + h, l2 = (0.5*(a + c)) - h.
+ *      Major axis, with no transcendental: v = hd >= 0 ? (hd + h, b) : (b, h - hd), n = sqrt((v.x*v.x) + (v.y*v.y)),
+ *      e = n > 0 ? (v.x/n, v.y/n) : (1, 0).
+ *  F5. Kind and result, d = ((double)(ix* - wl), (double)(iy* - wl)):
+ *      kind 0 (compact: S0 == 0, or not l1 > flat_cells2): T is S7's, bit for bit.
+ *      kind 1 (one flat direction: l1 > flat_cells2 and not l2 > flat_cells2): p = (d.x*e.x) + (d.y*e.y),
+ *      d' = (d.x - (p*e.x), d.y - (p*e.y)); T.x = x0 + (d'.x * resolution), T.y = y0 + (d'.y * resolution).
+ *      kind 2 (l2 > flat_cells2): d' = (0, 0), the translation is the guess's.
+ *      The angle is S7's in every kind; quality, accepted, at_edge, candidates, ia / iy / ix are S7's, unchanged.  info->T is the
+ *      shaped T, and that is what S8 hands to the ICP.
+ *  F6. Record (tbnav_icp_search_shape): the six sums, l1, l2, e, cells, kind, T_raw = S7's T, computed = 1.  computed = 0 and
+ *      everything else zero when the shape is off or no search ran.  With S0 == 0: l1 = l2 = ex = ey = 0.
+ *  flat_cells2 = 2.0 is a design constant, not a measurement.  Where it sits (a CPU prototype of this contract, 360 beams, the
+ *  default search parameters, 1 cm range noise): along a 2 m wide corridor l1 is 13.4-20.1 cells^2 (14.8 without noise) and
+ *  across it l2 is 0.10-0.17; over 7 + 7 consecutive pairs in the two rooms of tests/rbpf_cases.py the largest l1 is 0.48 / 0.82,
+ *  and 0.48 for ROOM_BENCH's 0.65 m bad guess with lin_cells = 14.  A uniform distribution over a window of +-2 cells has
+ *  variance exactly 2.0: windows with lin_cells <= 2 can never be declared flat.  On the corridor pairs (robot 10 cm further
+ *  along it, guess = truth) the search alone moves the guess 10-36 cm back and the line metric then ends 7.5-36 cm from the
+ *  truth; with the shape it ends 0.8-3.9 mm from it, and a guess also 15 cm and 0.05 rad off ACROSS the corridor ends 1.3 mm off
+ *  (32 mm without the search, 128 mm with the search alone): the correction across the corridor is kept.
+ *  KNOWN LIMITS.  A guess that is wrong ALONG an unobserved direction cannot be repaired by anyone: the shape only keeps the
+ *  search from making it worse.  Only the translation is examined, and only in the chosen angle's slice: an angle the scan does
+ *  not determine (a round room) is not detected.  The point metric still pulls the two scans of a corridor together afterwards;
+ *  the line metric is the one that keeps what the shape kept.  Translation accuracy of the search is one cell: the ICP behind
+ *  it is what refines it.
  *  KERNELS (csrc/icp_search.hip): icp_search_table, one workgroup per pair, stamps the target into a byte table in LDS (a
  *  compare-and-swap maximum on the byte's dword) and writes it padded with wl zero cells on every side; icp_search_score, one
  *  workgroup of 256 threads per (pair, angle), keeps the padded table and its angle's base cells in LDS, each thread owning
  *  translations and walking the points (base cells outside the table, whose window is only partly inside, take a
  *  bounds-tested path), and reduces one 64-bit key (score high, inverted rank low) per workgroup; icp_search_select reduces
  *  the na keys.  slack_q10 > 0 scores a second time against thr.  n_beams <= TBNAV_ICP_MAX_BEAMS with either metric.
+ *  icp_search_shape (csrc/icp_search_shape.hip), one workgroup per pair behind the final icp_search_select and only when the
+ *  shape is asked for, scores the chosen angle once more in the same way and reduces the integers of F3; its 64-byte record
+ *  comes back in the synchronisation that brings the selection back: no further synchronisation.
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
@@ -307,6 +346,38 @@ int tbnav_icp_search_scores(tbnav_icp* h, const float* target_scan, const float*
                             const double T_init[3], double T_out[3], tbnav_icp_search_info* info, uint32_t* scores);
 /* test hook: the table (S4) of one scan taken as a target: table [n][n] */
 int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uint8_t* table);
+
+/* ---- the shape of the score volume (F1-F6 of the CORRELATIVE SEARCH section) ---- */
+typedef struct tbnav_icp_search_shape_params {
+  int32_t drop_q10;     /* 256 */
+  int32_t reserved;
+  double flat_cells2;   /* 2.0 */
+} tbnav_icp_search_shape_params;
+
+typedef struct tbnav_icp_search_shape {
+  int64_t S0, Sx, Sy, Sxx, Sxy, Syy;  /* F3 */
+  double l1, l2, ex, ey;              /* F4 */
+  double T_raw[3];                    /* S7's T */
+  int32_t cells;
+  int32_t kind;                       /* F5: 0 compact, 1 one flat direction, 2 flat in both */
+  int32_t computed;                   /* 0: the shape is off or no search ran; all else is 0 then */
+  int32_t reserved;
+} tbnav_icp_search_shape;
+
+void tbnav_icp_default_search_shape_params(tbnav_icp_search_shape_params* p);
+/* turns the shape on wherever a search runs: tbnav_icp_match / _step / _step_batch (its realignment launches included) and the
+ * stateless tbnav_icp_search; params == NULL turns it off (and the handle's shape parameters go back to the defaults).  A new
+ * handle has it off.  It is stored but idle while the search itself is off (tbnav_icp_search honours it all the same, as it
+ * does the search parameters).  Parameters outside F1's limits are TBNAV_ERR_INVALID_ARG and change nothing. */
+int tbnav_icp_set_search_shape(tbnav_icp* h, const tbnav_icp_search_shape_params* params);
+/* either output may be null; params are the defaults while the shape is off */
+int tbnav_icp_get_search_shape(const tbnav_icp* h, int32_t* on, tbnav_icp_search_shape_params* params);
+/* the shape record beside tbnav_icp_last_search's, with the same lifetime (computed = 0 when none was formed) */
+int tbnav_icp_last_search_shape(const tbnav_icp* h, tbnav_icp_search_shape* shape);
+/* test hook, stateless: tbnav_icp_search with the shape applied and its record returned whether or not the handle has the
+ * shape on (with the handle's shape parameters, the defaults while it is off).  info and shape are required. */
+int tbnav_icp_search_with_shape(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
+                                const double T_init[3], double T_out[3], tbnav_icp_search_info* info, tbnav_icp_search_shape* shape);
 
 #ifdef __cplusplus
 }

@@ -116,6 +116,18 @@ class IcpSearchInfo(C.Structure):
                 ("accepted", C.c_int32), ("searched", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IcpSearchShapeParams(C.Structure):
+    """tbnav_icp_search_shape_params (include/tbnav_icp.h, F1)."""
+    _fields_ = [("drop_q10", C.c_int32), ("reserved", C.c_int32), ("flat_cells2", C.c_double)]
+
+
+class IcpSearchShape(C.Structure):
+    """tbnav_icp_search_shape (F6)."""
+    _fields_ = [("S0", C.c_int64), ("Sx", C.c_int64), ("Sy", C.c_int64), ("Sxx", C.c_int64), ("Sxy", C.c_int64), ("Syy", C.c_int64),
+                ("l1", C.c_double), ("l2", C.c_double), ("ex", C.c_double), ("ey", C.c_double), ("T_raw", C.c_double * 3),
+                ("cells", C.c_int32), ("kind", C.c_int32), ("computed", C.c_int32), ("reserved", C.c_int32)]
+
+
 ICP_SEARCH_MAX_SIDE, ICP_SEARCH_MAX_STAMP, ICP_SEARCH_MAX_LIN, ICP_SEARCH_MAX_ANG = 208, 8, 16, 90
 
 
@@ -304,6 +316,11 @@ def lib() -> C.CDLL:
         "tbnav_icp_search": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo)]),
         "tbnav_icp_search_scores": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), vp]),
         "tbnav_icp_search_table": (C.c_int, [vp, vp, i32, vp]),
+        "tbnav_icp_default_search_shape_params": (None, [C.POINTER(IcpSearchShapeParams)]),
+        "tbnav_icp_set_search_shape": (C.c_int, [vp, C.POINTER(IcpSearchShapeParams)]),
+        "tbnav_icp_get_search_shape": (C.c_int, [vp, C.POINTER(i32), C.POINTER(IcpSearchShapeParams)]),
+        "tbnav_icp_last_search_shape": (C.c_int, [vp, C.POINTER(IcpSearchShape)]),
+        "tbnav_icp_search_with_shape": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), C.POINTER(IcpSearchShape)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -62,6 +62,9 @@ struct IcpSearch {
   bool on = false;
   tbnav_icp_search_params p{};      // the defaults while the search is off
   tbnav_icp_search_info last{};     // tbnav_icp_last_search
+  bool shape_on = false;            // tbnav_icp_set_search_shape (F1-F6): idle while the search itself is off
+  tbnav_icp_search_shape_params shape_p{};   // the defaults while the shape is off
+  tbnav_icp_search_shape last_shape{};       // tbnav_icp_last_search_shape
   tbnav_icp_search_params stamp_of{};  // the parameters d_stamp was built from
   bool have_stamp = false;
   uint8_t* d_stamp = nullptr;       // [(2k+1)^2]
@@ -77,7 +80,9 @@ struct IcpSearch {
   size_t tgt_cap = 0;
   uint32_t* d_scores = nullptr;     // the test hook's score volume
   size_t scores_cap = 0;
-  std::vector<unsigned char> h_in, h_sel;
+  void* d_shape = nullptr;          // [chunk] the integers of F3 (icp_search_shape.hip)
+  size_t shape_cap = 0;
+  std::vector<unsigned char> h_in, h_sel, h_shape;
 };
 
 }  // namespace tbnav_icpdev
@@ -107,6 +112,7 @@ struct tbnav_icp {
   tbnav_icpdev::IcpSearch search;
   std::vector<std::array<double, 3>> h_init;        // T_init of h_pairs, as given (the search starts from the doubles)
   std::vector<tbnav_icp_search_info> h_sinfo;       // the search record of h_pairs (run_pairs)
+  std::vector<tbnav_icp_search_shape> h_sshape;     // and the shape record beside it (computed = 0 where the shape did not run)
 };
 
 namespace tbnav_icpdev {
@@ -117,7 +123,9 @@ int ensure_scans(tbnav_icp* h, size_t floats);
 
 // icp_search.hip: the search of h->h_pairs[0, n_pairs) from h->h_init (scans already in d_scans / d_stored, the beam table
 // built) with parameters sp -> h->h_sinfo[0, n_pairs).  scores (n_pairs == 1 only): the whole score volume, or null.
-int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores);
+// shp: the shape of the score volume (F1-F6) behind the selection -> h->h_sshape and the shaped T in h->h_sinfo, or null.
+int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
+                 const tbnav_icp_search_shape_params* shp);
 void search_free(tbnav_icp* h);
 
 }  // namespace tbnav_icpdev

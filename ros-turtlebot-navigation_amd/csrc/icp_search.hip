@@ -13,7 +13,8 @@
 //                      laser's range).  The workgroup reduces one 64-bit key, score high and inverted rank low.
 //   icp_search_select  one wave per pair: the maximum of the na keys, the candidate count and thr.
 // slack_q10 > 0 scores a second time against thr (pass 1: the key is the inverted rank alone, among score >= thr).
-// The score volume itself is written only for the test hook.
+// The score volume itself is written only for the test hook.  The shape of the score volume (F1-F6) is icp_search_shape.hip's:
+// its kernel is launched here behind the final icp_search_select and its record comes back with the selection.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -22,6 +23,7 @@
 
 #include "common.hpp"
 #include "icp_device.hpp"
+#include "icp_search_device.hpp"
 #include "tbnav_icp.h"
 
 namespace {
@@ -32,36 +34,11 @@ constexpr int kMaxStampSide = 2 * TBNAV_ICP_SEARCH_MAX_STAMP + 1;
 constexpr int kChunk = 1024;      // pairs per launch: bounds the table memory (43 KB a pair at the largest table)
 constexpr int kRankLinBits = 18;  // the linear index (< 181 * 33 * 33 = 197109) below D (<= 90^2 + 2 * 16^2) in the rank
 
-struct SearchConst {
-  double E, inv;
-  int n, side, wl, wa, k, nl, na;   // side = n + 2*wl
-  int tab_stride;                   // bytes of one padded table, a multiple of 16
-  unsigned slack;
-};
-
-struct SearchPair {
-  int32_t tgt, src;
-  double x0, y0;
-};
-
 // what one (pair, angle) workgroup leaves
 struct SearchRec {
   unsigned long long key;
   uint32_t count, points;
 };
-
-// what the host reads per pair
-struct SearchSel {
-  uint32_t score, lin, count, points, tgt_points, thr;
-};
-
-// floor((v + E) * inv) as an int; false: not a number, or so far out that neither a stamp nor a window reaches the table
-__device__ __forceinline__ bool cell_of(double v, double E, double inv, int& c) {
-  const double f = floor((v + E) * inv);
-  if (!(f >= -65536.0 && f <= 65536.0)) return false;
-  c = (int)f;
-  return true;
-}
 
 // table byte idx <- max(itself, v) by compare-and-swap on its dword
 __device__ __forceinline__ void byte_max(uint32_t* words, int idx, uint32_t v) {
@@ -117,21 +94,6 @@ __global__ __launch_bounds__(kThreads) void icp_search_table(const float* __rest
   uint4* out = reinterpret_cast<uint4*>(tables + (size_t)blockIdx.x * (size_t)sc.tab_stride);
   for (int i = t; i < sc.tab_stride / 16; i += kThreads) out[i] = lds_tab[i];
   if (t == 0) tgt_points[blockIdx.x] = n_points;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, kWave);
-  return v;
 }
 
 // blockIdx.x: the angle ia; blockIdx.y: the pair.  pass 0: the key is (score, inverted rank), count = the candidates at this
@@ -377,15 +339,18 @@ void search_free(tbnav_icp* h) {
   (void)hipFree(S.d_sel);
   (void)hipFree(S.d_tgt_points);
   (void)hipFree(S.d_scores);
+  (void)hipFree(S.d_shape);
   S = IcpSearch{};
 }
 
-int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores) {
-  if (!params_ok(sp) || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS || (scores && n_pairs != 1)) return TBNAV_ERR_INVALID_ARG;
+int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
+                 const tbnav_icp_search_shape_params* shp) {
+  if (!params_ok(sp) || (shp && !shape_params_ok(*shp)) || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS || (scores && n_pairs != 1)) return TBNAV_ERR_INVALID_ARG;
   IcpSearch& S = h->search;
   const SearchConst sc = make_const(sp);
   if (int rc = ensure_stamp(h, sp)) return rc;
   h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
+  h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
   const size_t vol = (size_t)sc.na * sc.nl * sc.nl;
   if (scores)
     if (int rc = ensure(S.d_scores, S.scores_cap, sizeof(uint32_t) * vol)) return rc;
@@ -429,6 +394,12 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
                          static_cast<SearchSel*>(S.d_sel), sc, 1);
       TBNAV_HIP(hipGetLastError());
     }
+    if (shp) {
+      if (int rc = ensure(S.d_shape, S.shape_cap, sizeof(ShapeRec) * (size_t)n)) return rc;
+      if (int rc = launch_shape(h, n, n_beams, sc, d_pairs, d_rot, *shp)) return rc;
+      S.h_shape.resize(sizeof(ShapeRec) * (size_t)n);
+      TBNAV_HIP(hipMemcpyAsync(S.h_shape.data(), S.d_shape, sizeof(ShapeRec) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
     S.h_sel.resize(sizeof(SearchSel) * (size_t)n);
     TBNAV_HIP(hipMemcpyAsync(S.h_sel.data(), S.d_sel, sizeof(SearchSel) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     if (scores) TBNAV_HIP(hipMemcpyAsync(scores, S.d_scores, sizeof(uint32_t) * vol, hipMemcpyDeviceToHost, h->stream));
@@ -453,6 +424,8 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
       o.accepted = (o.quality >= sp.min_quality && s.points > 0u && s.tgt_points > 0u) ? 1 : 0;
       o.searched = 1;
       o.reserved = 0;
+      if (shp)
+        shape_finish(reinterpret_cast<const ShapeRec*>(S.h_shape.data())[i], sp, *shp, T.data(), &o, &h->h_sshape[(size_t)(first + i)]);
     }
   }
   return TBNAV_OK;
@@ -502,8 +475,12 @@ int tbnav_icp_last_search(const tbnav_icp* h, tbnav_icp_search_info* info) {
   return TBNAV_OK;
 }
 
-int tbnav_icp_search_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3],
-                            double T_out[3], tbnav_icp_search_info* info, uint32_t* scores) {
+namespace {
+
+// the stateless entries: the search of one pair with the handle's parameters; the shape when the handle has it on, or when
+// shape_out asks for it
+int search_one(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3], double T_out[3],
+               tbnav_icp_search_info* info, uint32_t* scores, tbnav_icp_search_shape* shape_out) {
   if (!h || !target_scan || !source_scan || !T_init || !T_out || !info || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS)
     return TBNAV_ERR_INVALID_ARG;
   DevGuard guard(h->device);
@@ -516,15 +493,30 @@ int tbnav_icp_search_scores(tbnav_icp* h, const float* target_scan, const float*
   pr.tgt = 0; pr.src = 1;
   h->h_pairs.assign(1, pr);
   h->h_init.assign(1, {T_init[0], T_init[1], T_init[2]});
-  if (int rc = search_pairs(h, 1, n_beams, h->search.p, scores)) return rc;
+  const bool shape = h->search.shape_on || shape_out;
+  if (int rc = search_pairs(h, 1, n_beams, h->search.p, scores, shape ? &h->search.shape_p : nullptr)) return rc;
   *info = h->h_sinfo[0];
+  if (shape_out) *shape_out = h->h_sshape[0];
   T_out[0] = info->T[0]; T_out[1] = info->T[1]; T_out[2] = info->T[2];
   return TBNAV_OK;
 }
 
+}  // namespace
+
+int tbnav_icp_search_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3],
+                            double T_out[3], tbnav_icp_search_info* info, uint32_t* scores) {
+  return search_one(h, target_scan, source_scan, n_beams, T_init, T_out, info, scores, nullptr);
+}
+
 int tbnav_icp_search(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3],
                      double T_out[3], tbnav_icp_search_info* info) {
-  return tbnav_icp_search_scores(h, target_scan, source_scan, n_beams, T_init, T_out, info, nullptr);
+  return search_one(h, target_scan, source_scan, n_beams, T_init, T_out, info, nullptr, nullptr);
+}
+
+int tbnav_icp_search_with_shape(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
+                                const double T_init[3], double T_out[3], tbnav_icp_search_info* info, tbnav_icp_search_shape* shape) {
+  if (!shape) return TBNAV_ERR_INVALID_ARG;
+  return search_one(h, target_scan, source_scan, n_beams, T_init, T_out, info, nullptr, shape);
 }
 
 int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uint8_t* table) {

@@ -28,6 +28,11 @@
 // asked for: the two overloads above keep their meaning.  -DTBNAV_SCAN_ALIGNMENT_SEARCH beside
 // -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP makes the constructor turn the search on with its default parameters; it only changes a
 // default argument as well (alone it has no effect).
+//
+// ICPSearch::shape = true adds the shape of the search's score volume (tbnav_icp.h, items F1-F6; tbnav_icp_set_search_shape):
+// along a direction in which the scores are flat, a corridor's axis, the guess is kept instead of being pulled to where the two
+// scans overlay.  Off unless asked for.  -DTBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE beside the three defines above makes the
+// constructor's search carry shape = true; it only changes a default argument too (without the search it has no effect).
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -56,6 +61,12 @@
 #define TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT false
 #endif
 
+#ifdef TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT true
+#else
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT false
+#endif
+
 namespace bmapping {
 
 using rigid2d::Transform2D;
@@ -74,6 +85,9 @@ struct ICPSearch {
   double ang_step = 3.14159265358979323846 / 180.0;
   int slack_q10 = 0;           ///< selection slack in 1/1024, 0..1023
   double min_quality = 0.5;    ///< acceptance threshold
+  bool shape = false;          ///< the shape of the score volume (tbnav_icp_search_shape_params with its defaults below)
+  int shape_drop_q10 = 256;    ///< how far below the chosen score a candidate still counts, in 1/1024, 0..1023
+  double shape_flat_cells2 = 2.0;  ///< second moment (cells^2) above which a direction is flat, > 0
 };
 
 class ScanAlignment {
@@ -82,10 +96,14 @@ class ScanAlignment {
   using Matcher = std::function<bool(Transform2D&, const Transform2D&, const std::vector<float>&, const std::vector<float>&)>;
 
   ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT,
-                ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT, bool device_search = TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT)
+                ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT, bool device_search = TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT,
+                bool device_search_shape = TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT)
       : props_(props), Trs_(Trs) {
-    if (device_icp && device_search) useDeviceICP(-1, device_metric, ICPSearch());
-    else if (device_icp) useDeviceICP(-1, device_metric);
+    if (device_icp && device_search) {
+      ICPSearch search;
+      search.shape = device_search_shape;
+      useDeviceICP(-1, device_metric, search);
+    } else if (device_icp) useDeviceICP(-1, device_metric);
   }
 
   /// plug in a real scan matcher (e.g. a PCL ICP wrapper in a catkin workspace that has PCL)

@@ -1,6 +1,6 @@
 // cloud_alignment_device.cpp — ScanAlignment::useDeviceICP: the device ICP of include/tbnav_icp.h as the shim's matcher, with
 // its point-to-point metric (the reference's) or its point-to-line metric (an addition), and optionally its correlative search
-// in front of either (an addition too).
+// in front of either (an addition too), with or without the shape of its score volume.
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -46,6 +46,14 @@ void ScanAlignment::installDeviceICP(int device, ICPMetric metric, const ICPSear
     const int src = tbnav_icp_set_search(raw, &sp);
     if (src == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument("bmapping::ScanAlignment::useDeviceICP: search parameters outside their limits");
     if (src != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(src));
+    if (search->shape) {
+      tbnav_icp_search_shape_params fp;
+      tbnav_icp_default_search_shape_params(&fp);
+      fp.drop_q10 = search->shape_drop_q10; fp.flat_cells2 = search->shape_flat_cells2;
+      const int frc = tbnav_icp_set_search_shape(raw, &fp);
+      if (frc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument("bmapping::ScanAlignment::useDeviceICP: search shape parameters outside their limits");
+      if (frc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(frc));
+    }
   }
   matcher_ = [h](Transform2D& T, const Transform2D& T_init, const std::vector<float>& target, const std::vector<float>& source) {
     if (target.size() != source.size()) throw std::invalid_argument("bmapping::ScanAlignment: scans of different lengths");

@@ -73,6 +73,49 @@ int hst_icp_pf_run_search(int metric, int search, int lin_cells, int N, int k, d
   } catch (const std::exception& e) { g_icp_err = e.what(); return -1; }
 }
 
+// hst_icp_pf_run_search_shape: the filter with the search (lin_cells as given, all else the defaults) and, shape != 0, the shape
+// of its score volume (drop_q10 and flat_cells2 as given) in front of the ICP; everything else as hst_icp_pf_run_search.
+int hst_icp_pf_run_search_shape(int metric, int shape, int drop_q10, double flat_cells2, int lin_cells, int N, int k, double map_half, uint64_t seed,
+                                const float* scans, int n_beams, int n_scans, const double* odom, const double* u, int32_t* out_ok, double* out_T,
+                                double* out_pose, int32_t* out_neff) {
+  try {
+    if (metric != 0 && metric != 1) throw std::invalid_argument("hst_icp_pf_run_search_shape: metric must be 0 or 1");
+    const double d2r = rigid2d::PI / 180.0;
+    bmapping::LaserProperties props((float)(0.0 * d2r), (float)(360.0 * d2r), (float)(1.0 * d2r), 0.12f, 3.5f, 0.95, 0.0, 0.04, 0.01, 0.5);
+    Transform2D Trs;
+    bmapping::GridMapper grid(0.05, -map_half, map_half, -map_half, map_half, props, Trs);
+    bmapping::ScanAlignment aligner(props, Trs);
+    bmapping::ICPSearch sp;
+    sp.lin_cells = lin_cells;
+    sp.shape = shape != 0;
+    sp.shape_drop_q10 = drop_q10;
+    sp.shape_flat_cells2 = flat_cells2;
+    aligner.useDeviceICP(-1, metric == 1 ? bmapping::ICPMetric::PointToLine : bmapping::ICPMetric::PointToPoint, sp);
+    bmapping::ScanAlignment observer = aligner;  // shares the handle; keeps its own stored scan
+    Transform2D start(Vector2D(odom[1], odom[2]), odom[0]);
+    bmapping::ParticleFilter pf(N, k, 0.1, 0.2, 0.1, 0.2, 1e-10, 1e-10, 1e-10, 1e-10, 1e-8, 1e-8, 1.0, 20.0, 1.0, 10.0, aligner, start, grid);
+    bmapping::getTwister().seed(seed);
+    for (int s = 0; s < n_scans; ++s) {
+      std::vector<float> scan(scans + (size_t)s * n_beams, scans + (size_t)(s + 1) * n_beams);
+      rigid2d::Pose prev, cur;
+      prev.theta = odom[3 * s]; prev.x = odom[3 * s + 1]; prev.y = odom[3 * s + 2];
+      cur.theta = odom[3 * (s + 1)]; cur.x = odom[3 * (s + 1) + 1]; cur.y = odom[3 * (s + 1) + 2];
+      Twist2D tw; tw.w = u[3 * s]; tw.vx = u[3 * s + 1]; tw.vy = u[3 * s + 2];
+      const double dth = rigid2d::normalize_angle_PI(rigid2d::normalize_angle_PI(cur.theta) - rigid2d::normalize_angle_PI(prev.theta));
+      const Transform2D Tinit(Vector2D(cur.x - prev.x, cur.y - prev.y), dth);
+      Transform2D T;
+      out_ok[s] = observer.pclICPWrapper(T, Tinit, scan) ? 1 : 0;
+      const auto d = T.displacement();
+      out_T[3 * s] = d.theta; out_T[3 * s + 1] = d.x; out_T[3 * s + 2] = d.y;
+      pf.SLAM(scan, tw, cur, prev);
+      const auto p = pf.getRobotState().displacement();
+      out_pose[3 * s] = p.theta; out_pose[3 * s + 1] = p.x; out_pose[3 * s + 2] = p.y;
+      out_neff[s] = pf.effectiveParticles();
+    }
+    return 0;
+  } catch (const std::exception& e) { g_icp_err = e.what(); return -1; }
+}
+
 int hst_icp_pf_run_metric(int metric, int N, int k, double map_half, uint64_t seed, const float* scans, int n_beams, int n_scans,
                           const double* odom, const double* u, int32_t* out_ok, double* out_T, double* out_pose, int32_t* out_neff) {
   return hst_icp_pf_run_search(metric, 0, 0, N, k, map_half, seed, scans, n_beams, n_scans, odom, u, out_ok, out_T, out_pose, out_neff);

@@ -10,6 +10,10 @@ search=True | dict(...) (an addition with no counterpart in the reference) puts 
 CORRELATIVE SEARCH section in front of every alignment: it scores every pose of a window round the guess against a table of
 the target scan and starts the ICP from the best one, when that one is good enough.  The default is off.
 
+shape=True | dict(...) beside search (an addition too) measures the shape of the search's score volume (the header's items
+F1-F6) and keeps the guess along a direction in which the scores are flat, a corridor's axis: the search alone pulls two scans of
+a corridor on top of each other.  The default is off.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -71,6 +75,14 @@ _METRICS = {"point": capi.ICP_METRIC_POINT, "line": capi.ICP_METRIC_LINE}
 _SEARCH_FIELDS = tuple(f for f, _ in capi.IcpSearchParams._fields_)
 
 
+_SHAPE_FIELDS = ("drop_q10", "flat_cells2")
+
+
+def _search_shape(r: "capi.IcpSearchShape") -> dict:
+    return dict(S0=r.S0, Sx=r.Sx, Sy=r.Sy, Sxx=r.Sxx, Sxy=r.Sxy, Syy=r.Syy, l1=r.l1, l2=r.l2, ex=r.ex, ey=r.ey, T_raw=tuple(r.T_raw),
+                cells=r.cells, kind=r.kind, computed=r.computed)
+
+
 def _search_info(i: "capi.IcpSearchInfo") -> dict:
     return dict(T=tuple(i.T), quality=i.quality, score=i.score, points=i.points, candidates=i.candidates, ia=i.ia, iy=i.iy,
                 ix=i.ix, at_edge=i.at_edge, accepted=i.accepted, searched=i.searched)
@@ -79,7 +91,7 @@ def _search_info(i: "capi.IcpSearchInfo") -> dict:
 class ScanAlignment:
     """bmapping::ScanAlignment on one MI355X."""
 
-    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0, search=None):
+    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0, search=None, shape=None):
         self._L = capi.lib()
         self.params = params if params is not None else default_params()
         if metric not in _METRICS:
@@ -98,6 +110,54 @@ class ScanAlignment:
             except Exception:
                 self.close()
                 raise
+        if shape is not None and shape is not False:
+            try:
+                self.setSearchShape(**({} if shape is True else dict(shape)))
+            except Exception:
+                self.close()
+                raise
+
+    def setSearchShape(self, *off, **kw):
+        """tbnav_icp_set_search_shape: setSearchShape(drop_q10=..., flat_cells2=...) turns the shape of the score volume on
+        wherever a search runs, with the defaults (tbnav_icp_default_search_shape_params) for what is not named;
+        setSearchShape(None) turns it off.  It is idle while the search itself is off."""
+        if off:
+            if off != (None,) or kw:
+                raise TypeError("setSearchShape(None) turns the shape off; parameters go by keyword")
+            capi.check(self._L.tbnav_icp_set_search_shape(self._h, None), "tbnav_icp_set_search_shape")
+            return
+        p = capi.IcpSearchShapeParams()
+        self._L.tbnav_icp_default_search_shape_params(C.byref(p))
+        for key, v in kw.items():
+            if key not in _SHAPE_FIELDS:
+                raise TypeError(f"setSearchShape: no parameter {key!r} (one of {_SHAPE_FIELDS})")
+            setattr(p, key, v)
+        capi.check(self._L.tbnav_icp_set_search_shape(self._h, C.byref(p)), "tbnav_icp_set_search_shape")
+
+    def searchShapeParams(self):
+        """-> (on, dict of tbnav_icp_search_shape_params) as the handle holds them (the defaults while the shape is off)"""
+        on, p = C.c_int32(), capi.IcpSearchShapeParams()
+        capi.check(self._L.tbnav_icp_get_search_shape(self._h, C.byref(on), C.byref(p)), "tbnav_icp_get_search_shape")
+        return bool(on.value), {f: getattr(p, f) for f in _SHAPE_FIELDS}
+
+    def lastSearchShape(self) -> dict:
+        """the shape record beside lastSearch()'s (computed = 0: none was formed)"""
+        r = capi.IcpSearchShape()
+        capi.check(self._L.tbnav_icp_last_search_shape(self._h, C.byref(r)), "tbnav_icp_last_search_shape")
+        return _search_shape(r)
+
+    def searchWithShape(self, T_init, target_scan, source_scan):
+        """test hook, stateless: search() with the shape applied whether or not the handle has it on
+        -> (accepted, T, info dict, shape dict)"""
+        tgt = np.ascontiguousarray(target_scan, dtype=np.float32)
+        src = np.ascontiguousarray(source_scan, dtype=np.float32)
+        if tgt.size != src.size:
+            raise ValueError("target and source scans must have the same number of beams")
+        out = (C.c_double * 3)()
+        info, rec = capi.IcpSearchInfo(), capi.IcpSearchShape()
+        capi.check(self._L.tbnav_icp_search_with_shape(self._h, tgt.ctypes.data, src.ctypes.data, src.size, _d3(T_init), out,
+                                                       C.byref(info), C.byref(rec)), "tbnav_icp_search_with_shape")
+        return bool(info.accepted), tuple(out), _search_info(info), _search_shape(rec)
 
     def setSearch(self, *off, **kw):
         """tbnav_icp_set_search: setSearch(resolution=..., lin_cells=..., ...) turns the correlative search on for every later

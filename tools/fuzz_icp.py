@@ -2,13 +2,19 @@
 (tests/icp_restatement.py, tests/icp_line_restatement.py), bit for bit (run on the GPU box; tests/test_icp_fuzz_gpu.py runs a
 bounded sweep from a fixed seed inside the suite).
 
-usage: python tools/fuzz_icp.py [n_cases] [seed] [case]      (case: re-run that one case alone, verbosely)
+usage: python tools/fuzz_icp.py [--shape] [n_cases] [seed] [case]      (case: re-run that one case alone, verbosely)
 Every case draws its beam count (1 ... 4096, half of the draws k * 256 + {-1, 0, 1}), metric, laser, valid fraction, kind of
 scan (a room pair; a wrapped-ray pair with exact distance ties; one target point), Trs, max_corr_dist, both epsilons, max_iter
 and the error of its guess from (seed, case), and goes through tbnav_icp_match twice (the second run must give the same bits);
 every fourth also runs six scans through tbnav_icp_step_batch against the restatement's wrapper.  Prints one line per failing
 case with what is needed to reproduce it, and one summary line with the totals: cases per instantiation and per criterion,
 cases that held ties.
+
+--shape: the sweep of the shape of the correlative search's score volume instead (include/tbnav_icp.h, items F1-F6;
+csrc/icp_search_shape.hip) against tests/icp_search_shape_restatement.py with ==: every case draws a room or a corridor at a
+random heading and width, the robot's step, the error of the guess, the window, slack_q10, drop_q10 and flat_cells2
+(draw_shape), goes through tbnav_icp_search_with_shape, and every third through tbnav_icp_match with the search, the shape and
+the line metric on.  The summary line counts the cases per kind.  tests/test_icp_search_shape_fuzz_gpu.py imports draw_shape.
 """
 import math
 import os
@@ -25,12 +31,12 @@ g.load_package()
 import icp_cases as ic
 import icp_line_restatement as LR
 import icp_restatement as R
+import icp_search_restatement as S
+import icp_search_shape_restatement as F
 import oracle_api as orc
 from rtn_amd import icp
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
-only = int(sys.argv[3]) if len(sys.argv) > 3 else -1
+n_cases, seed, only = 200, 0, -1     # set by main()
 
 totals = dict(point_P={}, line_P={}, criterion={}, with_ties=0, batches=0, matches=0)
 
@@ -135,20 +141,94 @@ def one_case(i, verbose=False):
         a.close()
 
 
-fails = 0
-t0 = time.perf_counter()
-for i in range(n_cases):
-    if only >= 0 and i != only:
-        continue
+SHAPE_FIELDS = ("resolution", "half_extent", "sigma", "ang_step", "min_quality", "stamp_cells", "lin_cells", "ang_steps", "slack_q10")
+shape_totals = dict(kind={}, accepted=0, matches=0)
+
+
+def draw_shape(i, seed):
+    """case i of the --shape sweep -> (target scan, source scan, search Params, ShapeParams, guess, "room" | "corridor")"""
+    r = np.random.default_rng([seed, 7, i])
+    scene = "corridor" if r.random() < 0.5 else "room"
+    if scene == "corridor":
+        half = float(r.uniform(0.7, 1.3))
+        walls = (-50.0, 50.0, -half, half)
+        th = float(r.uniform(-math.pi, math.pi))
+        p0 = (th, 0.0, float(r.uniform(-0.2, 0.2)))
+        p1 = (th + float(r.normal(0, 0.01)), float(r.uniform(-0.15, 0.15)), p0[2] + float(r.normal(0, 0.01)))
+    else:
+        walls = (-2.2, 2.2, -2.0, 2.0) if r.random() < 0.5 else (-3.0, 3.0, -2.5, 2.5)
+        p0 = (float(r.uniform(-math.pi, math.pi)), float(r.uniform(-0.3, 0.3)), float(r.uniform(-0.3, 0.3)))
+        p1 = (p0[0] + float(r.normal(0, 0.05)), p0[1] + float(r.uniform(-0.1, 0.1)), p0[2] + float(r.uniform(-0.1, 0.1)))
+    srng = np.random.default_rng([seed, 8, i])
+    tgt = orc.room_scan(p0, walls=walls, rng=srng)
+    src = orc.room_scan(p1, walls=walls, rng=srng)
+    c, sn = math.cos(p0[0]), math.sin(p0[0])                   # the truth in the target scan's frame
+    dx, dy = p1[1] - p0[1], p1[2] - p0[2]
+    truth = (p1[0] - p0[0], c * dx + sn * dy, -sn * dx + c * dy)
+    e = float(r.choice([0.0, 0.5, 1.0]))
+    guess = (truth[0] + e * float(r.normal(0, 0.03)), truth[1] + e * float(r.normal(0, 0.1)), truth[2] + e * float(r.normal(0, 0.1)))
+    sp = S.Params(lin_cells=int(r.choice([3, 6, 6, 6, 10, 16])), ang_steps=int(r.choice([0, 5, 20])),
+                  slack_q10=int(r.choice([0, 0, 0, 32, 64])), stamp_cells=int(r.choice([3, 3, 5])))
+    fp = F.ShapeParams(drop_q10=int(r.choice([64, 256, 256, 256, 512, 1023])), flat_cells2=float(r.choice([0.5, 2.0, 2.0, 2.0, 4.0])))
+    return tgt, src, sp, fp, guess, scene
+
+
+def shape_case(i, verbose=False):
+    tgt, src, sp, fp, guess, scene = draw_shape(i, seed)
+    desc = dict(case=i, seed=seed, scene=scene, guess=guess, search=sp, shape=fp)
+    if verbose:
+        print(desc)
+    p = icp.default_params()
+    L = R.Laser(p.beam_min, p.beam_max, p.beam_delta, p.range_min, p.range_max)
+    a = icp.ScanAlignment(p, metric="line", search={f: getattr(sp, f) for f in SHAPE_FIELDS},
+                          shape=dict(drop_q10=fp.drop_q10, flat_cells2=fp.flat_cells2))
     try:
-        one_case(i, verbose=only >= 0)
-    except Exception as e:  # noqa: BLE001
-        fails += 1
-        print(f"[FAIL] icp case {i} (seed {seed}; replay: python tools/fuzz_icp.py {n_cases} {seed} {i}): {type(e).__name__}: {str(e)[:900]}")
-        if fails <= 3:
-            traceback.print_exc(limit=2)
-for k in ("point_P", "line_P", "criterion"):
-    totals[k] = dict(sorted(totals[k].items()))
-print(f"icp: {n_cases} cases done, failures so far {fails}; {totals}", flush=True)
-print(f"icp: wall time {time.perf_counter() - t0:.1f} s", flush=True)
-sys.exit(1 if fails else 0)
+        want, wsh = F.search(tgt, src, L, guess, sp, fp)
+        acc, T, info, sh = a.searchWithShape(guess, tgt, src)
+        if verbose:
+            print("kernel", info, sh, "\nrestatement", want, wsh)
+        for f in ("T", "quality", "score", "points", "candidates", "ia", "iy", "ix", "at_edge", "accepted", "searched"):
+            assert info[f] == getattr(want, f), (f, desc, info, want)
+        for f in ("S0", "Sx", "Sy", "Sxx", "Sxy", "Syy", "l1", "l2", "ex", "ey", "T_raw", "cells", "kind", "computed"):
+            assert sh[f] == getattr(wsh, f), (f, desc, sh, wsh)
+        assert acc == bool(want.accepted) and T == want.T, desc
+        _count(shape_totals["kind"], wsh.kind)
+        shape_totals["accepted"] += want.accepted
+        if i % 3 == 0:
+            res, _, _ = F.match(tgt, src, L, guess, sp, fp, icp=LR.match, found=(want, wsh))
+            _same(a.pclICP(guess, tgt, src), res, ("match", desc))
+            assert a.lastSearchShape() == sh, desc
+            shape_totals["matches"] += 1
+    finally:
+        a.close()
+
+
+def main():
+    global n_cases, seed, only
+    args = [v for v in sys.argv[1:] if v != "--shape"]
+    shape = "--shape" in sys.argv[1:]
+    n_cases = int(args[0]) if len(args) > 0 else 200
+    seed = int(args[1]) if len(args) > 1 else 0
+    only = int(args[2]) if len(args) > 2 else -1
+    flag = "--shape " if shape else ""
+    fails = 0
+    t0 = time.perf_counter()
+    for i in range(n_cases):
+        if only >= 0 and i != only:
+            continue
+        try:
+            (shape_case if shape else one_case)(i, verbose=only >= 0)
+        except Exception as e:  # noqa: BLE001
+            fails += 1
+            print(f"[FAIL] icp case {i} (seed {seed}; replay: python tools/fuzz_icp.py {flag}{n_cases} {seed} {i}): {type(e).__name__}: {str(e)[:900]}")
+            if fails <= 3:
+                traceback.print_exc(limit=2)
+    for k in ("point_P", "line_P", "criterion"):
+        totals[k] = dict(sorted(totals[k].items()))
+    print(f"icp: {n_cases} cases done, failures so far {fails}; {shape_totals if shape else totals}", flush=True)
+    print(f"icp: wall time {time.perf_counter() - t0:.1f} s", flush=True)
+    sys.exit(1 if fails else 0)
+
+
+if __name__ == "__main__":
+    main()

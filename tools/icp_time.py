@@ -1,5 +1,5 @@
 """Timing of the device ICP (include/tbnav_icp.h) on the GPU:
-python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N] [--search]
+python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N] [--search] [--shape]
   - latency of one synchronous tbnav_icp_step (host clock around the call, which ends in a stream synchronise) at 360 beams
     (1 deg) and 1080 beams (1/3 deg): median / p10 / p90 of 500 scans after 20 of warm-up, a robot driving round a room;
   - tbnav_icp_step_batch over 2000 scans of the same kind of run: median of 5 calls (after one of warm-up), per call and
@@ -12,6 +12,10 @@ python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--ma
   --search: the correlative search in front of the ICP (tbnav_icp_set_search, default parameters), in the same process on the
     same scans: every record above with the search off (the parent's rows) and again with it on under "<name>_search", and
     "search_alone_360" / "_1080": tbnav_icp_search by itself on consecutive scans of the same run;
+  --shape (with --search): the shape of the search's score volume on top of the search (tbnav_icp_set_search_shape, default
+    parameters), in the same process on the same scans: every "<name>_search" record again under "<name>_search_shape", and
+    "search_shape_alone_360" / "_1080": tbnav_icp_search with the shape on; "shape_over_search" holds the differences of the
+    medians (what the shape adds);
   --quick: a few scans only (what a `rocprofv3 --kernel-trace --stats` run of this script needs).
 Kernel times come from a separate rocprofv3 run, not from this script."""
 import argparse
@@ -44,8 +48,8 @@ def loop_run(n, n_beams, beam_delta_deg, seed=1):
     return scans, T_init
 
 
-def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100, search=None):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search)
+def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100, search=None, shape=None):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape)
     scans, T_init = loop_run(n_warm + n_time, n_beams, beam_delta_deg)
     ts, iters, fails, accepted = [], [], 0, 0
     for s in range(n_warm + n_time):
@@ -67,9 +71,9 @@ def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_it
     return rec
 
 
-def search_latency(n_beams, beam_delta_deg, n_warm, n_time):
+def search_latency(n_beams, beam_delta_deg, n_warm, n_time, shape=None):
     """tbnav_icp_search alone (default parameters): each scan of the run against the one before it"""
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg))
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg), shape=shape)
     scans, T_init = loop_run(n_warm + n_time + 1, n_beams, beam_delta_deg)
     ts, acc, qual = [], 0, []
     for s in range(1, n_warm + n_time + 1):
@@ -86,8 +90,8 @@ def search_latency(n_beams, beam_delta_deg, n_warm, n_time):
                 p90_us=float(np.percentile(ts, 90)), accepted=acc, mean_quality=float(np.mean(qual)))
 
 
-def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100, search=None):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search)
+def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100, search=None, shape=None):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape)
     scans, T_init = loop_run(n_scans, n_beams, beam_delta_deg, seed=2)
     ts = []
     for r in range(reps + 1):
@@ -113,7 +117,10 @@ def main():
     ap.add_argument("--metric", choices=("point", "line", "both"), default="point")
     ap.add_argument("--max-iter", type=int, default=100)
     ap.add_argument("--search", action="store_true")
+    ap.add_argument("--shape", action="store_true")
     a = ap.parse_args()
+    if a.shape and not a.search:
+        ap.error("--shape measures what it adds to the search: give --search too")
     n_warm, n_time, reps = (2, 10, 1) if a.quick else (20, 500, 5)
 
     def run(metric):
@@ -124,6 +131,12 @@ def main():
             res.update(step_360_search=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter, search=True),
                        step_1080_search=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter, search=True),
                        batch_2000_search=batch_time(2000, reps, metric=metric, max_iter=a.max_iter, search=True))
+        if a.shape:
+            res.update(step_360_search_shape=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter, search=True, shape=True),
+                       step_1080_search_shape=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter, search=True, shape=True),
+                       batch_2000_search_shape=batch_time(2000, reps, metric=metric, max_iter=a.max_iter, search=True, shape=True))
+            res["shape_over_search"] = {key: res[key + "_search_shape"][t] - res[key + "_search"][t]
+                                        for key, t in (("step_360", "median_us"), ("step_1080", "median_us"), ("batch_2000", "median_ms"))}
         return res
 
     if a.metric == "both":
@@ -137,6 +150,9 @@ def main():
     if a.search:
         res["search_alone_360"] = search_latency(360, 1.0, n_warm, n_time)
         res["search_alone_1080"] = search_latency(1080, 1.0 / 3.0, n_warm, n_time)
+    if a.shape:
+        res["search_shape_alone_360"] = search_latency(360, 1.0, n_warm, n_time, shape=True)
+        res["search_shape_alone_1080"] = search_latency(1080, 1.0 / 3.0, n_warm, n_time, shape=True)
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
