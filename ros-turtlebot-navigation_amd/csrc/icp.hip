@@ -369,30 +369,9 @@ int ensure_table(tbnav_icp* h, int n_beams) {
   return TBNAV_OK;
 }
 
-int ensure_scans(tbnav_icp* h, size_t floats) {
-  if (floats <= h->scans_cap) return TBNAV_OK;
-  if (h->d_scans) TBNAV_HIP(hipFree(h->d_scans));
-  h->d_scans = nullptr;
-  h->scans_cap = 0;
-  TBNAV_HIP(hipMalloc(&h->d_scans, sizeof(float) * floats));
-  h->scans_cap = floats;
-  return TBNAV_OK;
-}
-
 }  // namespace tbnav_icpdev
 
 namespace {
-
-int ensure_pairs(tbnav_icp* h, int n) {
-  if (n <= h->pairs_cap) return TBNAV_OK;
-  if (h->d_pairs) TBNAV_HIP(hipFree(h->d_pairs));
-  if (h->d_out) TBNAV_HIP(hipFree(h->d_out));
-  h->d_pairs = nullptr; h->d_out = nullptr; h->pairs_cap = 0;
-  TBNAV_HIP(hipMalloc(&h->d_pairs, sizeof(IcpPair) * (size_t)n));
-  TBNAV_HIP(hipMalloc(&h->d_out, sizeof(IcpOut) * (size_t)n));
-  h->pairs_cap = n;
-  return TBNAV_OK;
-}
 
 IcpPair make_pair(int tgt, int src, const double T[3]) {
   // pclICP's guess (cloud_alignment.cpp:171-183): float cos / sin / x / y
@@ -423,8 +402,8 @@ int launch(tbnav_icp* h, int n_pairs, int n_beams) {
   const size_t lds = (M::kNormals ? 2 : 1) * sizeof(float2) * (size_t)((n_beams + 3) & ~3);
   typename M::Params mp{};
   if constexpr (M::kNormals) mp = h->line;
-  hipLaunchKernelGGL((icp_align<M, P>), dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
-                     h->d_pairs, h->d_out, h->k, mp);
+  hipLaunchKernelGGL((icp_align<M, P>), dim3(n_pairs), dim3(kThreads), lds, h->stream, h->d_scans.as<float>(), h->d_stored.as<float>(),
+                     h->d_table, n_beams, h->d_pairs.as<IcpPair>(), h->d_out.as<IcpOut>(), h->k, mp);
   TBNAV_HIP(hipGetLastError());
   return TBNAV_OK;
 }
@@ -457,7 +436,8 @@ bool beams_ok(const tbnav_icp* h, int n_beams) {
 // correlative search on (tbnav_icp_set_search) every pair is searched first -> h->h_sinfo, and an accepted search's pose
 // replaces the pair's guess: one host round trip between the search and the alignment (the guess is formed here, with glibc).
 int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
-  if (int rc = ensure_pairs(h, n_pairs)) return rc;
+  if (int rc = h->d_pairs.reserve(sizeof(IcpPair) * (size_t)n_pairs)) return rc;
+  if (int rc = h->d_out.reserve(sizeof(IcpOut) * (size_t)n_pairs)) return rc;
   if (h->search.on) {
     if (int rc = search_pairs(h, n_pairs, n_beams, h->search.p, nullptr, h->search.shape_on ? &h->search.shape_p : nullptr)) return rc;
     for (int i = 0; i < n_pairs; ++i) {
@@ -468,11 +448,11 @@ int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
     h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
     h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
   }
-  TBNAV_HIP(hipMemcpyAsync(h->d_pairs, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(h->d_pairs.ptr, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
   const bool line = h->metric == TBNAV_ICP_METRIC_LINE;
   if (int rc = line ? dispatch<LineMetric>(h, n_pairs, n_beams) : dispatch<PointMetric>(h, n_pairs, n_beams)) return rc;
   h->h_out.resize((size_t)n_pairs);
-  TBNAV_HIP(hipMemcpyAsync(h->h_out.data(), h->d_out, sizeof(IcpOut) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(h->h_out.data(), h->d_out.ptr, sizeof(IcpOut) * (size_t)n_pairs, hipMemcpyDeviceToHost, h->stream));
   TBNAV_HIP(hipStreamSynchronize(h->stream));
   ++h->last_launches;
   return TBNAV_OK;
@@ -481,10 +461,10 @@ int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
 // the test hooks' scratch in d_scans, 4 floats per beam: the uploaded scan at its start, then the flags [n_beams] int and the
 // values [n_beams] float2 that the hook's kernel writes
 int hook_scratch(tbnav_icp* h, const float* scan, int n_beams, int*& flags, float2*& xy) {
-  if (int rc = ensure_scans(h, 4 * (size_t)n_beams)) return rc;
-  flags = reinterpret_cast<int*>(h->d_scans + n_beams);
-  xy = reinterpret_cast<float2*>(h->d_scans + 2 * (size_t)n_beams);  // 8-byte aligned
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_scans.reserve(sizeof(float) * 4 * (size_t)n_beams)) return rc;
+  flags = reinterpret_cast<int*>(h->d_scans.as<float>() + n_beams);
+  xy = reinterpret_cast<float2*>(h->d_scans.as<float>() + 2 * (size_t)n_beams);  // 8-byte aligned
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   return TBNAV_OK;
 }
 
@@ -512,14 +492,9 @@ void first_call(double T_out[3], int32_t* ok, tbnav_icp_info* info) {
 }
 
 int store_scan(tbnav_icp* h, const float* dev_src, const float* host_src, int n_beams) {
-  if (n_beams > h->stored_cap) {
-    if (h->d_stored) TBNAV_HIP(hipFree(h->d_stored));
-    h->d_stored = nullptr; h->stored_cap = 0;
-    TBNAV_HIP(hipMalloc(&h->d_stored, sizeof(float) * (size_t)n_beams));
-    h->stored_cap = n_beams;
-  }
-  if (dev_src) TBNAV_HIP(hipMemcpyAsync(h->d_stored, dev_src, sizeof(float) * (size_t)n_beams, hipMemcpyDeviceToDevice, h->stream));
-  else TBNAV_HIP(hipMemcpyAsync(h->d_stored, host_src, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_stored.reserve(sizeof(float) * (size_t)n_beams)) return rc;
+  if (dev_src) TBNAV_HIP(hipMemcpyAsync(h->d_stored.ptr, dev_src, sizeof(float) * (size_t)n_beams, hipMemcpyDeviceToDevice, h->stream));
+  else TBNAV_HIP(hipMemcpyAsync(h->d_stored.ptr, host_src, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   TBNAV_HIP(hipStreamSynchronize(h->stream));
   h->stored_beams = n_beams;
   h->have_stored = true;
@@ -592,10 +567,7 @@ void tbnav_icp_destroy(tbnav_icp* h) {
     DevGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->d_table);
-    (void)hipFree(h->d_stored);
-    (void)hipFree(h->d_scans);
-    (void)hipFree(h->d_pairs);
-    (void)hipFree(h->d_out);
+    for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out}) b->release();
     search_free(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);
   }
@@ -639,8 +611,8 @@ int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* n
   int* d_has;
   float2* d_nxy;
   if (int rc = hook_scratch(h, scan, n_beams, d_has, d_nxy)) return rc;
-  hipLaunchKernelGGL(icp_normals, dim3(1), dim3(kThreads), sizeof(float2) * (size_t)((n_beams + 3) & ~3), h->stream, h->d_scans,
-                     h->d_table, (int)n_beams, d_nxy, d_has, h->k, h->line);
+  hipLaunchKernelGGL(icp_normals, dim3(1), dim3(kThreads), sizeof(float2) * (size_t)((n_beams + 3) & ~3), h->stream,
+                     h->d_scans.as<float>(), h->d_table, (int)n_beams, d_nxy, d_has, h->k, h->line);
   TBNAV_HIP(hipGetLastError());
   TBNAV_HIP(hipMemcpyAsync(nxy, d_nxy, sizeof(float2) * (size_t)n_beams, hipMemcpyDeviceToHost, h->stream));
   TBNAV_HIP(hipMemcpyAsync(has, d_has, sizeof(int32_t) * (size_t)n_beams, hipMemcpyDeviceToHost, h->stream));
@@ -656,8 +628,8 @@ int tbnav_icp_cloud(tbnav_icp* h, const float* scan, int32_t n_beams, float* xy,
   int* d_valid;
   float2* d_xy;
   if (int rc = hook_scratch(h, scan, n_beams, d_valid, d_xy)) return rc;
-  hipLaunchKernelGGL(icp_cloud, dim3((n_beams + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->d_scans, h->d_table,
-                     (int)n_beams, d_xy, d_valid, h->k);
+  hipLaunchKernelGGL(icp_cloud, dim3((n_beams + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, h->d_scans.as<float>(),
+                     h->d_table, (int)n_beams, d_xy, d_valid, h->k);
   TBNAV_HIP(hipGetLastError());
   std::vector<float2> pts((size_t)n_beams);
   std::vector<int> valid((size_t)n_beams);
@@ -678,9 +650,9 @@ int tbnav_icp_match(tbnav_icp* h, const float* target_scan, const float* source_
   DevGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
-  if (int rc = ensure_scans(h, 2 * (size_t)n_beams)) return rc;
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_scans.reserve(sizeof(float) * 2 * (size_t)n_beams)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.as<float>() + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   clear_pairs(h);
   add_pair(h, 0, 1, T_init);
   h->last_launches = 0;
@@ -705,8 +677,8 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
     return TBNAV_OK;
   }
   if (int rc = ensure_table(h, n_beams)) return rc;
-  if (int rc = ensure_scans(h, (size_t)n_beams)) return rc;
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_scans.reserve(sizeof(float) * (size_t)n_beams)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   clear_pairs(h);
   add_pair(h, -1, 0, T_init);
   h->last_launches = 0;
@@ -716,7 +688,7 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
   const IcpOut o = h->h_out[0];
   result(o, T_out, info);
   *ok = converged(o.criterion) ? 1 : 0;
-  if (*ok) return store_scan(h, h->d_scans, nullptr, n_beams);  // :59 — a failure keeps the old scan (:53-56)
+  if (*ok) return store_scan(h, h->d_scans.as<float>(), nullptr, n_beams);  // :59 — a failure keeps the old scan (:53-56)
   return TBNAV_OK;
 }
 
@@ -728,8 +700,8 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
   DevGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
-  if (int rc = ensure_scans(h, (size_t)n_beams * (size_t)n_scans)) return rc;
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scans, sizeof(float) * (size_t)n_beams * (size_t)n_scans, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_scans.reserve(sizeof(float) * (size_t)n_beams * (size_t)n_scans)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, scans, sizeof(float) * (size_t)n_beams * (size_t)n_scans, hipMemcpyHostToDevice, h->stream));
   h->last_launches = 0;
   int s = 0;
   int target = -1;  // -1: the stored scan
@@ -773,7 +745,7 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
     ok[s] = converged(o.criterion) ? 1 : 0;
     if (ok[s]) target = s;
   }
-  if (target >= 0) return store_scan(h, h->d_scans + (size_t)target * n_beams, nullptr, n_beams);
+  if (target >= 0) return store_scan(h, h->d_scans.as<float>() + (size_t)target * n_beams, nullptr, n_beams);
   return TBNAV_OK;
 }
 

@@ -1,5 +1,5 @@
 // icp_device.hpp — what the device ICP (icp.hip) and the correlative search in front of it (icp_search.hip) share: the handle,
-// the by-value kernel constants, the cloud of contract item 1 (cloud_point with the beam table) and the device buffers.
+// the by-value kernel constants, the cloud of contract item 1 (cloud_point with the beam table) and the device buffers (DevBuf: grow, discard the contents).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,6 +57,29 @@ struct DevGuard {
   ~DevGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// a device buffer that only grows and forgets its contents when it does: every user writes it before reading it
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t cap = 0;   // bytes
+  // at least `bytes` bytes; on failure the buffer is left empty
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return TBNAV_OK;
+    if (ptr) TBNAV_HIP(hipFree(ptr));
+    ptr = nullptr; cap = 0;
+    void* p = nullptr;
+    TBNAV_HIP(hipMalloc(&p, bytes));
+    ptr = p;
+    cap = bytes;
+    return TBNAV_OK;
+  }
+  void release() {
+    (void)hipFree(ptr);
+    ptr = nullptr; cap = 0;
+  }
+  template <class T>
+  T* as() const { return static_cast<T*>(ptr); }
+};
+
 // the correlative search's state in the handle (tbnav_icp.h, CORRELATIVE SEARCH); the buffers are icp_search.hip's
 struct IcpSearch {
   bool on = false;
@@ -68,20 +91,13 @@ struct IcpSearch {
   tbnav_icp_search_params stamp_of{};  // the parameters d_stamp was built from
   bool have_stamp = false;
   uint8_t* d_stamp = nullptr;       // [(2k+1)^2]
-  uint8_t* d_tables = nullptr;      // [chunk][padded table]
-  size_t tables_cap = 0;
-  void* d_in = nullptr;             // per chunk: the pairs, then their rotations
-  size_t in_cap = 0;
-  void* d_rec = nullptr;            // [chunk][na] partial results
-  size_t rec_cap = 0;
-  void* d_sel = nullptr;            // [chunk] results
-  size_t sel_cap = 0;
-  uint32_t* d_tgt_points = nullptr; // [chunk]: the valid target points
-  size_t tgt_cap = 0;
-  uint32_t* d_scores = nullptr;     // the test hook's score volume
-  size_t scores_cap = 0;
-  void* d_shape = nullptr;          // [chunk] the integers of F3 (icp_search_shape.hip)
-  size_t shape_cap = 0;
+  DevBuf d_tables;                  // uint8_t [chunk][padded table]
+  DevBuf d_in;                      // per chunk: the pairs, then their rotations
+  DevBuf d_rec;                     // SearchRec [chunk][na] partial results
+  DevBuf d_sel;                     // SearchSel [chunk] results
+  DevBuf d_tgt_points;              // uint32_t [chunk]: the valid target points
+  DevBuf d_scores;                  // uint32_t: the test hook's score volume
+  DevBuf d_shape;                   // ShapeRec [chunk]: the integers of F3 (icp_search_shape.hip)
   std::vector<unsigned char> h_in, h_sel, h_shape;
 };
 
@@ -94,14 +110,11 @@ struct tbnav_icp {
   hipStream_t stream = nullptr;
   int table_beams = 0;                 // beam count the device table was built for
   float2* d_table = nullptr;           // cosf / sinf per beam [table_beams]
-  float* d_stored = nullptr;           // the stored scan (pclICPWrapper's old_scan) [stored_cap]
-  int stored_cap = 0, stored_beams = 0;
+  tbnav_icpdev::DevBuf d_stored;       // float [stored_beams]: the stored scan (pclICPWrapper's old_scan)
+  int stored_beams = 0;
   bool have_stored = false;
-  float* d_scans = nullptr;            // batch scans / match inputs
-  size_t scans_cap = 0;
-  tbnav_icpdev::IcpPair* d_pairs = nullptr;
-  tbnav_icpdev::IcpOut* d_out = nullptr;
-  int pairs_cap = 0;
+  tbnav_icpdev::DevBuf d_scans;        // float: batch scans / match inputs
+  tbnav_icpdev::DevBuf d_pairs, d_out; // IcpPair / IcpOut per alignment
   int last_launches = 0;
   int metric = TBNAV_ICP_METRIC_POINT;  // tbnav_icp_set_metric
   tbnav_icpdev::IcpLine line{TBNAV_ICP_LINE_NORMAL_MAX_GAP * TBNAV_ICP_LINE_NORMAL_MAX_GAP, TBNAV_ICP_LINE_MIN_COND,
@@ -119,7 +132,6 @@ namespace tbnav_icpdev {
 
 // icp.hip
 int ensure_table(tbnav_icp* h, int n_beams);
-int ensure_scans(tbnav_icp* h, size_t floats);
 
 // icp_search.hip: the search of h->h_pairs[0, n_pairs) from h->h_init (scans already in d_scans / d_stored, the beam table
 // built) with parameters sp -> h->h_sinfo[0, n_pairs).  scores (n_pairs == 1 only): the whole score volume, or null.

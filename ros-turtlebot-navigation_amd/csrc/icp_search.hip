@@ -14,11 +14,16 @@
 //   icp_search_select  one wave per pair: the maximum of the na keys, the candidate count and thr.
 // slack_q10 > 0 scores a second time against thr (pass 1: the key is the inverted rank alone, among score >= thr).
 // The score volume itself is written only for the test hook.  The shape of the score volume (F1-F6) is icp_search_shape.hip's:
-// its kernel is launched here behind the final icp_search_select and its record comes back with the selection.
+// its kernel is launched here behind the final icp_search_select and its record comes back with the selection.  What
+// icp_search_score does before it scores (load_table, base_cells) and its read for a slow-list point (slow_read) are
+// icp_search_device.hpp's scoring front, shared with that kernel.  On the host search_pairs walks the chunks in named steps
+// (pack_chunk, reserve_chunk, launch_table, score_pass, launch_shape) and search_finish forms S7's record, as shape_finish
+// forms F4 / F5's; every device buffer is a DevBuf (icp_device.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "common.hpp"
@@ -113,33 +118,13 @@ __global__ __launch_bounds__(kThreads) void icp_search_score(const float* __rest
   __shared__ uint32_t red_cnt[kThreads / kWave];
   const int t = threadIdx.x;
   const int ia = blockIdx.x, pair = blockIdx.y;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(tables + (size_t)pair * (size_t)sc.tab_stride);
-    for (int i = t; i < sc.tab_stride / 16; i += kThreads) lds_tab[i] = src[i];
-  }
+  load_table(lds_tab, tables, pair, sc, t);
   if (t == 0) { n_fast = 0u; n_slow = 0u; n_valid = 0u; }
   __syncthreads();
   const SearchPair pr = pairs[pair];
   const double2 cs = rot[(size_t)pair * sc.na + ia];
   const float* ss = pr.src < 0 ? stored : scans + (size_t)pr.src * n_beams;
-  uint32_t valid = 0u;
-  for (int i = t; i < n_beams; i += kThreads) {
-    float2 p;
-    if (!cloud_point(ss[i], beams[i], k, p)) continue;
-    ++valid;
-    const double sx = (double)p.x, sy = (double)p.y;
-    const double ax = (((cs.x * sx) - (cs.y * sy)) + pr.x0);
-    const double ay = (((cs.y * sx) + (cs.x * sy)) + pr.y0);
-    int bx, by;
-    if (!cell_of(ax, sc.E, sc.inv, bx) || !cell_of(ay, sc.E, sc.inv, by)) continue;
-    if (bx >= 0 && bx < sc.n && by >= 0 && by < sc.n) {
-      // the window's first cell in the padded table: rows by .. by + 2*wl, columns bx .. bx + 2*wl, all inside it
-      cells[atomicAdd(&n_fast, 1u)] = (uint16_t)(by * sc.side + bx);
-    } else if (bx >= -sc.wl && bx < sc.n + sc.wl && by >= -sc.wl && by < sc.n + sc.wl) {
-      // outside the table, the window reaches in: padded coordinates, 0 .. side - 1 <= 207 each
-      cells[n_beams - 1 - (int)atomicAdd(&n_slow, 1u)] = (uint16_t)(((by + sc.wl) << 8) | (bx + sc.wl));
-    }
-  }
+  const uint32_t valid = base_cells(ss, beams, n_beams, k, sc, cs, pr, cells, &n_fast, &n_slow, t);
   if (valid) atomicAdd(&n_valid, valid);
   __syncthreads();
   const int nf = (int)n_fast, ns = (int)n_slow;
@@ -162,12 +147,8 @@ __global__ __launch_bounds__(kThreads) void icp_search_score(const float* __rest
   }
   for (int p = 0; p < ns; ++p) {
     const int v = cells[n_beams - 1 - p];
-    const int py = v >> 8, px = v & 0xff;
 #pragma unroll
-    for (int j = 0; j < J; ++j) {
-      const int ry = py + iy[j] - sc.wl, rx = px + ix[j] - sc.wl;   // padded coordinates of the cell this candidate reads
-      if (ry >= sc.wl && ry < sc.n + sc.wl && rx >= sc.wl && rx < sc.n + sc.wl) acc[j] += tab[ry * sc.side + rx];
-    }
+    for (int j = 0; j < J; ++j) acc[j] += slow_read(tab, sc, v, iy[j], ix[j]);
   }
   const uint32_t thr = pass ? sel[pair].thr : 0u;
   unsigned long long key = 0ull;
@@ -244,18 +225,6 @@ __global__ __launch_bounds__(kWave) void icp_search_select(const SearchRec* __re
   }
 }
 
-template <class T>
-int ensure(T*& ptr, size_t& cap, size_t want) {
-  if (want <= cap) return TBNAV_OK;
-  if (ptr) TBNAV_HIP(hipFree(ptr));
-  ptr = nullptr; cap = 0;
-  void* p = nullptr;
-  TBNAV_HIP(hipMalloc(&p, want));
-  ptr = static_cast<T*>(p);
-  cap = want;
-  return TBNAV_OK;
-}
-
 int table_side(const tbnav_icp_search_params& p) { return 2 * (int)std::ceil(p.half_extent / p.resolution); }
 
 bool params_ok(const tbnav_icp_search_params& p) {
@@ -304,14 +273,37 @@ int ensure_stamp(tbnav_icp* h, const tbnav_icp_search_params& p) {
   return TBNAV_OK;
 }
 
+// the device buffers of a chunk of n pairs whose upload is in_bytes long (d_shape: only where the shape runs)
+int reserve_chunk(IcpSearch& S, int n, const SearchConst& sc, size_t in_bytes, bool shape) {
+  const size_t m = (size_t)n;
+  const std::pair<DevBuf*, size_t> want[] = {{&S.d_in, in_bytes},
+                                             {&S.d_tables, (size_t)sc.tab_stride * m},
+                                             {&S.d_rec, sizeof(SearchRec) * m * sc.na},
+                                             {&S.d_sel, sizeof(SearchSel) * m},
+                                             {&S.d_tgt_points, sizeof(uint32_t) * m},
+                                             {&S.d_shape, shape ? sizeof(ShapeRec) * m : 0}};
+  for (const auto& w : want)
+    if (int rc = w.first->reserve(w.second)) return rc;
+  return TBNAV_OK;
+}
+
+// icp_search_table over the n pairs at d_pairs -> d_tables, d_tgt_points
+int launch_table(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const SearchPair* d_pairs) {
+  IcpSearch& S = h->search;
+  hipLaunchKernelGGL(icp_search_table, dim3(n), dim3(kThreads), (size_t)sc.tab_stride, h->stream, h->d_scans.as<float>(),
+                     h->d_stored.as<float>(), h->d_table, n_beams, d_pairs, S.d_stamp, S.d_tables.as<uint8_t>(),
+                     S.d_tgt_points.as<uint32_t>(), h->k, sc);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
 template <int J>
 void launch_score(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const SearchPair* d_pairs, const double2* d_rot,
                   uint32_t* d_scores, int pass) {
   IcpSearch& S = h->search;
-  const size_t lds = (size_t)sc.tab_stride + ((sizeof(uint16_t) * (size_t)n_beams + 15) & ~(size_t)15);
-  hipLaunchKernelGGL((icp_search_score<J>), dim3(sc.na, n), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams,
-                     d_pairs, d_rot, S.d_tables, static_cast<const SearchSel*>(S.d_sel), static_cast<SearchRec*>(S.d_rec), d_scores,
-                     h->k, sc, pass);
+  hipLaunchKernelGGL((icp_search_score<J>), dim3(sc.na, n), dim3(kThreads), score_lds_bytes(sc, n_beams), h->stream,
+                     h->d_scans.as<float>(), h->d_stored.as<float>(), h->d_table, n_beams, d_pairs, d_rot, S.d_tables.as<uint8_t>(),
+                     S.d_sel.as<SearchSel>(), S.d_rec.as<SearchRec>(), d_scores, h->k, sc, pass);
 }
 
 // translations per thread -> J (nl^2 <= 33^2 = 1089 <= 5 * 256)
@@ -326,6 +318,59 @@ void dispatch_score(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, con
   else launch_score<5>(h, n, n_beams, sc, d_pairs, d_rot, d_scores, pass);
 }
 
+// one pass over the chunk: every (pair, angle) scored, then the selection per pair
+int score_pass(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const SearchPair* d_pairs, const double2* d_rot,
+               uint32_t* d_scores, int pass) {
+  IcpSearch& S = h->search;
+  dispatch_score(h, n, n_beams, sc, d_pairs, d_rot, d_scores, pass);
+  TBNAV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(icp_search_select, dim3(n), dim3(kWave), 0, h->stream, S.d_rec.as<SearchRec>(), S.d_tgt_points.as<uint32_t>(),
+                     S.d_sel.as<SearchSel>(), sc, pass);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// h_in <- pairs [first, first + n) of h->h_pairs with their guesses h->h_init, then (at the offset returned, 16-byte aligned)
+// their rotations (cos, sin of theta_a in double, glibc): one upload
+size_t pack_chunk(tbnav_icp* h, int first, int n, const SearchConst& sc, const tbnav_icp_search_params& sp) {
+  IcpSearch& S = h->search;
+  const size_t rot_at = (sizeof(SearchPair) * (size_t)n + 15) & ~(size_t)15;
+  S.h_in.resize(rot_at + sizeof(double2) * (size_t)n * sc.na);
+  SearchPair* hp = reinterpret_cast<SearchPair*>(S.h_in.data());
+  double2* hr = reinterpret_cast<double2*>(S.h_in.data() + rot_at);
+  for (int i = 0; i < n; ++i) {
+    const IcpPair& pr = h->h_pairs[(size_t)(first + i)];
+    const std::array<double, 3>& T = h->h_init[(size_t)(first + i)];
+    hp[i].tgt = pr.tgt; hp[i].src = pr.src; hp[i].x0 = T[1]; hp[i].y0 = T[2];
+    for (int ia = 0; ia < sc.na; ++ia) {
+      const double th = T[0] + (double)(ia - sc.wa) * sp.ang_step;
+      hr[(size_t)i * sc.na + ia] = make_double2(std::cos(th), std::sin(th));
+    }
+  }
+  return rot_at;
+}
+
+// S7 on the host: the record of one pair from its selection (shape_finish's counterpart)
+void search_finish(const SearchSel& s, const SearchConst& sc, const tbnav_icp_search_params& sp, const double T_init[3],
+                   tbnav_icp_search_info* info) {
+  tbnav_icp_search_info& o = *info;
+  o.ia = (int32_t)(s.lin / (uint32_t)(sc.nl * sc.nl));
+  o.iy = (int32_t)((s.lin / (uint32_t)sc.nl) % (uint32_t)sc.nl);
+  o.ix = (int32_t)(s.lin % (uint32_t)sc.nl);
+  o.T[0] = T_init[0] + (double)(o.ia - sc.wa) * sp.ang_step;
+  o.T[1] = T_init[1] + (double)(o.ix - sc.wl) * sp.resolution;
+  o.T[2] = T_init[2] + (double)(o.iy - sc.wl) * sp.resolution;
+  o.score = s.score;
+  o.points = (int32_t)s.points;
+  o.candidates = (int32_t)s.count;
+  o.quality = s.points ? (double)s.score / (255.0 * (double)s.points) : 0.0;
+  o.at_edge = ((sc.wa > 0 && (o.ia == 0 || o.ia == sc.na - 1)) ||
+               (sc.wl > 0 && (o.iy == 0 || o.iy == sc.nl - 1 || o.ix == 0 || o.ix == sc.nl - 1))) ? 1 : 0;
+  o.accepted = (o.quality >= sp.min_quality && s.points > 0u && s.tgt_points > 0u) ? 1 : 0;
+  o.searched = 1;
+  o.reserved = 0;
+}
+
 }  // namespace
 
 namespace tbnav_icpdev {
@@ -333,13 +378,7 @@ namespace tbnav_icpdev {
 void search_free(tbnav_icp* h) {
   IcpSearch& S = h->search;
   (void)hipFree(S.d_stamp);
-  (void)hipFree(S.d_tables);
-  (void)hipFree(S.d_in);
-  (void)hipFree(S.d_rec);
-  (void)hipFree(S.d_sel);
-  (void)hipFree(S.d_tgt_points);
-  (void)hipFree(S.d_scores);
-  (void)hipFree(S.d_shape);
+  for (DevBuf* b : {&S.d_tables, &S.d_in, &S.d_rec, &S.d_sel, &S.d_tgt_points, &S.d_scores, &S.d_shape}) b->release();
   S = IcpSearch{};
 }
 
@@ -353,79 +392,32 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
   h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
   const size_t vol = (size_t)sc.na * sc.nl * sc.nl;
   if (scores)
-    if (int rc = ensure(S.d_scores, S.scores_cap, sizeof(uint32_t) * vol)) return rc;
+    if (int rc = S.d_scores.reserve(sizeof(uint32_t) * vol)) return rc;
   for (int first = 0; first < n_pairs; first += kChunk) {
     const int n = n_pairs - first < kChunk ? n_pairs - first : kChunk;
-    // the chunk's pairs, then their rotations (cos, sin of theta_a in double, glibc), in one upload
-    const size_t rot_at = (sizeof(SearchPair) * (size_t)n + 15) & ~(size_t)15;
-    const size_t in_bytes = rot_at + sizeof(double2) * (size_t)n * sc.na;
-    S.h_in.resize(in_bytes);
-    SearchPair* hp = reinterpret_cast<SearchPair*>(S.h_in.data());
-    double2* hr = reinterpret_cast<double2*>(S.h_in.data() + rot_at);
-    for (int i = 0; i < n; ++i) {
-      const IcpPair& pr = h->h_pairs[(size_t)(first + i)];
-      const std::array<double, 3>& T = h->h_init[(size_t)(first + i)];
-      hp[i].tgt = pr.tgt; hp[i].src = pr.src; hp[i].x0 = T[1]; hp[i].y0 = T[2];
-      for (int ia = 0; ia < sc.na; ++ia) {
-        const double th = T[0] + (double)(ia - sc.wa) * sp.ang_step;
-        hr[(size_t)i * sc.na + ia] = make_double2(std::cos(th), std::sin(th));
-      }
-    }
-    if (int rc = ensure(S.d_in, S.in_cap, in_bytes)) return rc;
-    if (int rc = ensure(S.d_tables, S.tables_cap, (size_t)sc.tab_stride * (size_t)n)) return rc;
-    if (int rc = ensure(S.d_rec, S.rec_cap, sizeof(SearchRec) * (size_t)n * sc.na)) return rc;
-    if (int rc = ensure(S.d_sel, S.sel_cap, sizeof(SearchSel) * (size_t)n)) return rc;
-    if (int rc = ensure(S.d_tgt_points, S.tgt_cap, sizeof(uint32_t) * (size_t)n)) return rc;
-    TBNAV_HIP(hipMemcpyAsync(S.d_in, S.h_in.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
-    const SearchPair* d_pairs = static_cast<const SearchPair*>(S.d_in);
-    const double2* d_rot = reinterpret_cast<const double2*>(static_cast<const unsigned char*>(S.d_in) + rot_at);
-    hipLaunchKernelGGL(icp_search_table, dim3(n), dim3(kThreads), (size_t)sc.tab_stride, h->stream, h->d_scans, h->d_stored, h->d_table,
-                       n_beams, d_pairs, S.d_stamp, S.d_tables, S.d_tgt_points, h->k, sc);
-    TBNAV_HIP(hipGetLastError());
-    dispatch_score(h, n, n_beams, sc, d_pairs, d_rot, scores ? S.d_scores : nullptr, 0);
-    TBNAV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(icp_search_select, dim3(n), dim3(kWave), 0, h->stream, static_cast<const SearchRec*>(S.d_rec), S.d_tgt_points,
-                       static_cast<SearchSel*>(S.d_sel), sc, 0);
-    TBNAV_HIP(hipGetLastError());
-    if (sc.slack) {
-      dispatch_score(h, n, n_beams, sc, d_pairs, d_rot, nullptr, 1);
-      TBNAV_HIP(hipGetLastError());
-      hipLaunchKernelGGL(icp_search_select, dim3(n), dim3(kWave), 0, h->stream, static_cast<const SearchRec*>(S.d_rec), S.d_tgt_points,
-                         static_cast<SearchSel*>(S.d_sel), sc, 1);
-      TBNAV_HIP(hipGetLastError());
-    }
+    const size_t rot_at = pack_chunk(h, first, n, sc, sp);
+    if (int rc = reserve_chunk(S, n, sc, S.h_in.size(), shp != nullptr)) return rc;
+    TBNAV_HIP(hipMemcpyAsync(S.d_in.ptr, S.h_in.data(), S.h_in.size(), hipMemcpyHostToDevice, h->stream));
+    const SearchPair* d_pairs = S.d_in.as<SearchPair>();
+    const double2* d_rot = reinterpret_cast<const double2*>(S.d_in.as<unsigned char>() + rot_at);
+    if (int rc = launch_table(h, n, n_beams, sc, d_pairs)) return rc;
+    if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, scores ? S.d_scores.as<uint32_t>() : nullptr, 0)) return rc;
+    if (sc.slack)
+      if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, nullptr, 1)) return rc;
     if (shp) {
-      if (int rc = ensure(S.d_shape, S.shape_cap, sizeof(ShapeRec) * (size_t)n)) return rc;
       if (int rc = launch_shape(h, n, n_beams, sc, d_pairs, d_rot, *shp)) return rc;
       S.h_shape.resize(sizeof(ShapeRec) * (size_t)n);
-      TBNAV_HIP(hipMemcpyAsync(S.h_shape.data(), S.d_shape, sizeof(ShapeRec) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+      TBNAV_HIP(hipMemcpyAsync(S.h_shape.data(), S.d_shape.ptr, S.h_shape.size(), hipMemcpyDeviceToHost, h->stream));
     }
     S.h_sel.resize(sizeof(SearchSel) * (size_t)n);
-    TBNAV_HIP(hipMemcpyAsync(S.h_sel.data(), S.d_sel, sizeof(SearchSel) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (scores) TBNAV_HIP(hipMemcpyAsync(scores, S.d_scores, sizeof(uint32_t) * vol, hipMemcpyDeviceToHost, h->stream));
+    TBNAV_HIP(hipMemcpyAsync(S.h_sel.data(), S.d_sel.ptr, S.h_sel.size(), hipMemcpyDeviceToHost, h->stream));
+    if (scores) TBNAV_HIP(hipMemcpyAsync(scores, S.d_scores.ptr, sizeof(uint32_t) * vol, hipMemcpyDeviceToHost, h->stream));
     TBNAV_HIP(hipStreamSynchronize(h->stream));
-    const SearchSel* hs = reinterpret_cast<const SearchSel*>(S.h_sel.data());
     for (int i = 0; i < n; ++i) {
-      const SearchSel& s = hs[i];
-      const std::array<double, 3>& T = h->h_init[(size_t)(first + i)];
-      tbnav_icp_search_info& o = h->h_sinfo[(size_t)(first + i)];
-      o.ia = (int32_t)(s.lin / (uint32_t)(sc.nl * sc.nl));
-      o.iy = (int32_t)((s.lin / (uint32_t)sc.nl) % (uint32_t)sc.nl);
-      o.ix = (int32_t)(s.lin % (uint32_t)sc.nl);
-      o.T[0] = T[0] + (double)(o.ia - sc.wa) * sp.ang_step;
-      o.T[1] = T[1] + (double)(o.ix - sc.wl) * sp.resolution;
-      o.T[2] = T[2] + (double)(o.iy - sc.wl) * sp.resolution;
-      o.score = s.score;
-      o.points = (int32_t)s.points;
-      o.candidates = (int32_t)s.count;
-      o.quality = s.points ? (double)s.score / (255.0 * (double)s.points) : 0.0;
-      o.at_edge = ((sc.wa > 0 && (o.ia == 0 || o.ia == sc.na - 1)) ||
-                   (sc.wl > 0 && (o.iy == 0 || o.iy == sc.nl - 1 || o.ix == 0 || o.ix == sc.nl - 1))) ? 1 : 0;
-      o.accepted = (o.quality >= sp.min_quality && s.points > 0u && s.tgt_points > 0u) ? 1 : 0;
-      o.searched = 1;
-      o.reserved = 0;
-      if (shp)
-        shape_finish(reinterpret_cast<const ShapeRec*>(S.h_shape.data())[i], sp, *shp, T.data(), &o, &h->h_sshape[(size_t)(first + i)]);
+      const double* T_init = h->h_init[(size_t)(first + i)].data();
+      tbnav_icp_search_info* info = &h->h_sinfo[(size_t)(first + i)];
+      search_finish(reinterpret_cast<const SearchSel*>(S.h_sel.data())[i], sc, sp, T_init, info);
+      if (shp) shape_finish(reinterpret_cast<const ShapeRec*>(S.h_shape.data())[i], sp, *shp, T_init, info, &h->h_sshape[(size_t)(first + i)]);
     }
   }
   return TBNAV_OK;
@@ -486,9 +478,9 @@ int search_one(tbnav_icp* h, const float* target_scan, const float* source_scan,
   DevGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
-  if (int rc = ensure_scans(h, 2 * (size_t)n_beams)) return rc;
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = h->d_scans.reserve(sizeof(float) * 2 * (size_t)n_beams)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, target_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.as<float>() + n_beams, source_scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   IcpPair pr{};
   pr.tgt = 0; pr.src = 1;
   h->h_pairs.assign(1, pr);
@@ -526,21 +518,16 @@ int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uin
   IcpSearch& S = h->search;
   const SearchConst sc = make_const(S.p);
   if (int rc = ensure_table(h, n_beams)) return rc;
-  if (int rc = ensure_scans(h, (size_t)n_beams)) return rc;
+  if (int rc = h->d_scans.reserve(sizeof(float) * (size_t)n_beams)) return rc;
   if (int rc = ensure_stamp(h, S.p)) return rc;
-  if (int rc = ensure(S.d_in, S.in_cap, sizeof(SearchPair))) return rc;
-  if (int rc = ensure(S.d_tables, S.tables_cap, (size_t)sc.tab_stride)) return rc;
-  if (int rc = ensure(S.d_sel, S.sel_cap, sizeof(SearchSel))) return rc;
-  if (int rc = ensure(S.d_tgt_points, S.tgt_cap, sizeof(uint32_t))) return rc;
-  TBNAV_HIP(hipMemcpyAsync(h->d_scans, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
+  if (int rc = reserve_chunk(S, 1, sc, sizeof(SearchPair), false)) return rc;
+  TBNAV_HIP(hipMemcpyAsync(h->d_scans.ptr, scan, sizeof(float) * (size_t)n_beams, hipMemcpyHostToDevice, h->stream));
   SearchPair pr{};
   pr.tgt = 0; pr.src = 0;
-  TBNAV_HIP(hipMemcpyAsync(S.d_in, &pr, sizeof pr, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(icp_search_table, dim3(1), dim3(kThreads), (size_t)sc.tab_stride, h->stream, h->d_scans, h->d_stored, h->d_table,
-                     (int)n_beams, static_cast<const SearchPair*>(S.d_in), S.d_stamp, S.d_tables, S.d_tgt_points, h->k, sc);
-  TBNAV_HIP(hipGetLastError());
+  TBNAV_HIP(hipMemcpyAsync(S.d_in.ptr, &pr, sizeof pr, hipMemcpyHostToDevice, h->stream));
+  if (int rc = launch_table(h, 1, n_beams, sc, S.d_in.as<SearchPair>())) return rc;
   std::vector<uint8_t> padded((size_t)sc.tab_stride);
-  TBNAV_HIP(hipMemcpyAsync(padded.data(), S.d_tables, padded.size(), hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(padded.data(), S.d_tables.ptr, padded.size(), hipMemcpyDeviceToHost, h->stream));
   TBNAV_HIP(hipStreamSynchronize(h->stream));
   for (int iy = 0; iy < sc.n; ++iy)
     std::memcpy(table + (size_t)iy * sc.n, padded.data() + (size_t)(iy + sc.wl) * sc.side + sc.wl, (size_t)sc.n);

@@ -1,6 +1,7 @@
 // icp_search_device.hpp — what the correlative search's kernels (icp_search.hip) and the kernel that measures the shape of
 // its score volume (icp_search_shape.hip) share: the by-value constants, the per-pair input and result, the cell of a
-// coordinate and the wave reductions.
+// coordinate, the wave reductions and the scoring front (load_table, base_cells, slow_read: what icp_search_score and
+// icp_search_shape do before they score, and how either reads a table byte for a point of the slow list).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,6 +53,58 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   return v;
 }
 
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+  return v;
+}
+
+// ---- the scoring front.  Dynamic LDS of a scoring kernel: the padded table, then uint16 cells[n_beams], the fast list
+// growing up from 0 and the slow list down from n_beams - 1 (compacted by atomics: a sum of integers has no order) ----
+inline size_t score_lds_bytes(const SearchConst& sc, int n_beams) {
+  return (size_t)sc.tab_stride + ((sizeof(uint16_t) * (size_t)n_beams + 15) & ~(size_t)15);
+}
+
+// the pair's padded table into LDS in whole uint4s; the caller synchronises
+__device__ __forceinline__ void load_table(uint4* lds_tab, const uint8_t* __restrict__ tables, int pair, const SearchConst& sc, int t) {
+  const uint4* src = reinterpret_cast<const uint4*>(tables + (size_t)pair * (size_t)sc.tab_stride);
+  for (int i = t; i < sc.tab_stride / 16; i += kThreads) lds_tab[i] = src[i];
+}
+
+// the base cells of source scan ss rotated by cs = (cos, sin) and moved by (pr.x0, pr.y0), this thread's beams t, t + B, ...
+// A base cell inside the table goes to the fast list as the first cell of its window in the padded table (rows by .. by + 2*wl,
+// columns bx .. bx + 2*wl, all inside it); one outside it whose window reaches in goes to the slow list as its padded
+// coordinates (0 .. side - 1 <= 207 each), to be read with slow_read.  *n_fast and *n_slow are LDS counters the caller zeroed
+// before a barrier; the caller synchronises.  Returns this thread's count of valid points.
+__device__ __forceinline__ uint32_t base_cells(const float* __restrict__ ss, const float2* __restrict__ beams, int n_beams,
+                                               const IcpConst& k, const SearchConst& sc, double2 cs, const SearchPair& pr,
+                                               uint16_t* cells, uint32_t* n_fast, uint32_t* n_slow, int t) {
+  uint32_t valid = 0u;
+  for (int i = t; i < n_beams; i += kThreads) {
+    float2 p;
+    if (!cloud_point(ss[i], beams[i], k, p)) continue;
+    ++valid;
+    const double sx = (double)p.x, sy = (double)p.y;
+    const double ax = (((cs.x * sx) - (cs.y * sy)) + pr.x0);
+    const double ay = (((cs.y * sx) + (cs.x * sy)) + pr.y0);
+    int bx, by;
+    if (!cell_of(ax, sc.E, sc.inv, bx) || !cell_of(ay, sc.E, sc.inv, by)) continue;
+    if (bx >= 0 && bx < sc.n && by >= 0 && by < sc.n) {
+      cells[atomicAdd(n_fast, 1u)] = (uint16_t)(by * sc.side + bx);
+    } else if (bx >= -sc.wl && bx < sc.n + sc.wl && by >= -sc.wl && by < sc.n + sc.wl) {
+      cells[n_beams - 1 - (int)atomicAdd(n_slow, 1u)] = (uint16_t)(((by + sc.wl) << 8) | (bx + sc.wl));
+    }
+  }
+  return valid;
+}
+
+// what the slow-list point v adds to the candidate at (iy, ix) of the window: the table byte its cell holds, 0 outside the table
+__device__ __forceinline__ uint32_t slow_read(const uint8_t* tab, const SearchConst& sc, int v, int iy, int ix) {
+  const int ry = (v >> 8) + iy - sc.wl, rx = (v & 0xff) + ix - sc.wl;   // padded coordinates of the cell this candidate reads
+  if (ry >= sc.wl && ry < sc.n + sc.wl && rx >= sc.wl && rx < sc.n + sc.wl) return tab[ry * sc.side + rx];
+  return 0u;
+}
+
 // the seven integers of F3 for one pair, 64 bytes
 struct ShapeRec {
   long long S0, Sx, Sy, Sxx, Sxy, Syy;
@@ -61,7 +114,7 @@ struct ShapeRec {
 static_assert(sizeof(ShapeRec) == 64, "one 64-byte record per pair");
 
 // icp_search_shape.hip: icp_search_shape over the n pairs of a chunk, after the final icp_search_select on h->stream
-// (d_sel holds the choice) -> h->search.d_shape[0, n)
+// (d_sel holds the choice) -> h->search.d_shape[0, n), which the caller reserved
 int launch_shape(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const SearchPair* d_pairs, const double2* d_rot,
                  const tbnav_icp_search_shape_params& shp);
 // F4, F5, F6 on the host: the record of one pair from its integers; info->T becomes the shaped T

@@ -2,11 +2,12 @@
 // an addition with no counterpart in the reference).  A corridor's high scores form a ridge along it and a room's a compact blob:
 // the second moments of the chosen angle's slice tell the two apart, and the guess is kept along a direction the scan cannot see.
 //   icp_search_shape   one workgroup of 256 threads per pair, behind the final icp_search_select: it reads the choice
-//                      (sel[pair]: lin -> ia, score = best), scores that one angle again exactly as icp_search_score does (the
-//                      padded table and the base cells in LDS, a fast list and a bounds-tested slow list, up to 5 translations
-//                      per thread in one instantiation: a runtime loop over them, the points innermost), forms w = score - floor of F2 and the seven
-//                      integers of F3, and reduces them with wave shuffles and one LDS stage: integers have no order.  One
-//                      64-byte record per pair.
+//                      (sel[pair]: lin -> ia, score = best), scores that one angle again exactly as icp_search_score does,
+//                      through the same scoring front (icp_search_device.hpp: load_table, base_cells, slow_read; the padded
+//                      table and the base cells in LDS, a fast list and a bounds-tested slow list), with its own loop: up to 5
+//                      translations per thread in one instantiation, a runtime loop over them, the points innermost.  It forms
+//                      w = score - floor of F2 and the seven integers of F3, and reduces them with wave shuffles and one LDS
+//                      stage: integers have no order.  One 64-byte record per pair.
 // F4 / F5 are the host's (shape_finish below, fp64 without contraction: -ffp-contract=off, csrc/Makefile), where S7 runs; the
 // record comes back in the synchronisation that brings the selection back (icp_search.hip).
 #include <hip/hip_runtime.h>
@@ -27,13 +28,7 @@ constexpr int kSlots = 5;      // translations per thread: nl^2 <= 33^2 = 1089 <
 constexpr int kSums = 7;       // S0, Sx, Sy, Sxx, Sxy, Syy, cells
 static_assert((2 * TBNAV_ICP_SEARCH_MAX_LIN + 1) * (2 * TBNAV_ICP_SEARCH_MAX_LIN + 1) <= kSlots * kThreads, "the slots do not hold the window");
 
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// blockIdx.x: the pair.  The scoring is icp_search_score's for the one angle sel[pair] names.
+// blockIdx.x: the pair.  The scoring is icp_search_score's for the one angle sel[pair] names, behind the same front.
 __global__ __launch_bounds__(kThreads) void icp_search_shape(const float* __restrict__ scans, const float* __restrict__ stored,
                                                              const float2* __restrict__ beams, int n_beams,
                                                              const SearchPair* __restrict__ pairs, const double2* __restrict__ rot,
@@ -46,10 +41,7 @@ __global__ __launch_bounds__(kThreads) void icp_search_shape(const float* __rest
   __shared__ long long red[kThreads / kWave][kSums + 1];
   const int t = threadIdx.x;
   const int pair = blockIdx.x;
-  {
-    const uint4* src = reinterpret_cast<const uint4*>(tables + (size_t)pair * (size_t)sc.tab_stride);
-    for (int i = t; i < sc.tab_stride / 16; i += kThreads) lds_tab[i] = src[i];
-  }
+  load_table(lds_tab, tables, pair, sc, t);
   if (t == 0) { n_fast = 0u; n_slow = 0u; }
   __syncthreads();
   const int n_cand = sc.nl * sc.nl;
@@ -61,20 +53,7 @@ __global__ __launch_bounds__(kThreads) void icp_search_shape(const float* __rest
   const SearchPair pr = pairs[pair];
   const double2 cs = rot[(size_t)pair * sc.na + ia];
   const float* ss = pr.src < 0 ? stored : scans + (size_t)pr.src * n_beams;
-  for (int i = t; i < n_beams; i += kThreads) {
-    float2 p;
-    if (!cloud_point(ss[i], beams[i], k, p)) continue;
-    const double sx = (double)p.x, sy = (double)p.y;
-    const double ax = (((cs.x * sx) - (cs.y * sy)) + pr.x0);
-    const double ay = (((cs.y * sx) + (cs.x * sy)) + pr.y0);
-    int bx, by;
-    if (!cell_of(ax, sc.E, sc.inv, bx) || !cell_of(ay, sc.E, sc.inv, by)) continue;
-    if (bx >= 0 && bx < sc.n && by >= 0 && by < sc.n) {
-      cells[atomicAdd(&n_fast, 1u)] = (uint16_t)(by * sc.side + bx);
-    } else if (bx >= -sc.wl && bx < sc.n + sc.wl && by >= -sc.wl && by < sc.n + sc.wl) {
-      cells[n_beams - 1 - (int)atomicAdd(&n_slow, 1u)] = (uint16_t)(((by + sc.wl) << 8) | (bx + sc.wl));
-    }
-  }
+  (void)base_cells(ss, beams, n_beams, k, sc, cs, pr, cells, &n_fast, &n_slow, t);
   __syncthreads();
   const int nf = (int)n_fast, ns = (int)n_slow;
   const int per = (n_cand + kThreads - 1) / kThreads;                   // 1 .. kSlots, the same for every thread
@@ -91,11 +70,7 @@ __global__ __launch_bounds__(kThreads) void icp_search_shape(const float* __rest
     uint32_t acc = 0u;
 #pragma unroll 8
     for (int p = 0; p < nf; ++p) acc += tab[(int)cells[p] + off];
-    for (int p = 0; p < ns; ++p) {
-      const int v = cells[n_beams - 1 - p];
-      const int ry = (v >> 8) + iy - sc.wl, rx = (v & 0xff) + ix - sc.wl;   // padded coordinates of the cell this candidate reads
-      if (ry >= sc.wl && ry < sc.n + sc.wl && rx >= sc.wl && rx < sc.n + sc.wl) acc += tab[ry * sc.side + rx];
-    }
+    for (int p = 0; p < ns; ++p) acc += slow_read(tab, sc, cells[n_beams - 1 - p], iy, ix);
     if (!in || acc <= floor_) continue;
     const long long w = (long long)(acc - floor_);
     const long long dx = ix - sc.wl, dy = iy - sc.wl;
@@ -140,10 +115,9 @@ bool shape_params_ok(const tbnav_icp_search_shape_params& p) {
 int launch_shape(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const SearchPair* d_pairs, const double2* d_rot,
                  const tbnav_icp_search_shape_params& shp) {
   IcpSearch& S = h->search;
-  const size_t lds = (size_t)sc.tab_stride + ((sizeof(uint16_t) * (size_t)n_beams + 15) & ~(size_t)15);
-  hipLaunchKernelGGL(icp_search_shape, dim3(n), dim3(kThreads), lds, h->stream, h->d_scans, h->d_stored, h->d_table, n_beams, d_pairs,
-                     d_rot, S.d_tables, static_cast<const SearchSel*>(S.d_sel), static_cast<ShapeRec*>(S.d_shape), h->k, sc,
-                     (unsigned)shp.drop_q10);
+  hipLaunchKernelGGL(icp_search_shape, dim3(n), dim3(kThreads), score_lds_bytes(sc, n_beams), h->stream, h->d_scans.as<float>(),
+                     h->d_stored.as<float>(), h->d_table, n_beams, d_pairs, d_rot, S.d_tables.as<uint8_t>(), S.d_sel.as<SearchSel>(),
+                     S.d_shape.as<ShapeRec>(), h->k, sc, (unsigned)shp.drop_q10);
   TBNAV_HIP(hipGetLastError());
   return TBNAV_OK;
 }

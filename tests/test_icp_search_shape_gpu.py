@@ -259,6 +259,47 @@ def test_match_step_and_batch_are_the_restated_chain(gpu_pkg, metric, icp_fn):
     a.close(); b.close()
 
 
+LONG = S.Params(lin_cells=2, ang_steps=2)
+_long = {}
+
+
+def _long_run():
+    """1030 scans of the ellipse drive of tools/icp_time.py::loop_run (ROOM_BENCH, 500 scans a lap, 360 beams at 1 deg,
+    default_rng(1)): a fresh aligner forms 1029 pairs of them, scans 1..1024 in the search's first chunk and 1025..1029 in its
+    second"""
+    if not _long:
+        from rtn_amd import icp
+        n = 1030
+        phi = 2 * math.pi * np.arange(n) / 500.0
+        poses = np.stack([phi + math.pi / 2, 1.0 * np.cos(phi), 0.8 * np.sin(phi)], axis=1)
+        rng = np.random.default_rng(1)
+        _long["scans"] = np.stack([orc.room_scan(q, n_beams=360, beam_delta_deg=1.0, walls=rc.ROOM_BENCH, rng=rng) for q in poses])
+        _long["T_init"] = np.array([icp.init_guess(poses[s], poses[s - 1] if s else poses[0]) for s in range(n)])
+    return _long["scans"], _long["T_init"]
+
+
+@pytest.mark.parametrize("shape", [False, True], ids=["off", "on"])
+def test_a_batch_longer_than_one_chunk_is_the_restated_chain(gpu_pkg, shape):
+    """one wrapperBatch of 1029 pairs: more than the 1024 a launch of the search takes, so the second chunk's pairs, guesses
+    and records sit at first + i.  Every pair converges (a condition on this input, checked with the restatement on the CPU:
+    all 1029 pairs accepted, converged, kind 0), so scan s is aligned against scan s - 1 and the pairs either side of the
+    chunk's edge are restated one by one."""
+    scans, T_init = _long_run()
+    a, p = _aligner(gpu_pkg, search=_kw(LONG), shape=True if shape else None)
+    L = _laser(p)
+    ok, T, info = a.wrapperBatch(T_init, scans)
+    assert ok[1:].all(), np.flatnonzero(ok == 0)
+    want = None
+    for s in (1, 1023, 1024, 1025, 1026, 1029):
+        g = tuple(T_init[s])
+        want = F.match(scans[s - 1], scans[s], L, g, LONG, F0) if shape else S.match(scans[s - 1], scans[s], L, g, LONG)
+        _same((ok[s], T[s], info[s]), want[0], s)
+    _same_info(a.lastSearch(), want[1], "last")
+    if shape:
+        _same_shape(a.lastSearchShape(), want[2], "last")
+    a.close()
+
+
 def test_off_means_off(gpu_pkg):
     cases = [_corridor(3), _room(rc.ROOM_BENCH), _corridor(6, (0.6, 0.0, 0.0), (0.6, 0.10, 0.0))]
     a, p = _aligner(gpu_pkg, search=True, metric="line")
