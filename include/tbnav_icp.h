@@ -176,6 +176,55 @@
  *  not determine (a round room) is not detected.  The point metric still pulls the two scans of a corridor together afterwards;
  *  the line metric is the one that keeps what the shape kept.  Translation accuracy of the search is one cell: the ICP behind
  *  it is what refines it.
+ *  WIDE WINDOW (an addition to the search, off by default, tbnav_icp_set_search_wide; csrc/icp_search_wide.hip; restated in
+ *  tests/icp_search_wide_restatement.py, reproduced exactly).  S1 caps the window at +-16 cells because icp_search_score keeps the
+ *  whole padded table in LDS.  A guess further off than that (a long wheel slip, a robot that was picked up) is outside every
+ *  window of the first stage: the search is rejected and the ICP starts from the bad guess.  The wide window is a SECOND STAGE
+ *  that scores up to +-64 cells and +-180 steps, tiled over workgroups, and is charged only when it is needed.  All arithmetic is
+ *  S5-S7's: integer, or fp64 with every product and sum as parenthesised and no contraction.
+ *  W1. Parameters (tbnav_icp_search_wide_params; defaults in brackets): lin_cells W [48, 1..TBNAV_ICP_SEARCH_WIDE_MAX_LIN = 64];
+ *      ang_steps A [45, 0..TBNAV_ICP_SEARCH_WIDE_MAX_ANG = 180]; when [TBNAV_ICP_WIDE_ON_REJECT = 0; TBNAV_ICP_WIDE_ON_REJECT_OR_EDGE
+ *      = 1, TBNAV_ICP_WIDE_ALWAYS = 2]; one reserved int32.  Everything else is the first stage's tbnav_icp_search_params:
+ *      resolution, half_extent, sigma, stamp_cells, ang_step, slack_q10, min_quality.  Three conditions hold against the search
+ *      parameters the handle holds (the defaults while the search is off): W >= lin_cells, A >= ang_steps, and the table side
+ *      n <= TBNAV_ICP_SEARCH_WIDE_MAX_TABLE = 176.  The wide window then contains the first, so its best score is never below the
+ *      first stage's, and a tile of up to 33 translations per axis fits in the LDS the first stage's scoring kernel uses.
+ *      tbnav_icp_set_search_wide with a bad field or a violated condition is TBNAV_ERR_INVALID_ARG and changes nothing;
+ *      tbnav_icp_set_search with parameters that violate a condition while the wide stage is on is the same (params == NULL
+ *      stands for the defaults there); with the wide stage off tbnav_icp_set_search is unchanged.  The defaults are design
+ *      constants, not measurements: +-2.4 m and +-45 degrees.
+ *  W2. First stage: S1-S7 run unchanged and give the record `first`.  With when = ALWAYS the first stage is not run:
+ *      first.searched = 0 and every other field 0.
+ *  W3. The wide stage runs when when = ALWAYS, or first.accepted = 0, or when = ON_REJECT_OR_EDGE and first.at_edge = 1.
+ *  W4. Wide stage: S5, S6 and S7 with wl := W and wa := A, on the same table (the target is stamped once per pair, not once per
+ *      stage), the same clouds and the same doubles T_init.  theta_a = theta0 + (double)(ia - A) * ang_step, its cosine and sine
+ *      from the host's glibc.  ia, iy, ix, at_edge, candidates, quality and accepted are S6 / S7's over the wide window.  With
+ *      A = 180 and a step of pi/180 the first and the last angle are the same direction: S6's lowest linear index breaks the tie.
+ *  W5. Outcome: the wide stage's record if it ran, `first` otherwise.  S8 reads "the outcome" where it reads "the search":
+ *      tbnav_icp_match, _step, _step_batch (its realignment launches included) and the stateless tbnav_icp_search and
+ *      tbnav_icp_search_with_shape.  tbnav_icp_last_search returns the outcome; tbnav_icp_last_search_wide returns
+ *      tbnav_icp_search_wide_info (first, ran) with the same lifetime.  A wide stage that is on but did not run leaves every
+ *      result equal, bit for bit, to the same handle with the wide stage off.  tbnav_icp_step_batch stays n successive steps.
+ *      tbnav_icp_search_scores and tbnav_icp_search_table are the first stage's hooks and ignore the wide stage.
+ *  W6. Shape: F1-F6 apply to the stage that produced the outcome, with wl := W where that is the wide stage.  F3's sums stay
+ *      exact in int64: w < 2^20, dx^2 <= 2^12 and at most 129^2 cells put every sum below 2^47.  CPU evidence (corridor pair 3
+ *      of tests/test_icp_search_shape_restatement.py, guesses (0.45, 0.10, 0.15) and (0.45, 0.10, 0.6), first stage rejected
+ *      with q 0.50 and 0.11): at W = 32 and W = 64 with A = 30 the raw wide choice overlays the scans and moves the 10 cm along
+ *      the corridor back to 0; the shape returns kind 1 with l1 = 234 / 260 and l2 = 0.06 and keeps x at the guess's 0.10; the
+ *      line metric then ends 32 mm off along the corridor, against 128 mm from the raw choice.
+ *  W7. Limits: n_beams <= TBNAV_ICP_MAX_BEAMS, as for the first stage.  The wide stage is stored but idle while the search is
+ *      off; the stateless entries honour it anyway, as they do the shape.  tbnav_icp_set_search_wide(h, NULL) turns it off and
+ *      resets its parameters; tbnav_icp_set_search(h, NULL) leaves it stored.  A new handle has it off.
+ *  W8. Test hook tbnav_icp_search_wide_scores: stateless, the wide stage alone whatever `when` says, with the handle's search and
+ *      wide parameters (the defaults while they are off; the shape when the handle has it on); scores may be NULL, otherwise
+ *      [2A+1][2W+1][2W+1].
+ *  KERNELS (csrc/icp_search_wide.hip): icp_search_wide_score, one workgroup of 256 threads per (translation tile, angle, pair):
+ *  a tile is up to 33 x 33 translations; the base cells are shifted by the tile's first offset, so the workgroup needs the table
+ *  with tile - 1 zero cells on its high side only (side <= 208, read from the first stage's padded table in global memory);
+ *  icp_search_wide_select, one workgroup per pair, reduces the tiles x angles 64-bit keys (score, then the inverted 39-bit rank
+ *  D << 23 | linear index).  slack_q10 > 0 scores a second time against thr; the shape is a third pass over the chosen angle's
+ *  tiles, one partial record per tile that the host adds.  In a batch the wide stage runs behind the synchronisation that brings
+ *  a chunk's first-stage records back, for the pairs W3 names, and costs one more synchronisation only when there is one.
  *  KERNELS (csrc/icp_search.hip): icp_search_table, one workgroup per pair, stamps the target into a byte table in LDS (a
  *  compare-and-swap maximum on the byte's dword) and writes it padded with wl zero cells on every side; icp_search_score, one
  *  workgroup of 256 threads per (pair, angle), keeps the padded table and its angle's base cells in LDS, each thread owning
@@ -378,6 +427,42 @@ int tbnav_icp_last_search_shape(const tbnav_icp* h, tbnav_icp_search_shape* shap
  * shape on (with the handle's shape parameters, the defaults while it is off).  info and shape are required. */
 int tbnav_icp_search_with_shape(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
                                 const double T_init[3], double T_out[3], tbnav_icp_search_info* info, tbnav_icp_search_shape* shape);
+
+/* ---- the wide second stage (W1-W8 of the CORRELATIVE SEARCH section) ---- */
+#define TBNAV_ICP_SEARCH_WIDE_MAX_LIN 64
+#define TBNAV_ICP_SEARCH_WIDE_MAX_ANG 180
+#define TBNAV_ICP_SEARCH_WIDE_MAX_TABLE 176   /* the table side n */
+#define TBNAV_ICP_WIDE_ON_REJECT 0            /* the wide stage runs when the first stage is not accepted */
+#define TBNAV_ICP_WIDE_ON_REJECT_OR_EDGE 1    /* or when its choice sits on the border of its window */
+#define TBNAV_ICP_WIDE_ALWAYS 2               /* always; the first stage is not run */
+
+typedef struct tbnav_icp_search_wide_params {
+  int32_t lin_cells;    /* 48 */
+  int32_t ang_steps;    /* 45 */
+  int32_t when;         /* TBNAV_ICP_WIDE_ON_REJECT */
+  int32_t reserved;
+} tbnav_icp_search_wide_params;
+
+typedef struct tbnav_icp_search_wide_info {
+  tbnav_icp_search_info first;  /* the first stage's record (W2) */
+  int32_t ran;                  /* 1 when the wide stage ran */
+  int32_t reserved;
+} tbnav_icp_search_wide_info;
+
+void tbnav_icp_default_search_wide_params(tbnav_icp_search_wide_params* p);
+/* turns the wide stage on wherever a search runs (W5); params == NULL turns it off (and the handle's wide parameters go back to
+ * the defaults).  A new handle has it off.  It is stored but idle while the search itself is off.  Parameters outside W1's
+ * limits, or that violate one of W1's conditions against the handle's search parameters, are TBNAV_ERR_INVALID_ARG and change
+ * nothing. */
+int tbnav_icp_set_search_wide(tbnav_icp* h, const tbnav_icp_search_wide_params* params);
+/* either output may be null; params are the defaults while the wide stage is off */
+int tbnav_icp_get_search_wide(const tbnav_icp* h, int32_t* on, tbnav_icp_search_wide_params* params);
+/* the first stage's record and whether the wide stage ran, beside tbnav_icp_last_search's outcome and with its lifetime (all
+ * zero when no search ran or the wide stage is off) */
+int tbnav_icp_last_search_wide(const tbnav_icp* h, tbnav_icp_search_wide_info* info);
+/* test hook (W8), stateless: the wide stage alone; scores [2A+1][2W+1][2W+1] or NULL.  info is required. */
+int tbnav_icp_search_wide_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
+                                 const double T_init[3], double T_out[3], tbnav_icp_search_info* info, uint32_t* scores);
 
 #ifdef __cplusplus
 }

@@ -131,6 +131,20 @@ class IcpSearchShape(C.Structure):
 ICP_SEARCH_MAX_SIDE, ICP_SEARCH_MAX_STAMP, ICP_SEARCH_MAX_LIN, ICP_SEARCH_MAX_ANG = 208, 8, 16, 90
 
 
+class IcpSearchWideParams(C.Structure):
+    """tbnav_icp_search_wide_params (include/tbnav_icp.h, W1)."""
+    _fields_ = [("lin_cells", C.c_int32), ("ang_steps", C.c_int32), ("when", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IcpSearchWideInfo(C.Structure):
+    """tbnav_icp_search_wide_info (W5)."""
+    _fields_ = [("first", IcpSearchInfo), ("ran", C.c_int32), ("reserved", C.c_int32)]
+
+
+ICP_SEARCH_WIDE_MAX_LIN, ICP_SEARCH_WIDE_MAX_ANG, ICP_SEARCH_WIDE_MAX_TABLE = 64, 180, 176
+ICP_WIDE_ON_REJECT, ICP_WIDE_ON_REJECT_OR_EDGE, ICP_WIDE_ALWAYS = 0, 1, 2
+
+
 _lib = None
 
 
@@ -321,6 +335,11 @@ def lib() -> C.CDLL:
         "tbnav_icp_get_search_shape": (C.c_int, [vp, C.POINTER(i32), C.POINTER(IcpSearchShapeParams)]),
         "tbnav_icp_last_search_shape": (C.c_int, [vp, C.POINTER(IcpSearchShape)]),
         "tbnav_icp_search_with_shape": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), C.POINTER(IcpSearchShape)]),
+        "tbnav_icp_default_search_wide_params": (None, [C.POINTER(IcpSearchWideParams)]),
+        "tbnav_icp_set_search_wide": (C.c_int, [vp, C.POINTER(IcpSearchWideParams)]),
+        "tbnav_icp_get_search_wide": (C.c_int, [vp, C.POINTER(i32), C.POINTER(IcpSearchWideParams)]),
+        "tbnav_icp_last_search_wide": (C.c_int, [vp, C.POINTER(IcpSearchWideInfo)]),
+        "tbnav_icp_search_wide_scores": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

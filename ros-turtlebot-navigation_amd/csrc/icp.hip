@@ -439,7 +439,8 @@ int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
   if (int rc = h->d_pairs.reserve(sizeof(IcpPair) * (size_t)n_pairs)) return rc;
   if (int rc = h->d_out.reserve(sizeof(IcpOut) * (size_t)n_pairs)) return rc;
   if (h->search.on) {
-    if (int rc = search_pairs(h, n_pairs, n_beams, h->search.p, nullptr, h->search.shape_on ? &h->search.shape_p : nullptr)) return rc;
+    if (int rc = search_pairs(h, n_pairs, n_beams, h->search.p, nullptr, h->search.shape_on ? &h->search.shape_p : nullptr,
+                              h->search.wide_on ? &h->search.wide_p : nullptr)) return rc;
     for (int i = 0; i < n_pairs; ++i) {
       const tbnav_icp_search_info& si = h->h_sinfo[(size_t)i];
       if (si.accepted) h->h_pairs[(size_t)i] = make_pair(h->h_pairs[(size_t)i].tgt, h->h_pairs[(size_t)i].src, si.T);
@@ -447,6 +448,7 @@ int run_pairs(tbnav_icp* h, int n_pairs, int n_beams) {
   } else {
     h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
     h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
+    h->h_swide.assign((size_t)n_pairs, tbnav_icp_search_wide_info{});
   }
   TBNAV_HIP(hipMemcpyAsync(h->d_pairs.ptr, h->h_pairs.data(), sizeof(IcpPair) * (size_t)n_pairs, hipMemcpyHostToDevice, h->stream));
   const bool line = h->metric == TBNAV_ICP_METRIC_LINE;
@@ -540,6 +542,7 @@ int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
   h->device = dev;
   tbnav_icp_default_search_params(&h->search.p);
   tbnav_icp_default_search_shape_params(&h->search.shape_p);
+  tbnav_icp_default_search_wide_params(&h->search.wide_p);
   IcpConst& k = h->k;
   k.range_min = params->range_min;
   k.range_max = params->range_max;
@@ -659,6 +662,7 @@ int tbnav_icp_match(tbnav_icp* h, const float* target_scan, const float* source_
   if (int rc = run_pairs(h, 1, n_beams)) return rc;
   h->search.last = h->h_sinfo[0];
   h->search.last_shape = h->h_sshape[0];
+  h->search.last_wide = h->h_swide[0];
   result(h->h_out[0], T_out, info);
   return TBNAV_OK;
 }
@@ -674,6 +678,7 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
     first_call(T_out, ok, info);
     h->search.last = tbnav_icp_search_info{};
     h->search.last_shape = tbnav_icp_search_shape{};
+    h->search.last_wide = tbnav_icp_search_wide_info{};
     return TBNAV_OK;
   }
   if (int rc = ensure_table(h, n_beams)) return rc;
@@ -685,6 +690,7 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
   if (int rc = run_pairs(h, 1, n_beams)) return rc;
   h->search.last = h->h_sinfo[0];
   h->search.last_shape = h->h_sshape[0];
+  h->search.last_wide = h->h_swide[0];
   const IcpOut o = h->h_out[0];
   result(o, T_out, info);
   *ok = converged(o.criterion) ? 1 : 0;
@@ -715,15 +721,16 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
   // failed, so the target stayed an earlier scan), the scans from there are aligned against the actual target in another
   // launch — through the first one whose speculative alignment converged (the scans before it will probably fail against
   // any target, and the walk would need each of them next).
-  struct Done { IcpOut out; tbnav_icp_search_info search; tbnav_icp_search_shape shape; };
+  struct Done { IcpOut out; tbnav_icp_search_info search; tbnav_icp_search_shape shape; tbnav_icp_search_wide_info wide; };
   std::map<std::pair<int, int>, Done> done;  // (target, source) -> result, and the search in front of it
   h->search.last = tbnav_icp_search_info{};
   h->search.last_shape = tbnav_icp_search_shape{};
+  h->search.last_wide = tbnav_icp_search_wide_info{};
   if (s < n_scans) {
     clear_pairs(h);
     for (int q = s; q < n_scans; ++q) add_pair(h, q - 1, q, T_init + 3 * (size_t)q);
     if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
-    for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j], h->h_sshape[j]};
+    for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j], h->h_sshape[j], h->h_swide[j]};
   }
   for (; s < n_scans; ++s) {
     auto it = done.find({target, s});
@@ -735,12 +742,13 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
         if (spec != done.end() && converged(spec->second.out.criterion)) break;
       }
       if (int rc = run_pairs(h, (int)h->h_pairs.size(), n_beams)) return rc;
-      for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j], h->h_sshape[j]};
+      for (size_t j = 0; j < h->h_pairs.size(); ++j) done[{h->h_pairs[j].tgt, h->h_pairs[j].src}] = Done{h->h_out[j], h->h_sinfo[j], h->h_sshape[j], h->h_swide[j]};
       it = done.find({target, s});
     }
     const IcpOut& o = it->second.out;
     h->search.last = it->second.search;
     h->search.last_shape = it->second.shape;
+    h->search.last_wide = it->second.wide;
     result(o, T_out + 3 * (size_t)s, info ? info + s : nullptr);
     ok[s] = converged(o.criterion) ? 1 : 0;
     if (ok[s]) target = s;

@@ -88,6 +88,9 @@ struct IcpSearch {
   bool shape_on = false;            // tbnav_icp_set_search_shape (F1-F6): idle while the search itself is off
   tbnav_icp_search_shape_params shape_p{};   // the defaults while the shape is off
   tbnav_icp_search_shape last_shape{};       // tbnav_icp_last_search_shape
+  bool wide_on = false;             // tbnav_icp_set_search_wide (W1-W8): idle while the search itself is off
+  tbnav_icp_search_wide_params wide_p{};     // the defaults while the wide stage is off
+  tbnav_icp_search_wide_info last_wide{};    // tbnav_icp_last_search_wide
   tbnav_icp_search_params stamp_of{};  // the parameters d_stamp was built from
   bool have_stamp = false;
   uint8_t* d_stamp = nullptr;       // [(2k+1)^2]
@@ -98,7 +101,12 @@ struct IcpSearch {
   DevBuf d_tgt_points;              // uint32_t [chunk]: the valid target points
   DevBuf d_scores;                  // uint32_t: the test hook's score volume
   DevBuf d_shape;                   // ShapeRec [chunk]: the integers of F3 (icp_search_shape.hip)
-  std::vector<unsigned char> h_in, h_sel, h_shape;
+  DevBuf d_win;                     // the wide stage (icp_search_wide.hip): the escalated pairs' places, then their rotations
+  DevBuf d_wrec;                    // WideRec [pairs of a launch][na][tiles] partial results
+  DevBuf d_wsel;                    // SearchSel [escalated pairs] results
+  DevBuf d_wshape;                  // ShapeRec [escalated pairs][tiles]: F3's integers per tile
+  DevBuf d_wscores;                 // uint32_t: the wide test hook's score volume
+  std::vector<unsigned char> h_in, h_sel, h_shape, h_win, h_wsel, h_wshape;
 };
 
 }  // namespace tbnav_icpdev
@@ -126,6 +134,7 @@ struct tbnav_icp {
   std::vector<std::array<double, 3>> h_init;        // T_init of h_pairs, as given (the search starts from the doubles)
   std::vector<tbnav_icp_search_info> h_sinfo;       // the search record of h_pairs (run_pairs)
   std::vector<tbnav_icp_search_shape> h_sshape;     // and the shape record beside it (computed = 0 where the shape did not run)
+  std::vector<tbnav_icp_search_wide_info> h_swide;  // and the wide stage's (W5: the first stage's record, and whether the wide stage ran)
 };
 
 namespace tbnav_icpdev {
@@ -136,8 +145,11 @@ int ensure_table(tbnav_icp* h, int n_beams);
 // icp_search.hip: the search of h->h_pairs[0, n_pairs) from h->h_init (scans already in d_scans / d_stored, the beam table
 // built) with parameters sp -> h->h_sinfo[0, n_pairs).  scores (n_pairs == 1 only): the whole score volume, or null.
 // shp: the shape of the score volume (F1-F6) behind the selection -> h->h_sshape and the shaped T in h->h_sinfo, or null.
+// wp: the wide second stage (W1-W8) for the pairs W3 names -> h->h_sinfo holds the OUTCOME (W5) and h->h_swide the first
+// stage's record, or null; wide_scores (n_pairs == 1 only): the wide stage's score volume, or null.
 int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
-                 const tbnav_icp_search_shape_params* shp);
+                 const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp = nullptr,
+                 uint32_t* wide_scores = nullptr);
 void search_free(tbnav_icp* h);
 
 }  // namespace tbnav_icpdev

@@ -18,7 +18,8 @@
 // icp_search_score does before it scores (load_table, base_cells) and its read for a slow-list point (slow_read) are
 // icp_search_device.hpp's scoring front, shared with that kernel.  On the host search_pairs walks the chunks in named steps
 // (pack_chunk, reserve_chunk, launch_table, score_pass, launch_shape) and search_finish forms S7's record, as shape_finish
-// forms F4 / F5's; every device buffer is a DevBuf (icp_device.hpp).
+// forms F4 / F5's; every device buffer is a DevBuf (icp_device.hpp).  The wide second stage (W1-W8) is icp_search_wide.hip's:
+// search_pairs collects the pairs W3 names behind a chunk's synchronisation and hands them to wide_stage.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -350,6 +351,10 @@ size_t pack_chunk(tbnav_icp* h, int first, int n, const SearchConst& sc, const t
   return rot_at;
 }
 
+}  // namespace
+
+namespace tbnav_icpdev {
+
 // S7 on the host: the record of one pair from its selection (shape_finish's counterpart)
 void search_finish(const SearchSel& s, const SearchConst& sc, const tbnav_icp_search_params& sp, const double T_init[3],
                    tbnav_icp_search_info* info) {
@@ -371,25 +376,26 @@ void search_finish(const SearchSel& s, const SearchConst& sc, const tbnav_icp_se
   o.reserved = 0;
 }
 
-}  // namespace
-
-namespace tbnav_icpdev {
-
 void search_free(tbnav_icp* h) {
   IcpSearch& S = h->search;
   (void)hipFree(S.d_stamp);
-  for (DevBuf* b : {&S.d_tables, &S.d_in, &S.d_rec, &S.d_sel, &S.d_tgt_points, &S.d_scores, &S.d_shape}) b->release();
+  for (DevBuf* b : {&S.d_tables, &S.d_in, &S.d_rec, &S.d_sel, &S.d_tgt_points, &S.d_scores, &S.d_shape, &S.d_win, &S.d_wrec, &S.d_wsel,
+                    &S.d_wshape, &S.d_wscores}) b->release();
   S = IcpSearch{};
 }
 
 int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
-                 const tbnav_icp_search_shape_params* shp) {
+                 const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp, uint32_t* wide_scores) {
   if (!params_ok(sp) || (shp && !shape_params_ok(*shp)) || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS || (scores && n_pairs != 1)) return TBNAV_ERR_INVALID_ARG;
+  if ((wp && !wide_params_ok(*wp, sp)) || (wide_scores && (!wp || n_pairs != 1))) return TBNAV_ERR_INVALID_ARG;
+  const bool first_stage = !(wp && wp->when == TBNAV_ICP_WIDE_ALWAYS);   // W2
   IcpSearch& S = h->search;
   const SearchConst sc = make_const(sp);
   if (int rc = ensure_stamp(h, sp)) return rc;
   h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
   h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
+  h->h_swide.assign((size_t)n_pairs, tbnav_icp_search_wide_info{});
+  std::vector<int> esc;                                                  // W3: the chunk's pairs the wide stage runs for
   const size_t vol = (size_t)sc.na * sc.nl * sc.nl;
   if (scores)
     if (int rc = S.d_scores.reserve(sizeof(uint32_t) * vol)) return rc;
@@ -401,23 +407,38 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
     const SearchPair* d_pairs = S.d_in.as<SearchPair>();
     const double2* d_rot = reinterpret_cast<const double2*>(S.d_in.as<unsigned char>() + rot_at);
     if (int rc = launch_table(h, n, n_beams, sc, d_pairs)) return rc;
-    if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, scores ? S.d_scores.as<uint32_t>() : nullptr, 0)) return rc;
-    if (sc.slack)
-      if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, nullptr, 1)) return rc;
-    if (shp) {
-      if (int rc = launch_shape(h, n, n_beams, sc, d_pairs, d_rot, *shp)) return rc;
-      S.h_shape.resize(sizeof(ShapeRec) * (size_t)n);
-      TBNAV_HIP(hipMemcpyAsync(S.h_shape.data(), S.d_shape.ptr, S.h_shape.size(), hipMemcpyDeviceToHost, h->stream));
+    esc.clear();
+    if (first_stage) {
+      if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, scores ? S.d_scores.as<uint32_t>() : nullptr, 0)) return rc;
+      if (sc.slack)
+        if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, nullptr, 1)) return rc;
+      if (shp) {
+        if (int rc = launch_shape(h, n, n_beams, sc, d_pairs, d_rot, *shp)) return rc;
+        S.h_shape.resize(sizeof(ShapeRec) * (size_t)n);
+        TBNAV_HIP(hipMemcpyAsync(S.h_shape.data(), S.d_shape.ptr, S.h_shape.size(), hipMemcpyDeviceToHost, h->stream));
+      }
+      S.h_sel.resize(sizeof(SearchSel) * (size_t)n);
+      TBNAV_HIP(hipMemcpyAsync(S.h_sel.data(), S.d_sel.ptr, S.h_sel.size(), hipMemcpyDeviceToHost, h->stream));
+      if (scores) TBNAV_HIP(hipMemcpyAsync(scores, S.d_scores.ptr, sizeof(uint32_t) * vol, hipMemcpyDeviceToHost, h->stream));
+      TBNAV_HIP(hipStreamSynchronize(h->stream));
+      for (int i = 0; i < n; ++i) {
+        const double* T_init = h->h_init[(size_t)(first + i)].data();
+        tbnav_icp_search_info* info = &h->h_sinfo[(size_t)(first + i)];
+        search_finish(reinterpret_cast<const SearchSel*>(S.h_sel.data())[i], sc, sp, T_init, info);
+        if (shp) shape_finish(reinterpret_cast<const ShapeRec*>(S.h_shape.data())[i], sp, *shp, T_init, info, &h->h_sshape[(size_t)(first + i)]);
+        if (wp) {
+          h->h_swide[(size_t)(first + i)].first = *info;
+          if (!info->accepted || (wp->when == TBNAV_ICP_WIDE_ON_REJECT_OR_EDGE && info->at_edge)) esc.push_back(i);
+        }
+      }
+    } else {
+      for (int i = 0; i < n; ++i) esc.push_back(i);
     }
-    S.h_sel.resize(sizeof(SearchSel) * (size_t)n);
-    TBNAV_HIP(hipMemcpyAsync(S.h_sel.data(), S.d_sel.ptr, S.h_sel.size(), hipMemcpyDeviceToHost, h->stream));
-    if (scores) TBNAV_HIP(hipMemcpyAsync(scores, S.d_scores.ptr, sizeof(uint32_t) * vol, hipMemcpyDeviceToHost, h->stream));
-    TBNAV_HIP(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < n; ++i) {
-      const double* T_init = h->h_init[(size_t)(first + i)].data();
-      tbnav_icp_search_info* info = &h->h_sinfo[(size_t)(first + i)];
-      search_finish(reinterpret_cast<const SearchSel*>(S.h_sel.data())[i], sc, sp, T_init, info);
-      if (shp) shape_finish(reinterpret_cast<const ShapeRec*>(S.h_shape.data())[i], sp, *shp, T_init, info, &h->h_sshape[(size_t)(first + i)]);
+    // the wide stage, with the chunk's tables still on the device: further launches and one more synchronisation, and only
+    // when a pair escalated
+    if (!esc.empty()) {
+      if (int rc = wide_stage(h, first, esc, n_beams, sp, sc, d_pairs, *wp, wide_scores, shp)) return rc;
+      for (int i : esc) h->h_swide[(size_t)(first + i)].ran = 1;
     }
   }
   return TBNAV_OK;
@@ -444,11 +465,15 @@ void tbnav_icp_default_search_params(tbnav_icp_search_params* p) {
 int tbnav_icp_set_search(tbnav_icp* h, const tbnav_icp_search_params* params) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
   if (!params) {
+    tbnav_icp_search_params def;
+    tbnav_icp_default_search_params(&def);
+    if (h->search.wide_on && !wide_params_ok(h->search.wide_p, def)) return TBNAV_ERR_INVALID_ARG;   // W1
     h->search.on = false;
-    tbnav_icp_default_search_params(&h->search.p);
+    h->search.p = def;
     return TBNAV_OK;
   }
   if (!params_ok(*params)) return TBNAV_ERR_INVALID_ARG;
+  if (h->search.wide_on && !wide_params_ok(h->search.wide_p, *params)) return TBNAV_ERR_INVALID_ARG;     // W1
   h->search.p = *params;
   h->search.on = true;
   return TBNAV_OK;
@@ -472,7 +497,8 @@ namespace {
 // the stateless entries: the search of one pair with the handle's parameters; the shape when the handle has it on, or when
 // shape_out asks for it
 int search_one(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams, const double T_init[3], double T_out[3],
-               tbnav_icp_search_info* info, uint32_t* scores, tbnav_icp_search_shape* shape_out) {
+               tbnav_icp_search_info* info, uint32_t* scores, tbnav_icp_search_shape* shape_out, bool wide_hook = false,
+               uint32_t* wide_scores = nullptr) {
   if (!h || !target_scan || !source_scan || !T_init || !T_out || !info || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS)
     return TBNAV_ERR_INVALID_ARG;
   DevGuard guard(h->device);
@@ -486,7 +512,11 @@ int search_one(tbnav_icp* h, const float* target_scan, const float* source_scan,
   h->h_pairs.assign(1, pr);
   h->h_init.assign(1, {T_init[0], T_init[1], T_init[2]});
   const bool shape = h->search.shape_on || shape_out;
-  if (int rc = search_pairs(h, 1, n_beams, h->search.p, scores, shape ? &h->search.shape_p : nullptr)) return rc;
+  // the wide stage: as the handle has it (W7; the first stage's own hook, which asks for its volume, ignores it), or alone (W8)
+  tbnav_icp_search_wide_params wp = h->search.wide_p;
+  if (wide_hook) wp.when = TBNAV_ICP_WIDE_ALWAYS;
+  const bool wide = wide_hook || (h->search.wide_on && !scores);
+  if (int rc = search_pairs(h, 1, n_beams, h->search.p, scores, shape ? &h->search.shape_p : nullptr, wide ? &wp : nullptr, wide_scores)) return rc;
   *info = h->h_sinfo[0];
   if (shape_out) *shape_out = h->h_sshape[0];
   T_out[0] = info->T[0]; T_out[1] = info->T[1]; T_out[2] = info->T[2];
@@ -509,6 +539,11 @@ int tbnav_icp_search_with_shape(tbnav_icp* h, const float* target_scan, const fl
                                 const double T_init[3], double T_out[3], tbnav_icp_search_info* info, tbnav_icp_search_shape* shape) {
   if (!shape) return TBNAV_ERR_INVALID_ARG;
   return search_one(h, target_scan, source_scan, n_beams, T_init, T_out, info, nullptr, shape);
+}
+
+int tbnav_icp_search_wide_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
+                                 const double T_init[3], double T_out[3], tbnav_icp_search_info* info, uint32_t* scores) {
+  return search_one(h, target_scan, source_scan, n_beams, T_init, T_out, info, nullptr, nullptr, true, scores);
 }
 
 int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uint8_t* table) {

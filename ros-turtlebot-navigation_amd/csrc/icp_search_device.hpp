@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "icp_device.hpp"
 #include "tbnav_icp.h"
@@ -121,5 +122,19 @@ int launch_shape(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const 
 void shape_finish(const ShapeRec& r, const tbnav_icp_search_params& sp, const tbnav_icp_search_shape_params& shp,
                   const double T_init[3], tbnav_icp_search_info* info, tbnav_icp_search_shape* out);
 bool shape_params_ok(const tbnav_icp_search_shape_params& p);
+
+// icp_search.hip: S7 on the host, the record of one pair from its selection (sc and sp name the window: the wide stage calls it
+// with wl := W, wa := A)
+void search_finish(const SearchSel& s, const SearchConst& sc, const tbnav_icp_search_params& sp, const double T_init[3],
+                   tbnav_icp_search_info* info);
+
+// icp_search_wide.hip (WIDE WINDOW, W1-W8).  wide_params_ok: W1's limits against the search parameters sp.  wide_stage: the wide
+// stage for the pairs esc (places in the chunk that starts at pair `first`, whose tables d_tables and target counts are still
+// on the device, d_pairs its SearchPairs) -> h->h_sinfo / h->h_sshape of those pairs; it synchronises h->stream once.
+// scores (one pair only): the wide score volume, or null.  shp: the shape over the wide window, or null.
+bool wide_params_ok(const tbnav_icp_search_wide_params& wp, const tbnav_icp_search_params& sp);
+int wide_stage(tbnav_icp* h, int first, const std::vector<int>& esc, int n_beams, const tbnav_icp_search_params& sp,
+               const SearchConst& sc, const SearchPair* d_pairs, const tbnav_icp_search_wide_params& wp, uint32_t* scores,
+               const tbnav_icp_search_shape_params* shp);
 
 }  // namespace tbnav_icpdev

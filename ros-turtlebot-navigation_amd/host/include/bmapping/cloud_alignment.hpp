@@ -33,6 +33,12 @@
 // along a direction in which the scores are flat, a corridor's axis, the guess is kept instead of being pulled to where the two
 // scans overlay.  Off unless asked for.  -DTBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE beside the three defines above makes the
 // constructor's search carry shape = true; it only changes a default argument too (without the search it has no effect).
+//
+// ICPSearch::wide = true adds the search's wide second stage (tbnav_icp.h, items W1-W8; tbnav_icp_set_search_wide): a window of up
+// to +-64 cells and +-180 steps, scored only when the first stage is rejected (wide_when = OnReject, the default), so a guess
+// that is metres off is found and a good guess pays nothing.  Off unless asked for.  -DTBNAV_SCAN_ALIGNMENT_SEARCH_WIDE beside
+// -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP and -DTBNAV_SCAN_ALIGNMENT_SEARCH makes the constructor's search carry wide = true; it only
+// changes a default argument too (without the search it has no effect).
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -67,12 +73,21 @@
 #define TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT false
 #endif
 
+#ifdef TBNAV_SCAN_ALIGNMENT_SEARCH_WIDE
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_WIDE_DEFAULT true
+#else
+#define TBNAV_SCAN_ALIGNMENT_SEARCH_WIDE_DEFAULT false
+#endif
+
 namespace bmapping {
 
 using rigid2d::Transform2D;
 
 /// (addition) what the device ICP minimises: PointToPoint is the reference's (PCL's) metric and the default
 enum class ICPMetric { PointToPoint, PointToLine };
+
+/// (addition) when the search's wide second stage runs: TBNAV_ICP_WIDE_ON_REJECT, _ON_REJECT_OR_EDGE, _ALWAYS
+enum class ICPWideWhen { OnReject = 0, OnRejectOrEdge = 1, Always = 2 };
 
 /// (addition) the correlative search in front of the device ICP: tbnav_icp_search_params with its defaults
 struct ICPSearch {
@@ -88,6 +103,10 @@ struct ICPSearch {
   bool shape = false;          ///< the shape of the score volume (tbnav_icp_search_shape_params with its defaults below)
   int shape_drop_q10 = 256;    ///< how far below the chosen score a candidate still counts, in 1/1024, 0..1023
   double shape_flat_cells2 = 2.0;  ///< second moment (cells^2) above which a direction is flat, > 0
+  bool wide = false;           ///< the wide second stage (tbnav_icp_search_wide_params with its defaults below)
+  int wide_lin_cells = 48;     ///< its window +-wide_lin_cells cells, lin_cells..64
+  int wide_ang_steps = 45;     ///< its window +-wide_ang_steps steps of ang_step, ang_steps..180
+  ICPWideWhen wide_when = ICPWideWhen::OnReject;  ///< when it runs
 };
 
 class ScanAlignment {
@@ -97,11 +116,13 @@ class ScanAlignment {
 
   ScanAlignment(const LaserProperties& props, const Transform2D& Trs, bool device_icp = TBNAV_SCAN_ALIGNMENT_DEVICE_ICP_DEFAULT,
                 ICPMetric device_metric = TBNAV_SCAN_ALIGNMENT_METRIC_DEFAULT, bool device_search = TBNAV_SCAN_ALIGNMENT_SEARCH_DEFAULT,
-                bool device_search_shape = TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT)
+                bool device_search_shape = TBNAV_SCAN_ALIGNMENT_SEARCH_SHAPE_DEFAULT,
+                bool device_search_wide = TBNAV_SCAN_ALIGNMENT_SEARCH_WIDE_DEFAULT)
       : props_(props), Trs_(Trs) {
     if (device_icp && device_search) {
       ICPSearch search;
       search.shape = device_search_shape;
+      search.wide = device_search_wide;
       useDeviceICP(-1, device_metric, search);
     } else if (device_icp) useDeviceICP(-1, device_metric);
   }

@@ -54,6 +54,14 @@ void ScanAlignment::installDeviceICP(int device, ICPMetric metric, const ICPSear
       if (frc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument("bmapping::ScanAlignment::useDeviceICP: search shape parameters outside their limits");
       if (frc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(frc));
     }
+    if (search->wide) {
+      tbnav_icp_search_wide_params wp;
+      tbnav_icp_default_search_wide_params(&wp);
+      wp.lin_cells = search->wide_lin_cells; wp.ang_steps = search->wide_ang_steps; wp.when = static_cast<int32_t>(search->wide_when);
+      const int wrc = tbnav_icp_set_search_wide(raw, &wp);
+      if (wrc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument("bmapping::ScanAlignment::useDeviceICP: wide search parameters outside their limits");
+      if (wrc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(wrc));
+    }
   }
   matcher_ = [h](Transform2D& T, const Transform2D& T_init, const std::vector<float>& target, const std::vector<float>& source) {
     if (target.size() != source.size()) throw std::invalid_argument("bmapping::ScanAlignment: scans of different lengths");

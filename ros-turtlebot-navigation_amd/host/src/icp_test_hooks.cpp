@@ -69,7 +69,7 @@ extern "C" {
 
 const char* hst_icp_last_error() { return g_icp_err.c_str(); }
 
-// The four hst_icp_pf_run* put a ScanAlignment(props, Trs) on the device their own way and hand it to run_filter (whose
+// The hst_icp_pf_run* put a ScanAlignment(props, Trs) on the device their own way and hand it to run_filter (whose
 // comment has the arguments).  Each returns 0, or -1 (message in hst_icp_last_error).
 // hst_icp_pf_run: the point metric, no search.  hst_icp_pf_run_metric: the metric named (0: point-to-point, 1: point-to-line).
 // hst_icp_pf_run_search: the same with the correlative search in front of the ICP (search != 0; lin_cells as given, all else
@@ -103,6 +103,25 @@ int hst_icp_pf_run_search_shape(int metric, int shape, int drop_q10, double flat
     sp.shape = shape != 0;
     sp.shape_drop_q10 = drop_q10;
     sp.shape_flat_cells2 = flat_cells2;
+    aligner.useDeviceICP(-1, m, sp);
+    run_filter(aligner, N, k, map_half, seed, scans, n_beams, n_scans, odom, u, out_ok, out_T, out_pose, out_neff);
+    return 0;
+  } catch (const std::exception& e) { g_icp_err = e.what(); return -1; }
+}
+
+// hst_icp_pf_run_search_wide: the filter with the search (its defaults) and, wide != 0, its wide second stage (wide_lin_cells,
+// wide_ang_steps and when as given) in front of the ICP; everything else as hst_icp_pf_run_search.
+int hst_icp_pf_run_search_wide(int metric, int wide, int wide_lin_cells, int wide_ang_steps, int when, int N, int k, double map_half, uint64_t seed,
+                               const float* scans, int n_beams, int n_scans, const double* odom, const double* u, int32_t* out_ok, double* out_T,
+                               double* out_pose, int32_t* out_neff) {
+  try {
+    const bmapping::ICPMetric m = hook_metric(metric, "hst_icp_pf_run_search_wide");
+    bmapping::ScanAlignment aligner(hook_laser(), Transform2D());
+    bmapping::ICPSearch sp;
+    sp.wide = wide != 0;
+    sp.wide_lin_cells = wide_lin_cells;
+    sp.wide_ang_steps = wide_ang_steps;
+    sp.wide_when = static_cast<bmapping::ICPWideWhen>(when);
     aligner.useDeviceICP(-1, m, sp);
     run_filter(aligner, N, k, map_half, seed, scans, n_beams, n_scans, odom, u, out_ok, out_T, out_pose, out_neff);
     return 0;

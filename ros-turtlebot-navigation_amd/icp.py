@@ -14,6 +14,10 @@ shape=True | dict(...) beside search (an addition too) measures the shape of the
 F1-F6) and keeps the guess along a direction in which the scores are flat, a corridor's axis: the search alone pulls two scans of
 a corridor on top of each other.  The default is off.
 
+wide=True | dict(...) beside search (an addition too) adds the wide second stage of the header's items W1-W8: a window of up to
++-64 cells and +-180 steps, scored only when the first stage is rejected (when="reject", the default), or also when its choice
+sits on the border of its window ("reject_or_edge"), or always and in its place ("always").  The default is off.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -76,6 +80,8 @@ _SEARCH_FIELDS = tuple(f for f, _ in capi.IcpSearchParams._fields_)
 
 
 _SHAPE_FIELDS = ("drop_q10", "flat_cells2")
+_WIDE_FIELDS = ("lin_cells", "ang_steps", "when")
+_WIDE_WHEN = {"reject": capi.ICP_WIDE_ON_REJECT, "reject_or_edge": capi.ICP_WIDE_ON_REJECT_OR_EDGE, "always": capi.ICP_WIDE_ALWAYS}
 
 
 def _search_shape(r: "capi.IcpSearchShape") -> dict:
@@ -91,7 +97,8 @@ def _search_info(i: "capi.IcpSearchInfo") -> dict:
 class ScanAlignment:
     """bmapping::ScanAlignment on one MI355X."""
 
-    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0, search=None, shape=None):
+    def __init__(self, params: "capi.IcpParams | None" = None, metric="point", normal_window=0, normal_max_gap=0.0, search=None, shape=None,
+                 wide=None):
         self._L = capi.lib()
         self.params = params if params is not None else default_params()
         if metric not in _METRICS:
@@ -116,6 +123,64 @@ class ScanAlignment:
             except Exception:
                 self.close()
                 raise
+
+        if wide is not None and wide is not False:
+            try:
+                self.setSearchWide(**({} if wide is True else dict(wide)))
+            except Exception:
+                self.close()
+                raise
+
+    def setSearchWide(self, *off, **kw):
+        """tbnav_icp_set_search_wide: setSearchWide(lin_cells=..., ang_steps=..., when=...) turns the wide second stage on
+        wherever a search runs, with the defaults (tbnav_icp_default_search_wide_params) for what is not named; when is
+        "reject" | "reject_or_edge" | "always" or the C constant; setSearchWide(None) turns it off.  It is idle while the
+        search itself is off.  Its window must contain the search's, so call setSearch first."""
+        if off:
+            if off != (None,) or kw:
+                raise TypeError("setSearchWide(None) turns the wide stage off; parameters go by keyword")
+            capi.check(self._L.tbnav_icp_set_search_wide(self._h, None), "tbnav_icp_set_search_wide")
+            return
+        p = capi.IcpSearchWideParams()
+        self._L.tbnav_icp_default_search_wide_params(C.byref(p))
+        for key, v in kw.items():
+            if key not in _WIDE_FIELDS:
+                raise TypeError(f"setSearchWide: no parameter {key!r} (one of {_WIDE_FIELDS})")
+            if key == "when" and isinstance(v, str):
+                if v not in _WIDE_WHEN:
+                    raise ValueError(f"when must be one of {sorted(_WIDE_WHEN)}, not {v!r}")
+                v = _WIDE_WHEN[v]
+            setattr(p, key, v)
+        capi.check(self._L.tbnav_icp_set_search_wide(self._h, C.byref(p)), "tbnav_icp_set_search_wide")
+
+    def searchWideParams(self):
+        """-> (on, dict of tbnav_icp_search_wide_params) as the handle holds them (the defaults while the wide stage is off)"""
+        on, p = C.c_int32(), capi.IcpSearchWideParams()
+        capi.check(self._L.tbnav_icp_get_search_wide(self._h, C.byref(on), C.byref(p)), "tbnav_icp_get_search_wide")
+        return bool(on.value), {f: getattr(p, f) for f in _WIDE_FIELDS}
+
+    def lastSearchWide(self) -> dict:
+        """beside lastSearch()'s outcome: the first stage's record and whether the wide stage ran -> dict(first=..., ran=...)"""
+        r = capi.IcpSearchWideInfo()
+        capi.check(self._L.tbnav_icp_last_search_wide(self._h, C.byref(r)), "tbnav_icp_last_search_wide")
+        return dict(first=_search_info(r.first), ran=r.ran)
+
+    def searchWideScores(self, T_init, target_scan, source_scan, scores=True):
+        """test hook, stateless: the wide stage alone, whatever `when` says -> (accepted, T, info dict,
+        uint32 [2A+1][2W+1][2W+1], or None with scores=False)"""
+        tgt = np.ascontiguousarray(target_scan, dtype=np.float32)
+        src = np.ascontiguousarray(source_scan, dtype=np.float32)
+        if tgt.size != src.size:
+            raise ValueError("target and source scans must have the same number of beams")
+        p = self.searchWideParams()[1]
+        na, nl = 2 * p["ang_steps"] + 1, 2 * p["lin_cells"] + 1
+        vol = np.zeros((na, nl, nl), dtype=np.uint32) if scores else None
+        out = (C.c_double * 3)()
+        info = capi.IcpSearchInfo()
+        capi.check(self._L.tbnav_icp_search_wide_scores(self._h, tgt.ctypes.data, src.ctypes.data, src.size, _d3(T_init), out,
+                                                        C.byref(info), vol.ctypes.data if scores else None),
+                   "tbnav_icp_search_wide_scores")
+        return bool(info.accepted), tuple(out), _search_info(info), vol
 
     def setSearchShape(self, *off, **kw):
         """tbnav_icp_set_search_shape: setSearchShape(drop_q10=..., flat_cells2=...) turns the shape of the score volume on

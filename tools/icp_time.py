@@ -1,5 +1,5 @@
 """Timing of the device ICP (include/tbnav_icp.h) on the GPU:
-python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N] [--search] [--shape]
+python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--max-iter N] [--search] [--shape] [--wide [--when W]]
   - latency of one synchronous tbnav_icp_step (host clock around the call, which ends in a stream synchronise) at 360 beams
     (1 deg) and 1080 beams (1/3 deg): median / p10 / p90 of 500 scans after 20 of warm-up, a robot driving round a room;
   - tbnav_icp_step_batch over 2000 scans of the same kind of run: median of 5 calls (after one of warm-up), per call and
@@ -16,6 +16,13 @@ python tools/icp_time.py [--out FILE] [--quick] [--metric point|line|both] [--ma
     parameters), in the same process on the same scans: every "<name>_search" record again under "<name>_search_shape", and
     "search_shape_alone_360" / "_1080": tbnav_icp_search with the shape on; "shape_over_search" holds the differences of the
     medians (what the shape adds);
+  --wide (with --search): the search's wide second stage (tbnav_icp_set_search_wide, default window, --when reject |
+    reject_or_edge | always, default reject), in the same process on the same scans: every "<name>_search" record again under
+    "<name>_search_wide" (with the robot's good guesses and `reject` the wide stage never runs: "wide_ran" counts), and
+    "wide_over_search" holds the differences of the medians; "wide_alone_<W>_<A>_<beams>": tbnav_icp_search with when = always
+    (the wide stage's own cost, the table included) at (W, A) = (48, 45), (64, 20), (64, 180), with its ratio to
+    "search_alone_<beams>"; "escalated_step_360" / "_1080": tbnav_icp_step with every guess slipped by 1.6 m (first stage
+    rejected, wide stage, ICP) as one wall time;
   --quick: a few scans only (what a `rocprofv3 --kernel-trace --stats` run of this script needs).
 Kernel times come from a separate rocprofv3 run, not from this script."""
 import argparse
@@ -48,10 +55,12 @@ def loop_run(n, n_beams, beam_delta_deg, seed=1):
     return scans, T_init
 
 
-def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100, search=None, shape=None):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape)
+def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_iter=100, search=None, shape=None, wide=None, slip=0.0):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape,
+                          wide=wide)
     scans, T_init = loop_run(n_warm + n_time, n_beams, beam_delta_deg)
-    ts, iters, fails, accepted = [], [], 0, 0
+    T_init[1:, 1] += slip                                      # every guess off by `slip` metres in x
+    ts, iters, fails, accepted, ran = [], [], 0, 0, 0
     for s in range(n_warm + n_time):
         t0 = time.perf_counter()
         ok, T, info = a.pclICPWrapper(T_init[s], scans[s])
@@ -61,6 +70,7 @@ def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_it
             iters.append(info["iterations"])
             fails += 0 if ok else 1
             accepted += a.lastSearch()["accepted"] if search else 0
+            ran += a.lastSearchWide()["ran"] if wide else 0
     a.close()
     ts = np.array(ts)
     rec = dict(n_beams=n_beams, scans=n_time, median_us=float(np.median(ts)), p10_us=float(np.percentile(ts, 10)),
@@ -68,12 +78,14 @@ def step_latency(n_beams, beam_delta_deg, n_warm, n_time, metric="point", max_it
                at_max_iter=int(np.sum(np.array(iters) >= max_iter)), failures=fails)
     if search:
         rec["searches_accepted"] = accepted
+    if wide:
+        rec["wide_ran"] = ran
     return rec
 
 
-def search_latency(n_beams, beam_delta_deg, n_warm, n_time, shape=None):
+def search_latency(n_beams, beam_delta_deg, n_warm, n_time, shape=None, wide=None):
     """tbnav_icp_search alone (default parameters): each scan of the run against the one before it"""
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg), shape=shape)
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg), shape=shape, wide=wide)
     scans, T_init = loop_run(n_warm + n_time + 1, n_beams, beam_delta_deg)
     ts, acc, qual = [], 0, []
     for s in range(1, n_warm + n_time + 1):
@@ -90,8 +102,9 @@ def search_latency(n_beams, beam_delta_deg, n_warm, n_time, shape=None):
                 p90_us=float(np.percentile(ts, 90)), accepted=acc, mean_quality=float(np.mean(qual)))
 
 
-def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100, search=None, shape=None):
-    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape)
+def batch_time(n_scans, reps, n_beams=360, beam_delta_deg=1.0, metric="point", max_iter=100, search=None, shape=None, wide=None):
+    a = icp.ScanAlignment(icp.default_params(beam_delta_deg=beam_delta_deg, max_iter=max_iter), metric=metric, search=search, shape=shape,
+                          wide=wide)
     scans, T_init = loop_run(n_scans, n_beams, beam_delta_deg, seed=2)
     ts = []
     for r in range(reps + 1):
@@ -118,9 +131,13 @@ def main():
     ap.add_argument("--max-iter", type=int, default=100)
     ap.add_argument("--search", action="store_true")
     ap.add_argument("--shape", action="store_true")
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--when", choices=("reject", "reject_or_edge", "always"), default="reject")
     a = ap.parse_args()
     if a.shape and not a.search:
         ap.error("--shape measures what it adds to the search: give --search too")
+    if a.wide and not a.search:
+        ap.error("--wide measures what it adds to the search: give --search too")
     n_warm, n_time, reps = (2, 10, 1) if a.quick else (20, 500, 5)
 
     def run(metric):
@@ -137,6 +154,15 @@ def main():
                        batch_2000_search_shape=batch_time(2000, reps, metric=metric, max_iter=a.max_iter, search=True, shape=True))
             res["shape_over_search"] = {key: res[key + "_search_shape"][t] - res[key + "_search"][t]
                                         for key, t in (("step_360", "median_us"), ("step_1080", "median_us"), ("batch_2000", "median_ms"))}
+        if a.wide:
+            w = dict(when=a.when)
+            res.update(step_360_search_wide=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter, search=True, wide=w),
+                       step_1080_search_wide=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter, search=True, wide=w),
+                       batch_2000_search_wide=batch_time(2000, reps, metric=metric, max_iter=a.max_iter, search=True, wide=w),
+                       escalated_step_360=step_latency(360, 1.0, n_warm, n_time, metric, a.max_iter, search=True, wide=w, slip=1.6),
+                       escalated_step_1080=step_latency(1080, 1.0 / 3.0, n_warm, n_time, metric, a.max_iter, search=True, wide=w, slip=1.6))
+            res["wide_over_search"] = {key: res[key + "_search_wide"][t] - res[key + "_search"][t]
+                                       for key, t in (("step_360", "median_us"), ("step_1080", "median_us"), ("batch_2000", "median_ms"))}
         return res
 
     if a.metric == "both":
@@ -153,6 +179,13 @@ def main():
     if a.shape:
         res["search_shape_alone_360"] = search_latency(360, 1.0, n_warm, n_time, shape=True)
         res["search_shape_alone_1080"] = search_latency(1080, 1.0 / 3.0, n_warm, n_time, shape=True)
+    if a.wide:
+        for lin, ang in ((48, 45), (64, 20), (64, 180)):
+            for n_beams, dd in ((360, 1.0), (1080, 1.0 / 3.0)):
+                rec = search_latency(n_beams, dd, n_warm, n_time if ang < 180 else max(n_time // 5, 5),
+                                     wide=dict(lin_cells=lin, ang_steps=ang, when="always"))
+                rec["over_search_alone"] = rec["median_us"] / res["search_alone_%d" % n_beams]["median_us"]
+                res["wide_alone_%d_%d_%d" % (lin, ang, n_beams)] = rec
     print(json.dumps(res, indent=1))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
