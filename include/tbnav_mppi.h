@@ -240,6 +240,58 @@ int tbnav_mppi_group_enqueue_rng_batch(tbnav_mppi_group* g, const double* x0s, i
 int tbnav_mppi_group_last_controls(tbnav_mppi_group* g, double u_out[2]);
 int tbnav_mppi_group_synchronize(tbnav_mppi_group* g);
 
+/* ---- COST FIELD: a map term in the rollout loss (an OPTION the reference does not have; off by default) --------------
+ * The reference's loss is quadratic only (mppi.hpp:87-105): distance to the waypoint plus control effort.  A cost field adds a
+ * state cost sampled from a grid — an inflated obstacle map derived, for instance, from the filter's distance field
+ * (tbnav_rbpf_get_occ_dist) — so that the rollouts pay for crossing what the mapper has drawn.  This section is the whole
+ * specification; tests/mppi_field_restatement.py restates it in numpy.
+ *
+ * F1. Geometry.  nx, ny in 2 .. TBNAV_MPPI_FIELD_MAX_SIDE; (xmin, ymin), finite, are the world coordinates of the OUTER corner of
+ *     cell (0, 0); resolution finite and > 0; weight finite (0 and negative allowed).  Values are float[nx*ny], cell (ix, iy) at
+ *     index ix*ny + iy (x is the slow index — for the square grids the filter supports that is tbnav_rbpf_get_occ_dist's
+ *     idx = i*xsize + j, tbnav_rbpf.h:20-21: a field derived cell by cell from that array needs no transpose).  Every value must
+ *     be finite.  A value is taken at its cell's CENTRE.
+ * F2. Lookup of a position (x, y), all in fp64, inv = 1.0 / resolution formed on the host:
+ *       gx = ((x - xmin) * inv) - 0.5;  gx = gx > 0 ? gx : 0  (a NaN goes to 0);  gx = gx < nx-1 ? gx : nx-1
+ *       ix = min((int)floor(gx), nx-2);  fx = gx - ix                     (gy, iy, fy the same with ymin and ny)
+ *       c00 = v[ix*ny+iy], c01 = v[ix*ny+iy+1], c10 = v[(ix+1)*ny+iy], c11 = v[(ix+1)*ny+iy+1]      (widened to fp64)
+ *       a = c00 + fy*(c01 - c00);  b = c10 + fy*(c11 - c10);  c = a + fx*(b - a)
+ *     Bilinear: continuous everywhere, constant beyond the outermost cell centres, the stored value at a cell centre.  (A
+ *     nearest-cell lookup is discontinuous: the 1-2 ulp by which the device's trigonometry differs from libm would flip cells.
+ *     With this form a position error of d changes the cost by at most d * (max - min) / resolution.)  No position, however
+ *     large and whether or not it is finite, causes an access outside the array.
+ * F3. Loss.  With a field set, the loss of time step i = 0 .. T-1 of every rollout gains weight * c(x_i, y_i), the state AFTER
+ *     step i (traj.col(i), rk4.cpp:62-66) — the state the quadratic loss already uses; the last step gains it on top of the
+ *     terminal loss that replaces its running loss (mppi.cpp:105).  Everything downstream is unchanged: cumSumCost, the soft-min
+ *     with its 1e-8 floor, the clamp, the shift.
+ * F4. Scope.  A set field applies to every tick entry point of the handle (tbnav_mppi_new_controls*, _enqueue_dev, _enqueue_rng,
+ *     _enqueue_rng_batch, _shard_partials* and so the attached-communicator tick, _profile_tick, _profile_kernels*), with either
+ *     dynamics and every TBNAV_MPPI_OPT_TRIG (2 takes the three-evaluation form).  Such a handle runs the three-launch tick:
+ *     mppi_rollout_field (one lane per rollout), mppi_partials, mppi_combine; device-noise ticks sample into the handle's buffers
+ *     first.  It never takes the fused kernel, the noise-ahead draw or a captured graph (tbnav_mppi_enqueue_rng_batch launches its
+ *     ticks one by one), whatever TBNAV_MPPI_OPT_KERNEL says.  tbnav_mppi_last_kernel_names names the kernel;
+ *     tbnav_mppi_get_cost_to_go returns J with the field's share in it.
+ * F5. Off means untouched.  A handle that never had a field, or whose field was cleared, launches exactly the kernels it launched
+ *     before this section existed, with the same arguments.  Setting or clearing a field waits for the handle's device before it
+ *     replaces the buffer, and no graph of ticks captured before is replayed afterwards. */
+#define TBNAV_MPPI_FIELD_MAX_SIDE 4096
+typedef struct tbnav_mppi_cost_field {
+  int32_t nx, ny;     /* cells along x (slow index) and y, each 2 .. TBNAV_MPPI_FIELD_MAX_SIDE */
+  double xmin, ymin;  /* world coordinates of the outer corner of cell (0, 0) */
+  double resolution;  /* cell side, > 0 */
+  double weight;      /* what a unit of field value adds to a step's loss */
+} tbnav_mppi_cost_field;
+/* geom == NULL clears the field.  Anything outside F1 (a non-finite value, a null values_host included) is
+ * TBNAV_ERR_INVALID_ARG and changes nothing: a field set earlier stays in force.  The values are copied. */
+int tbnav_mppi_set_cost_field(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, const float* values_host);
+/* *on = 1 and *geom = the geometry in force, or *on = 0 (geom untouched).  Either output may be null. */
+int tbnav_mppi_get_cost_field(const tbnav_mppi* h, int32_t* on, tbnav_mppi_cost_field* geom);
+/* Test hook: F2 evaluated ON THE DEVICE, by the very function the rollout kernel calls, at n host positions xy[n][2]; without
+ * the weight.  TBNAV_ERR_INVALID_ARG when no field is set. */
+int tbnav_mppi_cost_field_lookup(tbnav_mppi* h, const double* xy, int32_t n, double* out);
+/* Every member of the group receives the field (or has it cleared), or none does. */
+int tbnav_mppi_group_set_cost_field(tbnav_mppi_group* g, const tbnav_mppi_cost_field* geom, const float* values_host);
+
 /* ---- parity / debug hooks --------------------------------------------------------------------- */
 
 /* Cost-to-go J of the last tick BEFORE the per-step min subtraction, host buffer [T][K]

@@ -54,6 +54,15 @@ class MppiParams(C.Structure):
     ]
 
 
+class MppiCostField(C.Structure):
+    """tbnav_mppi_cost_field (include/tbnav_mppi.h, COST FIELD)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("xmin", C.c_double), ("ymin", C.c_double), ("resolution", C.c_double),
+                ("weight", C.c_double)]
+
+
+MPPI_FIELD_MAX_SIDE = 4096
+
+
 class RbpfParams(C.Structure):
     """tbnav_rbpf_params (include/tbnav_rbpf.h)."""
     _fields_ = [
@@ -218,6 +227,10 @@ def lib() -> C.CDLL:
         "tbnav_mppi_profile_kernels": (C.c_int, [vp, dp, vp, vp, vp, i32, C.POINTER(C.c_float)]),
         "tbnav_mppi_profile_kernels_rng": (C.c_int, [vp, dp, C.c_uint64, C.c_uint64, vp, i32, C.POINTER(C.c_float)]),
         "tbnav_mppi_last_kernel_names": (C.c_int, [vp, C.c_char_p, i32, C.c_char_p, i32]),
+        "tbnav_mppi_set_cost_field": (C.c_int, [vp, C.POINTER(MppiCostField), vp]),
+        "tbnav_mppi_get_cost_field": (C.c_int, [vp, C.POINTER(i32), C.POINTER(MppiCostField)]),
+        "tbnav_mppi_cost_field_lookup": (C.c_int, [vp, vp, i32, vp]),
+        "tbnav_mppi_group_set_cost_field": (C.c_int, [vp, C.POINTER(MppiCostField), vp]),
         # communicators (include/tbnav_comm.h) and the sharded MPPI tick
         "tbnav_comm_unique_id": (C.c_int, [vp]),
         "tbnav_comm_unique_id_ipc": (C.c_int, [vp]),

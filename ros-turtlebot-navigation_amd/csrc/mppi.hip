@@ -50,6 +50,7 @@ int launch_rollout(tbnav_mppi* h, const double x0[3], const double* d_duL, const
   a.T = h->T; a.K = h->K;
   const dim3 grid((h->K + kWave - 1) / kWave), block(kWave);
   const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
+  if (h->field_on) return launch_rollout_field(h, a, usrc, d_duL, d_duR, st);   // (a cost field: its own kernel, whatever the handle's choice)
   if (h->scan_tc > 0 && h->dyn == 0) {  // (the arc dynamics live in the fused and the sequential kernels)
     h->prefix_rows = 0;
     const int TCv = h->scan_tc, C = (h->T + TCv - 1) / TCv;
@@ -233,7 +234,7 @@ bool pick_noise(tbnav_mppi* h, const double*& d_duL, const double*& d_duR) {
 
 // the perturbations can be drawn inside the fused kernel: its in-kernel form exists for 8 and 16 rollouts per workgroup (either sampler)
 bool rng_in_kernel(const tbnav_mppi* h) {
-  return h->fused_rng && (h->fused_r == 8 || h->fused_r == 16);
+  return fused_rng(h) && (h->fused_r == 8 || h->fused_r == 16);
 }
 
 // Noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD) where the tick is latency-bound: 8 rollouts per workgroup (K <= 2048 at 256 CUs), the
@@ -412,7 +413,7 @@ void tbnav_mppi_destroy(tbnav_mppi* h) {
   direct_teardown(h);
   exchange_words_free(h);
   (void)hipFree(h->d_raw); (void)hipFree(h->d_records); (void)hipFree(h->d_records_f); (void)hipFree(h->d_out);
-  (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag);
+  (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag); (void)hipFree(h->d_field);
   if (h->h_out) (void)hipHostFree(h->h_out);
   for (auto* g : {&h->tg, &h->tgs}) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); }
   (void)hipFree(h->d_tick0);
@@ -557,7 +558,7 @@ int tbnav_mppi_shard_partials(tbnav_mppi* h, const double x0[3], const double* d
   if (!h || !x0 || !d_records_out || !pick_noise(h, d_duL, d_duR)) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (h->fused_dev && kSlice % h->fused_r == 0) {
+  if (fused_dev(h) && kSlice % h->fused_r == 0) {
     // small K: the fused rollout+partials kernel, then its fine records folded into the K-slice records that the
     // ranks exchange (two short launches instead of three)
     const int rcf = launch_fused(h, x0, d_duL, d_duR, st);
@@ -603,7 +604,7 @@ int tbnav_mppi_enqueue_dev(tbnav_mppi* h, const double x0[3], const double* d_du
   if (h->comm) return sharded_tick(h, x0, d_duL, d_duR, nullptr, 0, stream);
   DeviceGuard guard(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (h->fused_dev) {
+  if (fused_dev(h)) {
     const int rcf = launch_fused(h, x0, d_duL, d_duR, st);
     if (rcf != TBNAV_OK) return rcf;
     return launch_combine(h, h->d_records_f, 1, st, h->fused_S);
@@ -625,7 +626,7 @@ int tbnav_mppi_profile_tick(tbnav_mppi* h, const double x0[3], const double* d_d
   for (auto& e : ev) TBNAV_HIP(hipEventCreate(&e));
   int rc = TBNAV_OK;
   TBNAV_HIP(hipEventRecord(ev[0], st));
-  if (h->fused_dev) {  // rollout and partials are one kernel: its time is reported under [0], [1] is the empty interval
+  if (fused_dev(h)) {  // rollout and partials are one kernel: its time is reported under [0], [1] is the empty interval
     rc = launch_fused(h, x0, d_duL, d_duR, st);
     if (rc == TBNAV_OK) { TBNAV_HIP(hipEventRecord(ev[1], st)); TBNAV_HIP(hipEventRecord(ev[2], st)); rc = launch_combine(h, h->d_records_f, 1, st, h->fused_S); }
   } else {
@@ -665,7 +666,7 @@ int tbnav_mppi_profile_kernels(tbnav_mppi* h, const double x0[3], const double* 
     ms[which] = t / (float)reps;
   };
   for (int i = 0; i < TBNAV_MPPI_NKERNELS; ++i) ms[i] = 0.f;
-  if (h->fused_dev) {
+  if (fused_dev(h)) {
     timed(0, [&] { return launch_fused(h, x0, d_duL, d_duR, st); });
     timed(2, [&] { return launch_combine(h, h->d_records_f, 1, st, h->fused_S); });
   } else {
@@ -680,7 +681,7 @@ int tbnav_mppi_profile_kernels(tbnav_mppi* h, const double x0[3], const double* 
 int tbnav_mppi_profile_kernels_rng(tbnav_mppi* h, const double x0[3], uint64_t seed, uint64_t tick, void* stream, int32_t reps,
                                    float ms[TBNAV_MPPI_NKERNELS]) {
   if (!h || !x0 || !ms || reps < 2 || (reps & 1)) return TBNAV_ERR_INVALID_ARG;
-  if (!(h->fused_dev && rng_in_kernel(h))) {
+  if (!(fused_dev(h) && rng_in_kernel(h))) {
     // no in-kernel noise for this configuration: the production tick samples into the handle's buffers and runs the plain kernels
     const int rc = tbnav_mppi_sample_noise(h, seed, tick, stream);
     return rc != TBNAV_OK ? rc : tbnav_mppi_profile_kernels(h, x0, nullptr, nullptr, stream, reps, ms);
@@ -733,6 +734,7 @@ int tbnav_mppi_last_kernel_names(const tbnav_mppi* h, char* rollout, int32_t rol
       case 2: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_scan<%d, %d, %d>", k[1], k[2], k[3]); break;
       case 3: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_prefix<%d>", k[1]); break;
       case 4: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_cost<%d>", k[1]); break;
+      case 5: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_field<%d>", k[1]); break;
       default: rollout[0] = 0;
     }
   }

@@ -20,7 +20,7 @@ using tbnav_mk::DirectPub;
 struct tbnav_mppi {
   tbnav_mppi_params p;
   int T = 0, K = 0, S = 0, device = 0;
-  int lk_rollout[5] = {0, 0, 0, 0, 0};  // the instantiation the last rollout launch picked: kind (1 fused, 2 scan, 3 prefix, 4 cost), template arguments
+  int lk_rollout[5] = {0, 0, 0, 0, 0};  // the instantiation the last rollout launch picked: kind (1 fused, 2 scan, 3 prefix, 4 cost, 5 field), template arguments
   int lk_combine[2] = {0, 0};           // ... and the last combine: KEEP, DIRECT  (tbnav_mppi_last_kernel_names)
   double xd[3] = {0, 0, 0};
   double uinit[2] = {0, 0};
@@ -102,6 +102,11 @@ struct tbnav_mppi {
   // publishes the records itself (and clears this); otherwise the tick launches mppi_direct_publish
   bool pub_pending = false;
   DirectPub pub_next{nullptr, 0, 0, 0, 0u, 0};
+  // cost field (tbnav_mppi.h, COST FIELD; mppi_field.hip): while field_on, every tick's rollout launch is mppi_rollout_field and the
+  // handle takes neither the fused kernel nor the noise-ahead draw nor a captured graph (tbnav_mh::fused_dev / fused_rng below)
+  bool field_on = false;
+  tbnav_mppi_cost_field field{0, 0, 0.0, 0.0, 0.0, 0.0};
+  float* d_field = nullptr;     // [nx][ny]
 };
 
 // One process driving several GPUs: the whole ensemble behind one object (what controller::MPPI built with n_gpus > 1 holds).
@@ -126,6 +131,15 @@ struct DeviceGuard {
   ~DeviceGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
 };
 
+// which ticks take the fused kernel (resident noise / noise drawn inside it): never a handle with a cost field
+inline bool fused_dev(const tbnav_mppi* h) { return h->fused_dev && !h->field_on; }
+inline bool fused_rng(const tbnav_mppi* h) { return h->fused_rng && !h->field_on; }
+// (mppi_field.hip) the rollout launch of a handle with a cost field; a's lds_from and the kernel's name are set there
+int launch_rollout_field(tbnav_mppi* h, RolloutArgs a, const USrc& usrc, const double* d_duL, const double* d_duR, hipStream_t st);
+// the two halves of tbnav_mppi_set_cost_field, apart so that a group can stage every member's copy before any member changes:
+// field_stage checks F1 and uploads the values (*d_new = nullptr for geom == nullptr); field_commit waits for the device and swaps
+int field_stage(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, const float* values_host, float** d_new);
+int field_commit(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, float* d_new);
 // (mppi.hip)
 Lam lam_of(double lambda);
 inline Lam lam_of(const tbnav_mppi* h) { return lam_of(h->p.lambda); }

@@ -418,6 +418,21 @@ int tbnav_mppi_group_set_option(tbnav_mppi_group* g, int32_t option, int32_t val
   if (option == TBNAV_MPPI_OPT_DIRECT_EXCHANGE) return group_direct_setup(g);   // (a group is attached already: the choice is made here)
   return TBNAV_OK;
 }
+// every member or none: all copies are checked and staged before the first member changes (tbnav_mppi.h, COST FIELD)
+int tbnav_mppi_group_set_cost_field(tbnav_mppi_group* g, const tbnav_mppi_cost_field* geom, const float* values_host) {
+  if (!g) return TBNAV_ERR_INVALID_ARG;
+  std::vector<float*> staged((size_t)g->n, nullptr);
+  for (int r = 0; r < g->n; ++r) {
+    const int rc = field_stage(g->m[r], geom, values_host, &staged[r]);
+    if (rc != TBNAV_OK) {
+      for (int q = 0; q < r; ++q) { DeviceGuard guard(g->m[q]->device); (void)hipFree(staged[q]); }
+      return rc;
+    }
+  }
+  int rc_all = TBNAV_OK;
+  for (int r = 0; r < g->n; ++r) { const int rc = field_commit(g->m[r], geom, staged[r]); if (rc != TBNAV_OK && rc_all == TBNAV_OK) rc_all = rc; }
+  return rc_all;
+}
 
 }  // extern "C"
 

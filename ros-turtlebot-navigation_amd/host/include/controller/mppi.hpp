@@ -36,6 +36,19 @@ struct LossFunc {
   double Q[3], R[2], P1[3];
 };
 
+/// Not in the reference: a map term of the rollout loss (include/tbnav_mppi.h, COST FIELD).  values[ix * ny + iy] is taken at the
+/// centre of cell (ix, iy); (xmin, ymin) is the outer corner of cell (0, 0); every rollout step's loss gains weight * (bilinear
+/// lookup at the step's position).  For a square map the layout is that of the filter's distance field.
+struct CostField {
+  int nx = 0, ny = 0;
+  double xmin = 0.0, ymin = 0.0, resolution = 0.0, weight = 1.0;
+  std::vector<float> values;
+};
+/// A field's values from distances to the nearest obstacle (nx * ny of them, metres): 1 where d <= r_robot, 0 where
+/// d >= r_inflate, ((r_inflate - d) / (r_inflate - r_robot))^2 between — formed in double, then rounded.
+/// Throws std::invalid_argument unless 0 <= r_robot < r_inflate and occ_dist.size() == nx * ny.
+std::vector<float> costFieldFromDistance(const std::vector<double>& occ_dist, int nx, int ny, double r_robot, double r_inflate);
+
 class MPPI {
  public:
   /// The reference's nine arguments (mppi.hpp:133-141).  n_gpus (not in the reference): > 1 splits the
@@ -60,6 +73,10 @@ class MPPI {
   /// Not in the reference: integrate the rollouts with the plant's own step, rigid2d::DiffDrive::feedforward of
   /// wheelsToTwist(u) * dt (exact arcs), instead of CartModel + RK4.  Off by default (tbnav_mppi_set_dynamics).
   void useExactArcDynamics(bool on = true);
+  /// Not in the reference: obstacle avoidance through a cost field (above).  Off by default; throws std::invalid_argument on a
+  /// field the library rejects (sizes outside 2 .. 4096, a non-finite number), and the field in force stays.
+  void setCostField(const CostField& field);
+  void clearCostField();
   int steps() const { return steps_; }
   int rollouts() const { return rollouts_; }
   int gpus() const;

@@ -62,6 +62,28 @@ void MPPI::useExactArcDynamics(bool on) {
   check(g_ ? tbnav_mppi_group_set_dynamics(g_, model) : tbnav_mppi_set_dynamics(h_, model), "useExactArcDynamics");
 }
 
+void MPPI::setCostField(const CostField& f) {
+  if (f.nx < 0 || f.ny < 0 || f.values.size() != (size_t)f.nx * (size_t)f.ny) throw std::invalid_argument("setCostField: values.size() != nx * ny");
+  tbnav_mppi_cost_field g{};
+  g.nx = f.nx; g.ny = f.ny; g.xmin = f.xmin; g.ymin = f.ymin; g.resolution = f.resolution; g.weight = f.weight;
+  check(g_ ? tbnav_mppi_group_set_cost_field(g_, &g, f.values.data()) : tbnav_mppi_set_cost_field(h_, &g, f.values.data()), "setCostField");
+}
+void MPPI::clearCostField() {
+  check(g_ ? tbnav_mppi_group_set_cost_field(g_, nullptr, nullptr) : tbnav_mppi_set_cost_field(h_, nullptr, nullptr), "clearCostField");
+}
+
+std::vector<float> costFieldFromDistance(const std::vector<double>& occ_dist, int nx, int ny, double r_robot, double r_inflate) {
+  if (!(0.0 <= r_robot && r_robot < r_inflate)) throw std::invalid_argument("costFieldFromDistance: 0 <= r_robot < r_inflate is required");
+  if (nx < 0 || ny < 0 || occ_dist.size() != (size_t)nx * (size_t)ny) throw std::invalid_argument("costFieldFromDistance: occ_dist.size() != nx * ny");
+  std::vector<float> c(occ_dist.size());
+  for (size_t i = 0; i < c.size(); ++i) {
+    const double d = occ_dist[i];
+    const double t = (r_inflate - d) / (r_inflate - r_robot);
+    c[i] = (float)(d <= r_robot ? 1.0 : (d >= r_inflate ? 0.0 : t * t));
+  }
+  return c;
+}
+
 WheelVelocities MPPI::newControls(const Pose& ps) {
   const double x0[3] = {ps.x, ps.y, ps.theta};  // mppi.cpp:75-76: state order (x, y, theta)
   double out[2] = {0.0, 0.0};

@@ -38,6 +38,26 @@ def _dptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def cost_field_from_distance(dist, r_robot: float, r_inflate: float) -> np.ndarray:
+    """A cost field (float32, the shape of `dist`) from distances to the nearest obstacle, e.g. what rbpf.get_occ_dist returns for
+    one particle: 1 where d <= r_robot, 0 where d >= r_inflate, ((r_inflate - d) / (r_inflate - r_robot))**2 between — formed in
+    fp64, then rounded.  0 <= r_robot < r_inflate.  (controller::costFieldFromDistance is the same arithmetic.)"""
+    if not (0.0 <= r_robot < r_inflate):
+        raise ValueError("cost_field_from_distance: 0 <= r_robot < r_inflate is required")
+    d = np.asarray(dist, dtype=np.float64)
+    t = (r_inflate - d) / (r_inflate - r_robot)
+    c = np.where(d <= r_robot, 1.0, np.where(d >= r_inflate, 0.0, t * t))
+    return c.astype(np.float32)
+
+
+def _field_args(values, xmin, ymin, resolution, weight):
+    v = np.ascontiguousarray(values, dtype=np.float32)
+    if v.ndim != 2:
+        raise ValueError("setCostField: values must have shape [nx][ny]")
+    g = capi.MppiCostField(v.shape[0], v.shape[1], xmin, ymin, resolution, weight)
+    return g, v
+
+
 class MPPI:
     """controller::MPPI (mppi.hpp:119-185) on one MI355X."""
 
@@ -133,6 +153,29 @@ class MPPI:
         out = (C.c_double * 2)()
         capi.check(self._L.tbnav_mppi_new_controls(self._h, x0, noise.ctypes.data, out), "new_controls")
         return out[0], out[1]
+
+    # ---- cost field (tbnav_mppi.h, COST FIELD: an option the reference does not have) ----
+    def setCostField(self, values, xmin: float, ymin: float, resolution: float, weight: float = 1.0):
+        """values[nx][ny] (x the slow index, taken at cell centres), the outer corner of cell (0, 0) at (xmin, ymin): every
+        rollout step's loss gains weight * (bilinear lookup at the step's position)."""
+        g, v = _field_args(values, xmin, ymin, resolution, weight)
+        capi.check(self._L.tbnav_mppi_set_cost_field(self._h, C.byref(g), v.ctypes.data), "set_cost_field")
+
+    def clearCostField(self):
+        capi.check(self._L.tbnav_mppi_set_cost_field(self._h, None, None), "set_cost_field(clear)")
+
+    def costField(self):
+        """None, or the geometry in force as a dict (nx, ny, xmin, ymin, resolution, weight)."""
+        on, g = C.c_int32(), capi.MppiCostField()
+        capi.check(self._L.tbnav_mppi_get_cost_field(self._h, C.byref(on), C.byref(g)), "get_cost_field")
+        return {k: getattr(g, k) for k, _ in g._fields_} if on.value else None
+
+    def costFieldLookup(self, xy) -> np.ndarray:
+        """The field's lookup evaluated on the device at positions xy[n][2] (without the weight)."""
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty(len(xy))
+        capi.check(self._L.tbnav_mppi_cost_field_lookup(self._h, xy.ctypes.data, len(xy), out.ctypes.data), "cost_field_lookup")
+        return out
 
     # ---- device-resident variants ----
     def newControlsDev(self, x0, d_duL: int, d_duR: int, stream: int = 0):
@@ -273,6 +316,14 @@ class MPPIGroup:
 
     def setOption(self, option: int, value: int):
         capi.check(self._L.tbnav_mppi_group_set_option(self._h, option, value), "tbnav_mppi_group_set_option")
+
+    def setCostField(self, values, xmin: float, ymin: float, resolution: float, weight: float = 1.0):
+        """MPPI.setCostField on every member, or on none."""
+        g, v = _field_args(values, xmin, ymin, resolution, weight)
+        capi.check(self._L.tbnav_mppi_group_set_cost_field(self._h, C.byref(g), v.ctypes.data), "group_set_cost_field")
+
+    def clearCostField(self):
+        capi.check(self._L.tbnav_mppi_group_set_cost_field(self._h, None, None), "group_set_cost_field(clear)")
 
     def setWaypoint(self, x, y, theta):
         capi.check(self._L.tbnav_mppi_group_set_waypoint(self._h, x, y, theta), "group_set_waypoint")
