@@ -23,6 +23,8 @@
  *   M = min m_r;  s_r = exp(((m_r - M) * -1.0) / lambda)
  *   W  = sum s_r*A_r + 1e-8 * sum n_r
  *   uL(i) += (sum s_r*B_r + 1e-8 * sum D_r) / W     (then clamp to +-max_wheel_vel, mppi.cpp:124-125)
+ * A consumer skips records with n <= 0 (no rollouts: their other fields are not looked at), and a record whose rollouts' costs all
+ * overflowed carries m = +inf, A = B = C = 0 with its D, E and n: it weighs nothing beside a finite record and counts in the floor.
  */
 #ifndef TBNAV_MPPI_H
 #define TBNAV_MPPI_H

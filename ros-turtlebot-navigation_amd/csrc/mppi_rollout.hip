@@ -610,7 +610,11 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
       run = l + run;
       suf[q] = run;  // lane-local suffix sum from the lane's last step
     }
-    const double tail = tbnav::wave_scan_incl_rev(run, lane) - run;  // cost of every later lane's steps
+    // cost of every later lane's steps.  A lane whose own steps overflowed (run = +inf) would form inf - inf here and hand its
+    // steps J = NaN where the suffix sums of the other kernels give +inf: its tail is the scan itself, +inf (with two steps per
+    // lane that also covers a second step whose own loss is finite behind an overflowing first one: the lane weighs nothing)
+    const double scan = tbnav::wave_scan_incl_rev(run, lane);
+    const double tail = (run == __builtin_huge_val()) ? scan : scan - run;
 #pragma unroll
     for (int q = 0; q < TL; ++q) {
       const int i = lane * TL + q;
@@ -636,8 +640,10 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
     auto gmin = [](double x, double y) { return fmin(x, y); };
     auto gsum = [](double x, double y) { return x + y; };
     const double mn = tbnav::group_reduce_dpp<R>(j, gmin);
-    // exp(-(J - min)/lambda) with the reference's association: (J - min) * -1.0 / lambda (mppi.cpp:117)
-    const double e = ok ? exp(div_lambda((j - mn) * -1.0, lam)) : 0.0;
+    // exp(-(J - min)/lambda) with the reference's association: (J - min) * -1.0 / lambda (mppi.cpp:117).  A rollout whose cost
+    // overflowed (J = +inf) weighs nothing, as in mppi_partials — and as a missing rollout (j = +inf by construction): when every
+    // live rollout of the group overflowed, mn = +inf and j - mn would be NaN; the record is then m = +inf, A = B = C = 0
+    const double e = (j == inf) ? 0.0 : exp(div_lambda((j - mn) * -1.0, lam));
     const double A = tbnav::group_reduce_dpp<R>(e, gsum), B = tbnav::group_reduce_dpp<R>(e * l, gsum), C = tbnav::group_reduce_dpp<R>(e * rg, gsum);
     const double D = tbnav::group_reduce_dpp<R>(l, gsum), E = tbnav::group_reduce_dpp<R>(rg, gsum);
     if (rr == 0) {

@@ -115,7 +115,8 @@ __global__ __launch_bounds__(kWave) void mppi_merge_records(int T, int Sf, int p
   for (int r = r0 + lane; r < r1; r += kWave) {
     const double* rec = fine + ((size_t)i * Sf + r) * TBNAV_MPPI_REC;
     if (rec[6] > 0.0) {
-      const double sc = exp(div_lambda((rec[0] - M) * -1.0, lam));
+      // (a fine record whose rollouts all overflowed, m = +inf: weight 0 — also when the slice's minimum is +inf itself, inf - inf)
+      const double sc = (rec[0] == inf) ? 0.0 : exp(div_lambda((rec[0] - M) * -1.0, lam));
       A += sc * rec[1]; B += sc * rec[2]; C += sc * rec[3];
       D += rec[4]; E += rec[5]; n += rec[6];
     }
