@@ -400,6 +400,18 @@ int tbnav_rbpf_raycast_box_cells(const tbnav_rbpf* h, int32_t* need_cells, int32
  * line point at one row of a rocprofv3 --stats summary. */
 int tbnav_rbpf_last_kernel_names(const tbnav_rbpf* h, char* propose, int32_t propose_cap, char* raycast, int32_t raycast_cap,
                                  int32_t* raycast_workgroups);
+/* Which distance-transform kernel served each particle's stored field (csrc/rbpf_field.hip).  Waits for the handle's stream.
+ *   *cols   the column-tile width create chose from the map size: 64 -> rbpf_edt<64>, 32 -> rbpf_edt<32>, 0 -> the map is too large
+ *           for the LDS transform: whole fields come from rbpf_field_by_query, tier[] then carries no information.
+ *   tier[p] (N values) what the LAST transform launch that covered particle p decided for it (a SLAM call in the window / full modes
+ *           covers every particle, an on-demand field — get_dist_code, get_occ_dist, integrate_scan — only its own):
+ *             0  rbpf_edt_compact<144> (at most 144 non-empty map rows)      1  rbpf_edt_compact<288> (at most 288)
+ *             2  rbpf_edt<cols> (any number of rows)                        -1  no launch has covered p since create
+ *           A particle that launch skipped because its field was fresh (injected, or whole already) reports 0, and so does a particle
+ *           whose map was empty: rbpf_edt_compact<144> is the kernel that looked at it, and it wrote nothing.  A resampling does not
+ *           move the values with the particles.
+ * Either pointer may be NULL.  Measurement hook: lets a test assert the instantiation a case was written for. */
+int tbnav_rbpf_last_field_kernels(tbnav_rbpf* h, int32_t* tier, int32_t* cols);
 
 #ifdef __cplusplus
 }

@@ -856,6 +856,7 @@ int create_impl(const tbnav_rbpf_params* P, uint64_t max_pool_bytes, tbnav_rbpf*
     if (e == hipSuccess) { *h->h_box_need = 0; e = hipHostGetDevicePointer((void**)&h->d_box_need_host, h->h_box_need, 0); }
     if (e == hipSuccess) e = hipMemset(h->d_nocc[0], 0, sizeof(int) * N);
     if (e == hipSuccess) e = hipMemset(h->d_skip, 0, sizeof(int) * N);
+    if (e == hipSuccess) e = hipMemset(h->d_tier, 0xFF, sizeof(int) * N);  // -1: no transform launch has covered the particle yet (tbnav_rbpf_last_field_kernels)
     // empty maps: the field "everything unreached" is what any lookup computes, no stored field needed (state 0)
     if (e == hipSuccess) e = hipMemset(h->d_fstate, 0, sizeof(int) * N);
     if (e == hipSuccess) e = hipMemset(h->d_fstate_alt, 0, sizeof(int) * N);

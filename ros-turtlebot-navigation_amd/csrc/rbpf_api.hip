@@ -255,6 +255,17 @@ int tbnav_rbpf_last_kernel_names(const tbnav_rbpf* h, char* propose, int32_t pro
   return TBNAV_OK;
 }
 
+int tbnav_rbpf_last_field_kernels(tbnav_rbpf* h, int32_t* tier, int32_t* cols) {
+  if (!h) return TBNAV_ERR_INVALID_ARG;
+  if (cols) *cols = h->edt_cols;
+  if (tier) {
+    DeviceGuard guard(h->device);
+    TBNAV_HIP(hipStreamSynchronize(h->stream));
+    TBNAV_HIP(hipMemcpy(tier, h->d_tier, sizeof(int32_t) * h->N, hipMemcpyDeviceToHost));
+  }
+  return TBNAV_OK;
+}
+
 int tbnav_rbpf_raycast_box_cells(const tbnav_rbpf* h, int32_t* need_cells, int32_t* array_cells) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
   if (need_cells) *need_cells = h->lk_box_need;

@@ -244,6 +244,16 @@ class ParticleFilter:
         capi.check(self._L.tbnav_rbpf_last_kernel_names(self._h, a, 64, b, 64, C.byref(n)), "last_kernel_names")
         return a.value.decode(), b.value.decode(), int(n.value)
 
+    def lastFieldKernels(self):
+        """Per particle, the distance-transform kernel that served its stored field last, as rocprofv3 prints it
+        (tbnav_rbpf_last_field_kernels): "rbpf_edt_compact<144>", "rbpf_edt_compact<288>", "rbpf_edt<64>" / "rbpf_edt<32>";
+        "rbpf_field_by_query" for every particle of a map too large for the transform; "" where no launch has covered the particle."""
+        tier, cols = np.empty(self.N, dtype=np.int32), C.c_int32()
+        capi.check(self._L.tbnav_rbpf_last_field_kernels(self._h, tier.ctypes.data, C.byref(cols)), "last_field_kernels")
+        if cols.value == 0:
+            return ["rbpf_field_by_query"] * self.N
+        names = {-1: "", 0: "rbpf_edt_compact<144>", 1: "rbpf_edt_compact<288>", 2: f"rbpf_edt<{cols.value}>"}
+        return [names[int(t)] for t in tier]
 
     def raycastBoxCells(self):
         """(cells the particles' boxes needed lately, cells of the last launch's LDS array) of rbpf_raycast_box."""

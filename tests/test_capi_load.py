@@ -69,6 +69,17 @@ def test_create_rejects_bad_arguments(pkg):
     assert L.tbnav_mppi_create(C.byref(p), C.byref(h)) == pkg.capi.ERR_INVALID_ARG
 
 
+def test_last_field_kernels_is_declared_exported_and_rejects_a_null_handle(pkg):
+    """tbnav_rbpf_last_field_kernels (include/tbnav_rbpf.h): in the header, in the library, in the Python table — and
+    TBNAV_ERR_INVALID_ARG before any device call."""
+    L = pkg.capi.lib()
+    assert "tbnav_rbpf_last_field_kernels" in pkg.capi.declared_symbols() and hasattr(L, "tbnav_rbpf_last_field_kernels")
+    cols = C.c_int32(-7)
+    assert L.tbnav_rbpf_last_field_kernels(None, None, C.byref(cols)) == pkg.capi.ERR_INVALID_ARG and cols.value == -7
+    from rtn_amd.rbpf import ParticleFilter
+    assert callable(ParticleFilter.lastFieldKernels)
+
+
 def test_comm_and_group_entry_points_fail_loudly_without_gpu_and_reject_bad_arguments(pkg):
     """include/tbnav_comm.h + the group constructors: bad arguments are TBNAV_ERR_INVALID_ARG before any device or RCCL call;
     without a GPU a communicator / group cannot be made (no CPU path, no silent single-rank stand-in)."""

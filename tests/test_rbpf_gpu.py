@@ -434,6 +434,12 @@ def test_distance_field_tiers_random_occupancy(gpu_pkg, rows_used, expect):
     for p in range(N):
         want = orc.exact_edt_codes(occs[p], 200, prev_codes[p])
         assert np.array_equal(pf_d.distCode(p).reshape(xs, xs), want), expect
+    # the kernel each particle's field came from, by name (tbnav_rbpf_last_field_kernels): the tier the row count asks for
+    kernel = {"compact-144": "rbpf_edt_compact<144>", "compact-288": "rbpf_edt_compact<288>", "general": "rbpf_edt<64>"}
+    rows = [int(o.any(axis=1).sum()) for o in occs]
+    want_names = [kernel["compact-144" if r <= 144 else "compact-288" if r <= 288 else "general"] for r in rows]
+    assert rows[0] == rows_used and want_names[0] == kernel[expect]
+    assert pf_d.lastFieldKernels() == want_names, expect
 
 
 def test_device_noise_source_statistics_and_filter_health(gpu_pkg):
