@@ -22,6 +22,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <queue>
 #include <stdexcept>
 #include <string>
@@ -222,6 +223,10 @@ class CellStore {
 };
 inline void CellStore::throw_out_of_window() { throw Thrown{OUT_OF_WINDOW}; }
 
+// Instrumentation of PF::scan_match (the project's own option, not the reference): while it points somewhere, every cell
+// Grid::likelihood looks up widens the box {i0, i1, j0, j1} (inclusive) there.  Per thread: particles run in parallel.
+inline thread_local int* g_look_box = nullptr;
+
 // bmapping::GridMapper (+ its LaserScanner base), grid_mapper.cpp / sensor_model.cpp
 class Grid {
  public:
@@ -268,6 +273,11 @@ class Grid {
     for (size_t b = 0; b + 1 < pts.size(); b += 2) {
       double pz = 0.0;
       const unsigned int idx = world2rowmajor(pts[b], pts[b + 1]);
+      if (g_look_box) {
+        const int li = (int)(idx / xsize_), lj = (int)(idx % xsize_);
+        g_look_box[0] = std::min(g_look_box[0], li); g_look_box[1] = std::max(g_look_box[1], li);
+        g_look_box[2] = std::min(g_look_box[2], lj); g_look_box[3] = std::max(g_look_box[3], lj);
+      }
       const double z = exact_field_ ? exact_dist(idx) : map_.at(idx).occ_dist;
       pz += laser_.z_hit * pdf_normal(z, var_hit);
       pz += laser_.z_rand / laser_.z_max;
@@ -564,6 +574,7 @@ class PF {
     const size_t stride = icp_ok ? (size_t)3 * k + 3 : 3;  // draws per particle, in particle order
     const T2 T_icp = make_T(Ticp[1], Ticp[2], Ticp[0]);
     if (sm_on) { sm_centers.resize((size_t)N * 3); sm_scores.resize(N); }
+    sm_stats.assign(sm_on && icp_ok ? (size_t)N : 0, SmStats{});
     // (particles are independent inside this loop; with orc_set_threads(n > 1) it is spread over n cores — the
     //  "all host cores" CPU baseline of bench_rbpf.py.  Same results: every particle reads its own slice of the draws.)
     // (an exception must not leave an OpenMP region: what the reference would have thrown — at the first particle that
@@ -672,6 +683,16 @@ class PF {
   int sm_iters = 5, sm_max_moves = 64;
   std::vector<double> sm_centers;  // [N][3] (theta, x, y) of the last call
   std::vector<double> sm_scores;   // [N]
+  // What the matcher did for each particle in the last call (empty when it did not run): rounds run, moves taken, halvings,
+  // trial angles that normalize_angle_PI took across +-pi, the box {i0, i1, j0, j1} (inclusive; i0 > i1: nothing looked up — an empty
+  // map) of every cell any trial pose looked up, and the least |sc / cand_best - (1 + 1e-9)| over all comparisons made (how far
+  // the nearest decision was from going the other way; +inf without a comparison).
+  struct SmStats {
+    int32_t rounds = 0, moves = 0, halvings = 0, wraps = 0;
+    int32_t box[4] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN};
+    double margin = std::numeric_limits<double>::infinity();
+  };
+  mutable std::vector<SmStats> sm_stats;  // [N]
 
   // Hill climbing on the particle's own likelihood field (the scoring function is the reference's
   // GridMapper::likelihoodFieldModel, grid_mapper.cpp:69-133).  From the pose c0: evaluate the six neighbours
@@ -681,22 +702,26 @@ class PF {
   // neighbouring poses often have the SAME factors on different beams, and a bare > would follow rounding noise.
   static constexpr double kSmGain = 1.0 + 1e-9;
   double scan_match(Particle& particle, const float* scan, int n, double c[3]) const {
+    SmStats& st = sm_stats[&particle - set.data()];
+    struct BoxScope { explicit BoxScope(int* b) { g_look_box = b; } ~BoxScope() { g_look_box = nullptr; } } scope(st.box);
     double best = particle.grid.likelihood(scan, n, make_T(c[1], c[2], c[0]));
     double lstep = sm_lstep, astep = sm_astep;
     int refinements = 0;
     for (int round = 0; round < sm_max_moves && refinements < sm_iters; ++round) {
+      ++st.rounds;
       double cand_best = best, cand[3] = {c[0], c[1], c[2]};
       for (int m = 0; m < 6; ++m) {
         double q[3] = {c[0], c[1], c[2]};
         const double sgn = (m & 1) ? -1.0 : 1.0;
         if (m < 2) q[1] = c[1] + sgn * lstep;
         else if (m < 4) q[2] = c[2] + sgn * lstep;
-        else q[0] = normalize_angle_PI(c[0] + sgn * astep);
+        else { q[0] = normalize_angle_PI(c[0] + sgn * astep); if (std::fabs(q[0] - (c[0] + sgn * astep)) > PI) ++st.wraps; }
         const double sc = particle.grid.likelihood(scan, n, make_T(q[1], q[2], q[0]));
+        st.margin = std::min(st.margin, std::fabs(sc / cand_best - kSmGain));
         if (sc > cand_best * kSmGain) { cand_best = sc; cand[0] = q[0]; cand[1] = q[1]; cand[2] = q[2]; }
       }
-      if (cand_best > best) { best = cand_best; c[0] = cand[0]; c[1] = cand[1]; c[2] = cand[2]; }
-      else { lstep *= 0.5; astep *= 0.5; ++refinements; }
+      if (cand_best > best) { best = cand_best; c[0] = cand[0]; c[1] = cand[1]; c[2] = cand[2]; ++st.moves; }
+      else { lstep *= 0.5; astep *= 0.5; ++refinements; ++st.halvings; }
     }
     return best;
   }
@@ -961,6 +986,18 @@ void orc_pf_get_scan_match(void* pf, double* centers, double* scores) {
   auto* f = static_cast<orc::PF*>(pf);
   if (centers) std::memcpy(centers, f->sm_centers.data(), sizeof(double) * f->sm_centers.size());
   if (scores) std::memcpy(scores, f->sm_scores.data(), sizeof(double) * f->sm_scores.size());
+}
+// What the matcher did per particle in the last orc_pf_slam call (PF::SmStats): counts [N][4] = rounds, moves, halvings, wrapped trial
+// angles; box [N][4] = i0, i1, j0, j1 of the looked-up cells; margin [N].  Returns the number of particles it ran for (0: it did not run).
+int orc_pf_get_scan_match_stats(void* pf, int32_t* counts, int32_t* box, double* margin) {
+  auto* f = static_cast<orc::PF*>(pf);
+  for (size_t i = 0; i < f->sm_stats.size(); ++i) {
+    const auto& s = f->sm_stats[i];
+    if (counts) { counts[i * 4] = s.rounds; counts[i * 4 + 1] = s.moves; counts[i * 4 + 2] = s.halvings; counts[i * 4 + 3] = s.wraps; }
+    if (box) for (int c = 0; c < 4; ++c) box[i * 4 + c] = s.box[c];
+    if (margin) margin[i] = s.margin;
+  }
+  return (int)f->sm_stats.size();
 }
 void* orc_pf_grid(void* pf, int p) { return &static_cast<orc::PF*>(pf)->set.at(p).grid; }  // borrowed orc_gm handle
 int orc_pf_best(void* pf) { return static_cast<orc::PF*>(pf)->best(); }

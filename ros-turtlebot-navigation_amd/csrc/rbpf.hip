@@ -147,7 +147,7 @@ int status_from_err(const int err[4]) {
   if (err[2]) return TBNAV_ERR_PDF_VARIANCE;
   if (err[1]) return TBNAV_ERR_ETA_ZERO;
   if (err[3] & 8) return TBNAV_ERR_POOL_EXHAUSTED;  // no free log-odds tile left (the scan of that particle was not applied)
-  if (err[3] & 4) return TBNAV_ERR_UNSUPPORTED;  // a likelihood lookup left the particle's refreshed window (cannot happen: see rbpf_window)
+  if (err[3] & 4) return TBNAV_ERR_UNSUPPORTED;  // a likelihood lookup left the particle's refreshed window: slam_impl's window rule missed a lookup (it once missed the scan matcher's travel)
   if (err[3]) return TBNAV_ERR_BRESENHAM;
   return TBNAV_OK;
 }
@@ -476,11 +476,14 @@ int scan_enqueue(tbnav_rbpf* h, const float* scan, int n_beams, const double u[3
   {
     // every lookup of this call lies within `half` metres of the particle's CURRENT position: the sampled poses
     // sit at T(pose)*T_icp (or the motion-model pose) +- the sampling noise, the laser at |Trs| from them, and
-    // a valid beam ends less than range_max from the laser
+    // a valid beam ends less than range_max from the laser.  With the scan matcher on, the samples sit round the MATCHED
+    // pose and the matcher's own trial poses look cells up too: a trial pose of round r is at most (r + 1) * lstep from
+    // T(pose)*T_icp and r < max_moves, so its travel is bounded by max_moves * lstep (3.2 m with the default step)
     double sig = 0.0;
     for (int q = 1; q < 3; ++q) sig = std::max(sig, std::max(h->p.sample_range[q], h->p.motion_noise[q]));
     const double move = std::max(std::hypot(T_icp[1], T_icp[2]), std::fabs(u[1]));
-    const double half = (double)h->p.range_max + std::hypot(h->p.Trs[1], h->p.Trs[2]) + move + 8.0 * std::sqrt(sig);
+    double half = (double)h->p.range_max + std::hypot(h->p.Trs[1], h->p.Trs[2]) + move + 8.0 * std::sqrt(sig);
+    if (h->sm_on && c.icp_ok) half += h->sm.max_moves * h->sm.lstep;
     int half_cells = (int)std::ceil(half / h->p.resolution) + 3;
     if (h->full_edt || half_cells > h->xsize) half_cells = h->xsize;  // whole map
     if (h->df_mode != 2) {  // query mode needs neither windows nor skip flags: the proposal kernel reads the field state itself

@@ -30,9 +30,11 @@ __global__ __launch_bounds__(256) void rbpf_densify(GridC g, int p0, TilePool P,
 // The distance field is recomputed from the occupancy bitmap from scratch (it has no state of its own apart
 // from "cells out of reach keep their value"), and the only reader between two scans is the next scan's
 // likelihood: beam end points within range_max of poses near the particle's predicted pose.  So the refresh
-// runs at the START of the next SLAM call, for a window round the particle that provably contains every
-// lookup of that call (checked in the likelihood: a miss is reported, never read stale); the whole field of a
-// particle is produced on demand (tbnav_rbpf_get_occ_dist / get_dist_code, particle export).
+// runs at the START of the next SLAM call, for a window round the particle sized by slam_impl to contain every
+// lookup of that call: the samples' reach round T(pose)*T_icp and, with the scan matcher on, the matcher's travel
+// bound max_moves * lstep on top (tests/test_scanmatch_cases.py holds the bound against the oracle's looked-up
+// cells).  Checked in the likelihood all the same: a miss is reported (TBNAV_ERR_UNSUPPORTED), never read stale.
+// The whole field of a particle is produced on demand (tbnav_rbpf_get_occ_dist / get_dist_code, particle export).
 // state[p]: 0 = bitmap changed since the last transform, 1 = window fresh, 2 = whole field fresh (or injected).
 __global__ void rbpf_window(GridC g, int N, int half_cells, int mark_fresh, const double* __restrict__ pose, int* __restrict__ state,
                             int* __restrict__ skip, int4* __restrict__ win) {

@@ -438,6 +438,15 @@ class PfAPI:
         self.L.orc_pf_get_scan_match(self.h, _p(c), _p(sc))
         return c, sc
 
+    def scan_match_stats(self):
+        """What the matcher did per particle in the last slam() call (PF::SmStats), or None when it did not run: rounds, moves,
+        halvings, wraps [N]; box [N][4] = (i0, i1, j0, j1), inclusive, of every cell a trial pose looked up (i0 > i1: none);
+        margin [N] = the least |sc / cand_best - (1 + 1e-9)| over all comparisons."""
+        cnt = np.zeros((self.N, 4), dtype=np.int32); box = np.zeros((self.N, 4), dtype=np.int32); margin = np.zeros(self.N)
+        if self.L.orc_pf_get_scan_match_stats(self.h, _p(cnt), _p(box), _p(margin)) == 0:
+            return None
+        return dict(rounds=cnt[:, 0], moves=cnt[:, 1], halvings=cnt[:, 2], wraps=cnt[:, 3], box=box, margin=margin)
+
     def set_particles(self, pose=None, prev=None, w=None):
         arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (pose, prev, w)]
         self.L.orc_pf_set_particles(self.h, *[None if a is None else _p(a) for a in arrs])

@@ -27,6 +27,25 @@ def _rel(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))
 
 
+def _stage_row(pf_o, pf_d, tr_o, st):
+    """One scan's differences between the device and the oracle, stage by stage (what _assert_every_stage bounds)."""
+    tr_d = pf_d.trace()
+    wo, wd = pf_o.particles()[2], pf_d.particles()[2]
+    (pose_d, idx_d) = pf_d.getRobotState()
+    pose_o = pf_o.particles()[0][pf_o.best()]
+    return dict(
+        eta=float(np.max(np.abs(tr_d["eta"] - tr_o["eta"]) / np.abs(tr_o["eta"]))),
+        p_scan=float(np.max(np.abs(tr_d["p_scan"] - tr_o["p_scan"]) / np.abs(tr_o["p_scan"]))),
+        w=float(np.max(np.abs(wd - wo) / np.abs(wo))),
+        neff=(st.neff, tr_o["neff"]), resampled=(st.resampled, tr_o["resampled"]),
+        parents_equal=(not st.resampled) or np.array_equal(tr_d["resample_idx"], tr_o["resample_idx"]),
+        best=(idx_d, pf_o.best()), best_xy=float(np.hypot(pose_d[1] - pose_o[1], pose_d[2] - pose_o[2])),
+        best_th=float(abs(pose_d[0] - pose_o[0])),
+        sampled=float(np.max(np.abs(tr_d["sampled"] - tr_o["sampled"]))), p_pose=_rel(tr_d["p_pose"], tr_o["p_pose"]),
+        mu=float(np.max(np.abs(tr_d["mu"] - tr_o["mu"]))), new_pose=float(np.max(np.abs(tr_d["new_pose"] - tr_o["new_pose"]))),
+        w_raw=_rel(tr_d["weight_raw"], tr_o["weight_raw"]))
+
+
 def _free_run(gpu_pkg, df_mode, N, k, map_half, walls, n_scans, inc, seed, force_resample_at=None, start=(0.0, 0.0, 0.0),
               oracle_exact_field=False, oracle_window=None, pool_bytes=0, n_beams=360, empty_at=(), walls_at=None, ref_reach=None, **extra):
     """Oracle filter and device filter side by side, same scans, same draws, nothing injected.  oracle_exact_field: the
@@ -52,21 +71,7 @@ def _free_run(gpu_pkg, df_mode, N, k, map_half, walls, n_scans, inc, seed, force
         tr_o = pf_o.slam(scan, u, cur, prev, True, t_icp, normals)
         st = pf_d.SLAM(scan, u, cur, prev, True, t_icp, normals)
         assert st.status == 0 and tr_o["rc"] == 0
-        tr_d = pf_d.trace()
-        wo, wd = pf_o.particles()[2], pf_d.particles()[2]
-        (pose_d, idx_d) = pf_d.getRobotState()
-        pose_o = pf_o.particles()[0][pf_o.best()]
-        rows.append(dict(
-            eta=float(np.max(np.abs(tr_d["eta"] - tr_o["eta"]) / np.abs(tr_o["eta"]))),
-            p_scan=float(np.max(np.abs(tr_d["p_scan"] - tr_o["p_scan"]) / np.abs(tr_o["p_scan"]))),
-            w=float(np.max(np.abs(wd - wo) / np.abs(wo))),
-            neff=(st.neff, tr_o["neff"]), resampled=(st.resampled, tr_o["resampled"]),
-            parents_equal=(not st.resampled) or np.array_equal(tr_d["resample_idx"], tr_o["resample_idx"]),
-            best=(idx_d, pf_o.best()), best_xy=float(np.hypot(pose_d[1] - pose_o[1], pose_d[2] - pose_o[2])),
-            best_th=float(abs(pose_d[0] - pose_o[0])),
-            sampled=float(np.max(np.abs(tr_d["sampled"] - tr_o["sampled"]))), p_pose=_rel(tr_d["p_pose"], tr_o["p_pose"]),
-            mu=float(np.max(np.abs(tr_d["mu"] - tr_o["mu"]))), new_pose=float(np.max(np.abs(tr_d["new_pose"] - tr_o["new_pose"]))),
-            w_raw=_rel(tr_d["weight_raw"], tr_o["weight_raw"])))
+        rows.append(_stage_row(pf_o, pf_d, tr_o, st))
     return pf_o, pf_d, rows
 
 

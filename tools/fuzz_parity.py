@@ -76,7 +76,11 @@ def rbpf_case(i):
     desc = dict(N=N, k=k, half=half, bd=bd, spread=spread, trs=trs, icp_ok=icp_ok, sm=sm, mode=mode)
     extra = dict(sample_range=[spread * 0.1, spread, spread], Trs=trs)
     n_beams = int(round(360 / bd))
-    pf_o = orc.PfAPI(orc.pf_params(N=N, k=k, map_min=-half, map_max=half, beam_delta_deg=bd, **extra))
+    # the matcher in query mode: on half of those cases nothing is injected and the oracle reads the exact field itself (its own
+    # stream: the other draws stay as they were) — the matcher's lookups then go through the bitmap query, not a stored array
+    exact = sm and mode == "query" and bool(np.random.default_rng([seed, 5, i]).random() < 0.5)
+    desc["exact"] = exact
+    pf_o = orc.PfAPI(orc.pf_params(N=N, k=k, map_min=-half, map_max=half, beam_delta_deg=bd, **extra), exact_field=exact)
     pf_d = ParticleFilter(default_params(N=N, k=k, map_min=-half, map_max=half, beam_delta_deg=bd, **extra), df_mode=mode)
     band_rows = int(np.random.default_rng([seed, 3, i]).choice([0, 0, 3, 7, 20]))  # (its own stream: the other draws stay as they were)
     if band_rows:
@@ -89,7 +93,7 @@ def rbpf_case(i):
     srng = np.random.default_rng(i)
     # compare against the oracle only on runs whose distance fields are injected from the first scan on: without that the
     # two filters legitimately drift apart (exact EDT vs the reference's brushfire) and so do their maps
-    inject = (mode == "query" and bool(rng.random() < 0.7)) or sm
+    inject = ((mode == "query" and bool(rng.random() < 0.7)) or sm) and not exact
     for s, (prev, cur, t_icp, u) in enumerate(steps):
         scan = orc.room_scan(poses[s], n_beams=n_beams, beam_delta_deg=bd, walls=walls, rng=srng)
         if rng.random() < 0.3:
@@ -110,7 +114,7 @@ def rbpf_case(i):
         tr_d = pf_d.trace()
         # log-odds are bit-exact whenever the poses that drive the raycast agree; compare through the oracle grid
         po, _, wo = pf_o.particles(); pd, _, wd = pf_d.particles()
-        if inject or use_sm:
+        if inject or use_sm or exact:
             # k = 2 or 3 samples give a rank-deficient covariance: its LLT stops at a pivot whose SIGN is rounding noise
             # (particle_filter.cpp:214 draws from it all the same), so the drawn pose is only reproducible to ~sqrt(eps)
             if k >= 4 or k == 1:
