@@ -294,6 +294,14 @@ int tbnav_rbpf_get_trace(tbnav_rbpf* h, double* sampled, double* p_scan, double*
  *  likelihood     : GridMapper::likelihoodFieldModel (grid_mapper.cpp:69-133) of the particle's map at `pose`.
  *  particle_map   : GridMapper::gridMap (grid_mapper.cpp:185-226) of that particle (int8, transposed, G entries). */
 int tbnav_rbpf_integrate_scan(tbnav_rbpf* h, int32_t particle, const float* scan, int32_t n_beams, const double pose[3]);
+/* integrate_scan for particles [first, first + count) in ONE map-update launch of count workgroups, particle first + i at
+ * poses[i] (theta, x, y): the launch a scan of the filter makes, without the proposal — with 18 particles or more the kernel
+ * reports the boxes' need as it does there, so TBNAV_RBPF_OPT_RAYCAST_ADAPT's instantiations are reachable with chosen poses
+ * (tests).  Stored fields of those particles are marked stale, not refreshed: in the stored-field modes (WINDOW / FULL) and
+ * the REFERENCE mode it returns TBNAV_ERR_UNSUPPORTED and touches nothing — use tbnav_rbpf_integrate_scan per particle there.
+ * Synchronous. */
+int tbnav_rbpf_integrate_scan_many(tbnav_rbpf* h, int32_t first, int32_t count, const float* scan, int32_t n_beams,
+                                   const double* poses /*[count][3]*/);
 int tbnav_rbpf_likelihood(tbnav_rbpf* h, int32_t particle, const float* scan, int32_t n_beams, const double pose[3], double* out);
 int tbnav_rbpf_particle_map(tbnav_rbpf* h, int32_t particle, int8_t* map);
 
@@ -313,7 +321,8 @@ int tbnav_rbpf_particle_map(tbnav_rbpf* h, int32_t particle, int8_t* map);
  *                           own launch configuration.  After tbnav_rbpf_set_log_odds the set of that particle is
  *                           rebuilt in ascending cell order (its history is unknown).
  * TBNAV_RBPF_OPT_RAYCAST_ORDERED 1 = always use the beam-ordered raycast kernel (development / A-B runs).
- * TBNAV_RBPF_OPT_RAYCAST_THREADS 256 | 512 | 1024 threads per workgroup of the tile raycast (default 0: chosen per launch, see _RAYCAST_ADAPT).
+ * TBNAV_RBPF_OPT_RAYCAST_THREADS 512 | 1024 threads per workgroup of rbpf_raycast_box (default 0: chosen per launch, see _RAYCAST_ADAPT).  256 is
+ *                                accepted and selects the beam-ordered kernel rbpf_raycast: the box kernel has no 256-thread instantiation.
  * TBNAV_RBPF_OPT_COUNT_CELLS     1 = the tile raycast counts the cells it updates (tbnav_rbpf_scan_counts).
  * TBNAV_RBPF_OPT_RAYCAST_FORM    retired.  0 is accepted (the box-counter kernel rbpf_raycast_box, the only form); 1 — round 2's first tile kernel,
  *                                removed in round 4 — is TBNAV_ERR_INVALID_ARG: the beam-ordered kernel is selected by _RAYCAST_ORDERED.

@@ -278,6 +278,7 @@ def lib() -> C.CDLL:
         "tbnav_rbpf_pool_stats": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "tbnav_rbpf_set_option": (C.c_int, [vp, i32, i32]),
         "tbnav_rbpf_integrate_scan": (C.c_int, [vp, i32, vp, i32, dp]),
+        "tbnav_rbpf_integrate_scan_many": (C.c_int, [vp, i32, i32, vp, i32, vp]),
         "tbnav_rbpf_likelihood": (C.c_int, [vp, i32, vp, i32, dp, dp]),
         "tbnav_rbpf_particle_map": (C.c_int, [vp, i32, vp]),
         "tbnav_rbpf_scan_counts": (C.c_int, [vp, C.POINTER(u64), C.POINTER(u64), i32]),

@@ -111,6 +111,27 @@ int tbnav_rbpf_integrate_scan(tbnav_rbpf* h, int32_t particle, const float* scan
   return TBNAV_OK;
 }
 
+// The same map update for particles [first, first + count) in ONE launch, every particle at a pose of its own: what a scan of the
+// filter launches (count workgroups, so the box need is reported and the adaptive instantiations are reachable) without the proposal.
+int tbnav_rbpf_integrate_scan_many(tbnav_rbpf* h, int32_t first, int32_t count, const float* scan, int32_t n_beams, const double* poses) {
+  if (!h || !scan || n_beams <= 0 || !poses || first < 0 || count <= 0 || first > h->N - count) return TBNAV_ERR_INVALID_ARG;
+  if (h->ref_field || h->df_mode != 2) return TBNAV_ERR_UNSUPPORTED;  // (a stored field per particle: tbnav_rbpf_integrate_scan refreshes it)
+  DeviceGuard guard(h->device);
+  ++h->scans_done;
+  ScanC c;
+  int rc = one_particle_consts(h, first, scan, n_beams, c);
+  if (rc != TBNAV_OK) return rc;
+  StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  TBNAV_HIP(hipMemcpy(sp.pose + (size_t)first * 3, poses, sizeof(double) * 3 * (size_t)count, hipMemcpyHostToDevice));
+  for (int q = 0; q < 4; ++q) h->h_err[q] = 0;
+  rc = launch_raycast(h, c, count, nullptr, nullptr);
+  if (rc != TBNAV_OK) return rc;
+  TBNAV_HIP(hipMemsetAsync(h->d_fstate + first, 0, sizeof(int) * (size_t)count, h->stream));  // the maps changed: stored fields of these particles are stale
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  return status_from_err(h->h_err);
+}
+
 int tbnav_rbpf_likelihood(tbnav_rbpf* h, int32_t particle, const float* scan, int32_t n_beams, const double pose[3], double* out) {
   if (!h || !scan || n_beams <= 0 || !pose || !out || particle < 0 || particle >= h->N) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);

@@ -139,6 +139,37 @@ class ParticleFilter:
         capi.check(self._L.tbnav_rbpf_best_map(self._h, m.ctypes.data), "best_map")
         return m
 
+    # ---- one particle's GridMapper (bmapping::GridMapper::integrateScan, grid_mapper.cpp:140-182) ----
+    def integrateScan(self, p: int, scan, pose, check=True) -> int:
+        """Moves particle p to pose (theta, x, y) and ray-casts the scan into its map (tbnav_rbpf_integrate_scan)."""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        rc = self._L.tbnav_rbpf_integrate_scan(self._h, int(p), scan.ctypes.data, scan.size, _d3(pose))
+        if check:
+            capi.check(rc, "tbnav_rbpf_integrate_scan")
+        return rc
+
+    def integrateScanMany(self, scan, poses, first: int = 0, check=True) -> int:
+        """One map-update launch for particles [first, first + len(poses)), particle first + i at poses[i] (theta, x, y):
+        tbnav_rbpf_integrate_scan_many (query mode only)."""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+        rc = self._L.tbnav_rbpf_integrate_scan_many(self._h, int(first), poses.shape[0], scan.ctypes.data, scan.size, poses.ctypes.data)
+        if check:
+            capi.check(rc, "tbnav_rbpf_integrate_scan_many")
+        return rc
+
+    def particleMap(self, p: int) -> np.ndarray:
+        """GridMapper::gridMap of particle p (tbnav_rbpf_particle_map): int8, transposed, G entries."""
+        m = np.empty(self.G, dtype=np.int8)
+        capi.check(self._L.tbnav_rbpf_particle_map(self._h, int(p), m.ctypes.data), "particle_map")
+        return m
+
+    def gatherLocal(self, parents):
+        """A resample's copies (tbnav_rbpf_gather_local): slot m becomes a copy of slot parents[m] (tile tables shared, copy-on-write); -1 keeps."""
+        par = np.ascontiguousarray(parents, dtype=np.int32)
+        assert par.size == self.N
+        capi.check(self._L.tbnav_rbpf_gather_local(self._h, par.ctypes.data), "gather_local")
+
     # ---- state access ----
     def particles(self):
         pose = np.empty((self.N, 3)); prev = np.empty((self.N, 3)); w = np.empty(self.N)

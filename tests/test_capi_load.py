@@ -80,6 +80,17 @@ def test_last_field_kernels_is_declared_exported_and_rejects_a_null_handle(pkg):
     assert callable(ParticleFilter.lastFieldKernels)
 
 
+def test_integrate_scan_many_is_declared_exported_and_rejects_bad_arguments(pkg):
+    """tbnav_rbpf_integrate_scan_many (include/tbnav_rbpf.h): in the header, in the library, in the Python table, with both
+    wrappers — and TBNAV_ERR_INVALID_ARG before any device call."""
+    L = pkg.capi.lib()
+    assert "tbnav_rbpf_integrate_scan_many" in pkg.capi.declared_symbols() and hasattr(L, "tbnav_rbpf_integrate_scan_many")
+    scan, poses = (C.c_float * 4)(), (C.c_double * 3)()
+    assert L.tbnav_rbpf_integrate_scan_many(None, 0, 1, C.cast(scan, C.c_void_p), 4, C.cast(poses, C.c_void_p)) == pkg.capi.ERR_INVALID_ARG
+    from rtn_amd.rbpf import ParticleFilter
+    assert callable(ParticleFilter.integrateScan) and callable(ParticleFilter.integrateScanMany)
+
+
 def test_comm_and_group_entry_points_fail_loudly_without_gpu_and_reject_bad_arguments(pkg):
     """include/tbnav_comm.h + the group constructors: bad arguments are TBNAV_ERR_INVALID_ARG before any device or RCCL call;
     without a GPU a communicator / group cannot be made (no CPU path, no silent single-rank stand-in)."""

@@ -1,0 +1,472 @@
+"""The map update's case table (tests/raycast_cases.py) on the CPU, with the oracle's GridMapper alone (end_points, free_index,
+world2rowmajor, integrate_scan) and a restatement of "the events of each cell, in beam order": every case reaches what it names,
+the order-sensitive cases are order-sensitive, the restated selector names exactly the instantiations csrc/rbpf_raycast.hip
+ships, every instantiation has a case of every group that applies to it, and no case leaves its map.  No device."""
+import importlib.util
+import os
+import re
+
+import numpy as np
+import pytest
+
+import raycast_cases as rcs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ros-turtlebot-navigation_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+CASES = rcs.cases()
+IDS = [c.id for c in CASES]
+
+
+@pytest.fixture(scope="module")
+def refs():
+    return {c.id: rcs.reference(c.id, True) for c in CASES}
+
+
+@pytest.fixture(scope="module")
+def plans(refs):
+    return {c.id: rcs.plans(c.id) for c in CASES}
+
+
+def _cell(cells, robot, off):
+    return robot + off[0] * cells + off[1]
+
+
+def _final(c):
+    return len(c.steps) - 1
+
+
+def _overflowed(e, ends, robot, kev):
+    """End-point cells whose slot is replayed exhaustively: more than kev events, or the robot's own cell."""
+    return [q for q in set(ends.tolist()) if len(e[q]) > kev or q == robot]
+
+
+def _stray(evs, owner, bv):
+    return any(((b - (owner - 32)) % bv) > 63 for b, _ in evs)
+
+
+def _writer(q, e, ends, robot, cells, kev):
+    """Which pass of rbpf_raycast_box writes cell q of a one-band step."""
+    evs = e[q]
+    if q == robot:
+        return "robot"
+    if q in set(ends.tolist()):
+        return "3a" if len(evs) <= kev else "3b"
+    dx, dy = q // cells - robot // cells, q % cells - robot % cells
+    return "hot" if (max(abs(dx), abs(dy)) <= rcs.kHotSide // 2 and len(evs) >= rcs.kHotMin) else "plain"
+
+
+# ---- the table ---------------------------------------------------------------------------------------------------------------------------
+def test_the_table_is_within_the_sizes_it_may_use():
+    assert len(IDS) == len(set(IDS))
+    want = {"align", "map_edge_last_pair", "corner", "sensor_offset", "bv_lds_last", "bv_lds_first_ordered", "all_zero_length",
+            "zero_length_but_one", "stray", "wrap", "overflow_64", "overflow_65", "robot_cell_endpoint", "hot_is_endpoint", "hot_window_leaves_box",
+            "bands_natural_4p2m", "robot_in_last_band", "cow_across_bands", "toggle_each_writer", "threads_256"}
+    want |= {f"bv_{b}" for b in (1, 2, 63, 64, 65, 127, 128, 129, 170, 171, 255, 256, 257, 341, 342, 511, 512, 513, 1023, 1024, 1025)}
+    want |= {f"events_{k}" for k in (3, 4, 5, 7, 8, 9)} | {f"hot_{k}" for k in (15, 16, 79, 80)} | {f"band_rows_{r}" for r in (1, 3, 4, 5)}
+    assert want <= set(IDS), sorted(want - set(IDS))
+    for c in CASES:
+        assert 18 <= c.N <= 32 and len(c.steps) <= 8 and rcs.cells_of(c) in (80, 200), c.id
+        assert c.group in ("bv", "slots", "hot", "bands", "cow", "toggle") and set(c.forms) <= set(rcs.FORMS), c.id
+        assert c.steps[-1].mark and all((s.scan is None) != (s.gather is None) for s in c.steps), c.id
+    assert rcs.cells_of(rcs.case("bands_natural_4p2m")) == 200
+    # no odd-sided map: create refuses one (its vectorised copies want G % 4 == 0), so the pair past a map's last column does not exist
+    assert "if (xsize < 4 || xsize > 32000 || (xsize & 1)) return TBNAV_ERR_UNSUPPORTED;" in open(os.path.join(CSRC, "rbpf.hip")).read()
+    assert rcs.case("sensor_offset").trs != (0.0, 0.0, 0.0) and rcs.case("align").N == 32
+    assert sorted(rcs.shifts(32, "diag")) == sorted((p, 31 - p) for p in range(32))
+    sh = rcs.shifts(18)
+    assert len(set(sh)) == 18 and {a & 1 for a, _ in sh} == {0, 1} == {b & 1 for _, b in sh}
+
+
+def test_no_case_leaves_its_map_or_the_kernel_s_limits(refs):
+    for c in CASES:
+        cells = refs[c.id]["cells"]
+        for s, r in enumerate(refs[c.id]["steps"]):
+            if r["rc"] is None:
+                continue
+            assert r["rc"] == [0] * c.N, (c.id, s, r["rc"])                      # the oracle alone integrates it with status 0
+            for p, box in enumerate(r["boxes"]):
+                assert box is not None and r["robots"][p] >= 0 and (r["ends"][p] >= 0).all(), (c.id, s, p)
+                minx, miny, bh, bw = box
+                assert 0 <= minx and minx + bh <= cells and 0 <= miny and bh <= rcs.kBoxSideMax, (c.id, s, p, box)
+                tiles = (((minx + bh - 1) >> 5) - (minx >> 5) + 1) * (((miny + bw - 1) >> 5) - (miny >> 5) + 1)
+                assert tiles <= rcs.kMapTilesMax, (c.id, s, p, tiles)
+                assert miny + bw <= ((cells + 31) & ~31), (c.id, s, p)           # the pair past an odd map's last column is inside its tile
+
+
+def test_the_restated_events_give_the_oracle_s_bits(refs):
+    """cell -> events in beam order, replayed with plain float64 adds, IS the oracle's map update: every touched cell's new value,
+    and no other cell changes."""
+    checked = 0
+    for c in CASES:
+        ref = refs[c.id]
+        for s, r in enumerate(ref["steps"]):
+            for p, e in r["ev"].items():
+                want = e["before"].copy()
+                for q, evs in e["events"].items():
+                    want[q] = rcs.replay(e["before"][q], evs, ref["d_free"], ref["d_occ"])
+                assert np.array_equal(want, e["after"]), (c.id, s, p)
+                checked += len(e["events"])
+    assert checked > 100000
+
+
+# ---- every case does what it names ---------------------------------------------------------------------------------------------------------
+def test_bv_and_segments_per_ray(refs):
+    bvs = set()
+    for c in CASES:
+        for st in c.steps:
+            if st.scan is not None:
+                bv, _ = rcs.scan_stats(st.scan, c.range_max)
+                bvs.add(bv)
+                if "bv" in c.claims:
+                    assert bv == c.claims["bv"], (c.id, bv)
+                if c.n_beams == rcs.N_HAND and c.id not in ("hot_15", "hot_16", "hot_79", "hot_80", "hot_is_endpoint", "hot_window_leaves_box",
+                                                             "robot_in_last_band", "toggle_each_writer", "robot_cell_endpoint"):
+                    assert bv == rcs.N_HAND, c.id                                  # (zero-length fill: beam indices are scan indices)
+    # S = clamp(NT / Bv, 1, 4) changes between these, for 512 and for 1024 threads
+    for nt, edges in ((512, (128, 170, 256)), (1024, (256, 341, 512))):
+        for i, e in enumerate(edges):
+            assert {e, e + 1} <= bvs and (rcs.segments(nt, e), rcs.segments(nt, e + 1)) == (4 - i, 3 - i), (nt, e)
+    assert {1, 2, 63, 64, 65, 1023, 1024, 1025} <= bvs
+
+
+def test_the_lds_limit_is_where_the_restated_rule_puts_it():
+    last, first = rcs.case("bv_lds_last"), rcs.case("bv_lds_first_ordered")
+    assert first.claims["bv"] == last.claims["bv"] + 1 == first.n_beams == last.n_beams
+    for c, box in ((last, True), (first, False)):
+        bv, rmax = rcs.scan_stats(c.steps[0].scan, c.range_max)
+        for form in ("box1024", "box512w6"):
+            name, cap = rcs.select(c.range_max, c.trs, rcs.form_opts(c, form), bv, rmax, 0)
+            assert (cap is not None) == box and (name == rcs.FORM_KERNEL[form]) == box, (c.id, form, name)
+        if box:       # the bytes at the edge: one beam more is over kMaxLds - 4096
+            cap = rcs.select(c.range_max, c.trs, dict(THREADS=1024), bv, rmax, 0)[1]
+            assert rcs.box_lds_bytes(cap, bv) <= rcs.kMaxLds - 4096 < rcs.box_lds_bytes(cap, bv + 1)
+
+
+def test_zero_length_rays_edges_corners_and_the_sensor_offset(refs):
+    for cid in ("all_zero_length", "zero_length_but_one"):
+        c = rcs.case(cid)
+        for r in refs[cid]["steps"]:
+            for p in range(c.N):
+                assert int((r["ends"][p] == r["robots"][p]).sum()) == c.claims["zero_length"], (cid, p)
+                e = r["ev"][p]["events"]
+                assert len(e[r["robots"][p]]) >= c.claims["zero_length"]
+    r = refs["all_zero_length"]["steps"][0]
+    assert all(b[2] == 1 and b[3] == 2 for b in r["boxes"]) and all(len(r["ev"][p]["events"]) == 1 for p in r["ev"])
+    c = rcs.case("map_edge_last_pair")
+    for r in refs[c.id]["steps"]:
+        for p, (minx, miny, bh, bw) in enumerate(r["boxes"]):
+            assert miny + bw - 1 == 79 and (r["ends"][p] % 80).max() == c.claims["last_column"] == 79, (p, miny, bw)
+    c = rcs.case("corner")
+    robots = {divmod(int(q), 80) for q in refs[c.id]["steps"][0]["robots"]}
+    assert set(c.claims["corners"]) <= robots
+    for p, (minx, miny, bh, bw) in enumerate(refs[c.id]["steps"][0]["boxes"]):
+        assert bh > 8 and bw > 8, p                                                  # a real fan, inside
+    # the sensor offset: the rays start in the ROBOT's cell while the end points are taken from the sensor (grid_mapper.cpp:558)
+    c = rcs.case("sensor_offset")
+    g = rcs.oracle_grid(c)
+    far = 0
+    for p in range(c.N):
+        th, x, y = c.steps[0].poses[p]
+        sx = x + np.cos(th) * c.trs[1] - np.sin(th) * c.trs[2]
+        sy = y + np.sin(th) * c.trs[1] + np.cos(th) * c.trs[2]
+        far += g.world2rowmajor(sx, sy) != g.world2rowmajor(x, y)
+    g.close()
+    assert far >= c.N // 2
+
+
+def test_the_slot_cases_hold_the_events_they_name(refs):
+    for c in CASES:
+        if "events" not in c.claims:
+            continue
+        cells, r = refs[c.id]["cells"], refs[c.id]["steps"][_final(c)]
+        for p in range(c.N):
+            e, ends, robot = r["ev"][p]["events"], r["ends"][p], r["robots"][p]
+            bv = len(ends)
+            T = _cell(cells, robot, c.claims.get("target", (0, 1)))
+            evs = e[T]
+            assert len(evs) == c.claims["events"] and {k for _, k in evs} == {0, 1}, (c.id, p, evs)     # ends and frees mixed
+            owners = [b for b, k in evs if k == 1]                                  # whichever beam wins the slot: one that ends there
+            if c.claims.get("stray"):
+                assert bv >= 130 and len(evs) <= rcs.kBoxEv and all(_stray(evs, o, bv) for o in owners), (c.id, p)
+                lo, hi = min(owners), max(owners)
+                assert 70 <= hi - lo <= 90 and all(ends[b] == robot for b in range(lo + 2, hi)), (c.id, p)
+            else:
+                assert not any(_stray(evs, o, bv) for o in owners), (c.id, p)
+            if "wrap" in c.claims:
+                assert tuple(sorted(b for b, _ in evs)) == tuple(sorted(c.claims["wrap"])), (c.id, p, evs)
+                # ... and the high beams first (the mask walked from bit 0) gives other bits than the reference's order
+                e0 = r["ev"][p]
+                hi_first = [x for x in evs if x[0] >= bv // 2] + [x for x in evs if x[0] < bv // 2]
+                assert rcs.replay(e0["before"][T], hi_first, refs[c.id]["d_free"], refs[c.id]["d_occ"]) != e0["after"][T], (c.id, p)
+                # the 64-beam window of every possible owner straddles index 0: the mask is walked from a bit that is not bit 0
+                assert all(o - 32 < 0 or o - 32 + 63 >= bv for o in owners), (c.id, p)
+            # the cell is in 3a with eight-event slots iff it holds at most eight, with four-event slots iff at most four
+    assert {rcs.case(f"events_{k}").claims["events"] for k in (3, 4, 5, 7, 8, 9)} == {rcs.kBoxEvFour - 1, rcs.kBoxEvFour, rcs.kBoxEvFour + 1,
+                                                                                    rcs.kBoxEv - 1, rcs.kBoxEv, rcs.kBoxEv + 1}
+
+
+def test_the_robot_s_cell_is_an_end_point_with_fewer_events_than_a_slot_holds(refs):
+    c = rcs.case("robot_cell_endpoint")
+    for r in refs[c.id]["steps"]:
+        for p in range(c.N):
+            evs = r["ev"][p]["events"][r["robots"][p]]
+            ends, frees = sum(k for _, k in evs), sum(1 - k for _, k in evs)
+            # what the slot lists (the end points: the walk records nothing for a ray's first cell) fits even a four-event slot
+            assert (ends, frees) == (c.claims["robot_ends"], c.claims["robot_frees"]) and ends <= rcs.kBoxEvFour, (p, evs)
+            assert _overflowed(r["ev"][p]["events"], r["ends"][p], r["robots"][p], 8) == [r["robots"][p]]
+
+
+def test_the_overflow_cases_list_64_and_65_slots(refs):
+    got = {8: set(), 4: set()}
+    for c in CASES:
+        if "overflow" not in c.claims:
+            continue
+        for r in refs[c.id]["steps"]:
+            for p in range(c.N):
+                e, ends, robot = r["ev"][p]["events"], r["ends"][p], r["robots"][p]
+                n8, n4 = len(_overflowed(e, ends, robot, 8)), len(_overflowed(e, ends, robot, 4))
+                assert (n8, n4) == tuple(c.claims["overflow"]), (c.id, p, n8, n4)
+                assert robot in set(ends.tolist())                                  # the robot's own cell is an end point: forced exhaustive
+        got[8].add(c.claims["overflow"][0]); got[4].add(c.claims["overflow"][1])
+    assert {64, 65} <= got[8] and {64, 65} <= got[4]                               # the list of kWave slots: full, and one over, in either form
+
+
+def test_the_hot_cases_hold_the_counts_they_name(refs):
+    for c in CASES:
+        if "hot" not in c.claims:
+            continue
+        cells, r = refs[c.id]["cells"], refs[c.id]["steps"][_final(c)]
+        for p in range(c.N):
+            e, ends, robot = r["ev"][p]["events"], r["ends"][p], r["robots"][p]
+            evs = e[_cell(cells, robot, (0, 1))]
+            assert sum(1 for _, k in evs if k == 0) == c.claims["hot"], (c.id, p)
+            assert (sum(1 for _, k in evs if k == 1) > 0) == bool(c.claims.get("hot_end")), (c.id, p)
+            assert robot not in set(ends.tolist()) and len(e[robot]) == len(ends), (c.id, p)    # the robot's own cell: one free add per beam, no end point
+    assert {rcs.case(f"hot_{k}").claims["hot"] for k in (15, 16, 79, 80)} == {rcs.kHotMin - 1, rcs.kHotMin, rcs.kVeryHot - 1, rcs.kVeryHot}
+    c = rcs.case("hot_window_leaves_box")
+    cells, r = refs[c.id]["cells"], refs[c.id]["steps"][0]
+    for p in range(c.N):
+        minx, miny, bh, bw = r["boxes"][p]
+        rx, ry = divmod(int(r["robots"][p]), cells)
+        assert rx == minx and ry - miny <= 1, p                                     # the robot in the box's corner: half the window is outside
+        e, ends = r["ev"][p]["events"], set(r["ends"][p].tolist())
+        hot = [q for q, evs in e.items() if q not in ends and q != r["robots"][p] and len(evs) >= rcs.kHotMin
+               and max(abs(q // cells - rx), abs(q % cells - ry)) <= 3]
+        assert len(hot) >= 3 and any(len(e[q]) >= rcs.kVeryHot for q in hot), (p, len(hot))
+
+
+def _band_counts(c, form, plans, refs, s):
+    pl = plans[c.id][form][s]
+    if pl is None or pl[1] is None:
+        return None
+    return [rcs.bands_of(b, pl[1]) for b in refs[c.id]["steps"][s]["boxes"]]
+
+
+def test_the_band_cases_take_the_bands_they_name(refs, plans):
+    c = rcs.case("bands_natural_4p2m")
+    for form in rcs.BOX_FORMS:
+        for s in range(len(c.steps)):
+            bands = _band_counts(c, form, plans, refs, s)
+            assert bands is not None and all(len(b) == c.claims["bands"] for b in bands), (form, s, [len(b) for b in bands])
+    assert c.opts == {} and rcs.tile_cap_of(4.2, c.trs, 0) == 173 * 173 and rcs.tile_cap_of(4.25, c.trs, 0) == 0
+    unaligned = set()
+    for rows in (1, 3, 4, 5):
+        c = rcs.case(f"band_rows_{rows}")
+        for form in rcs.BOX_FORMS:
+            bands = _band_counts(c, form, plans, refs, 0)
+            assert all(len(b) >= max(3, 20 // (rows + 1)) for b in bands), (c.id, form, [len(b) for b in bands])
+            assert all(rows <= n <= 2 * rows for b in bands for _, n in b[:-1]), (c.id, form)     # (the array is `rows` rows of the WIDEST box the scan allows)
+            if any(x0 % rcs.kSl for b in bands for x0, _ in b[1:]):
+                unaligned.add(rows)
+            # end points in several bands, rays crossing them: every band of every particle holds an end point, and the robot's row is in one band
+            cells = refs[c.id]["cells"]
+            for p, b in enumerate(bands):
+                ex = refs[c.id]["steps"][0]["ends"][p] // cells
+                assert sum(1 for x0, n in b if ((ex >= x0) & (ex < x0 + n)).any()) >= 3, (c.id, form, p)
+    assert unaligned == {1, 3, 4, 5}                                               # bands that do not start on a multiple of kSl rows
+    c = rcs.case("robot_in_last_band")
+    cells = refs[c.id]["cells"]
+    for form in rcs.BOX_FORMS:
+        for p, b in enumerate(_band_counts(c, form, plans, refs, 0)):
+            rx = int(refs[c.id]["steps"][0]["robots"][p]) // cells
+            assert len(b) >= 2 and b[-1][0] <= rx < b[-1][0] + b[-1][1], (form, p, b, rx)
+    for cid in ("bands_outgrown", "cow_outgrown"):
+        c = rcs.case(cid)
+        for form in ("box512w8", "box512w8ev4", "box512w8c16"):
+            for s in c.claims["outgrown_at"]:
+                assert plans[cid][form][s][0] == rcs.FORM_KERNEL[form], (cid, form, s, plans[cid][form][s])
+                assert all(len(b) >= 2 for b in _band_counts(c, form, plans, refs, s)), (cid, form, s)
+
+
+def test_the_cow_cases_write_a_shared_tile_in_several_bands(refs, plans):
+    for cid, least in (("cow_across_bands", 3), ("cow_outgrown", 2)):
+        c = rcs.case(cid)
+        g = next(s for s, st in enumerate(c.steps) if st.gather is not None)
+        assert any(par != p for p, par in enumerate(c.steps[g].gather)) and g >= 1 and c.steps[g + 1].scan is not None
+        # children integrate at poses of their own: parent and child diverge, and the parent's map is compared as well (every particle is)
+        assert not np.array_equal(c.steps[g + 1].poses[0], c.steps[g + 1].poses[1])
+        forms = rcs.BOX_FORMS if cid == "cow_across_bands" else ("box512w8", "box512w8ev4", "box512w8c16")
+        for form in forms:
+            spans = []
+            for p, b in enumerate(_band_counts(c, form, plans, refs, g + 1)):
+                per_tile = {}
+                for x0, n in b:
+                    for t in range(x0 >> 5, ((x0 + n - 1) >> 5) + 1):
+                        per_tile[t] = per_tile.get(t, 0) + 1
+                spans.append(max(per_tile.values()))
+            # (an outgrown box takes two bands, and where the cut falls on a tile border no tile is in both: most particles, not all)
+            assert (min(spans) >= least) if cid == "cow_across_bands" else (sum(s >= least for s in spans) >= c.N // 2), (cid, form, spans)
+
+
+def test_the_toggle_case_moves_a_cell_across_the_cut_through_every_writer(refs):
+    c = rcs.case("toggle_each_writer")
+    cells = refs[c.id]["cells"]
+    for kev, want in ((8, {("3a", 1), ("3a", -1), ("3b", 1), ("3b", -1), ("robot", 1), ("robot", -1), ("plain", -1), ("hot", -1)}),
+                      (4, {("3a", 1), ("3b", 1), ("3b", -1), ("robot", 1), ("robot", -1), ("plain", -1), ("hot", -1)})):
+        for p in range(c.N):
+            seen = set()
+            for r in refs[c.id]["steps"]:
+                e = r["ev"][p]
+                for q in e["occ_before"] ^ e["occ_after"]:
+                    seen.add((_writer(q, e["events"], r["ends"][p], r["robots"][p], cells, kev), 1 if q in e["occ_after"] else -1))
+            # (a plain or hot cell takes free adds only: it can leave the occupied set, never enter it; with four-event slots a cell of
+            #  at most four events, one of them an end point, cannot come back under the cut: ln 9 + ln 9 - 3 * 0.619 > ln 9)
+            assert want <= seen, (kev, p, sorted(want - seen))
+    # the robot's cell goes up as an end point (forced exhaustive) and comes down through its own path (no end point in the second scan)
+    r0, r1 = refs[c.id]["steps"]
+    assert r0["robots"][0] in set(r0["ends"][0].tolist()) and r1["robots"][0] not in set(r1["ends"][0].tolist())
+
+
+# ---- order ---------------------------------------------------------------------------------------------------------------------------------
+def test_each_order_sensitive_case_is_order_sensitive(refs):
+    """Applying a target cell's events in reversed order gives other float64 bits than the oracle's value (for every particle): a
+    kernel that replays them in another order writes another map."""
+    n = 0
+    for c in CASES:
+        if not c.claims.get("order"):
+            continue
+        ref = refs[c.id]
+        cells, r = ref["cells"], ref["steps"][_final(c)]
+        for p in range(c.N):
+            e, ends, robot = r["ev"][p], r["ends"][p], r["robots"][p]
+            if "events" in c.claims:
+                targets = [_cell(cells, robot, c.claims.get("target", (0, 1)))]
+            elif "robot_ends" in c.claims:
+                targets = [robot]
+            elif "overflow" in c.claims:
+                targets = [q for q in _overflowed(e["events"], ends, robot, 8) if q != robot]
+            else:
+                targets = [q for q in set(ends.tolist()) if q != robot]
+            diff = [q for q in targets if rcs.replay(e["before"][q], e["events"][q][::-1], ref["d_free"], ref["d_occ"]) != e["after"][q]]
+            assert diff, (c.id, p)
+            n += 1
+    assert n >= 12 * 18
+    assert {c.id for c in CASES if c.claims.get("order")} >= {"stray", "wrap", "overflow_64", "overflow_65", "toggle_each_writer"} | {f"events_{k}" for k in (3, 4, 5, 7, 8, 9)}
+
+
+def test_the_hot_counts_do_not_collapse_into_one_product(refs):
+    """n sequential adds of d_free differ from v + n * d_free: the hot paths (a chain, or add_repeated's integer steps) must add."""
+    for k in (15, 16, 79, 80):
+        c = rcs.case(f"hot_{k}")
+        ref = refs[c.id]
+        r = ref["steps"][_final(c)]
+        for p in range(c.N):
+            e, T = r["ev"][p], _cell(ref["cells"], r["robots"][p], (0, 1))
+            v = e["before"][T]
+            assert v != 0.0 and e["after"][T] != v + k * ref["d_free"], (c.id, p)
+
+
+# ---- the selector --------------------------------------------------------------------------------------------------------------------------
+def test_the_restated_selector_is_the_host_code_s():
+    """The literals of launch_raycast as csrc/rbpf.hip writes them: a change there must come to raycast_cases.select too."""
+    src = open(os.path.join(CSRC, "rbpf.hip")).read()
+    for piece in ("const long side = (long)std::floor(2.0 * reach / h->p.resolution) + 3;", "cap_win = (side * ((side + 2) & ~1L) + 7) & ~7L;",
+                  "((78L * 1024 - (long)box_lds_bytes(0, (size_t)bvn) - (long)kBoxStaticLds) / 4) & ~7L;",
+                  "if (cap_win > cap_fit) cap_win = std::max(cap_fit, (side + 9) & ~7L);",
+                  "cap_win = std::min(cap_win, (h->raycast_band_rows * ((side + 2) & ~1L) + 7) & ~7L);",
+                  "const long want = ((long)need + need / 8 + 512 + 7) & ~7L;", "cap4 = std::max(((long)need + 256 + 7) & ~7L, (side + 9) & ~7L);",
+                  "(size_t)R * (std::max(bytes, nz_lds) + kBoxStaticLds) <= (size_t)kMaxLds", "h->raycast_adapt != 2 && cap4 > 0 && cap4 <= cap_win;",
+                  "h->raycast_cell16 != 0 && cap_win > 0 && cap_win < 65528 && c.Bv + 64 < 32768;", "const bool force4 = h->raycast_adapt == 3;",
+                  "if (h->raycast_cell16 == 2 && c16_ok && nt == 512) c16 = true;",
+                  "c.Bv < 32768 - kWave && nt >= 512 && lds_win <= (size_t)kMaxLds - 4096", "h->tile_cap = (side * side <= 30000) ? (int)(side * side) : 0;",
+                  "const int need_slot = (int)(h->rc_launches++ % 3u);"):
+        assert piece in src, f"csrc/rbpf.hip no longer writes `{piece}`: restate the change in tests/raycast_cases.py (select) or update this list"
+    dev = open(os.path.join(CSRC, "rbpf_device.hpp")).read()
+    for piece in ("return 4 * cap + 2 * ev * bv + 8 * 64 + 4 * bv + 2 * ((bv + 1) & ~(size_t)1);", "size_t h = 256; while (h < 2 * (bv + 64)) h *= 2;",
+                  "constexpr size_t kBoxStaticLds = 896;", "constexpr int kMaxLds = 160 * 1024;", "constexpr int kHotMin = 16;", "constexpr int kVeryHot = 80;",
+                  "constexpr int kBoxEv = 8;", "constexpr int kBoxEvFour = 4;", "constexpr int kHotSide = 7;", "constexpr int kBoxSideMax = 176;",
+                  "constexpr int kMapTilesMax = 64;"):
+        assert piece in dev, piece
+    ray = open(os.path.join(CSRC, "rbpf_raycast.hip")).read()
+    for piece in ("(blockIdx.x & 15u) == 1u", "*box_need_host = box_need[(need_slot + 2) % 3];", "S = S < 1 ? 1 : (S > 4 ? 4 : S);", "constexpr int kSl = 4, kSlSh = 2;"):
+        assert piece in ray, piece
+
+
+def _selected(plans):
+    names = {}
+    for c in CASES:
+        for form, pl in plans[c.id].items():
+            for s, x in enumerate(pl):
+                if x is not None:
+                    names.setdefault(x[0], set()).add((c.id, form, s))
+    return names
+
+
+def test_threads_256_selects_the_beam_ordered_kernel(plans):
+    assert [x[0] for x in plans["threads_256"]["threads256"]] == ["rbpf_raycast"] * 2
+    c = rcs.case("threads_256")
+    bv, rmax = rcs.scan_stats(c.steps[0].scan, c.range_max)
+    assert rcs.select(c.range_max, c.trs, dict(THREADS=512), bv, rmax, 0)[0] != "rbpf_raycast"
+    hdr = open(os.path.join(ROOT, "include", "tbnav_rbpf.h")).read()
+    assert "256 is\n *                                accepted and selects the beam-ordered kernel rbpf_raycast" in hdr
+
+
+def test_every_form_runs_the_kernel_it_is_for_and_no_unreachable_combination_is_named(plans):
+    names = _selected(plans)
+    assert set(names) == set(rcs.FORM_KERNEL.values())
+    assert not set(names) & set(rcs.UNREACHABLE)
+    # a form's marked steps run the form's kernel, except where the case says why not
+    why_not = {"all_zero_length", "zero_length_but_one",            # no long beam: the array is smaller than need + 256
+               "bands_natural_4p2m", "bv_lds_last", "bv_lds_first_ordered",   # too large for four (three) workgroups per CU
+               "band_rows_1", "band_rows_3", "band_rows_4", "band_rows_5", "robot_in_last_band", "cow_across_bands"}   # BAND_ROWS caps the array below need + 256
+    for c in CASES:
+        for form, pl in plans[c.id].items():
+            last = pl[-1][0]
+            if last != rcs.FORM_KERNEL[form]:
+                assert c.id in why_not, (c.id, form, last)
+
+
+def test_every_instantiation_has_a_case_of_every_group_that_applies(refs, plans):
+    names = _selected(plans)
+    groups = {k: {rcs.case(cid).group for cid, _, _ in v} for k, v in names.items()}
+    for k in set(rcs.FORM_KERNEL.values()):
+        want = {"bv", "slots", "hot", "cow", "toggle"} | ({"bands"} if k != "rbpf_raycast" else set())    # (the beam-ordered kernel has no bands)
+        assert want <= groups[k], (k, sorted(want - groups[k]))
+    # ... and for the bands and cow groups a step that really takes several bands in that instantiation
+    for grp in ("bands", "cow"):
+        banded = set()
+        for c in CASES:
+            if c.group != grp:
+                continue
+            for form in c.forms:
+                for s, x in enumerate(plans[c.id][form]):
+                    if x is not None and x[1] is not None and (grp == "bands" or (s > 0 and c.steps[s - 1].gather is not None)):
+                        if all(len(b) >= 2 for b in _band_counts(c, form, plans, refs, s)):
+                            banded.add(x[0])
+        assert banded == set(rcs.FORM_KERNEL.values()) - {"rbpf_raycast"}, (grp, sorted(banded))
+
+
+def test_the_selector_names_all_six_instantiations_of_the_listing(plans):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    spec = importlib.util.spec_from_file_location("isa_always_valu", os.path.join(ROOT, "tools", "isa_always_valu.py"))
+    isa = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa)
+    shipped = set()
+    for l in isa.listing("rbpf_raycast"):
+        m = re.match(r"\s*\.amdhsa_kernel\s+_ZN8tbnav_rk\d+(rbpf_raycast(?:_box)?)(?:ILi(\d+)ELi(\d+)ELb([01])ELi(\d+)EE)?(?:E?v|EvT)?", l)
+        if m and (m.group(1) == "rbpf_raycast_box") == (m.group(2) is not None):
+            shipped.add(m.group(1) if m.group(2) is None else
+                        f"rbpf_raycast_box<{m.group(2)}, {m.group(3)}, {'true' if m.group(4) == '1' else 'false'}, {m.group(5)}>")
+    assert len(shipped) == 7 and shipped == set(_selected(plans)), (sorted(shipped), sorted(_selected(plans)))
