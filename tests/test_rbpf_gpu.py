@@ -486,8 +486,9 @@ def test_noise_drawn_inside_the_proposal_kernel_equals_sampled_noise(gpu_pkg, N,
     stored; the beam table rides in through the launch's leading workgroup; since round 6 the option, not the default — the stored-first
     kernel is the faster one).  Same contract as MPPI's in-kernel sampler: the filter equals, bit for bit, (a) the
     filter with TBNAV_RBPF_OPT_NOISE_IN_KERNEL = 0 (rbpf_sample_normals stores the stream first, the default) and (b) a
-    filter fed the regenerated stream (tbnav_rbpf_get_normals) as HOST normals — the path the oracle tests drive.  k = 300: more
-    samples than threads; alternating: ICP-failed scans (three normals per particle); a forced resampling on the way (the
+    filter fed the regenerated stream (tbnav_rbpf_get_normals) as HOST normals — the path the oracle tests drive.  k = 300: the
+    512-thread instantiation, several samples per lane of wave 0 (NOT more samples than threads — the LDS rule moves to 512 threads
+    long before; tests/propose_cases.py has k >= 513); alternating: ICP-failed scans (three normals per particle); a forced resampling on the way (the
     resampling offset's normal is the one value the kernel does store)."""
     from rtn_amd import capi
     a, b, h = _dev(gpu_pkg, N=N, k=k), _dev(gpu_pkg, N=N, k=k), _dev(gpu_pkg, N=N, k=k)
