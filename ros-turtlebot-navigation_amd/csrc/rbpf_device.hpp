@@ -1,7 +1,7 @@
 // rbpf_device.hpp — what the RBPF kernel files and the host side (rbpf_host.hpp + rbpf*.hip: handle, launches, C-ABI) share: the launch-argument
 // structs, the tiled copy-on-write map's accessors, world -> cell, wave reductions, the exact-transform / resampling / migration
 // helpers and the declarations of every kernel.  What only one family needs lives in that family's file: the distance lookups
-// and likelihoods in rbpf_propose.hip, rays and add_repeated in rbpf_raycast.hip; the normalise / selection body, which runs in
+// in rbpf_lookup.hpp, the likelihoods in rbpf_propose.hip, rays and add_repeated in rbpf_raycast.hip; the normalise / selection body, which runs in
 // a kernel of its own AND as workgroup 0 of the map update, in rbpf_normalize.hpp.  Kernels are defined in their family's file
 // and launched from the host files; the template kernels are explicitly instantiated where they are defined.  Everything is compiled
 // -ffp-contract=off (csrc/Makefile): grid indices, log-odds, Neff and parent lists are bit-exact targets.
@@ -290,7 +290,7 @@ __device__ __forceinline__ double uniform_d(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// ---- proposal side: what the host needs of it (lookups, likelihoods and the kernels' helpers are in rbpf_propose.hip) ----
+// ---- proposal side: what the host needs of it (the lookups are in rbpf_lookup.hpp, likelihoods and the kernels' helpers in rbpf_propose.hip) ----
 constexpr int kMixLut = 1024, kMixLds = 128;
 struct Trace {
   double *sampled, *p_scan, *p_pose, *mu, *sigma, *eta, *new_pose, *weight_raw;

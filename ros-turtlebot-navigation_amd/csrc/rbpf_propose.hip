@@ -2,8 +2,9 @@
 // grid_mapper.cpp:69-133; sensor_model.cpp:43-112): the handle's mixture table, the production noise source, the
 // one-pose likelihood (bmapping::GridMapper::likelihoodFieldModel), the per-particle scan matcher (option N1) and
 // rbpf_propose itself — one workgroup per particle: k samples, one lookup per beam at their centre, stable-beam collapse,
-// Gaussian proposal, new pose, weight *= eta.
+// Gaussian proposal, new pose, weight *= eta.  Where a lookup gets its distance code from: rbpf_lookup.hpp.
 #include "rbpf_device.hpp"
+#include "rbpf_lookup.hpp"
 
 namespace tbnav_rk {
 
@@ -22,172 +23,6 @@ static __device__ unsigned long long g_wgp[4096][3];   // [workgroup] entry, exi
 #define WGP_IN()
 #define WGP_OUT()
 #endif
-// GridMapper::likelihoodFieldModel for ONE pose, evaluated by one wave (lanes stride the valid beams).
-// beams[b] = (r*cos a_b, r*sin a_b) in the sensor frame, built on the host exactly as
-// sensor_model.cpp:73-108 does.  Returns the product in every lane; *oob is set if a beam leaves
-// the world (the reference throws from world2RowMajor).
-template <class Word> __device__ __forceinline__ int row_nearest_f(Word word, int words, int j, int cap);
-__device__ __forceinline__ int row_nearest(const unsigned long long* row, int words, int j, int cap);
-
-// Where a lookup gets its distance code from.
-//  field  : the particle's u16 field is authoritative (injected, or whole-field fresh) -> read it
-//  window : the field was refreshed inside `win` for this call -> read it, report a lookup outside the window
-//  query  : no field refresh at all — the squared distance to the nearest occupied cell is computed from the
-//           occupancy bitmap at the looked-up cell: rows i, i+-1, i+-2, ... each contribute (dr^2 + nearest set
-//           bit in that row)^2 and the walk stops once dr^2 >= best.  A beam ends on or next to a wall, so this
-//           is a handful of rows; the result is the exact transform's value (same integer arithmetic), and a
-//           cell with no obstacle within cell_radius keeps its stored code, like the transform.
-struct DistSrc {
-  const uint16_t* code;             // [G] of the particle; NULL when the handle keeps no stored field (query mode only)
-  OccT occ;                         // the particle's occupancy bits (tiled)
-  int4 win;
-  int mode;                         // 0 field, 1 window, 2 query
-  // query mode, optional: the part of the bitmap round the particle held in LDS (rows R0..R1, 64-cell word
-  // columns W0..W0+nW-1; any[r] = row r has a set bit inside those columns).  nW == 0: no tile.
-  const unsigned long long* tbm;
-  const int* tany;
-  int R0, R1, W0, nW;
-  // optional, with the LDS tile: lut7[m] = least (c - 3)^2 over the set bits c of the 7-bit pattern m (100: none) — lets a
-  // lookup read the 7 x 7 cells round it as seven table look-ups instead of seven 64-column bit scans
-  const unsigned char* lut7;
-  // reference-field mode: where a stored-field lookup that reads kCodePending leaves cell + 1 (NULL: nobody asks)
-  int* pend;
-};
-// a stored code as the lookups read it: a pending cell (the reference-field mode's lazy brushfire has not written it) is reported
-__device__ __forceinline__ uint16_t stored_code(const GridC& g, const DistSrc& d, int ci, int cj) {
-  const uint16_t v = d.code[(size_t)ci * g.xsize + cj];
-  if (v == kCodePending && d.pend) *d.pend = ci * g.xsize + cj + 1;
-  return v;
-}
-// Walk rows i, i+-1, i+-2, ... of an occupancy bitmap (stride `words` u64 per row, rows row_lo..row_hi present,
-// cell columns [0, words*64) relative to the bitmap) and return the least squared distance found (INT_MAX: none
-// within `radius`).  row_any(r) says whether row r can hold a set bit.
-template <class RowWord, class RowAny>
-__device__ __forceinline__ int nearest_d2_rows(RowWord row_word, int words, int row_lo, int row_hi, int radius,
-                                               int ci, int cj, RowAny row_any) {
-  int best = 0x7fffffff;
-  for (int dr = 0; dr <= radius; ++dr) {
-    if (dr * dr >= best) break;
-    if (ci + dr > row_hi && ci - dr < row_lo) break;
-    for (int sg = 0; sg < (dr ? 2 : 1); ++sg) {
-      const int r = sg ? ci - dr : ci + dr;
-      if (r < row_lo || r > row_hi || !row_any(r)) continue;
-      int cap = radius;
-      if (best != 0x7fffffff) { cap = (int)sqrtf((float)(best - dr * dr)) + 1; cap = cap < radius ? cap : radius; }
-      const int f = row_nearest_f([&](int w) { return row_word(r, w); }, words, cj, cap);
-      if (f != 255) { const int cand = dr * dr + f * f; best = cand < best ? cand : best; }
-    }
-  }
-  return best;
-}
-// The whole search.  Inlined by the scan matcher (~100 poses x Bv lookups per particle, many of them beyond the 7 x 7 look);
-// the proposal kernel inlines a lookup at four places, and with both row walks in each of them it was ~100 KB of code against
-// a 64 KB instruction cache shared by two CUs: there only the 7 x 7 look on the LDS tile is inline (it decides nearly
-// every lookup of a beam that ends on or next to a wall) and the rest is ONE out-of-line copy.
-__device__ __forceinline__ uint16_t nearest_code_query_body(const GridC& g, const DistSrc& d, int radius, int ci, int cj);
-__device__ __attribute__((noinline)) uint16_t nearest_code_query_full(const GridC g, const DistSrc d, int radius, int ci, int cj) {
-  return nearest_code_query_body(g, d, radius, ci, cj);
-}
-template <bool OUTLINE = true>
-__device__ __forceinline__ uint16_t nearest_code_query(const GridC& g, const DistSrc& d, int radius, int ci, int cj) {
-  if constexpr (!OUTLINE) return nearest_code_query_body(g, d, radius, ci, cj);
-  if (d.nW > 0 && d.lut7) {
-    const int C0 = d.W0 * 64, C1 = (d.W0 + d.nW) * 64 - 1;
-    const int p0 = cj - C0 - 3, wi = p0 >> 5;
-    if (ci - 3 >= d.R0 && ci + 3 <= d.R1 && p0 >= 0 && wi + 1 < 2 * d.nW && cj <= C1) {
-      int clear = radius + 1;
-      if (d.R0 > 0) clear = min(clear, ci - d.R0 + 1);
-      if (d.R1 < g.xsize - 1) clear = min(clear, d.R1 - ci + 1);
-      if (C0 > 0) clear = min(clear, cj - C0 + 1);
-      if (C1 < g.ysize - 1) clear = min(clear, C1 - cj + 1);
-      const unsigned int* t32 = reinterpret_cast<const unsigned int*>(d.tbm) + wi;
-      const int sh = p0 & 31, stride = 2 * d.nW;
-      int bw = 0x7fffffff;
-#pragma unroll
-      for (int dr = -3; dr <= 3; ++dr) {
-        const unsigned int* rp = t32 + (ci + dr - d.R0) * stride;
-        const unsigned int pat = __builtin_amdgcn_alignbit(rp[1], rp[0], sh) & 0x7Fu;
-        bw = min(bw, dr * dr + (int)d.lut7[pat]);
-      }
-      if (bw <= 9 && bw <= clear * clear) return (uint16_t)bw;
-    }
-  }
-  return nearest_code_query_full(g, d, radius, ci, cj);
-}
-__device__ __forceinline__ uint16_t nearest_code_query_body(const GridC& g, const DistSrc& d, int radius, int ci, int cj) {
-  if (d.nW > 0) {
-    // LDS tile first.  Its answer is the map's answer when no cell outside the tile can be nearer: a side of the
-    // tile that is not the map's own border is (distance to that side + 1) cells away at least.
-    const int C0 = d.W0 * 64, C1 = (d.W0 + d.nW) * 64 - 1;
-    if (ci >= d.R0 && ci <= d.R1 && cj >= C0 && cj <= C1) {
-      int clear = radius + 1;  // nothing beyond the radius matters
-      if (d.R0 > 0) clear = min(clear, ci - d.R0 + 1);
-      if (d.R1 < g.xsize - 1) clear = min(clear, d.R1 - ci + 1);
-      if (C0 > 0) clear = min(clear, cj - C0 + 1);
-      if (C1 < g.ysize - 1) clear = min(clear, C1 - cj + 1);
-      bool looked7 = false;
-      {
-        // A beam ends on or next to a wall: the 7 x 7 cells round the looked-up cell first.  Every cell outside them is
-        // >= 4 cells away, so a result <= 9 (and <= clear^2) is the map's answer.  Row by row: the seven bits round the
-        // column (one v_alignbit on two adjacent dwords of the LDS tile) index a 128-entry table of least column offsets.
-        const int p0 = cj - C0 - 3, wi = p0 >> 5;
-        if (d.lut7 && ci - 3 >= d.R0 && ci + 3 <= d.R1 && p0 >= 0 && wi + 1 < 2 * d.nW) {
-          const unsigned int* t32 = reinterpret_cast<const unsigned int*>(d.tbm) + wi;
-          const int sh = p0 & 31, stride = 2 * d.nW;
-          int bw = 0x7fffffff;
-#pragma unroll
-          for (int dr = -3; dr <= 3; ++dr) {
-            const unsigned int* rp = t32 + (ci + dr - d.R0) * stride;
-            const unsigned int pat = __builtin_amdgcn_alignbit(rp[1], rp[0], sh) & 0x7Fu;
-            bw = min(bw, dr * dr + (int)d.lut7[pat]);
-          }
-          if (bw <= 9 && bw <= clear * clear) return (uint16_t)bw;
-          looked7 = true;
-        }
-      }
-      if (!looked7) {
-        // (no table, or the 7 x 7 window sticks out of the tile) the same 7 rows, 64 columns each, by bit scans, branch-free
-        const int cjr = cj - C0, s0 = cjr - 32, w = s0 >> 6, sh = s0 & 63;
-        int bw = 0x7fffffff;
-#pragma unroll
-        for (int dr = -3; dr <= 3; ++dr) {
-          const int r = ci + dr;
-          if (r < d.R0 || r > d.R1) continue;
-          const unsigned long long* row = d.tbm + (size_t)(r - d.R0) * d.nW;
-          const unsigned long long lo64 = (w >= 0 && w < d.nW) ? row[w] : 0ull, hi64 = (w + 1 >= 0 && w + 1 < d.nW) ? row[w + 1] : 0ull;
-          const unsigned long long W = sh ? ((lo64 >> sh) | (hi64 << (64 - sh))) : lo64;  // bit i = column s0 + i, the cell at bit 32
-          const unsigned long long L = W & 0x1FFFFFFFFull, Rr = W >> 33;
-          int f = 1 << 12;
-          if (L) f = __clzll((long long)L) - 31;
-          if (Rr) f = min(f, __ffsll((long long)Rr));
-          bw = min(bw, dr * dr + f * f);
-        }
-        if (bw <= 9 && bw <= clear * clear) return (uint16_t)bw;
-      }
-      const int* any = d.tany;
-      const int R0 = d.R0;
-      const unsigned long long* tbm = d.tbm;
-      const int nW = d.nW;
-      const int best = nearest_d2_rows([tbm, nW, R0](int r, int w) { return tbm[(size_t)(r - R0) * nW + w]; }, d.nW, d.R0, d.R1, radius, ci, cj - C0,
-                                       [any, R0](int r) { return any[r - R0] != 0; });
-      if (best != 0x7fffffff && best <= clear * clear && best <= radius * radius) return (uint16_t)best;
-      if (best == 0x7fffffff && clear > radius) return d.code ? d.code[(size_t)ci * g.xsize + cj] : kCodeUnreached;
-    }
-  }
-  const OccT occ = d.occ;
-  const int best = nearest_d2_rows([&occ](int r, int w) { return occ.word(r, w); }, g.words, 0, g.xsize - 1, radius, ci, cj,
-                                   [&occ](int r) { return occ.row_any(r); });
-  // nothing within cell_radius_: the stored code if the handle keeps a stored field (injected / materialised), else
-  // "never reached" (the reference keeps whatever an earlier brushfire left there, grid_mapper.cpp:310-313)
-  return (best <= radius * radius) ? (uint16_t)best : (d.code ? d.code[(size_t)ci * g.xsize + cj] : kCodeUnreached);
-}
-// Distance code of cell (ci, cj), or -1 when a windowed lookup falls outside the refreshed window.
-template <bool OUTLINE = true>
-__device__ __forceinline__ int lookup_code(const GridC& g, const DistSrc& d, int radius, int ci, int cj) {
-  if (d.mode == 2) return nearest_code_query<OUTLINE>(g, d, radius, ci, cj);
-  if (d.mode == 1 && (ci < d.win.x || ci > d.win.y || cj < d.win.z || cj > d.win.w)) return -1;
-  return stored_code(g, d, ci, cj);
-}
 
 // Mixture term of one beam as a function of the distance code it lands on (grid_mapper.cpp:119-121).
 __device__ __forceinline__ double beam_mixture(const ScanC& c, uint16_t code) {
@@ -198,10 +33,6 @@ __device__ __forceinline__ double beam_mixture(const ScanC& c, uint16_t code) {
   return pz;
 }
 
-// ctag/ccell/cpz (nullable): per-beam cache filled once per particle for the centre of its k samples — the
-// samples lie within ~1e-4 m of it, so nearly every (sample, beam) lands on the same cell (no lookup at all) or at
-// least the same code, and takes its mixture term from LDS instead of re-evaluating sqrt + exp.  Read-only here;
-// a miss computes the term afresh.
 // Tms = T(pose) * Trs  (rigid2d.cpp:214-224) as (X, Y, sin, cos); Trs.theta == 0 (the shipped robot) needs one sincos
 __device__ __forceinline__ void sensor_transform(const ScanC& c, double th, double x, double y, double out[4]) {
   double s0, c0;
@@ -211,52 +42,35 @@ __device__ __forceinline__ void sensor_transform(const ScanC& c, double th, doub
   if (c.Trs[0] == 0.0) { out[2] = s0; out[3] = c0; }  // th + 0.0 == th: same bits
   else sincos(th + c.Trs[0], &out[2], &out[3]);
 }
-// Mixture term of one beam seen from one sensor pose (grid_mapper.cpp:100-121).  (cc, tg, pzc) is the beam's cache
-// entry — cell / code / term at the centre of the particle's samples (0xFFFFFFFF: none): the samples lie within
-// ~1e-4 m of the centre, so nearly every (sample, beam) lands on the same cell (no lookup at all) or at least the
-// same code, and takes its term from the cache instead of re-evaluating sqrt + exp.  A beam that leaves the world
-// sets *oob (the reference throws from world2RowMajor) and contributes 1.
 // The mixture term depends on the distance code and on constants fixed at create (z_hit, sigma_hit, z_rand / z_max,
 // resolution, max_occ_dist): the handle tabulates it ONCE for the codes below kMixLut (rbpf_mix_lut, same device code
 // as beam_mixture -> same bits) and the kernels read the table — its first kMixLds entries from LDS, the rest from
 // global memory — instead of a square root, a division and an exponential per beam.
-struct MixLut { const double* lds; const double* glob; };  // either may be NULL
+struct MixLut { const double* lds; const double* glob; };  // lds == NULL: a kernel that stages no head of the table
 __device__ __forceinline__ double mix_term(const ScanC& c, const MixLut& L, int cd) {
   if (L.lds && cd < kMixLds) return L.lds[cd];
   if (L.glob && cd < kMixLut) return L.glob[cd];
   return beam_mixture(c, (uint16_t)cd);
 }
-__device__ __forceinline__ double beam_factor(const ScanC& c, const DistSrc& ds, int radius, const double2 pt, double X, double Y,
-                                              double st, double ct, unsigned int cc, unsigned int tg, double pzc, int* oob,
-                                              const MixLut& L = MixLut{nullptr, nullptr}) {
-  const double ex = ct * pt.x - st * pt.y + X;
-  const double ey = st * pt.x + ct * pt.y + Y;
-  int ci, cj;
-  if (!world2cell(c.g, ex, ey, ci, cj)) { *oob |= 1; return 1.0; }
-  if (cc == (unsigned int)(ci * c.g.xsize + cj)) return pzc;  // same cell -> same code -> same term
-  // (window mode: the window is sized so that a miss cannot happen — if it ever does it is reported, never read stale)
-  const int cd = lookup_code(c.g, ds, radius, ci, cj);
-  if (cd < 0) { *oob |= 2; return 1.0; }
-  return (tg == (unsigned int)cd) ? pzc : mix_term(c, L, cd);
-}
-// GridMapper::likelihoodFieldModel for ONE pose, evaluated by one wave (lanes stride the valid beams).
-__device__ __forceinline__ double wave_scan_likelihood_t(const ScanC& c, const double2* __restrict__ beams,
-                                                         const DistSrc& ds, int radius, int n_occ,
-                                                         double X, double Y, double st, double ct, int lane, int* oob,
-                                                         const MixLut& L = MixLut{nullptr, nullptr}) {
+// GridMapper::likelihoodFieldModel (grid_mapper.cpp:69-133) for ONE pose, evaluated by one wave: lanes stride the valid beams —
+// beams[b] = (r*cos a_b, r*sin a_b) in the sensor frame, built on the host exactly as sensor_model.cpp:73-108 does — and multiply
+// their terms in beam order; the wave's butterfly closes the product, which every lane returns.  *oob bit 0: a beam leaves the
+// world (the reference throws from world2RowMajor); bit 1: a windowed lookup outside the refreshed window.  Such a beam contributes 1.
+__device__ __forceinline__ double wave_scan_likelihood(const ScanC& c, const double2* __restrict__ beams, const DistSrc& ds, int radius,
+                                                       int n_occ, double th, double x, double y, int lane, int* oob, const MixLut& L) {
   if (n_occ == 0) return 1.0;  // grid_mapper.cpp:94-98
-  double p = 1.0;
-  for (int b = lane; b < c.Bv; b += kWave) p *= beam_factor(c, ds, radius, beams[b], X, Y, st, ct, 0xFFFFFFFFu, 0xFFFFFFFFu, 0.0, oob, L);
-  return wave_prod(p);
-}
-__device__ __forceinline__ double wave_scan_likelihood(const ScanC& c, const double2* __restrict__ beams,
-                                                       const DistSrc& ds, int radius, int n_occ,
-                                                       double th, double x, double y, int lane, int* oob,
-                                                       const MixLut& L = MixLut{nullptr, nullptr}) {
-  if (n_occ == 0) return 1.0;
   double T[4];
   sensor_transform(c, th, x, y, T);
-  return wave_scan_likelihood_t(c, beams, ds, radius, n_occ, T[0], T[1], T[2], T[3], lane, oob, L);
+  double p = 1.0;
+  for (int b = lane; b < c.Bv; b += kWave) {
+    const double2 pt = beams[b];
+    int ci, cj;
+    if (!world2cell(c.g, T[3] * pt.x - T[2] * pt.y + T[0], T[2] * pt.x + T[3] * pt.y + T[1], ci, cj)) { *oob |= 1; continue; }
+    const int cd = lookup_code(c.g, ds, radius, ci, cj);
+    if (cd < 0) { *oob |= 2; continue; }
+    p *= mix_term(c, L, cd);
+  }
+  return wave_prod(p);
 }
 
 // particle_filter.cpp:383-437 (odometry part precomputed on the host: rot1, trans, rot2)
@@ -332,59 +146,6 @@ __device__ __forceinline__ void normal3(const NoiseSrc& ns, size_t g, double& n0
   n0 = odd ? b0 : a0; n1 = odd ? a1 : b0; n2 = odd ? b1 : a1;
 }
 
-
-
-
-
-
-// ---- per-particle scan matcher (SURVEY.md 8-f N1 — an OPTION, not the reference) -----------------------------
-// The reference matches scan to scan ONCE per call with PCL ICP (cloud_alignment.cpp:37-223) and every particle
-// samples round T(pose) * T_icp (particle_filter.cpp:146-153,181-188).  With scan matching on, each particle
-// refines that pose against ITS OWN map before sampling, gmapping-style: hill climbing on the likelihood field
-// (GridMapper::likelihoodFieldModel, grid_mapper.cpp:69-133 — the reference's own scoring function).  From the
-// current pose evaluate the six neighbours +x, -x, +y, -y, +theta, -theta (world frame); move to the best of them if it
-// is better by a factor > 1 + 1e-9 (the likelihood only sees cells, so neighbouring poses often carry the same
-// factors on different beams: a bare > would follow rounding noise); otherwise halve both steps; stop after
-// `iters` halvings (or max_moves rounds).
-// Workgroup = particle, 6 waves: wave m scores neighbour m (lanes over the beams, lookups on the LDS slice of the
-// bitmap), thread 0 applies the rule.  Same rule, same order of comparisons as oracle/rbpf_oracle.cpp::scan_match.
-
-// The 7 x 7 look of the query mode (or a read of the stored field) and nothing else: the code (>= 0), -1 = a windowed lookup
-// outside the refreshed window, kNeedSearch = the query mode's answer needs the row walks (nearest_code_query_body).  The
-// proposal kernel defers those to a phase of their own — ONE inlined copy of the search per phase, run by all threads over the
-// marked entries — instead of calling an out-of-line copy from inside its lookup loops (round 3: seven call sites, 224 B of
-// scratch per lane for the saves and restores round them).
-constexpr int kNeedSearch = -2;
-__device__ __forceinline__ int lookup_code_fast(const GridC& g, const DistSrc& d, int radius, int ci, int cj) {
-  if (d.mode == 2) {
-    if (d.nW > 0 && d.lut7) {
-      const int C0 = d.W0 * 64, C1 = (d.W0 + d.nW) * 64 - 1;
-      const int p0 = cj - C0 - 3, wi = p0 >> 5;
-      if (ci - 3 >= d.R0 && ci + 3 <= d.R1 && p0 >= 0 && wi + 1 < 2 * d.nW && cj <= C1) {
-        int clear = radius + 1;
-        if (d.R0 > 0) clear = min(clear, ci - d.R0 + 1);
-        if (d.R1 < g.xsize - 1) clear = min(clear, d.R1 - ci + 1);
-        if (C0 > 0) clear = min(clear, cj - C0 + 1);
-        if (C1 < g.ysize - 1) clear = min(clear, C1 - cj + 1);
-        const unsigned int* t32 = reinterpret_cast<const unsigned int*>(d.tbm) + wi;
-        const int sh = p0 & 31, stride = 2 * d.nW;
-        int bw = 0x7fffffff;
-#pragma unroll
-        for (int dr = -3; dr <= 3; ++dr) {
-          const unsigned int* rp = t32 + (ci + dr - d.R0) * stride;
-          const unsigned int pat = __builtin_amdgcn_alignbit(rp[1], rp[0], sh) & 0x7Fu;
-          bw = min(bw, dr * dr + (int)d.lut7[pat]);
-        }
-        if (bw <= 9 && bw <= clear * clear) return bw;
-      }
-    }
-    return kNeedSearch;
-  }
-  if (d.mode == 1 && (ci < d.win.x || ci > d.win.y || cj < d.win.z || cj > d.win.w)) return -1;
-  return stored_code(g, d, ci, cj);
-}
-
-
 __global__ void rbpf_mix_lut(ScanC c, double* __restrict__ out) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q < kMixLut) out[q] = beam_mixture(c, (uint16_t)q);
@@ -428,11 +189,11 @@ __global__ __launch_bounds__(256) void rbpf_field_by_query(GridC g, int radius, 
   const int ci = (int)(cell / g.xsize), cj = (int)(cell - (size_t)ci * g.xsize);
   uint16_t* code = codes + (size_t)particle * G;
   const DistSrc ds{code, occ_of(P, M, trow_occ, particle), make_int4(0, 0, 0, 0), 2, nullptr, nullptr, 0, 0, 0, 0};
-  code[cell] = nearest_code_query(g, ds, radius, ci, cj);  // a cell out of reach keeps its stored code, like the transform
+  code[cell] = nearest_code_query_body(g, ds, radius, ci, cj);  // a cell out of reach keeps its stored code, like the transform
 }
 // GridMapper::likelihoodFieldModel (grid_mapper.cpp:69-133) of ONE particle's map at an arbitrary pose — the host
-// class bmapping::GridMapper's method of that name (tbnav_rbpf_likelihood).  One wave; product in beam order per lane,
-// closed by the wave's butterfly.
+// class bmapping::GridMapper's method of that name (tbnav_rbpf_likelihood).  One wave, no LDS slice: its query-mode lookups
+// walk the rows of the global bitmap.
 __global__ __launch_bounds__(kWave) void rbpf_likelihood_one(ScanC c, const double2* __restrict__ beams, const uint16_t* __restrict__ codes,
                                                             TilePool P, MapT M, const int* __restrict__ trow_occ,
                                                             const int* __restrict__ fstate, int radius, const int* __restrict__ n_occ,
@@ -446,6 +207,18 @@ __global__ __launch_bounds__(kWave) void rbpf_likelihood_one(ScanC c, const doub
   if (oob & 1) atomicOr(&err[0], 1);
   if (lane == 0) *out = v;
 }
+
+// ---- per-particle scan matcher (SURVEY.md 8-f N1 — an OPTION, not the reference) -----------------------------
+// The reference matches scan to scan ONCE per call with PCL ICP (cloud_alignment.cpp:37-223) and every particle
+// samples round T(pose) * T_icp (particle_filter.cpp:146-153,181-188).  With scan matching on, each particle
+// refines that pose against ITS OWN map before sampling, gmapping-style: hill climbing on the likelihood field
+// (GridMapper::likelihoodFieldModel, grid_mapper.cpp:69-133 — the reference's own scoring function).  From the
+// current pose evaluate the six neighbours +x, -x, +y, -y, +theta, -theta (world frame); move to the best of them if it
+// is better by a factor > 1 + 1e-9 (the likelihood only sees cells, so neighbouring poses often carry the same
+// factors on different beams: a bare > would follow rounding noise); otherwise halve both steps; stop after
+// `iters` halvings (or max_moves rounds).
+// Workgroup = particle, 6 waves: wave m scores neighbour m (lanes over the beams, lookups on the LDS slice of the
+// bitmap), thread 0 applies the rule.  Same rule, same order of comparisons as oracle/rbpf_oracle.cpp::scan_match.
 __global__ __launch_bounds__(kMatchThreads) void rbpf_scanmatch(ScanC c, ScanMatchC sm, const double2* __restrict__ beams,
                                                                 const uint16_t* __restrict__ codes,
                                                                 TilePool P, MapT M,
@@ -487,25 +260,11 @@ __global__ __launch_bounds__(kMatchThreads) void rbpf_scanmatch(ScanC c, ScanMat
     sensor_transform(c, mu0[0], mu0[1], mu0[2], Tc);
     int sci, scj;
     if (world2cell(c.g, Tc[0], Tc[1], sci, scj)) {
-      const int R0 = max(0, sci - occ_half), R1 = min(c.g.xsize - 1, sci + occ_half);
-      const int W0 = max(0, scj - occ_half) >> 6, W1 = min(c.g.ysize - 1, scj + occ_half) >> 6, nW = W1 - W0 + 1;
-      int* ta = reinterpret_cast<int*>(tile_bm + (size_t)(R1 - R0 + 1) * nW);
-      for (int r = tid; r <= R1 - R0; r += kMatchThreads) {
-        unsigned long long acc = 0ull;
-        for (int w = 0; w < nW; ++w) {
-          const unsigned long long v = ds.occ.word(R0 + r, W0 + w);
-          tile_bm[r * nW + w] = v;
-          acc |= v;
-        }
-        ta[r] = acc != 0ull;
-      }
-      __shared__ unsigned char sm_lut7[128];  // nearest_code_query's 7 x 7 look (visible after the barrier below)
-      if (tid < 128) {
-        int best = 100;
-        for (int cbit = 0; cbit < 7; ++cbit) if ((tid >> cbit) & 1) { const int dc = cbit - 3; best = min(best, dc * dc); }
-        sm_lut7[tid] = (unsigned char)best;
-      }
-      ds.tany = ta; ds.R0 = R0; ds.R1 = R1; ds.W0 = W0; ds.nW = nW; ds.lut7 = sm_lut7;
+      const Slice sl = slice_round(c.g, occ_half, sci, scj);
+      slice_copy_rows(ds.occ, sl, tile_bm, tid, kMatchThreads);
+      __shared__ unsigned char sm_lut7[128];
+      fill_lut7(sm_lut7, tid);
+      attach_slice(ds, sl, tile_bm, sm_lut7);  // (visible after the barrier below)
     }
   }
   if (tid == 0) { cur[0] = mu0[0]; cur[1] = mu0[1]; cur[2] = mu0[2]; steps[0] = sm.lstep; steps[1] = sm.astep; refinements = 0; done = 0; }
@@ -525,7 +284,7 @@ __global__ __launch_bounds__(kMatchThreads) void rbpf_scanmatch(ScanC c, ScanMat
       int cd;
       if ((e >> 16) == cell1) cd = (int)(e & 0xFFFFull);
       else {
-        cd = lookup_code<false>(c.g, ds, radius, ci, cj);
+        cd = lookup_code(c.g, ds, radius, ci, cj);
         if (cd < 0) { oob |= 2; continue; }
         *slot = (cell1 << 16) | (unsigned long long)cd;
       }
@@ -788,10 +547,10 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     // block ends within range_max of it, and its nearest obstacle is usually a few cells further at most
     int sci, scj;
     if (world2cell(c.g, Tc[0], Tc[1], sci, scj)) {
-      const int R0 = max(0, sci - occ_half), R1 = min(c.g.xsize - 1, sci + occ_half);
-      const int W0 = max(0, scj - occ_half) >> 6, W1 = min(c.g.ysize - 1, scj + occ_half) >> 6, nW = W1 - W0 + 1;
+      const Slice sl = slice_round(c.g, occ_half, sci, scj);
+      const int R0 = sl.R0, R1 = sl.R1, W0 = sl.W0, nW = sl.nW;
       unsigned long long* tb = tile_bm;
-      int* ta = reinterpret_cast<int*>(tile_bm + (size_t)(R1 - R0 + 1) * nW);
+      int* ta = sl.any(tile_bm);
       // Two round trips instead of a chain of dependent ones per word: the ids of the tiles under the window go to LDS
       // first, then every row requests its (up to kStC) 32-bit pieces at once.
       constexpr int kStC = 12, kStIds = 256;
@@ -823,25 +582,10 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
           }
           ta[r] = acc != 0ull;
         }
-      } else {
-        for (int r = tid; r <= R1 - R0; r += NT) {
-          unsigned long long acc = 0ull;
-          for (int w = 0; w < nW; ++w) {
-            const unsigned long long v = ds.occ.word(R0 + r, W0 + w);
-            tb[r * nW + w] = v;
-            acc |= v;
-          }
-          ta[r] = acc != 0ull;
-        }
-      }
-      // the 128-entry table of the 7 x 7 look (visible after the barrier below)
+      } else slice_copy_rows(ds.occ, sl, tile_bm, tid, NT);
       __shared__ unsigned char sh_lut7[128];
-      if (tid < 128) {
-        int best = 100;
-        for (int cbit = 0; cbit < 7; ++cbit) if ((tid >> cbit) & 1) { const int dc = cbit - 3; best = min(best, dc * dc); }
-        sh_lut7[tid] = (unsigned char)best;
-      }
-      ds.tany = ta; ds.R0 = R0; ds.R1 = R1; ds.W0 = W0; ds.nW = nW; ds.lut7 = sh_lut7;
+      fill_lut7(sh_lut7, tid);
+      attach_slice(ds, sl, tile_bm, sh_lut7);  // (visible after the barrier below)
     }
     if (barrier_or_leave(late_beams())) return;   // (workgroup-uniform: nothing written yet)
     staged = true;

@@ -80,45 +80,7 @@ __device__ __forceinline__ bool add_log_odds(const TilePool& P, unsigned int id,
   return was != now;
 }
 
-// Ordered log of the occupied-set changes of one scan, per particle (reference distance-field mode only): entry =
-// cell index, bit 31 set = the cell LEFT the set.  Same order as the reference's occ_cells_ insert / erase calls
-// (grid_mapper.cpp:153-177 -> updateCellState/updateCellHash :438-546): beam by beam, the ray's free cells in
-// free_index order, then the end point.  ev == NULL: no log.
-
-
-// Is map cell (cx, cy) one of the FREE cells of ray r (i.e. some n in [0, count) has ray_cell(r, n) == it)?
-__device__ __forceinline__ bool on_ray(const Ray& r, int cx, int cy) {
-  switch (r.kind) {
-    case 0: { const int n = (cy - r.y0) * r.sy; return cx == r.x0 && n >= 0 && n < r.count; }
-    case 1: { const int n = (cx - r.x0) * r.sx; return cy == r.y0 && n >= 0 && n < r.count; }
-    case 4: { const int n = (cx - r.x0) * r.sx; return n >= 0 && n < r.count && cy == r.y0 + r.sy * n; }
-    default: {
-      if (cx == r.x0 && cy == r.y0) return r.count > 0;
-      const int n = (r.kind == 2) ? cx - r.xa : cy - r.ya;      // steps along the major axis
-      if (n < 1 || n > r.dmaj - 1) return false;
-      const int t = ((r.kind == 2) ? cy - r.ya : cx - r.xa) * r.sgn;  // offset along the minor axis
-      // ray_cell gives offset c = max(0, ceil(a / (2*dmaj))) with a = 2*dmin*n - dmaj; test t == c without dividing
-      const int a = 2 * r.dmin * n - r.dmaj, d2 = 2 * r.dmaj;
-      return (a <= 0) ? (t == 0) : (t >= 1 && d2 * (t - 1) < a && a <= d2 * t);
-    }
-  }
-}
-
-// Tile version of the raycast (the default): no per-beam barrier.
-//  F. every distinct END-POINT cell (<= Bv of them; the only cells that see both kinds of update in one scan,
-//     and there the floating-point add order matters) is flagged in an LDS tile covering the scan's bounding
-//     box (<= (2*range_max/res + 3)^2 cells) and gets a slot: a short list of (beam, kind) events;
-//  1. every (beam, step) pair looks at its cell in the tile: a plain cell bumps its 15-bit counter (order-free
-//     LDS atomic), a flagged cell records the event "beam b, free" in the cell's slot; every beam also records
-//     "beam b, occupied" in its own end point's slot;
-//  2. one LANE per end-point cell replays its slot in beam order ("+= l_free" / "+= l_occ": exactly the
-//     reference's sequence of adds for that cell).  A slot that overflowed (kEvCap events; e.g. the robot's
-//     own cell) is replayed by a whole wave instead, which tests the cell against every beam;
-//  3. every other touched cell gets its count of "+= l_free" (same addend each time, so the order among
-//     them is immaterial) — bit-identical to the beam-ordered loop, checked against it and the oracle.
-// LDS (ints): ex ey own rk rxy rdd ecnt [Bv each] | ev u16[Bv][kEvCap] | tile u32[(cap+1)/2] (two 16-bit
-// halves per word: bit 15 = end-point flag, low 15 bits = free-add count, or the slot index when flagged).
-// The same reductions without LDS round trips: an inclusive scan inside each row of 16 lanes by DPP shifts, then the row
+// Integer wave reductions without LDS round trips: an inclusive scan inside each row of 16 lanes by DPP shifts, then the row
 // totals broadcast down the rows (row_bcast:15 / :31); lane 63 holds the result.  (__shfl_xor is ds_bpermute: six
 // dependent LDS-latency steps per reduction.)
 template <class Op> __device__ __forceinline__ int wave_reduce_dpp(int v, int ident, Op op) {
@@ -133,12 +95,6 @@ template <class Op> __device__ __forceinline__ int wave_reduce_dpp(int v, int id
 __device__ __forceinline__ int wave_min_dpp(int v) { return wave_reduce_dpp(v, 0x7FFFFFFF, [](int a, int b) { return a < b ? a : b; }); }
 __device__ __forceinline__ int wave_max_dpp(int v) { return wave_reduce_dpp(v, (int)0x80000000, [](int a, int b) { return a > b ? a : b; }); }
 __device__ __forceinline__ int wave_sum_dpp(int v) { return wave_reduce_dpp(v, 0, [](int a, int b) { return a + b; }); }
-// ---- dense view of the occupancy bits -----------------------------------------------------------------------
-// The packed form of a ray straight from its two ends, selects only (what pack_ray(make_ray(..)) returns; the Ray struct's
-// case analysis turns into a private array the compiler indexes at run time).  Along the major axis the ray starts at
-// its LOW end (xa, ya) — the robot's cell or, for a reversed ray, the end point — takes dmaj steps and moves c_t =
-// max(0, ceil((2 dmin t - dmaj) / (2 dmaj))) cells sideways (negated if neg); its free cells are the robot's cell and
-// the cells strictly between the ends.
 // n times  x = fl(x + d)  — the updates one cell takes from n beams (grid_mapper.cpp:438-477 adds the same log-odds once per beam) —
 // bit for bit WITHOUT the chain of n dependent adds (13 ns each for one lane: the robot's own cell takes one per beam).  While x
 // stays in one binade it is m * u (u = ulp(x), m a 53-bit integer) and d = kd * ud with ud = u / 2^sh: x + d = (m + q) u + rem ud
@@ -185,6 +141,11 @@ __device__ __forceinline__ double add_repeated(double x, const double d, int n) 
   }
   return x;
 }
+// The packed form of a ray straight from its two ends, selects only (the Ray struct's case analysis turns into a private
+// array the compiler indexes at run time).  Along the major axis the ray starts at
+// its LOW end (xa, ya) — the robot's cell or, for a reversed ray, the end point — takes dmaj steps and moves c_t =
+// max(0, ceil((2 dmin t - dmaj) / (2 dmaj))) cells sideways (negated if neg); its free cells are the robot's cell and
+// the cells strictly between the ends.
 struct RayP { int xa, ya, dmaj, dmin; bool ymajor, neg; };
 __device__ __forceinline__ RayP ray_packed(int x0, int y0, int x1, int y1) {
   const int dx = x1 - x0, dy = y1 - y0, adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
@@ -197,7 +158,7 @@ __device__ __forceinline__ RayP ray_packed(int x0, int y0, int x1, int y1) {
   r.dmaj = r.ymajor ? ady : adx; r.dmin = r.ymajor ? adx : ady;
   return r;
 }
-// Is (cx, cy) a free cell of the ray (x0, y0) -> (x1, y1)?  Same set as on_ray(make_ray(..)).
+// Is (cx, cy) a free cell of the ray (x0, y0) -> (x1, y1), i.e. ray_cell(make_ray(..), n) for some n in [0, count)?
 __device__ __forceinline__ bool on_ray_packed(int x0, int y0, int x1, int y1, int cx, int cy) {
   const RayP r = ray_packed(x0, y0, x1, y1);
   if (r.dmaj == 0) return false;  // the beam ends in the robot's cell: no free cell
@@ -210,7 +171,7 @@ __device__ __forceinline__ bool on_ray_packed(int x0, int y0, int x1, int y1, in
 }
 
 // ---- the default map update: box counters ------------------------------------------------------------------------
-// Same contract as rbpf_raycast_tile (bit-identical maps) with fewer, cheaper phases:
+// The contract: maps bit-identical to rbpf_raycast's, the beam-ordered form below.  The phases:
 //  F. the beams' end-point cells — the only cells that see both l_free and l_occ in one scan, i.e. where the floating-
 //     point add order matters — are flagged in an LDS array with one 32-bit word per cell of the scan's bounding box
 //     (bit 31; bits 16-30 = the cell's slot in the list of distinct end-point cells);

@@ -112,7 +112,7 @@ CASES = tuple(_sizes() + _beams() + [
     _case("last-wave-only", "split", valid={2: "last-wave"}, reset_at=(2,), expect=dict(segments_at={2: (False, False, False, True)})),
     _case("segments-512", "split", k=98, valid={2: "segments-8"}, reset_at=(2,), threads=512,
           expect=dict(segments_at={2: (True,) + (False,) * 6 + (True,)})),
-    # ---- lookups (query mode): lookup_code_fast, the deferred searches, the staging forms, the tiers of mix_term
+    # ---- lookups (query mode): lookup_code_fast (look7), the deferred searches, the staging forms, the tiers of mix_term
     # the limit of the 7 x 7 look, on a hand-made map of two cells (the method of scanmatch_cases' slice-clear: single-beam scans, the robot
     # backing away 3 cells per scan along its heading 0): scan 0 marks A = (94, 60) with beam 0, scan 1 marks B = (93, 63) with beam 5, and
     # scan 2's only beam ends on L = (90, 60).  d2(L, A) = 16, four cells along the row and outside the look; d2(L, B) = 18, at (3, 3), its
@@ -293,7 +293,7 @@ def nearest_d2(case, ij, occ):
 
 
 def look7_fits(case, ij, box):
-    """Whether lookup_code_fast's 7 x 7 look can run at all at the cells ij: its rows lie inside the slice's and its seven columns inside
+    """Whether the 7 x 7 look (csrc/rbpf_lookup.hpp: look7, what lookup_code_fast is in query mode) can run at all at the cells ij: its rows lie inside the slice's and its seven columns inside
     the slice's 32-bit pieces (`ci - 3 >= R0 && ci + 3 <= R1 && p0 >= 0 && wi + 1 < 2 * nW && cj <= C1`)."""
     R0, R1, C0, C1 = box
     ci, cj = ij[..., 0], ij[..., 1]
@@ -302,7 +302,7 @@ def look7_fits(case, ij, box):
 
 
 def look7_settles(case, ij, occ, box):
-    """Which lookups lookup_code_fast's 7 x 7 look settles: the look fits the slice (look7_fits), and the nearest occupied cell among its
+    """Which lookups look7 settles (the others come back from lookup_code_fast as kNeedSearch): the look fits the slice (look7_fits), and the nearest occupied cell among its
     49 is within d2 <= 9 and <= clear^2."""
     R0, R1, C0, C1 = box
     oi, oj = occ // case.cells, occ % case.cells

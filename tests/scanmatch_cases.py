@@ -1,5 +1,5 @@
-"""The case table of the RBPF scan matcher (csrc/rbpf_propose.hip: rbpf_scanmatch, with the lookups it makes through lookup_code /
-nearest_code_query and its per-beam cell cache).  Plain data and the two host expressions that decide which lookup path a case takes,
+"""The case table of the RBPF scan matcher (csrc/rbpf_propose.hip: rbpf_scanmatch, with the lookups it makes through csrc/rbpf_lookup.hpp's
+lookup_code / nearest_code_query_body and its per-beam cell cache).  Plain data and the two host expressions that decide which lookup path a case takes,
 restated: slam_impl's window half-width and the LDS bitmap slice.  tests/test_scanmatch_cases.py proves the table on the CPU with the
 oracle alone (the matcher really moves, leaves the slice / the window, wraps, hits the move cap where a case says so, and no
 decision of any matcher call is nearer than 5e-10 to going the other way); tests/test_rbpf_scanmatch_gpu.py runs it on the device,

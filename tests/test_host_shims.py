@@ -311,6 +311,57 @@ def test_grid_mapper_class_surface_against_the_oracle(host, gpu_pkg, reference_f
 
 
 @pytest.mark.gpu
+def test_grid_mapper_default_field_likelihood_is_the_exact_field_s(host, gpu_pkg):
+    """GridMapper::likelihoodFieldModel in the DEFAULT mode (rbpf_likelihood_one with query-mode lookups: no LDS slice, the row
+    walks on the global bitmap, inlined) at 1e-9 against the oracle's GridMapper over the exact field — the brute-force transform
+    of the oracle's own occupied cells, injected through set_occ_dist (tests/test_oracle_exact_field.py pins that to the oracle's
+    exact_field switch, bit for bit).  Shipped 80 x 80 map, ROOM_SMALL, three scans integrated on both sides, the fourth scan
+    scored at: its own pose; two poses a few centimetres off; a pose far enough out that most beams end well away from every
+    occupied cell (the walks go rows deep); a pose from which beams leave the world (both sides report it).
+    The "unreached" fallback itself cannot occur on this map: cell_radius is 200 cells (max_occ_dist 10 m at 0.05 m) and no two
+    cells of an 80 x 80 map are more than 112 apart, so once a cell is occupied every cell has an obstacle within reach (asserted
+    below).  The far pose asks for what the map does allow: beams whose nearest obstacle is beyond the three cells a 7 x 7
+    look would settle, up to ten cells away."""
+    host.hst_gm_create.restype = C.c_void_p
+    grid = _arr([0.05, -2.0, 2.0, -2.0, 2.0]); laser = orc.lds01_laser(); trs = _arr([0.0, 0.0, 0.0])
+    g = C.c_void_p(host.hst_gm_create(_p(grid), _p(laser), _p(orc.MIX), _p(trs), 0))
+    assert g.value, host.hst_last_error()
+    o = orc.GridAPI("orc", grid=tuple(grid))
+    _, poses = rc.trajectory(4, inc=(0.04, 0.03, 0.02))
+    rng = np.random.default_rng(4)
+    scans = [orc.room_scan(poses[s], walls=rc.ROOM_SMALL, rng=rng) for s in range(4)]
+    for s in range(3):
+        assert host.hst_gm_integrate_scan(g, _p(scans[s]), 360, _p(_arr(poses[s]))) == 0, host.hst_last_error()
+        assert o.integrate_scan(scans[s], poses[s]) == 0
+    occ = np.zeros(o.G, dtype=np.uint8)
+    occ[o.occ_cells()] = 1
+    radius = int(o.constants()[3])
+    codes = orc.exact_edt_codes(occ.reshape(o.xsize, o.ysize), radius, np.full((o.xsize, o.ysize), 0xFFFF, np.uint16))
+    assert radius == 200 and occ.any() and codes.max() < 0xFFFF       # (no cell out of reach: see above)
+    o.set_occ_dist((np.sqrt(codes.astype(np.float64)) * 0.05).ravel())
+    scan, own = scans[3], np.array(poses[3])
+
+    def end_codes(q):
+        xy = o.end_points(scan, q)
+        return codes[np.floor((xy[:, 0] + 2.0) / 0.05).astype(int), np.floor((xy[:, 1] + 2.0) / 0.05).astype(int)]
+
+    far = own + np.array([0.1, 0.35, -0.25])
+    assert end_codes(own).max() <= 9 and (end_codes(far) > 9).sum() > 180 and end_codes(far).max() > 81
+    lik = C.c_double()
+    for q in (own, own + np.array([0.01, 0.02, -0.015]), own + np.array([-0.02, -0.03, 0.04]), far):
+        want, err = o.likelihood(scan, q)
+        assert err == 0 and want > 0.0
+        assert host.hst_gm_likelihood(g, _p(scan), 360, _p(_arr(q)), C.byref(lik)) == 0, host.hst_last_error()
+        print("likelihood at", q, ":", lik.value, "oracle", want, "rel", abs(lik.value - want) / want)
+        assert abs(lik.value - want) <= 1e-9 * abs(want), (q, lik.value, want)
+    out = own + np.array([0.0, 0.6, 0.0])
+    assert o.likelihood(scan, out)[1] != 0
+    assert host.hst_gm_likelihood(g, _p(scan), 360, _p(_arr(out)), C.byref(lik)) == 1
+    assert b"NOT in the bounds of the world" in host.hst_last_error()
+    host.hst_gm_destroy(g); o.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("odometry_mode", [0, 1])
 def test_closed_loop_tick_sequence_equals_the_oracle_loop(host, gpu_pkg, odometry_mode):
     """SURVEY.md 8-f N3 as PARITY, not only as a property: the first 200 ticks of the closed loop

@@ -136,7 +136,7 @@ def _rows(runs, cid):
 def test_the_restated_literals_are_the_host_code_s_and_the_kernel_s():
     host = open(os.path.join(CSRC, "rbpf.hip")).read()
     dev = open(os.path.join(CSRC, "rbpf_device.hpp")).read()
-    ker = open(os.path.join(CSRC, "rbpf_propose.hip")).read()
+    ker = open(os.path.join(CSRC, "rbpf_propose.hip")).read() + open(os.path.join(CSRC, "rbpf_lookup.hpp")).read()   # (its lookups)
     api = open(os.path.join(CSRC, "rbpf_api.hip")).read()
     for src, pieces in ((host, ("sizeof(double) * ((12 + kUnCap) * h->k + 3 * (c.Bv > 0 ? c.Bv : 1)) + sizeof(unsigned int) * 4 * (c.Bv > 0 ? c.Bv : 1);",
                                 "if (h->df_mode == 2) {\n    // LDS copy of the occupancy bitmap",

@@ -7,6 +7,9 @@ import __graft_entry__ as g
 g.load_package()
 import bench_rbpf, rbpf_cases as rc
 from rtn_amd.rbpf import ParticleFilter, default_params
+if os.environ.get("TBNAV_DEV_LIB"):   # (A/B runs of two builds of the library in one call, as tools/rbpf_driver.py)
+    from rtn_amd import capi
+    capi.LIB_PATH = os.path.abspath(os.environ["TBNAV_DEV_LIB"])
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
 n_scans = 14
 steps, poses = rc.trajectory(n_scans, inc=(0.07, 0.10, 0.05))
