@@ -63,6 +63,21 @@ class MppiCostField(C.Structure):
 MPPI_FIELD_MAX_SIDE = 4096
 
 
+class NavParams(C.Structure):
+    """tbnav_nav_params (include/tbnav_nav.h, G1)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("xmin", C.c_double), ("ymin", C.c_double), ("resolution", C.c_double),
+                ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NavSolveInfo(C.Structure):
+    """tbnav_nav_solve_info."""
+    _fields_ = [("solved", C.c_int32), ("goal", C.c_int32 * 2), ("rounds", C.c_int32), ("launches", C.c_int32), ("tiles", C.c_int32 * 2),
+                ("tile_visits", C.c_int64)]
+
+
+NAV_MAX_SIDE, NAV_MAX_COST, NAV_UNREACHED = 2048, 64, 0xFFFFFFFF
+
+
 class RbpfParams(C.Structure):
     """tbnav_rbpf_params (include/tbnav_rbpf.h)."""
     _fields_ = [
@@ -231,6 +246,18 @@ def lib() -> C.CDLL:
         "tbnav_mppi_get_cost_field": (C.c_int, [vp, C.POINTER(i32), C.POINTER(MppiCostField)]),
         "tbnav_mppi_cost_field_lookup": (C.c_int, [vp, vp, i32, vp]),
         "tbnav_mppi_group_set_cost_field": (C.c_int, [vp, C.POINTER(MppiCostField), vp]),
+        # goal field (include/tbnav_nav.h)
+        "tbnav_nav_create": (C.c_int, [C.POINTER(NavParams), C.POINTER(vp)]),
+        "tbnav_nav_destroy": (None, [vp]),
+        "tbnav_nav_set_cost": (C.c_int, [vp, vp]),
+        "tbnav_nav_solve": (C.c_int, [vp, i32, i32]),
+        "tbnav_nav_cell_of": (C.c_int, [vp, dbl, dbl, C.POINTER(i32), C.POINTER(i32)]),
+        "tbnav_nav_get_cost_to_go": (C.c_int, [vp, vp]),
+        "tbnav_nav_get_field": (C.c_int, [vp, dbl, vp]),
+        "tbnav_nav_path": (C.c_int, [vp, i32, i32, vp, i32, C.POINTER(i32)]),
+        "tbnav_nav_last_solve": (C.c_int, [vp, C.POINTER(NavSolveInfo), C.c_char_p, i32]),
+        "tbnav_nav_apply_to_mppi": (C.c_int, [vp, vp, dbl, dbl]),
+        "tbnav_nav_apply_to_mppi_group": (C.c_int, [vp, vp, dbl, dbl]),
         # communicators (include/tbnav_comm.h) and the sharded MPPI tick
         "tbnav_comm_unique_id": (C.c_int, [vp]),
         "tbnav_comm_unique_id_ipc": (C.c_int, [vp]),

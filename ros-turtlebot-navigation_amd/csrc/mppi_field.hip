@@ -212,6 +212,19 @@ int tbnav_mh::launch_rollout_field(tbnav_mppi* h, RolloutArgs a, const USrc& usr
   return TBNAV_OK;
 }
 
+namespace {
+// what both stagings share: the kernel's dynamic LDS allowed for this handle, and room for the values on its device (current here)
+int field_alloc(tbnav_mppi* h, size_t n, float** d) {
+  // the kernel's dynamic LDS, as tbnav_mppi_create allows it for mppi_rollout_cost (lds_from only ever grows afterwards)
+  const int lds_max = (int)field_lds_bytes(h, h->lds_from);
+  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  TBNAV_HIP(hipMalloc((void**)d, n * sizeof(float)));
+  return TBNAV_OK;
+}
+}  // namespace
+
 int tbnav_mh::field_stage(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, const float* values_host, float** d_new) {
   if (!h || !d_new) return TBNAV_ERR_INVALID_ARG;
   *d_new = nullptr;
@@ -221,14 +234,26 @@ int tbnav_mh::field_stage(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, cons
   for (size_t i = 0; i < n; ++i) if (!std::isfinite(values_host[i])) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
-  // the kernel's dynamic LDS, as tbnav_mppi_create allows it for mppi_rollout_cost (lds_from only ever grows afterwards)
-  const int lds_max = (int)field_lds_bytes(h, h->lds_from);
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
   float* d = nullptr;
-  TBNAV_HIP(hipMalloc((void**)&d, n * sizeof(float)));
+  const int rc = field_alloc(h, n, &d);
+  if (rc != TBNAV_OK) return rc;
   const hipError_t e = hipMemcpy(d, values_host, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(d); TBNAV_HIP(e); }
+  *d_new = d;
+  return TBNAV_OK;
+}
+
+int tbnav_mh::field_stage_device(tbnav_mppi* h, const tbnav_mppi_cost_field& geom, const float* d_values, int src_device, float** d_new) {
+  if (!h || !d_new || !d_values || !geom_ok(geom)) return TBNAV_ERR_INVALID_ARG;
+  *d_new = nullptr;
+  const size_t n = (size_t)geom.nx * geom.ny;
+  DeviceGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  float* d = nullptr;
+  const int rc = field_alloc(h, n, &d);
+  if (rc != TBNAV_OK) return rc;
+  const hipError_t e = src_device == h->device ? hipMemcpy(d, d_values, n * sizeof(float), hipMemcpyDeviceToDevice)
+                                               : hipMemcpyPeer(d, h->device, d_values, src_device, n * sizeof(float));
   if (e != hipSuccess) { (void)hipFree(d); TBNAV_HIP(e); }
   *d_new = d;
   return TBNAV_OK;

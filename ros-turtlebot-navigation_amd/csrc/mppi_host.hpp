@@ -140,6 +140,9 @@ int launch_rollout_field(tbnav_mppi* h, RolloutArgs a, const USrc& usrc, const d
 // field_stage checks F1 and uploads the values (*d_new = nullptr for geom == nullptr); field_commit waits for the device and swaps
 int field_stage(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, const float* values_host, float** d_new);
 int field_commit(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, float* d_new);
+// field_stage for values that are on a device already (nav.hip: tbnav_nav_apply_to_mppi): d_values, nx*ny floats on src_device and
+// finite by the caller's construction, are copied device to device (a peer copy when src_device is not the handle's)
+int field_stage_device(tbnav_mppi* h, const tbnav_mppi_cost_field& geom, const float* d_values, int src_device, float** d_new);
 // (mppi.hip)
 Lam lam_of(double lambda);
 inline Lam lam_of(const tbnav_mppi* h) { return lam_of(h->p.lambda); }

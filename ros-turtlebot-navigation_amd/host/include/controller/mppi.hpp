@@ -17,6 +17,7 @@
 
 struct tbnav_mppi;        // C-ABI handle
 struct tbnav_mppi_group;  // the same over several GPUs (include/tbnav_mppi.h)
+namespace planner { class GoalField; }  // planner/goal_field.hpp: hands its field to the controller's handle on the device
 
 namespace controller {
 
@@ -83,6 +84,7 @@ class MPPI {
   std::vector<double> controls() const;      ///< warm-start matrix u, [2][T]
 
  private:
+  friend class planner::GoalField;
   tbnav_mppi* h_ = nullptr;         // n_gpus == 1
   tbnav_mppi_group* g_ = nullptr;   // n_gpus > 1
   int steps_ = 0, rollouts_ = 0;

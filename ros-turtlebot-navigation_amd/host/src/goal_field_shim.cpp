@@ -1,0 +1,91 @@
+// goal_field_shim.cpp — planner::GoalField over the C-ABI of include/tbnav_nav.h.  Status codes become the exceptions the other
+// shims throw (std::invalid_argument for a bad argument and for the reference's out-of-world text, std::runtime_error otherwise);
+// there is no CPU path.
+#include <cmath>
+#include <stdexcept>
+#include <string>
+
+#include "planner/goal_field.hpp"
+#include "tbnav_nav.h"
+
+namespace planner {
+namespace {
+void check(int rc, const char* where) {
+  if (rc == TBNAV_OK) return;
+  const std::string text = tbnav_status_string(rc);
+  if (rc == TBNAV_ERR_OUT_OF_WORLD) throw std::invalid_argument(text);  // what the reference throws (grid_mapper.cpp:856)
+  std::string msg = std::string(where) + ": " + text;
+  if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+  const char* hip = tbnav_last_hip_error();
+  if (hip && *hip) msg += std::string(" [") + hip + "]";
+  throw std::runtime_error(msg);
+}
+}  // namespace
+
+std::vector<std::uint8_t> navCostFromDistance(const std::vector<double>& occ_dist, int nx, int ny, double r_robot, double r_inflate, double k) {
+  if (!(0.0 <= r_robot && r_robot < r_inflate) || !(0.0 <= k && k <= 63.0))
+    throw std::invalid_argument("navCostFromDistance: 0 <= r_robot < r_inflate and 0 <= k <= 63 are required");
+  if (nx < 0 || ny < 0 || occ_dist.size() != (size_t)nx * (size_t)ny) throw std::invalid_argument("navCostFromDistance: occ_dist.size() != nx * ny");
+  std::vector<std::uint8_t> c(occ_dist.size());
+  for (size_t i = 0; i < c.size(); ++i) {
+    const double d = occ_dist[i];
+    double t = (r_inflate - d) / (r_inflate - r_robot);
+    t = t > 0.0 ? t : 0.0;   // (a NaN goes to 0)
+    t = t < 1.0 ? t : 1.0;
+    c[i] = (std::uint8_t)(d <= r_robot ? 0.0 : 1.0 + std::rint(k * t * t));
+  }
+  return c;
+}
+
+GoalField::GoalField(int nx, int ny, double xmin, double ymin, double resolution) : nx_(nx), ny_(ny) {
+  tbnav_nav_params p{};
+  p.nx = nx; p.ny = ny; p.xmin = xmin; p.ymin = ymin; p.resolution = resolution; p.device = -1;
+  check(tbnav_nav_create(&p, &h_), "planner::GoalField");
+}
+GoalField::~GoalField() { tbnav_nav_destroy(h_); }
+GoalField::GoalField(GoalField&& o) noexcept : h_(o.h_), nx_(o.nx_), ny_(o.ny_) { o.h_ = nullptr; }
+
+void GoalField::setCost(const std::vector<std::uint8_t>& cost) {
+  if (cost.size() != (size_t)nx_ * (size_t)ny_) throw std::invalid_argument("setCost: cost.size() != nx * ny");
+  check(tbnav_nav_set_cost(h_, cost.data()), "setCost");
+}
+std::array<int, 2> GoalField::cellOf(double x, double y) const {
+  int32_t ix = 0, iy = 0;
+  check(tbnav_nav_cell_of(h_, x, y, &ix, &iy), "cellOf");
+  return {ix, iy};
+}
+void GoalField::solve(double x, double y) {
+  const auto c = cellOf(x, y);
+  check(tbnav_nav_solve(h_, c[0], c[1]), "solve");
+}
+std::vector<std::uint32_t> GoalField::costToGo() {
+  std::vector<std::uint32_t> d((size_t)nx_ * ny_);
+  check(tbnav_nav_get_cost_to_go(h_, d.data()), "costToGo");
+  return d;
+}
+std::vector<float> GoalField::field(double cap) {
+  std::vector<float> v((size_t)nx_ * ny_);
+  check(tbnav_nav_get_field(h_, cap, v.data()), "field");
+  return v;
+}
+std::vector<std::array<int, 2>> GoalField::path(double x, double y) {
+  const auto c = cellOf(x, y);
+  int32_t n = 0;
+  const int rc = tbnav_nav_path(h_, c[0], c[1], nullptr, 0, &n);   // the length first: "buffer too small" with n set
+  if (n <= 0) check(rc, "path");
+  std::vector<int32_t> cells((size_t)2 * n);
+  check(tbnav_nav_path(h_, c[0], c[1], cells.data(), n, &n), "path");
+  std::vector<std::array<int, 2>> out((size_t)n);
+  for (int i = 0; i < n; ++i) out[i] = {cells[2 * i], cells[2 * i + 1]};
+  return out;
+}
+void GoalField::applyTo(controller::MPPI& mppi, double cap, double weight) {
+  check(mppi.g_ ? tbnav_nav_apply_to_mppi_group(h_, mppi.g_, cap, weight) : tbnav_nav_apply_to_mppi(h_, mppi.h_, cap, weight), "applyTo");
+}
+int GoalField::rounds() const {
+  tbnav_nav_solve_info info{};
+  check(tbnav_nav_last_solve(h_, &info, nullptr, 0), "rounds");
+  return info.rounds;
+}
+
+}  // namespace planner

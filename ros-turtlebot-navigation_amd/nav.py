@@ -1,0 +1,101 @@
+"""Python mirror of planner::GoalField over the C-ABI of include/tbnav_nav.h (tests / tools plumbing): the exact cost-to-go to a
+goal cell over a cost grid, solved on the device, and its hand-over to an MPPI handle as a cost field.  The header is the
+specification (G1-G6); the shipped host surface for ROS nodes is the C++ class in host/include/planner/goal_field.hpp.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+
+def nav_cost_from_distance(dist, r_robot: float, r_inflate: float, k: float) -> np.ndarray:
+    """A cost grid (uint8, the shape of `dist`, tbnav_nav.h G2) from distances to the nearest obstacle, e.g. what
+    rbpf.get_occ_dist returns for one particle: 0 (blocked) where d <= r_robot; elsewhere 1 + rint(k * t * t) with
+    t = (r_inflate - d) / (r_inflate - r_robot) clamped to 0 .. 1 — 1 in the open, 1 + k at the robot's radius; fp64.
+    0 <= r_robot < r_inflate and 0 <= k <= 63.  (planner::navCostFromDistance is the same arithmetic, bit for bit.)"""
+    if not (0.0 <= r_robot < r_inflate) or not (0.0 <= k <= 63.0):
+        raise ValueError("nav_cost_from_distance: 0 <= r_robot < r_inflate and 0 <= k <= 63 are required")
+    d = np.asarray(dist, dtype=np.float64)
+    t = (r_inflate - d) / (r_inflate - r_robot)
+    t = np.where(t > 0.0, t, 0.0)
+    t = np.where(t < 1.0, t, 1.0)
+    return np.where(d <= r_robot, 0.0, 1.0 + np.rint(k * t * t)).astype(np.uint8)
+
+
+class GoalField:
+    """tbnav_nav on one MI355X.  Cells are (ix, iy), arrays [nx][ny]."""
+
+    def __init__(self, nx: int, ny: int, xmin: float, ymin: float, resolution: float, device: int = -1):
+        p = capi.NavParams(nx, ny, xmin, ymin, resolution, device, 0)
+        self.nx, self.ny, self.xmin, self.ymin, self.resolution = nx, ny, xmin, ymin, resolution
+        self._L = capi.lib()
+        self._h = C.c_void_p()
+        capi.check(self._L.tbnav_nav_create(C.byref(p), C.byref(self._h)), "tbnav_nav_create")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.tbnav_nav_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setCost(self, cost):
+        """G2: uint8 [nx][ny]; what the next solve uses."""
+        c = np.asarray(cost)
+        if c.shape != (self.nx, self.ny) or c.dtype.kind not in "ui" or (c.size and (c.min() < 0 or c.max() > 255)):
+            raise ValueError("setCost: cost must be an integer array of shape [nx][ny] with values 0 .. 255")
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        capi.check(self._L.tbnav_nav_set_cost(self._h, c.ctypes.data), "tbnav_nav_set_cost")
+
+    def solve(self, ix: int, iy: int):
+        capi.check(self._L.tbnav_nav_solve(self._h, ix, iy), "tbnav_nav_solve")
+
+    def solveAt(self, x: float, y: float):
+        """solve with the goal given in world coordinates."""
+        self.solve(*self.cellOf(x, y))
+
+    def cellOf(self, x: float, y: float) -> tuple:
+        ix, iy = C.c_int32(), C.c_int32()
+        capi.check(self._L.tbnav_nav_cell_of(self._h, x, y, C.byref(ix), C.byref(iy)), "tbnav_nav_cell_of")
+        return ix.value, iy.value
+
+    def costToGo(self) -> np.ndarray:
+        d = np.empty((self.nx, self.ny), dtype=np.uint32)
+        capi.check(self._L.tbnav_nav_get_cost_to_go(self._h, d.ctypes.data), "tbnav_nav_get_cost_to_go")
+        return d
+
+    def field(self, cap: float) -> np.ndarray:
+        v = np.empty((self.nx, self.ny), dtype=np.float32)
+        capi.check(self._L.tbnav_nav_get_field(self._h, cap, v.ctypes.data), "tbnav_nav_get_field")
+        return v
+
+    def path(self, ix: int, iy: int) -> np.ndarray:
+        """G6: int32 [n][2], start and goal included."""
+        n = C.c_int32(0)
+        rc = self._L.tbnav_nav_path(self._h, ix, iy, None, 0, C.byref(n))
+        if n.value <= 0:   # (a path has a cell at least: the length query answered something else than "buffer too small")
+            capi.check(rc, "tbnav_nav_path")
+        cells = np.empty((n.value, 2), dtype=np.int32)
+        capi.check(self._L.tbnav_nav_path(self._h, ix, iy, cells.ctypes.data, n.value, C.byref(n)), "tbnav_nav_path")
+        return cells
+
+    def lastSolve(self) -> dict:
+        info, name = capi.NavSolveInfo(), C.create_string_buffer(64)
+        capi.check(self._L.tbnav_nav_last_solve(self._h, C.byref(info), name, 64), "tbnav_nav_last_solve")
+        return dict(solved=bool(info.solved), goal=(info.goal[0], info.goal[1]), rounds=info.rounds, launches=info.launches,
+                    tiles=(info.tiles[0], info.tiles[1]), tile_visits=int(info.tile_visits), kernel=name.value.decode())
+
+    def applyTo(self, mppi, cap: float, weight: float):
+        """tbnav_nav_apply_to_mppi(_group): the field of `cap` becomes the cost field of an rtn_amd.mppi.MPPI or MPPIGroup."""
+        from .mppi import MPPIGroup
+        if isinstance(mppi, MPPIGroup):
+            capi.check(self._L.tbnav_nav_apply_to_mppi_group(self._h, mppi._h, cap, weight), "tbnav_nav_apply_to_mppi_group")
+        else:
+            capi.check(self._L.tbnav_nav_apply_to_mppi(self._h, mppi._h, cap, weight), "tbnav_nav_apply_to_mppi")
