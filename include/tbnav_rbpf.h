@@ -286,6 +286,10 @@ int tbnav_rbpf_get_trace(tbnav_rbpf* h, double* sampled, double* p_scan, double*
                          double* sigma, double* eta, double* new_pose, double* weight_raw,
                          int32_t* resample_parent);
 
+/* children [N]: how many slots chose each particle in the LAST resampling (of tbnav_rbpf_slam or tbnav_rbpf_gather_local) — the
+ * counts the table copies took their reference counts from.  Meaningful only after a call that resampled. */
+int tbnav_rbpf_get_children(tbnav_rbpf* h, int32_t* children /*[N]*/);
+
 /* ---- one particle's map on its own: the methods of bmapping::GridMapper (grid_mapper.hpp:128-140) ------------------
  * The host class bmapping::GridMapper is a one-particle handle driven through these three calls (same kernels as
  * the filter's per-particle update).  pose = (theta, x, y) of the ROBOT in the map frame.

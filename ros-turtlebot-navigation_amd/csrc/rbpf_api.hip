@@ -39,6 +39,14 @@ int tbnav_rbpf_get_trace(tbnav_rbpf* h, double* sampled, double* p_scan, double*
   return TBNAV_OK;
 }
 
+int tbnav_rbpf_get_children(tbnav_rbpf* h, int32_t* children) {
+  if (!h || !children) return TBNAV_ERR_INVALID_ARG;
+  DeviceGuard guard(h->device);
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  TBNAV_HIP(hipMemcpy(children, h->d_parent + h->N, sizeof(int) * (size_t)h->N, hipMemcpyDeviceToHost));
+  return TBNAV_OK;
+}
+
 int tbnav_rbpf_best_state(tbnav_rbpf* h, double pose[3], int32_t* best_index) {
   if (!h || !pose) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);

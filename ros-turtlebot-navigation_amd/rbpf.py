@@ -216,6 +216,12 @@ class ParticleFilter:
         capi.check(self._L.tbnav_rbpf_get_trace(self._h, *[a.ctypes.data for a in t.values()]), "get_trace")
         return t
 
+    def children(self) -> np.ndarray:
+        """How many slots chose each particle in the last resampling (tbnav_rbpf_get_children); meaningful only after one."""
+        out = np.empty(self.N, dtype=np.int32)
+        capi.check(self._L.tbnav_rbpf_get_children(self._h, out.ctypes.data), "get_children")
+        return out
+
     def setScanMatching(self, on: bool = True, lstep: float = 0.05, astep: float = 0.05, iterations: int = 5):
         """Option, not the reference: every particle refines T(pose) * T_icp against its own map (hill climbing on
         the likelihood field) before the samples are drawn round it."""

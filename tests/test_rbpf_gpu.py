@@ -670,6 +670,7 @@ def test_parallel_exact_chains_equal_the_sequential_sums_bit_for_bit(gpu_pkg, n)
     binade), 20 orders of magnitude of spread, zeros, weights that are exact multiples of the running sum's half-ulp."""
     import ctypes as C
     import torch
+    import resample_cases as rsc
     from rtn_amd import capi
     from rtn_amd.rbpf import resample_global
     pf = _dev(gpu_pkg, N=1, k=2)
@@ -683,21 +684,23 @@ def test_parallel_exact_chains_equal_the_sequential_sums_bit_for_bit(gpu_pkg, n)
         "zeros": np.where(rng.random(n) < 0.5, 0.0, rng.random(n)),
         "half_ulps": np.ldexp(2.0 * rng.integers(1, 1 << 20, n).astype(np.float64) + 1.0, -53 - 8),   # odd multiples of 2^-61: ties once the sum passes 2^-8
         "skewed_resample": np.where(np.arange(n) % 97 == 5, 1.0, 1e-6 * rng.random(n)),
+        "last": np.where(np.arange(n) == n - 1, 1.0, 0.0),   # all weight on the last particle: the selection is clamped at n - 1
     }
     for name, w in cases.items():
         if n == 1:
             w = np.array([0.37])
         if w.sum() == 0.0:
             w[0] = 1.0
-        z = float(rng.standard_normal())
-        parents_h, wn_h, st_h = resample_global(w, z)
         dw = torch.from_numpy(w).cuda()
-        parents_d = np.empty(n, dtype=np.int32)
-        st = capi.RbpfStats()
-        capi.check(pf._L.tbnav_rbpf_resample_global_dev(pf._h, dw.data_ptr(), n, 0, C.c_double(z), parents_d.ctypes.data, C.byref(st)), "resample_global_dev")
-        assert (st.sum_w, st.sq_sum, st.neff, st.resampled) == (st_h.sum_w, st_h.sq_sum, st_h.neff, st_h.resampled), (name, n, st.sum_w - st_h.sum_w, st.sq_sum - st_h.sq_sum)
-        if st.resampled:
-            assert np.array_equal(parents_d, parents_h), (name, n)
+        # a drawn z, and the table's (tests/resample_cases.py): the first slots all on parent 0, the last ones past the last running sum
+        for z in (float(rng.standard_normal()),) + rsc.Z_VALUES:
+            parents_h, wn_h, st_h = resample_global(w, z)
+            parents_d = np.empty(n, dtype=np.int32)
+            st = capi.RbpfStats()
+            capi.check(pf._L.tbnav_rbpf_resample_global_dev(pf._h, dw.data_ptr(), n, 0, C.c_double(z), parents_d.ctypes.data, C.byref(st)), "resample_global_dev")
+            assert (st.sum_w, st.sq_sum, st.neff, st.resampled) == (st_h.sum_w, st_h.sq_sum, st_h.neff, st_h.resampled), (name, n, z, st.sum_w - st_h.sum_w, st.sq_sum - st_h.sq_sum)
+            if st.resampled:
+                assert np.array_equal(parents_d, parents_h), (name, n, z)
     pf.close()
 
 
