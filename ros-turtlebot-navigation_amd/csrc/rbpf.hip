@@ -10,7 +10,8 @@
 //   rbpf_field.hip     rbpf_densify, rbpf_window, rbpf_edt<C>, rbpf_edt_compact<R> (stored-field modes, on-demand fields)
 //   rbpf_resample.hip  rbpf_normalize, rbpf_resample_apply, rbpf_pool_init, dense <-> tiles, rbpf_argmax, rbpf_export_map
 //   rbpf_migrate.hip   particle blobs for the sharded filter's cross-rank resample
-//   rbpf_device.hpp    what they share: launch-argument structs, map accessors, reductions, kernel declarations
+//   rbpf_device.hpp    what they share: launch-argument structs, map accessors, reductions, kernel declarations, the lists of forms
+//   rbpf_plan.hpp      which form a scan gets and with how much LDS: the selection, as plain host arithmetic (no HIP, testable on a CPU)
 //   rbpf_normalize.hpp the normalise / selection body (a kernel of its own and workgroup 0 of the map update)
 #include "rbpf_host.hpp"
 
@@ -79,8 +80,6 @@ ExportCuts derive_export_cuts(double cut_occ) {
   return c;
 }
 
-size_t edt_lds_bytes(int xs, int words, int C) { return (size_t)xs * words * 8 + (size_t)xs * C * 5; }
-
 // the part of ScanC the beam mixture term needs (also what the handle's table of it is built from at create)
 bool mixture_consts(const tbnav_rbpf* h, ScanC& c) {
   const tbnav_rbpf_params& P = h->p;
@@ -147,7 +146,7 @@ int status_from_err(const int err[4]) {
   if (err[2]) return TBNAV_ERR_PDF_VARIANCE;
   if (err[1]) return TBNAV_ERR_ETA_ZERO;
   if (err[3] & 8) return TBNAV_ERR_POOL_EXHAUSTED;  // no free log-odds tile left (the scan of that particle was not applied)
-  if (err[3] & 4) return TBNAV_ERR_UNSUPPORTED;  // a likelihood lookup left the particle's refreshed window: slam_impl's window rule missed a lookup (it once missed the scan matcher's travel)
+  if (err[3] & 4) return TBNAV_ERR_UNSUPPORTED;  // a likelihood lookup left the particle's refreshed window: the window rule (lookup_half_cells) missed a lookup (it once missed the scan matcher's travel)
   if (err[3]) return TBNAV_ERR_BRESENHAM;
   return TBNAV_OK;
 }
@@ -233,123 +232,66 @@ int resample_on_device(tbnav_rbpf* h) {
   return TBNAV_OK;
 }
 
+#define TBNAV_TRY(call) do { const int tbnav_rc_ = (call); if (tbnav_rc_ != TBNAV_OK) return tbnav_rc_; } while (0)
+
+static int launch_normalize(tbnav_rbpf* h, const NormArgs& a) {
+  hipLaunchKernelGGL(rbpf_normalize, dim3(1), dim3(256), 0, h->stream, a.N, a.zp, a.weight, a.weight_out, a.cs, a.parent, a.out,
+                     a.gate, a.gate_prev, a.seq, a.seq_val, a.children);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// default: box counters (rbpf_raycast_box), the form the plan names
+static int launch_raycast_box(tbnav_rbpf* h, const ScanC& c, const RaycastPlan& p, const double* sens, const NormArgs* nz, int* err,
+                              const double2* beams_dev) {
+  const StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
+  const MapT M = map_of(h);
+  unsigned long long* touched = h->count_touched ? h->d_touched : nullptr;
+  const NormArgs na = nz ? *nz : NormArgs{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr};
+  const size_t lds_launch = nz ? std::max(p.lds, sizeof(double) * 2 * kNormChunk) : p.lds;  // (workgroup 0's two arrays)
+  const int need_slot = (int)(h->rc_launches++ % 3u);
+#define TBNAV_X(NT_, WPS_, C16_, EV_)                                                                                                           \
+  if (p.threads == NT_ && p.wps == WPS_ && p.c16 == C16_ && p.ev == EV_) {                                                                      \
+    hipLaunchKernelGGL((rbpf_raycast_box<NT_, WPS_, C16_, EV_>), dim3(p.grid), dim3(NT_), lds_launch, h->stream, c, h->pool, M, beams_dev,     \
+                       sp.pose, sens, h->d_trow[h->cur], h->d_nocc[h->cur], err, (int)p.cap_win, touched, na, h->d_box_need,                   \
+                       h->d_box_need_host, need_slot, p.hash_words);                                                                            \
+    TBNAV_HIP(hipGetLastError());                                                                                                               \
+    return TBNAV_OK;                                                                                                                            \
+  }
+  TBNAV_RAYCAST_BOX_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have: never another form in its place)
+}
+
+// beam-ordered kernel: scans the LDS tile cannot hold, and the reference distance-field mode (it logs the occupied-set changes in
+// the reference's order); the normalise behind it as a launch of its own
+static int launch_raycast_ordered(tbnav_rbpf* h, const ScanC& c, const RaycastPlan& p, const NormArgs* nz, int* err, const double2* beams_dev) {
+  OccLog log{nullptr, nullptr, 0};
+  if (h->ref_field) TBNAV_TRY(ref_field_prepare_log(h, c.Bv, log));
+  const int bvn = c.Bv > 0 ? c.Bv : 1;
+  hipLaunchKernelGGL(rbpf_raycast, dim3(p.grid), dim3(kWave), sizeof(int) * (2 * bvn + (h->TT + 31) / 32), h->stream, c, h->pool, map_of(h),
+                     beams_dev, state_ptrs(h->d_state[h->cur], h->N).pose, h->d_trow[h->cur], h->d_nocc[h->cur], err, log,
+                     nz ? nz->gate_prev : nullptr);
+  TBNAV_HIP(hipGetLastError());
+  return nz ? launch_normalize(h, *nz) : TBNAV_OK;
+}
+
 // GridMapper::integrateScan's map update (grid_mapper.cpp:140-178) for particles [c.p0, c.p0 + count) at their poses.
 // sens: the sensor transforms the proposal kernel left for exactly these poses (NULL: the raycast derives them).
 // nz (optional): the weights' normalise / select step to run with this update — inside the box-counter kernel's launch as
 // workgroup 0 (no second stream, no event), behind the other map-update kernels as a launch of its own.
+// Which kernel, and how large its LDS array: plan_raycast (rbpf_plan.hpp), from the handle's options, the scan and the boxes'
+// need — a mapped word the device writes asynchronously, so it is read ONCE: what the selection used is what is reported.
 int launch_raycast(tbnav_rbpf* h, const ScanC& c, int count, const double* sens, const NormArgs* nz, int* err,
                    const double2* beams_dev) {
   if (!err) err = h->d_err;
   if (!beams_dev) beams_dev = h->d_beams;
-  const int* gp = nz ? nz->gate_prev : nullptr;
-  hipStream_t st = h->stream;
-  StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
-  const int bvn = c.Bv > 0 ? c.Bv : 1;
-  const MapT M = map_of(h);
-  int nt = h->raycast_threads;
-  const bool nt_auto = nt == 0;
-  if (nt == 0) nt = 1024;
-  // rbpf_raycast_box: one u32 per cell of the box, the box padded to whole groups of 8 cells along y
-  long cap_win = 0, cap4 = 0;
-  if (h->tile_cap > 0) {
-    // every end point lies within `reach` of the robot's position: at most floor(2 reach / res) + 2 rows or columns (+1 spare);
-    // along y the box is padded to whole pairs of cells
-    const double reach = c.rmax + std::hypot(h->p.Trs[1], h->p.Trs[2]);
-    const long side = (long)std::floor(2.0 * reach / h->p.resolution) + 3;
-    cap_win = (side * ((side + 2) & ~1L) + 7) & ~7L;
-    // ... but no more than lets TWO workgroups share a CU's 160 KB (the kernel works a larger box through in bands of rows;
-    // at least one padded row must fit)
-    const long cap_fit = ((78L * 1024 - (long)box_lds_bytes(0, (size_t)bvn) - (long)kBoxStaticLds) / 4) & ~7L;
-    if (cap_win > cap_fit) cap_win = std::max(cap_fit, (side + 9) & ~7L);
-    // (test hook: at most about this many rows of the box per band, to drive the band loop on small maps)
-    if (h->raycast_band_rows > 0) cap_win = std::min(cap_win, (h->raycast_band_rows * ((side + 2) & ~1L) + 7) & ~7L);
-    // ... and no more than the particles' boxes needed lately (+ 1/8 + 512 words for what a scan's motion changes): the bound
-    // above is the scan's longest beam in every direction from every pose, a room's box is a fraction of that — the array is
-    // what keeps a CU at two workgroups.  A box that outgrows the guess costs its particle a second band, not correctness.
-    const int need = (h->raycast_adapt && h->h_box_need) ? *reinterpret_cast<volatile int*>(h->h_box_need) : 0;
-    if (need > 0) {
-      const long want = ((long)need + need / 8 + 512 + 7) & ~7L;
-      cap_win = std::min(cap_win, std::max(want, (side + 9) & ~7L));
-      // FOUR 512-thread workgroups per CU — every one of 1000 particles resident at once instead of 768 and a second, partial
-      // round (round 4; measured 24.6 / 30.8 / 37.1 us with 1 / 2 / 3 workgroups per CU, 48.3 for 1000 particles on 768 slots) —
-      // when the boxes' need plus a margin of three rows or so fits a quarter of the CU's LDS.  The margin is tighter than the
-      // three-per-CU form's 1/8 + 512: a box that outgrows it costs its particle a second band, never correctness.
-      cap4 = std::max(((long)need + 256 + 7) & ~7L, (side + 9) & ~7L);
-    }
-  }
-  // Residency the launch gets: R workgroups per CU need R x (dynamic + static LDS) <= 160 KB; 4 and 3 per CU are 512-thread
-  // workgroups (64 / 80 registers a lane), 2 per CU 1024 threads (64).  Two cell formats: 32-bit words (slot in the word) and,
-  // when that buys a higher residency, 16-bit words + a slot table (C16: a few more instructions per walk step).  Measured at
-  // cfg3, N = 1000 / 4000, 32-bit words: 1024 x 2: 55.8 / 191 us; 512 x 2: 54.4 / 199; 512 x 3: 47.9 / 163; 512 x 4 (four
-  // events a slot instead of eight: what lets the bench room's 8272-cell boxes in): 41.7 / 143.
-  const size_t nz_lds = nz ? sizeof(double) * 2 * kNormChunk : (size_t)0;
-  auto fits = [&](int R, size_t bytes) { return (size_t)R * (std::max(bytes, nz_lds) + kBoxStaticLds) <= (size_t)kMaxLds; };
-  const bool may4 = h->raycast_adapt != 2 && cap4 > 0 && cap4 <= cap_win;
-  int wps = 8;
-  bool c16 = false;
-  const bool pick = nt_auto || nt == 512;
-  const bool c16_ok = h->raycast_cell16 != 0 && cap_win > 0 && cap_win < 65528 && c.Bv + 64 < 32768;
-  // (measured, N = 1000: the 16-bit form costs ~15 % at EQUAL residency — 57.2 against 49.8 us at three per CU: twice the
-  //  same-dword collisions of the LDS adds where rays converge, the sub-word arithmetic of every step — so going from three to
-  //  four per CU with it loses, 51.5 against 49.8 us, and it is used only where the 32-bit form is stuck at TWO per CU: the
-  //  SURVEY room's 13 860-cell boxes, 63.7 -> 60.7 us)
-  // (four per CU: with eight events a slot where they fit, with four where only they do — measured in a 3 x 1.9 m room whose cells take
-  //  5-10 events: 39.4 us with four-event slots against 37.7 with three workgroups per CU and eight)
-  size_t ev_slot = kBoxEv;  // (what the instantiation launched below holds per slot)
-  const bool force4 = h->raycast_adapt == 3;  // (tests: four-event slots wherever four workgroups fit)
-  if (pick && may4 && !force4 && fits(4, box_lds_bytes((size_t)cap4, (size_t)bvn, kBoxEv))) { nt = 512; cap_win = cap4; }
-  else if (pick && may4 && fits(4, box_lds_bytes((size_t)cap4, (size_t)bvn, kBoxEvFour))) { nt = 512; cap_win = cap4; ev_slot = kBoxEvFour; }
-  else if (pick && cap_win > 0 && fits(3, box_lds_bytes((size_t)cap_win, (size_t)bvn))) { nt = 512; wps = 6; }
-  else if (pick && may4 && c16_ok && fits(4, box16_lds_bytes((size_t)cap4, (size_t)bvn, kBoxEv))) { nt = 512; cap_win = cap4; c16 = true; }
-  // (no 16-bit form with four-event slots: its niche — boxes that fit four per CU only with BOTH economies — is a few hundred cells wide, and
-  //  the instantiation was the one map-update kernel left with a spill; such boxes run three per CU in <512, 6, true, 8>)
-  else if (pick && c16_ok && fits(3, box16_lds_bytes((size_t)cap_win, (size_t)bvn))) { nt = 512; wps = 6; c16 = true; }
-  else if (nt == 512) wps = 6;
-  if (h->raycast_cell16 == 2 && c16_ok && nt == 512) c16 = true;   // (tests / A-B: the 16-bit form wherever it can run)
-  if (c16) ev_slot = kBoxEv;   // (the 16-bit form has eight-event slots only)
-  const size_t lds_win = c16 ? box16_lds_bytes((size_t)cap_win, (size_t)bvn, ev_slot) : box_lds_bytes((size_t)cap_win, (size_t)bvn, ev_slot);
-  if (cap_win > 0 && !h->ref_field && c.Bv < 32768 - kWave && nt >= 512 && lds_win <= (size_t)kMaxLds - 4096) {
-    // default: box counters (rbpf_raycast_box)
-    unsigned long long* touched = h->count_touched ? h->d_touched : nullptr;
-    const NormArgs na = nz ? *nz : NormArgs{0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr};
-    const int blocks = count + (nz ? 1 : 0);
-    const size_t lds_launch = nz ? std::max(lds_win, sizeof(double) * 2 * kNormChunk) : lds_win;  // (workgroup 0's two arrays)
-    const int need_slot = (int)(h->rc_launches++ % 3u);
-    h->lk_raycast = nt == 512 ? 512 : 1024; h->lk_raycast_wps = wps; h->lk_raycast_c16 = c16 ? 1 : 0; h->lk_raycast_ev = (int)ev_slot; h->lk_raycast_grid = blocks;
-    h->lk_box_cap = (int)cap_win; h->lk_box_need = (h->raycast_adapt && h->h_box_need) ? *reinterpret_cast<volatile int*>(h->h_box_need) : 0;
-    const int hash_words = c16 ? (int)box16_hash_words((size_t)bvn) : 0;
-#define TBNAV_BOX(NT_, WPS_, C16_, EV_) hipLaunchKernelGGL((rbpf_raycast_box<NT_, WPS_, C16_, EV_>), dim3(blocks), dim3(NT_), lds_launch, st, c, h->pool, M, beams_dev, sp.pose, sens, \
-                                                h->d_trow[h->cur], h->d_nocc[h->cur], err, (int)cap_win, touched, na, h->d_box_need, h->d_box_need_host, need_slot, hash_words)
-    const bool ev4 = ev_slot == (size_t)kBoxEvFour;
-    if (nt == 512 && wps == 8 && c16) TBNAV_BOX(512, 8, true, 8);
-    else if (nt == 512 && wps == 8 && ev4) TBNAV_BOX(512, 8, false, 4);
-    else if (nt == 512 && wps == 8) TBNAV_BOX(512, 8, false, 8);
-    else if (nt == 512 && c16) TBNAV_BOX(512, 6, true, 8);
-    else if (nt == 512) TBNAV_BOX(512, 6, false, 8);
-    else TBNAV_BOX(1024, 8, false, 8);
-#undef TBNAV_BOX
-    TBNAV_HIP(hipGetLastError());
-    return TBNAV_OK;
-  }
-  {
-    // beam-ordered kernel: scans the LDS tile cannot hold, and the reference distance-field mode (it logs the
-    // occupied-set changes in the reference's order)
-    OccLog log{nullptr, nullptr, 0};
-    if (h->ref_field) {
-      const int rc2 = ref_field_prepare_log(h, c.Bv, log);
-      if (rc2 != TBNAV_OK) return rc2;
-    }
-    h->lk_raycast = 0; h->lk_raycast_grid = count;
-    hipLaunchKernelGGL(rbpf_raycast, dim3(count), dim3(kWave), sizeof(int) * (2 * bvn + (h->TT + 31) / 32), st, c, h->pool, M, beams_dev,
-                       sp.pose, h->d_trow[h->cur], h->d_nocc[h->cur], err, log, gp);
-  }
-  TBNAV_HIP(hipGetLastError());
-  if (nz) {
-    hipLaunchKernelGGL(rbpf_normalize, dim3(1), dim3(256), 0, st, nz->N, nz->zp, nz->weight, nz->weight_out, nz->cs, nz->parent, nz->out,
-                       nz->gate, nz->gate_prev, nz->seq, nz->seq_val, nz->children);
-    TBNAV_HIP(hipGetLastError());
-  }
-  return TBNAV_OK;
+  const int need = (h->raycast_adapt && h->h_box_need) ? *reinterpret_cast<volatile int*>(h->h_box_need) : 0;
+  RaycastPlan p = plan_raycast(RaycastIn{h->tile_cap, h->p.resolution, {h->p.Trs[0], h->p.Trs[1], h->p.Trs[2]}, c.rmax, c.Bv,
+                                         h->raycast_threads, h->raycast_adapt, h->raycast_cell16, h->raycast_band_rows, need, h->ref_field});
+  p.grid = count + (p.box() && nz ? 1 : 0);
+  h->last_raycast = p;
+  return p.box() ? launch_raycast_box(h, c, p, sens, nz, err, beams_dev) : launch_raycast_ordered(h, c, p, nz, err, beams_dev);
 }
 
 // the scan's valid beams into d_beams (shared by slam_impl and the one-particle entry points)
@@ -371,11 +313,164 @@ int upload_beams(tbnav_rbpf* h, const std::vector<double2>& beams, int n_beams, 
   return TBNAV_OK;
 }
 
+// ---- the stages of scan_enqueue, in launch order ----------------------------------------------------------------------------------------
+static int mark(tbnav_rbpf* h, int i) {   // event timing (tbnav_rbpf_set_timing): ev[i] on the handle's stream
+  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[i], h->stream));
+  return TBNAV_OK;
+}
+
+// rbpf_sample_normals for the n_norm normals of one scan into d_normals (the last is the resampling offset's).  sharded: this shard's
+// slice of the ensemble's stream, from `base`, + the ensemble's resampling offset at z_index (same on every rank); else the
+// stream's first n_norm.  n_copy beams are carried from host_beams to dev_beams on the way.
+static int launch_sample_normals(tbnav_rbpf* h, size_t n_norm, unsigned long long seed, unsigned long long scan, bool sharded, size_t base,
+                                 size_t z_index, const double2* host_beams, double2* dev_beams, int n_copy) {
+  const int blocks = (int)std::min<size_t>((n_norm / 2 + 255) / 256, 4096);
+  hipLaunchKernelGGL(rbpf_sample_normals, dim3(blocks), dim3(256), 0, h->stream, sharded ? n_norm - 1 : n_norm, seed, scan, h->d_normals,
+                     host_beams, dev_beams, n_copy, (size_t)0, (size_t)0, sharded ? base : (size_t)0, sharded ? z_index : ~(size_t)0,
+                     sharded ? n_norm - 1 : (size_t)0);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// What the hand-over of device noise needs: the offset's slot, the "table is there" words and a copy of the beam table, the last two
+// in fine-grained device memory.  false: the platform gives none — the option switches itself off for good (the stored-first form
+// computes the same values).
+static bool ensure_noise_handover(tbnav_rbpf* h) {
+  hipError_t ea = hipSuccess;
+  if (!h->d_zslot) {
+    ea = hipMalloc((void**)&h->d_zslot, sizeof(double));
+    if (ea == hipSuccess) ea = hipExtMallocWithFlags((void**)&h->d_beam_ready, sizeof(unsigned int) * kReadyCopies * kReadyStride, hipDeviceMallocFinegrained);
+    if (ea == hipSuccess) ea = hipMemsetAsync(h->d_beam_ready, 0, sizeof(unsigned int) * kReadyCopies * kReadyStride, h->stream);
+    h->beam_seq = 0;
+  }
+  if (ea == hipSuccess && h->fg_beams_cap < h->max_beams) {
+    ea = hipStreamSynchronize(h->stream);
+    (void)hipFree(h->d_beams_fg); h->d_beams_fg = nullptr; h->fg_beams_cap = 0;
+    if (ea == hipSuccess) ea = hipExtMallocWithFlags((void**)&h->d_beams_fg, sizeof(double2) * h->max_beams, hipDeviceMallocFinegrained);
+    if (ea == hipSuccess) h->fg_beams_cap = h->max_beams;
+  }
+  if (ea == hipSuccess) return true;
+  (void)hipGetLastError();
+  (void)hipFree(h->d_zslot); (void)hipFree(h->d_beam_ready); (void)hipFree(h->d_beams_fg);
+  h->d_zslot = nullptr; h->d_beam_ready = nullptr; h->d_beams_fg = nullptr; h->fg_beams_cap = 0;
+  h->noise_in_kernel = 0;
+  return false;
+}
+
+// The scan's noise, staged: where the proposal kernel gets its normals from, and the handle's record of it (last_drawn / last_normals /
+// last_z_*: tbnav_rbpf_get_normals, the normalise).  in_kernel: drawn inside the proposal kernel, whose leading workgroup also carries
+// the beam table over (src) — unless a kernel in front of it needs the table on the device (the per-particle scan matcher), the scan
+// comes prepared with its chunk (tbnav_rbpf_slam_batch), or the option is off: then `normals` is a stored stream — the caller's,
+// the batch's, or what rbpf_sample_normals stores first, as up to round 4
+// (... or the reference-field mode may have to run the proposal twice: the stored stream is there for the second run)
+struct ScanNoise { NoiseSrc src{}; const double* normals = nullptr; bool in_kernel = false; };
+static int stage_noise(tbnav_rbpf* h, const ScanC& c, const double* normals, const Prefetched* pre, int slot, ScanNoise& out) {
+  hipStream_t st = h->stream;
+  const size_t n_norm = (size_t)h->N * c.stride_normals + 1;
+  const double2* const host_beams = h->h_beams + (size_t)slot * h->max_beams;
+  const bool sharded = h->rng_n_global != 0;  // this shard's slice of the ensemble's stream + the ensemble's resampling offset
+  const size_t base = sharded ? (size_t)h->rng_first * c.stride_normals : 0;
+  const size_t z_index = sharded ? (size_t)h->rng_n_global * c.stride_normals : (size_t)h->N * c.stride_normals;
+  bool dn = !pre && !normals && !(h->sm_on && c.icp_ok) && h->noise_in_kernel == 1 && !h->ref_field;
+  if (dn) dn = ensure_noise_handover(h);
+  h->last_drawn.valid = false;
+  if (dn) {
+    if (++h->beam_seq == 0u) ++h->beam_seq;   // (0 is the cleared word)
+    out.src = NoiseSrc{h->seed, h->scan_index, base, z_index, h->d_zslot, host_beams, h->d_beams, h->d_beams_fg, h->d_beam_ready, h->beam_seq};
+    h->last_drawn.seed = h->seed; h->last_drawn.scan = h->scan_index; h->last_drawn.base = base; h->last_drawn.z_index = z_index;
+    h->last_drawn.n = n_norm; h->last_drawn.valid = true;
+  } else if (!pre) {   // (a prepared scan's were drawn with the rest of its chunk)
+    if (n_norm > h->normals_cap) {
+      TBNAV_HIP(hipStreamSynchronize(st));  // (a scan still in flight reads the old buffer)
+      (void)hipFree(h->d_normals);
+      h->d_normals = nullptr;
+      TBNAV_HIP(hipMalloc((void**)&h->d_normals, sizeof(double) * n_norm));
+      h->normals_cap = n_norm;
+    }
+    if (normals) TBNAV_HIP(hipMemcpyAsync(h->d_normals, normals, sizeof(double) * n_norm, hipMemcpyHostToDevice, st));
+    else TBNAV_TRY(launch_sample_normals(h, n_norm, h->seed, h->scan_index, sharded, base, z_index, host_beams, h->d_beams, c.Bv));
+  }
+  ++h->scan_index;
+  out.in_kernel = dn;
+  out.normals = dn ? nullptr : (pre ? pre->d_normals : h->d_normals);
+  h->last_normals = out.normals;
+  h->last_z_index = (size_t)h->N * c.stride_normals;
+  h->last_z_ptr = dn ? h->d_zslot : out.normals + h->last_z_index;
+  return TBNAV_OK;
+}
+
+// Distance-field refresh for this call's lookups, windowed (the stored-field modes; query mode needs neither windows nor skip
+// flags: the proposal kernel reads the field state itself)
+static int refresh_fields(tbnav_rbpf* h, const ScanC& c, const double u[3], const double T_icp[3], double spread, bool matching) {
+  if (h->df_mode == 2) return TBNAV_OK;
+  const int half_cells = lookup_half_cells((double)h->p.range_max, h->p.Trs, T_icp, u, spread, matching ? h->sm.max_moves * h->sm.lstep : 0.0,
+                                           h->p.resolution, h->full_edt, h->xsize);
+  hipLaunchKernelGGL(rbpf_window, dim3((h->N + 255) / 256), dim3(256), 0, h->stream, c.g, h->N, half_cells, h->df_mode == 1 ? 1 : 0,
+                     state_ptrs(h->d_state[h->cur], h->N).pose, h->d_fstate, h->d_skip, h->d_win);
+  TBNAV_HIP(hipGetLastError());
+  if (h->df_mode != 1) return TBNAV_OK;
+  const int tiles = std::min((2 * half_cells + 1 + kWave - 1) / kWave + 1, (h->ysize + kWave - 1) / kWave);
+  return run_distance_field(h, c.g, 0, h->N, tiles);
+}
+
+// which particles' lookups go to the stored field: skip[p] == eq (query mode reads the field state itself)
+struct SkipRule { const int* arr; int eq; };
+static SkipRule skip_rule(const tbnav_rbpf* h) { return h->df_mode == 2 ? SkipRule{h->d_fstate, 2} : SkipRule{h->d_skip, 1}; }
+
+// N1 option: every particle refines T(pose) * T_icp against its own map first; the samples are drawn round that (d_center)
+static int launch_scanmatch(tbnav_rbpf* h, const ScanC& c, const ProposePlan& pp, const double2* beams_dev, int* d_err, const int* gate_prev) {
+  const SkipRule sk = skip_rule(h);
+  hipLaunchKernelGGL(rbpf_scanmatch, dim3(h->N), dim3(kMatchThreads), pp.sm_lds, h->stream, c, h->sm, beams_dev, h->d_code[h->cur],
+                     h->pool, map_of(h), h->d_trow[h->cur], sk.arr, sk.eq, h->df_mode, h->radius, pp.occ_half,
+                     h->d_nocc[h->cur], h->d_win, state_ptrs(h->d_state[h->cur], h->N).pose, h->d_center, h->d_score, d_err, gate_prev, h->d_mixlut);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// the proposal, in the form the plan names (center: the matcher's poses, or NULL)
+static int launch_propose(tbnav_rbpf* h, const ScanC& c, const ProposePlan& pp, const ScanNoise& nz, const double2* beams_dev, const double* center,
+                          int* d_err, const int* gate_prev) {
+  const SkipRule sk = skip_rule(h);
+  const StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
+  int* const pend = h->ref_field ? h->d_pend : nullptr;
+  h->last_propose = pp;
+#define TBNAV_X(NT_, DN_)                                                                                                                        \
+  if (pp.threads == NT_ && pp.dn == DN_) {                                                                                                       \
+    hipLaunchKernelGGL((rbpf_propose<NT_, DN_>), dim3(h->N + (DN_ ? 1 : 0)), dim3(NT_), pp.lds, h->stream, c, beams_dev, h->d_code[h->cur],      \
+                       h->pool, map_of(h), h->d_trow[h->cur], sk.arr, sk.eq, h->df_mode, h->radius, pp.occ_half, h->d_nocc[h->cur], h->d_win,    \
+                       nz.normals, center, sp.pose, sp.prev, sp.weight, h->tr, h->d_sens, d_err, gate_prev, h->d_mixlut, nz.src, pend);          \
+    TBNAV_HIP(hipGetLastError());                                                                                                                \
+    return TBNAV_OK;                                                                                                                             \
+  }
+  TBNAV_PROPOSE_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have)
+}
+
+// legacy placement (TBNAV_RBPF_FULL_EDT=1): whole field of every particle right after the map update,
+// where the reference runs its brushfire (grid_mapper.cpp:181)
+static int place_full_fields(tbnav_rbpf* h, const ScanC& c) {
+  TBNAV_HIP(hipMemsetAsync(h->d_skip, 0, sizeof(int) * h->N, h->stream));
+  return run_distance_field(h, c.g, 0, h->N, (h->ysize + kWave - 1) / kWave);
+}
+
+// the map changed: every field is stale until the next refresh (whole-map mode: fresh everywhere).  In query mode
+// the states are all zero already unless a field was injected or materialised since the last call.
+static int mark_fields_stale(tbnav_rbpf* h) {
+  if (h->full_edt) {
+    TBNAV_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_fstate, 2, h->N, h->stream));
+    h->fstate_dirty = true;
+  } else if (h->fstate_dirty || h->df_mode != 2) {
+    TBNAV_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_fstate, 0, h->N, h->stream));
+    h->fstate_dirty = h->df_mode != 2;
+  }
+  return TBNAV_OK;
+}
+
 int scan_enqueue(tbnav_rbpf* h, const float* scan, int n_beams, const double u[3], const double cur_odom[3],
                  const double prev_odom[3], int icp_ok, const double T_icp[3], const double* normals,
                  tbnav_rbpf_stats* out, bool local_only, int slot, const int* gate_prev, ScanTicket& tk,
                  const Prefetched* pre, hipEvent_t weights_ready) {
-  hipStream_t st = h->stream;
   int* const d_err = h->d_err + 4 * slot;
   int* const h_err = h->h_err + 4 * slot;
   ++h->scans_done;
@@ -388,212 +483,51 @@ int scan_enqueue(tbnav_rbpf* h, const float* scan, int n_beams, const double u[3
   if (rc != TBNAV_OK) { out->status = rc; return rc; }
   out->n_valid_beams = c.Bv;
   tk.slot = slot; tk.n_valid = c.Bv; tk.local_only = local_only;
-  if (!pre) {
-    rc = upload_beams(h, beams, n_beams, c.Bv, /*stage_only=*/normals == nullptr, slot);  // device noise: the noise kernel carries the beams over
-    if (rc != TBNAV_OK) return rc;
-  }
-  const size_t n_norm = (size_t)h->N * c.stride_normals + 1;
-  // device noise: drawn inside the proposal kernel, whose leading workgroup also carries the beam table over (NoiseSrc) — unless a
-  // kernel in front of it needs the table on the device (the per-particle scan matcher), the scan comes prepared with its chunk
-  // (tbnav_rbpf_slam_batch), or the option is off: then rbpf_sample_normals stores the same values first, as up to round 4
-  // (... or the reference-field mode may have to run the proposal twice: the stored stream is there for the second run)
-  bool dn = !pre && !normals && !(h->sm_on && c.icp_ok) && h->noise_in_kernel == 1 && !h->ref_field;
-  NoiseSrc ns{};
-  if (dn) {
-    // (the hand-over needs fine-grained device memory: where the platform does not give any, the option switches itself off for good —
-    //  the stored-first form computes the same values)
-    hipError_t ea = hipSuccess;
-    if (!h->d_zslot) {
-      ea = hipMalloc((void**)&h->d_zslot, sizeof(double));
-      if (ea == hipSuccess) ea = hipExtMallocWithFlags((void**)&h->d_beam_ready, sizeof(unsigned int) * kReadyCopies * kReadyStride, hipDeviceMallocFinegrained);
-      if (ea == hipSuccess) ea = hipMemsetAsync(h->d_beam_ready, 0, sizeof(unsigned int) * kReadyCopies * kReadyStride, st);
-      h->beam_seq = 0;
-    }
-    if (ea == hipSuccess && h->fg_beams_cap < h->max_beams) {
-      ea = hipStreamSynchronize(st);
-      (void)hipFree(h->d_beams_fg); h->d_beams_fg = nullptr; h->fg_beams_cap = 0;
-      if (ea == hipSuccess) ea = hipExtMallocWithFlags((void**)&h->d_beams_fg, sizeof(double2) * h->max_beams, hipDeviceMallocFinegrained);
-      if (ea == hipSuccess) h->fg_beams_cap = h->max_beams;
-    }
-    if (ea != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(h->d_zslot); (void)hipFree(h->d_beam_ready); (void)hipFree(h->d_beams_fg);
-      h->d_zslot = nullptr; h->d_beam_ready = nullptr; h->d_beams_fg = nullptr; h->fg_beams_cap = 0;
-      h->noise_in_kernel = 0;
-      dn = false;
-    }
-  }
-  if (dn) {
-    if (++h->beam_seq == 0u) ++h->beam_seq;   // (0 is the cleared word)
-    ns.seed = h->seed; ns.scan = h->scan_index;
-    ns.base = h->rng_n_global ? (size_t)h->rng_first * c.stride_normals : 0;
-    ns.z_index = h->rng_n_global ? (size_t)h->rng_n_global * c.stride_normals : (size_t)h->N * c.stride_normals;
-    ns.z_out = h->d_zslot;
-    ns.host_beams = (const double2*)(h->h_beams + (size_t)slot * h->max_beams); ns.dev_beams = h->d_beams; ns.fg_beams = h->d_beams_fg;
-    ns.ready = h->d_beam_ready; ns.seq = h->beam_seq;
-  }
-  h->last_drawn.valid = false;
-  if (dn) {
-    h->last_drawn.seed = ns.seed; h->last_drawn.scan = ns.scan; h->last_drawn.base = ns.base; h->last_drawn.z_index = ns.z_index;
-    h->last_drawn.n = n_norm; h->last_drawn.valid = true;
-  } else {
-  if (!pre && n_norm > h->normals_cap) {
-    TBNAV_HIP(hipStreamSynchronize(st));  // (a scan still in flight reads the old buffer)
-    (void)hipFree(h->d_normals);
-    h->d_normals = nullptr;
-    TBNAV_HIP(hipMalloc((void**)&h->d_normals, sizeof(double) * n_norm));
-    h->normals_cap = n_norm;
-  }
-  if (pre) {
-    // (drawn with the rest of its chunk)
-  } else if (normals) {
-    TBNAV_HIP(hipMemcpyAsync(h->d_normals, normals, sizeof(double) * n_norm, hipMemcpyHostToDevice, st));
-  } else {
-    const int blocks = (int)std::min<size_t>((n_norm / 2 + 255) / 256, 4096);
-    if (h->rng_n_global)  // this shard's slice of the ensemble's stream + the ensemble's resampling offset (same on every rank)
-      hipLaunchKernelGGL(rbpf_sample_normals, dim3(blocks), dim3(256), 0, st, n_norm - 1, (unsigned long long)h->seed,
-                         (unsigned long long)h->scan_index, h->d_normals, (const double2*)(h->h_beams + (size_t)slot * h->max_beams), h->d_beams, c.Bv,
-                         (size_t)0, (size_t)0, (size_t)h->rng_first * c.stride_normals, (size_t)h->rng_n_global * c.stride_normals, n_norm - 1);
-    else
-    hipLaunchKernelGGL(rbpf_sample_normals, dim3(blocks), dim3(256), 0, st, n_norm, (unsigned long long)h->seed,
-                       (unsigned long long)h->scan_index, h->d_normals, (const double2*)(h->h_beams + (size_t)slot * h->max_beams), h->d_beams, c.Bv);
-    TBNAV_HIP(hipGetLastError());
-  }
-  }
-  ++h->scan_index;
+  // (device noise: the noise kernel carries the beams over)
+  if (!pre) TBNAV_TRY(upload_beams(h, beams, n_beams, c.Bv, /*stage_only=*/normals == nullptr, slot));
+  ScanNoise noise;
+  TBNAV_TRY(stage_noise(h, c, normals, pre, slot, noise));
   const double2* const beams_dev = pre ? pre->d_beams : h->d_beams;
-  const double* const normals_dev = dn ? nullptr : (pre ? pre->d_normals : h->d_normals);
-  h->last_normals = normals_dev;
-  h->last_z_index = (size_t)h->N * c.stride_normals;
-  h->last_z_ptr = dn ? h->d_zslot : normals_dev + h->last_z_index;
   for (int q = 0; q < 4; ++q) h_err[q] = 0;  // mapped: the scan that last owned the slot has been waited for
   h->h_norm[slot] = NormOut{};
-  StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
+  const bool matching = h->sm_on && c.icp_ok;
+  const double spread = sampling_spread(h->p.sample_range, h->p.motion_noise);
+  ProposePlan pp = plan_propose(ProposeIn{h->k, c.Bv, h->df_mode, h->xsize, h->words, (double)h->p.range_max, spread, h->p.resolution});
+  pp.dn = noise.in_kernel;
 
   // ---- distance-field refresh for this call's lookups (windowed), then the particle update
   if (h->ref_field) { rc = ref_field_before_propose(h); if (rc != TBNAV_OK) { out->status = rc; return rc; } }
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[0], st));
-  {
-    // every lookup of this call lies within `half` metres of the particle's CURRENT position: the sampled poses
-    // sit at T(pose)*T_icp (or the motion-model pose) +- the sampling noise, the laser at |Trs| from them, and
-    // a valid beam ends less than range_max from the laser.  With the scan matcher on, the samples sit round the MATCHED
-    // pose and the matcher's own trial poses look cells up too: a trial pose of round r is at most (r + 1) * lstep from
-    // T(pose)*T_icp and r < max_moves, so its travel is bounded by max_moves * lstep (3.2 m with the default step)
-    double sig = 0.0;
-    for (int q = 1; q < 3; ++q) sig = std::max(sig, std::max(h->p.sample_range[q], h->p.motion_noise[q]));
-    const double move = std::max(std::hypot(T_icp[1], T_icp[2]), std::fabs(u[1]));
-    double half = (double)h->p.range_max + std::hypot(h->p.Trs[1], h->p.Trs[2]) + move + 8.0 * std::sqrt(sig);
-    if (h->sm_on && c.icp_ok) half += h->sm.max_moves * h->sm.lstep;
-    int half_cells = (int)std::ceil(half / h->p.resolution) + 3;
-    if (h->full_edt || half_cells > h->xsize) half_cells = h->xsize;  // whole map
-    if (h->df_mode != 2) {  // query mode needs neither windows nor skip flags: the proposal kernel reads the field state itself
-      hipLaunchKernelGGL(rbpf_window, dim3((h->N + 255) / 256), dim3(256), 0, st, c.g, h->N, half_cells, h->df_mode == 1 ? 1 : 0,
-                         sp.pose, h->d_fstate, h->d_skip, h->d_win);
-      TBNAV_HIP(hipGetLastError());
-    }
-    if (h->df_mode == 1) {
-      const int tiles = std::min((2 * half_cells + 1 + kWave - 1) / kWave + 1, (h->ysize + kWave - 1) / kWave);
-      rc = run_distance_field(h, c.g, 0, h->N, tiles);
-      if (rc != TBNAV_OK) return rc;
-    }
-  }
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[1], st));
-  size_t propose_lds = sizeof(double) * ((12 + kUnCap) * h->k + 3 * (c.Bv > 0 ? c.Bv : 1)) + sizeof(unsigned int) * 4 * (c.Bv > 0 ? c.Bv : 1);
-  const size_t propose_lds_base = propose_lds;  // (what follows adds the LDS slice of the occupancy bitmap)
-  int occ_half = 0;
-  if (h->df_mode == 2) {
-    // LDS copy of the occupancy bitmap round each particle's sensor: reach of a lookup (range_max + sampling
-    // spread) plus a margin for the walk to the nearest obstacle; shrunk, then dropped, if it would not fit
-    double sig = 0.0;
-    for (int q = 1; q < 3; ++q) sig = std::max(sig, std::max(h->p.sample_range[q], h->p.motion_noise[q]));
-    const int reach = (int)std::ceil(((double)h->p.range_max + 8.0 * std::sqrt(sig)) / h->p.resolution) + 2;
-    for (int margin : {48, 16, 0}) {
-      const int half = reach + margin;
-      const int rows = std::min(h->xsize, 2 * half + 1), nw = std::min(h->words, (2 * half + 1 + 63) / 64 + 1);
-      const size_t bytes = (size_t)rows * nw * 8 + (size_t)rows * 4;
-      if (bytes <= 48 * 1024) { occ_half = half; propose_lds += bytes; break; }
-    }
-  }
-  if (propose_lds > (size_t)kMaxLds - 3072) return TBNAV_ERR_UNSUPPORTED;  // scan x samples too large for one workgroup's LDS
-  const int* skip_arr = h->df_mode == 2 ? h->d_fstate : h->d_skip;
-  const int skip_eq = h->df_mode == 2 ? 2 : 1;
-  const double* center = nullptr;
-  if (h->sm_on && c.icp_ok) {
-    // N1 option: every particle refines T(pose) * T_icp against its own map first; the samples are drawn round that
-    const size_t sm_lds = sizeof(double2) * (c.Bv > 0 ? c.Bv : 1) + sizeof(double) * kMixLut + sizeof(unsigned long long) * 4 * (c.Bv > 0 ? c.Bv : 1) +
-                          (propose_lds - propose_lds_base);
-    hipLaunchKernelGGL(rbpf_scanmatch, dim3(h->N), dim3(kMatchThreads), sm_lds, st, c, h->sm, beams_dev, h->d_code[h->cur],
-                       h->pool, map_of(h), h->d_trow[h->cur], skip_arr, skip_eq, h->df_mode, h->radius, occ_half,
-                       h->d_nocc[h->cur], h->d_win, sp.pose, h->d_center, h->d_score, d_err, gate_prev, h->d_mixlut);
-    TBNAV_HIP(hipGetLastError());
-    center = h->d_center;
-  }
-  // workgroup size: four waves when four workgroups fit a CU's LDS (the 360-beam scans: 38 KB each), eight when the scan's
-  // tables leave room for two or three only (1080 beams: 58 KB) — measured: 360 beams 32 us per 1000 particles with 256
-  // threads against 43 with 512; the configs[4] shard 0.80 ms with 256 against 0.61 with 512
-  h->lk_propose = (propose_lds + 3072 > (size_t)kMaxLds / 4) ? 2 * kProposeThreads : kProposeThreads;
-  h->lk_propose_dn = dn ? 1 : 0;
-  int* const pend = h->ref_field ? h->d_pend : nullptr;
-#define TBNAV_PROPOSE(NT_, DN_) hipLaunchKernelGGL((rbpf_propose<NT_, DN_>), dim3(h->N + (DN_ ? 1 : 0)), dim3(NT_), propose_lds, st, c, beams_dev,                    \
-                     h->d_code[h->cur], h->pool, map_of(h), h->d_trow[h->cur], skip_arr, skip_eq, h->df_mode, h->radius, occ_half,                       \
-                     h->d_nocc[h->cur], h->d_win, normals_dev, center, sp.pose, sp.prev, sp.weight, h->tr, h->d_sens, d_err, gate_prev, h->d_mixlut, ns, pend)
-  auto launch_propose = [&]() -> int {
-    if (propose_lds + 3072 > (size_t)kMaxLds / 4) { if (dn) TBNAV_PROPOSE(2 * kProposeThreads, true); else TBNAV_PROPOSE(2 * kProposeThreads, false); }
-    else { if (dn) TBNAV_PROPOSE(kProposeThreads, true); else TBNAV_PROPOSE(kProposeThreads, false); }
-    TBNAV_HIP(hipGetLastError());
-    return TBNAV_OK;
-  };
-#undef TBNAV_PROPOSE
-  rc = launch_propose();
-  if (rc != TBNAV_OK) return rc;
+  TBNAV_TRY(mark(h, 0));
+  TBNAV_TRY(refresh_fields(h, c, u, T_icp, spread, matching));
+  TBNAV_TRY(mark(h, 1));
+  if (!pp.fits) return TBNAV_ERR_UNSUPPORTED;  // scan x samples too large for one workgroup's LDS
+  if (matching) TBNAV_TRY(launch_scanmatch(h, c, pp, beams_dev, d_err, gate_prev));
+  const double* const center = matching ? h->d_center : nullptr;
+  TBNAV_TRY(launch_propose(h, c, pp, noise, beams_dev, center, d_err, gate_prev));
   if (h->ref_field) {  // lookups that met cells the lazy brushfire has not written: resume those states, run the proposal again
-    rc = ref_field_settle(h, h_err, launch_propose);
+    rc = ref_field_settle(h, h_err, [&]() { return launch_propose(h, c, pp, noise, beams_dev, center, d_err, gate_prev); });
     if (rc != TBNAV_OK) { out->status = rc; return rc; }
   }
-  if (weights_ready) TBNAV_HIP(hipEventRecord(weights_ready, st));  // (sharded filter: the exchange starts here, beside the map update)
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[2], st));
+  if (weights_ready) TBNAV_HIP(hipEventRecord(weights_ready, h->stream));  // (sharded filter: the exchange starts here, beside the map update)
+  TBNAV_TRY(mark(h, 2));
   // normalise / select needs only the weights the proposal kernel left: it rides in the map update's launch as one extra
   // workgroup (the chain of adds it is made of would otherwise sit on the critical path, and a second stream costs an
   // event and a dependent boundary).  With event timing on it is a launch of its own, so that the intervals mean what
   // they say.
-  const double* z_norm = h->last_z_ptr;
   tk.seq = (unsigned int)h->scans_done;
-  const NormArgs nz{h->N, z_norm, sp.weight, sp.weight, h->d_cs, h->d_parent, h->d_norm + slot, h->d_gate + slot, gate_prev,
+  double* const weight = state_ptrs(h->d_state[h->cur], h->N).weight;
+  const NormArgs nz{h->N, h->last_z_ptr, weight, weight, h->d_cs, h->d_parent, h->d_norm + slot, h->d_gate + slot, gate_prev,
                     tk.poll ? h->d_seq + slot : nullptr, tk.seq, h->d_parent + h->N};
-  auto launch_normalize = [&](hipStream_t s2) -> int {
-    hipLaunchKernelGGL(rbpf_normalize, dim3(1), dim3(256), 0, s2, h->N, z_norm, sp.weight, sp.weight, h->d_cs, h->d_parent, h->d_norm + slot,
-                       nullptr, nullptr, nullptr, 0u, h->d_parent + h->N);
-    TBNAV_HIP(hipGetLastError());
-    return TBNAV_OK;
-  };
   const bool overlap = !local_only && !h->timing;
   if ((gate_prev || tk.poll) && !overlap) return TBNAV_ERR_INVALID_ARG;  // (a gated or polled scan is a batch scan: never local-only or timed)
-  rc = launch_raycast(h, c, h->N, h->d_sens, overlap ? &nz : nullptr, d_err, beams_dev);
-  if (rc != TBNAV_OK) return rc;
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[3], st));
-  if (h->full_edt) {
-    // legacy placement (TBNAV_RBPF_FULL_EDT=1): whole field of every particle right after the map update,
-    // where the reference runs its brushfire (grid_mapper.cpp:181)
-    TBNAV_HIP(hipMemsetAsync(h->d_skip, 0, sizeof(int) * h->N, st));
-    rc = run_distance_field(h, c.g, 0, h->N, (h->ysize + kWave - 1) / kWave);
-    if (rc != TBNAV_OK) return rc;
-  }
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[4], st));
-  if (!local_only && !overlap) {
-    rc = launch_normalize(st);
-    if (rc != TBNAV_OK) return rc;
-  }
-  if (h->timing) TBNAV_HIP(hipEventRecord(h->ev[5], st));
-  // the map changed: every field is stale until the next refresh (whole-map mode: fresh everywhere).  In query mode
-  // the states are all zero already unless a field was injected or materialised since the last call.
-  if (h->full_edt) {
-    TBNAV_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_fstate, 2, h->N, st));
-    h->fstate_dirty = true;
-  } else if (h->fstate_dirty || h->df_mode != 2) {
-    TBNAV_HIP(hipMemsetD32Async((hipDeviceptr_t)h->d_fstate, 0, h->N, st));
-    h->fstate_dirty = h->df_mode != 2;
-  }
-  return TBNAV_OK;
+  TBNAV_TRY(launch_raycast(h, c, h->N, h->d_sens, overlap ? &nz : nullptr, d_err, beams_dev));
+  TBNAV_TRY(mark(h, 3));
+  if (h->full_edt) TBNAV_TRY(place_full_fields(h, c));
+  TBNAV_TRY(mark(h, 4));
+  if (!local_only && !overlap)   // (no gate, no flag: see above)
+    TBNAV_TRY(launch_normalize(h, NormArgs{nz.N, nz.zp, nz.weight, nz.weight_out, nz.cs, nz.parent, nz.out, nullptr, nullptr, nullptr, 0u, nz.children}));
+  TBNAV_TRY(mark(h, 5));
+  return mark_fields_stale(h);
 }
 
 int scan_finish(tbnav_rbpf* h, const ScanTicket& tk, tbnav_rbpf_stats* out) {
@@ -706,6 +640,163 @@ int pool_free_tiles(tbnav_rbpf* h, uint64_t* free_tiles) {
   *free_tiles = f;
   return TBNAV_OK;
 }
+// ---- create, in stages: each goes on only while `e` is hipSuccess and leaves the first failure in it ---------------------------------------
+static void dev_alloc(hipError_t& e, void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); }
+#define TBNAV_A(ptr, bytes) dev_alloc(e, (void**)&(ptr), (bytes))
+
+static void create_buffers(tbnav_rbpf* h, hipError_t& e) {
+  const int N = h->N;
+  const size_t table_entries = (size_t)N * h->TT;
+  for (int b = 0; b < 2; ++b) {
+    TBNAV_A(h->d_state[b], sizeof(double) * 7 * N);
+    TBNAV_A(h->d_table[b], sizeof(unsigned int) * table_entries);
+    TBNAV_A(h->d_nocc[b], sizeof(int) * N);
+    TBNAV_A(h->d_trow[b], sizeof(int) * (size_t)N * h->TW);
+  }
+  TBNAV_A(h->d_shed, sizeof(unsigned int) * table_entries);
+  TBNAV_A(h->d_cs, sizeof(double) * N);
+  TBNAV_A(h->d_sens, sizeof(double) * 4 * N);
+  TBNAV_A(h->d_tile_scratch, sizeof(unsigned int) * h->TT);
+  TBNAV_A(h->d_touched, sizeof(unsigned long long) * 2);
+  TBNAV_A(h->d_box_need, sizeof(int) * 3);
+  TBNAV_A(h->d_parent, sizeof(int) * 2 * N);
+  TBNAV_A(h->d_best, sizeof(int));
+  TBNAV_A(h->d_best_pose, sizeof(double) * 3);
+  TBNAV_A(h->d_export, h->G);
+  TBNAV_A(h->d_fstate, sizeof(int) * N);
+  TBNAV_A(h->d_fstate_alt, sizeof(int) * N);
+  TBNAV_A(h->d_center, sizeof(double) * 3 * N);
+  TBNAV_A(h->d_score, sizeof(double) * N);
+  TBNAV_A(h->d_skip, sizeof(int) * N);
+  TBNAV_A(h->d_win, sizeof(int4) * N);
+  TBNAV_A(h->d_tier, sizeof(int) * N);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_err, sizeof(int) * 4 * kScanSlots, hipHostMallocMapped);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_norm, sizeof(NormOut) * kScanSlots, hipHostMallocMapped);
+  if (e == hipSuccess) { std::memset(h->h_err, 0, sizeof(int) * 4 * kScanSlots); std::memset((void*)h->h_norm, 0, sizeof(NormOut) * kScanSlots); }
+  TBNAV_A(h->d_gate, sizeof(int) * kScanSlots);
+  if (e == hipSuccess) e = hipMemset(h->d_gate, 0, sizeof(int) * kScanSlots);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_seq, sizeof(unsigned int) * kScanSlots, hipHostMallocMapped);
+  if (e == hipSuccess) { std::memset(h->h_seq, 0, sizeof(unsigned int) * kScanSlots); e = hipHostGetDevicePointer((void**)&h->d_seq, h->h_seq, 0); }
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_err, h->h_err, 0);
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_norm, h->h_norm, 0);
+  // the proposal's trace: sampled, p_scan, p_pose, mu, sigma, eta, new_pose, weight_raw, back to back
+  const size_t kk = (size_t)h->k;
+  const size_t trace_doubles = (size_t)N * (kk * 3 + kk + kk + 3 + 9 + 1 + 3 + 1);
+  TBNAV_A(h->d_trace, sizeof(double) * trace_doubles);
+  if (e == hipSuccess) {
+    double* t = h->d_trace;
+    h->tr.sampled = t; t += (size_t)N * kk * 3;
+    h->tr.p_scan = t; t += (size_t)N * kk;
+    h->tr.p_pose = t; t += (size_t)N * kk;
+    h->tr.mu = t; t += (size_t)N * 3;
+    h->tr.sigma = t; t += (size_t)N * 9;
+    h->tr.eta = t; t += (size_t)N;
+    h->tr.new_pose = t; t += (size_t)N * 3;
+    h->tr.weight_raw = t;
+    e = hipMemset(h->d_trace, 0, sizeof(double) * trace_doubles);
+  }
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  for (auto& ev : h->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
+}
+
+// the tile pool: everything the particles' maps can ever need if that fits the budget, else the budget.
+// Default budget: half of the memory that is free now (several handles can live side by side).
+static void create_pool(tbnav_rbpf* h, uint64_t max_pool_bytes, hipError_t& e) {
+  if (e != hipSuccess) return;
+  size_t free_b = 0, total_b = 0;
+  e = hipMemGetInfo(&free_b, &total_b);
+  const size_t per_tile = sizeof(double) * kTileCells + sizeof(unsigned int) * kTS + sizeof(int) + sizeof(unsigned int);
+  const size_t budget = max_pool_bytes ? (size_t)max_pool_bytes : free_b / 2;
+  // worst case: every table entry its own tile, plus the tiles the entries left since the last resample (still named by
+  // the shed notes until the next resample settles them), plus the zero tile
+  size_t cap = 2 * (size_t)h->N * h->TT + 1;
+  if (cap * per_tile > budget) cap = budget / per_tile;
+  if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
+  if (cap < (size_t)h->N + 2 && e == hipSuccess) e = hipErrorOutOfMemory;  // not even one tile per particle
+  h->pool.cap = (unsigned int)cap;
+  h->pool.shards = pool_lists_for(cap);
+  h->pool.shard_cap = (unsigned int)((cap + h->pool.shards - 1) / h->pool.shards);
+  TBNAV_A(h->pool.lo, sizeof(double) * kTileCells * cap);
+  TBNAV_A(h->pool.bm, sizeof(unsigned int) * kTS * cap);
+  TBNAV_A(h->pool.ref, sizeof(int) * cap);
+  TBNAV_A(h->pool.ring, sizeof(unsigned int) * (size_t)h->pool.shard_cap * h->pool.shards);
+  TBNAV_A(h->pool.ctr, sizeof(unsigned long long) * kPoolCtrWords);
+}
+
+// initParticleSet, particle_filter.cpp:125-138, and empty maps
+static void create_state(tbnav_rbpf* h, hipError_t& e) {
+  if (e != hipSuccess) return;
+  const int N = h->N;
+  const size_t table_entries = (size_t)N * h->TT;
+  std::vector<double> s((size_t)7 * N);
+  for (int i = 0; i < N; ++i) {
+    for (int q = 0; q < 3; ++q) { s[(size_t)i * 3 + q] = h->p.pose0[q]; s[(size_t)3 * N + i * 3 + q] = h->p.pose0[q]; }
+    s[(size_t)6 * N + i] = 1.0 / N;
+  }
+  e = hipMemcpy(h->d_state[0], s.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice);
+  // empty maps: every table entry names the shared zero tile (log_odds_prior_ = log(1) = 0)
+  if (e == hipSuccess) e = hipMemset(h->d_table[0], 0, sizeof(unsigned int) * table_entries);
+  if (e == hipSuccess) e = hipMemset(h->d_shed, 0, sizeof(unsigned int) * table_entries);
+  if (e == hipSuccess) e = hipMemset(h->pool.lo, 0, sizeof(double) * kTileCells);  // tile 0
+  if (e == hipSuccess) e = hipMemset(h->pool.ref, 0, sizeof(int) * h->pool.cap);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rbpf_pool_init, dim3(1024), dim3(256), 0, h->stream, h->pool);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemset(h->d_touched, 0, sizeof(unsigned long long) * 2);
+  if (e == hipSuccess) {  // the queue's scratch memory, before the first map update that needs it (see the kernel)
+    hipLaunchKernelGGL(rbpf_warm_scratch, dim3(1024), dim3(512), 0, h->stream, reinterpret_cast<int*>(h->d_touched), 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemset(h->d_box_need, 0, sizeof(int) * 3);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_box_need, sizeof(int), hipHostMallocMapped);
+  if (e == hipSuccess) { *h->h_box_need = 0; e = hipHostGetDevicePointer((void**)&h->d_box_need_host, h->h_box_need, 0); }
+  if (e == hipSuccess) e = hipMemset(h->d_nocc[0], 0, sizeof(int) * N);
+  if (e == hipSuccess) e = hipMemset(h->d_skip, 0, sizeof(int) * N);
+  if (e == hipSuccess) e = hipMemset(h->d_tier, 0xFF, sizeof(int) * N);  // -1: no transform launch has covered the particle yet (tbnav_rbpf_last_field_kernels)
+  // empty maps: the field "everything unreached" is what any lookup computes, no stored field needed (state 0)
+  if (e == hipSuccess) e = hipMemset(h->d_fstate, 0, sizeof(int) * N);
+  if (e == hipSuccess) e = hipMemset(h->d_fstate_alt, 0, sizeof(int) * N);
+  h->fstate_dirty = false;
+  if (e == hipSuccess) {
+    std::vector<int4> w(N, make_int4(0, h->xsize - 1, 0, h->ysize - 1));
+    e = hipMemcpy(h->d_win, w.data(), sizeof(int4) * N, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = hipMemset(h->d_trow[0], 0, sizeof(int) * (size_t)N * h->TW);
+  if (e == hipSuccess) e = hipMemset(h->pool.bm, 0, sizeof(unsigned int) * kTS);  // tile 0
+}
+
+// dynamic LDS beyond the 64 KB default, for every kernel form that can be launched with it (the forms: rbpf_device.hpp's lists)
+static void create_lds_attributes(tbnav_rbpf* h, hipError_t& e) {
+  auto lds = [&e](const void* kernel, size_t bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+  if (h->edt_cols == 64) lds(reinterpret_cast<const void*>(&rbpf_edt<64>), edt_lds_bytes(h->xsize, h->words, 64));
+  if (h->edt_cols == 32) lds(reinterpret_cast<const void*>(&rbpf_edt<32>), edt_lds_bytes(h->xsize, h->words, 32));
+  // (2.3 KB of static LDS: the embedded normalise's scan scratch)
+#define TBNAV_X(NT_, WPS_, C16_, EV_) lds(reinterpret_cast<const void*>(&rbpf_raycast_box<NT_, WPS_, C16_, EV_>), kMaxLds - 4096);
+  TBNAV_RAYCAST_BOX_FORMS(TBNAV_X)
+#undef TBNAV_X
+  lds(reinterpret_cast<const void*>(&rbpf_raycast), kMaxLds - 1024);
+  // the proposal / scan-match kernels carry the scan, the per-sample data and the bitmap slice: more than the 64 KB
+  // default for long scans or many samples
+#define TBNAV_X(NT_, DN_) lds(reinterpret_cast<const void*>(&rbpf_propose<NT_, DN_>), kMaxLds - 3072);   /* (2.3 KB static) */
+  TBNAV_PROPOSE_FORMS(TBNAV_X)
+#undef TBNAV_X
+  lds(reinterpret_cast<const void*>(&rbpf_scanmatch), kMaxLds - 1024);
+  lds(reinterpret_cast<const void*>(&rbpf_edt_compact<kEdtRowsA>), edt_compact_lds(kEdtRowsA));
+  lds(reinterpret_cast<const void*>(&rbpf_edt_compact<kEdtRowsB>), edt_compact_lds(kEdtRowsB));
+}
+
+// the beam mixture term per distance code: constants of the handle, tabulated once
+static void create_mix_lut(tbnav_rbpf* h, hipError_t& e) {
+  TBNAV_A(h->d_mixlut, sizeof(double) * kMixLut);
+  ScanC cm{};
+  if (e == hipSuccess && mixture_consts(h, cm)) {  // (a zero variance is reported by the first scan, as the reference throws there)
+    hipLaunchKernelGGL(rbpf_mix_lut, dim3(kMixLut / 256), dim3(256), 0, h->stream, cm, h->d_mixlut);
+    e = hipGetLastError();
+  }
+}
+#undef TBNAV_A
+
 int create_impl(const tbnav_rbpf_params* P, uint64_t max_pool_bytes, tbnav_rbpf** out) {
   if (!P || !out) return TBNAV_ERR_INVALID_ARG;
   *out = nullptr;
@@ -718,12 +809,6 @@ int create_impl(const tbnav_rbpf_params* P, uint64_t max_pool_bytes, tbnav_rbpf*
   if (P->num_particles > (1 << 20)) return TBNAV_ERR_UNSUPPORTED;
   const int radius = (int)static_cast<unsigned int>(std::ceil((10.0 - 0.0) / P->resolution));         // cell_radius_, grid_mapper.cpp:50
   if (radius > 254) return TBNAV_ERR_UNSUPPORTED;  // row-pass distances are stored as u8 (and radius^2 must fit the u16 code)
-  const int words = (ysize + 63) / 64;
-  int C = 64;
-  if (edt_lds_bytes(xsize, words, C) > (size_t)kMaxLds) C = 32;
-  // larger maps (xsize > ~640, e.g. BASELINE configs[4]'s 2000 x 2000): no LDS distance transform.  The SLAM path then
-  // always answers lookups by query, and an on-demand field is produced cell by cell with the same query.
-  if (edt_lds_bytes(xsize, words, C) > (size_t)kMaxLds) C = 0;
   int ndev = 0;
   {
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -741,168 +826,25 @@ int create_impl(const tbnav_rbpf_params* P, uint64_t max_pool_bytes, tbnav_rbpf*
   h->p = *P; h->device = dev; h->N = P->num_particles; h->k = P->num_samples_mode;
   h->host_threads = default_host_threads();
   h->host_affinity = host_cpu_budget(h->host_quota_cpus);
-  h->xsize = xsize; h->ysize = ysize; h->words = words; h->radius = radius; h->edt_cols = C;
+  h->xsize = xsize; h->ysize = ysize; h->words = (ysize + 63) / 64; h->radius = radius;
+  h->edt_cols = edt_cols_for(xsize, h->words);
   h->G = (size_t)xsize * ysize;
   h->TW = (xsize + kTS - 1) / kTS; h->TT = h->TW * h->TW;
-  {
-    // every beam shorter than range_max ends within this many cells of the robot cell (+2 for the laser offset / rounding)
-    const double reach = (double)P->range_max + std::sqrt(P->Trs[1] * P->Trs[1] + P->Trs[2] * P->Trs[2]);
-    const long side = 2 * ((long)std::ceil(reach / P->resolution) + 2) + 1;
-    h->tile_cap = (side * side <= 30000) ? (int)(side * side) : 0;
-    h->df_mode = 2;  // exact query at lookup; the other modes are selected with tbnav_rbpf_set_option
-    h->full_edt = false;
-  }
+  h->tile_cap = tile_cap_for((double)P->range_max, P->Trs, P->resolution);
+  h->df_mode = 2;  // exact query at lookup; the other modes are selected with tbnav_rbpf_set_option
+  h->full_edt = false;
   // log-odds constants with the host libm, exactly as the reference's ctor (grid_mapper.cpp:42-47)
   h->l_prior = std::log(0.5 / (1 - 0.5));
   h->l_occ = std::log(0.90 / (1 - 0.90));
   h->l_free = std::log(0.35 / (1 - 0.35));
   h->cut_occ = find_occ_cut(h->l_occ, 0.90);
   h->cuts = derive_export_cuts(h->cut_occ);
-  const int N = h->N;
   hipError_t e = hipSuccess;
-  auto A = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-  const size_t table_entries = (size_t)N * h->TT;
-  for (int b = 0; b < 2; ++b) {
-    A((void**)&h->d_state[b], sizeof(double) * 7 * N);
-    A((void**)&h->d_table[b], sizeof(unsigned int) * table_entries);
-    A((void**)&h->d_nocc[b], sizeof(int) * N);
-    A((void**)&h->d_trow[b], sizeof(int) * (size_t)N * h->TW);
-  }
-  A((void**)&h->d_shed, sizeof(unsigned int) * table_entries);
-  A((void**)&h->d_cs, sizeof(double) * N);
-  A((void**)&h->d_sens, sizeof(double) * 4 * N);
-  A((void**)&h->d_tile_scratch, sizeof(unsigned int) * h->TT);
-  A((void**)&h->d_touched, sizeof(unsigned long long) * 2);
-  A((void**)&h->d_box_need, sizeof(int) * 3);
-  A((void**)&h->d_parent, sizeof(int) * 2 * N);
-  A((void**)&h->d_best, sizeof(int));
-  A((void**)&h->d_best_pose, sizeof(double) * 3);
-  A((void**)&h->d_export, h->G);
-  A((void**)&h->d_fstate, sizeof(int) * N);
-  A((void**)&h->d_fstate_alt, sizeof(int) * N);
-  A((void**)&h->d_center, sizeof(double) * 3 * N);
-  A((void**)&h->d_score, sizeof(double) * N);
-  A((void**)&h->d_skip, sizeof(int) * N);
-  A((void**)&h->d_win, sizeof(int4) * N);
-  A((void**)&h->d_tier, sizeof(int) * N);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_err, sizeof(int) * 4 * kScanSlots, hipHostMallocMapped);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_norm, sizeof(NormOut) * kScanSlots, hipHostMallocMapped);
-  if (e == hipSuccess) { std::memset(h->h_err, 0, sizeof(int) * 4 * kScanSlots); std::memset((void*)h->h_norm, 0, sizeof(NormOut) * kScanSlots); }
-  A((void**)&h->d_gate, sizeof(int) * kScanSlots);
-  if (e == hipSuccess) e = hipMemset(h->d_gate, 0, sizeof(int) * kScanSlots);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_seq, sizeof(unsigned int) * kScanSlots, hipHostMallocMapped);
-  if (e == hipSuccess) { std::memset(h->h_seq, 0, sizeof(unsigned int) * kScanSlots); e = hipHostGetDevicePointer((void**)&h->d_seq, h->h_seq, 0); }
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_err, h->h_err, 0);
-  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->d_norm, h->h_norm, 0);
-  const size_t kk = (size_t)h->k;
-  const size_t trace_doubles = (size_t)N * (kk * 3 + kk + kk + 3 + 9 + 1 + 3 + 1);
-  A((void**)&h->d_trace, sizeof(double) * trace_doubles);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  for (auto& ev : h->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
-  // ---- the tile pool: everything the particles' maps can ever need if that fits the budget, else the budget.
-  //      Default budget: half of the memory that is free now (several handles can live side by side).
-  if (e == hipSuccess) {
-    size_t free_b = 0, total_b = 0;
-    e = hipMemGetInfo(&free_b, &total_b);
-    const size_t per_tile = sizeof(double) * kTileCells + sizeof(unsigned int) * kTS + sizeof(int) + sizeof(unsigned int);
-    const size_t budget = max_pool_bytes ? (size_t)max_pool_bytes : free_b / 2;
-    // worst case: every table entry its own tile, plus the tiles the entries left since the last resample (still named by
-    // the shed notes until the next resample settles them), plus the zero tile
-    size_t cap = 2 * table_entries + 1;
-    if (cap * per_tile > budget) cap = budget / per_tile;
-    if (cap > 0xFFFFFFF0ull) cap = 0xFFFFFFF0ull;
-    if (cap < (size_t)N + 2 && e == hipSuccess) e = hipErrorOutOfMemory;  // not even one tile per particle
-    h->pool.cap = (unsigned int)cap;
-    h->pool.shards = pool_lists_for(cap);
-    h->pool.shard_cap = (unsigned int)((cap + h->pool.shards - 1) / h->pool.shards);
-    A((void**)&h->pool.lo, sizeof(double) * kTileCells * cap);
-    A((void**)&h->pool.bm, sizeof(unsigned int) * kTS * cap);
-    A((void**)&h->pool.ref, sizeof(int) * cap);
-    A((void**)&h->pool.ring, sizeof(unsigned int) * (size_t)h->pool.shard_cap * h->pool.shards);
-    A((void**)&h->pool.ctr, sizeof(unsigned long long) * kPoolCtrWords);
-  }
-  if (e == hipSuccess) {
-    double* t = h->d_trace;
-    h->tr.sampled = t; t += (size_t)N * kk * 3;
-    h->tr.p_scan = t; t += (size_t)N * kk;
-    h->tr.p_pose = t; t += (size_t)N * kk;
-    h->tr.mu = t; t += (size_t)N * 3;
-    h->tr.sigma = t; t += (size_t)N * 9;
-    h->tr.eta = t; t += (size_t)N;
-    h->tr.new_pose = t; t += (size_t)N * 3;
-    h->tr.weight_raw = t;
-    e = hipMemset(h->d_trace, 0, sizeof(double) * trace_doubles);
-  }
-  if (e == hipSuccess) {  // initParticleSet, particle_filter.cpp:125-138
-    std::vector<double> s((size_t)7 * N);
-    for (int i = 0; i < N; ++i) {
-      for (int q = 0; q < 3; ++q) { s[(size_t)i * 3 + q] = P->pose0[q]; s[(size_t)3 * N + i * 3 + q] = P->pose0[q]; }
-      s[(size_t)6 * N + i] = 1.0 / N;
-    }
-    e = hipMemcpy(h->d_state[0], s.data(), sizeof(double) * 7 * N, hipMemcpyHostToDevice);
-    // empty maps: every table entry names the shared zero tile (log_odds_prior_ = log(1) = 0)
-    if (e == hipSuccess) e = hipMemset(h->d_table[0], 0, sizeof(unsigned int) * table_entries);
-    if (e == hipSuccess) e = hipMemset(h->d_shed, 0, sizeof(unsigned int) * table_entries);
-    if (e == hipSuccess) e = hipMemset(h->pool.lo, 0, sizeof(double) * kTileCells);  // tile 0
-    if (e == hipSuccess) e = hipMemset(h->pool.ref, 0, sizeof(int) * h->pool.cap);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(rbpf_pool_init, dim3(1024), dim3(256), 0, h->stream, h->pool);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemset(h->d_touched, 0, sizeof(unsigned long long) * 2);
-    if (e == hipSuccess) {  // the queue's scratch memory, before the first map update that needs it (see the kernel)
-      hipLaunchKernelGGL(rbpf_warm_scratch, dim3(1024), dim3(512), 0, h->stream, reinterpret_cast<int*>(h->d_touched), 0);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemset(h->d_box_need, 0, sizeof(int) * 3);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->h_box_need, sizeof(int), hipHostMallocMapped);
-    if (e == hipSuccess) { *h->h_box_need = 0; e = hipHostGetDevicePointer((void**)&h->d_box_need_host, h->h_box_need, 0); }
-    if (e == hipSuccess) e = hipMemset(h->d_nocc[0], 0, sizeof(int) * N);
-    if (e == hipSuccess) e = hipMemset(h->d_skip, 0, sizeof(int) * N);
-    if (e == hipSuccess) e = hipMemset(h->d_tier, 0xFF, sizeof(int) * N);  // -1: no transform launch has covered the particle yet (tbnav_rbpf_last_field_kernels)
-    // empty maps: the field "everything unreached" is what any lookup computes, no stored field needed (state 0)
-    if (e == hipSuccess) e = hipMemset(h->d_fstate, 0, sizeof(int) * N);
-    if (e == hipSuccess) e = hipMemset(h->d_fstate_alt, 0, sizeof(int) * N);
-    h->fstate_dirty = false;
-    if (e == hipSuccess) {
-      std::vector<int4> w(N, make_int4(0, xsize - 1, 0, ysize - 1));
-      e = hipMemcpy(h->d_win, w.data(), sizeof(int4) * N, hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemset(h->d_trow[0], 0, sizeof(int) * (size_t)N * h->TW);
-    if (e == hipSuccess) e = hipMemset(h->pool.bm, 0, sizeof(unsigned int) * kTS);  // tile 0
-  }
-  if (e == hipSuccess && C > 0) {
-    const int lds = (int)edt_lds_bytes(xsize, words, C);
-    e = (C == 64) ? hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_edt<64>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-                  : hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_edt<32>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  }
-  // (2.3 KB of static LDS: the embedded normalise's scan scratch)
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<512, 6, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<512, 6, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<512, 8, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<512, 8, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<512, 8, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast_box<1024, 8, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 4096);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_raycast), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 1024);
-  // the proposal / scan-match kernels carry the scan, the per-sample data and the bitmap slice: more than the 64 KB
-  // default for long scans or many samples
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_propose<kProposeThreads, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 3072);  // (2.3 KB static)
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_propose<2 * kProposeThreads, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 3072);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_propose<kProposeThreads, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 3072);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_propose<2 * kProposeThreads, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 3072);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_scanmatch), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds - 1024);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_edt_compact<kEdtRowsA>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)edt_compact_lds(kEdtRowsA));
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rbpf_edt_compact<kEdtRowsB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)edt_compact_lds(kEdtRowsB));
-  A((void**)&h->d_mixlut, sizeof(double) * kMixLut);
-  if (e == hipSuccess) {
-    ScanC cm{};
-    if (mixture_consts(h, cm)) {  // (a zero variance is reported by the first scan, as the reference throws there)
-      hipLaunchKernelGGL(rbpf_mix_lut, dim3(kMixLut / 256), dim3(256), 0, h->stream, cm, h->d_mixlut);
-      e = hipGetLastError();
-    }
-  }
+  create_buffers(h, e);
+  create_pool(h, max_pool_bytes, e);
+  create_state(h, e);
+  create_lds_attributes(h, e);
+  create_mix_lut(h, e);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     const int rc = tbnav::hip_fail(e, "tbnav_rbpf_create allocation", __FILE__, __LINE__);
@@ -948,7 +890,6 @@ void tbnav_rbpf_destroy(tbnav_rbpf* h) {
   (void)hipFree(h->d_gw); (void)hipFree(h->d_gcs); (void)hipFree(h->d_gparent); (void)hipFree(h->d_gz);
   (void)hipFree(h->d_gw_raw); (void)hipFree(h->d_sendbuf); (void)hipFree(h->d_recvbuf); (void)hipFree(h->d_sizes); (void)hipFree(h->d_status);
   if (h->ev_w) (void)hipEventDestroy(h->ev_w);
-  if (h->ev_g) (void)hipEventDestroy(h->ev_g);
   if (h->stream2) (void)hipStreamDestroy(h->stream2);
   (void)hipFree(h->d_zslot); (void)hipFree(h->d_beam_ready); (void)hipFree(h->d_beams_fg);
   (void)hipFree(h->d_beams); (void)hipFree(h->d_normals); (void)hipFree(h->d_parent); (void)hipFree(h->d_best); (void)hipFree(h->d_best_pose); (void)hipFree(h->d_export); (void)hipFree(h->d_tier); (void)hipFree(h->d_fstate); (void)hipFree(h->d_skip); (void)hipFree(h->d_win); (void)hipFree(h->d_center); (void)hipFree(h->d_mixlut); (void)hipFree(h->d_bslots); (void)hipFree(h->d_bcount); (void)hipFree(h->d_bitems); (void)hipFree(h->d_bhdr); (void)hipFree(h->d_score);
@@ -995,15 +936,9 @@ int tbnav_rbpf_get_normals(tbnav_rbpf* h, double* out, int64_t n) {
       TBNAV_HIP(hipMalloc((void**)&h->d_normals, sizeof(double) * nn));
       h->normals_cap = nn;
     }
-    const int blocks = (int)std::min<size_t>((nn / 2 + 255) / 256, 4096);
     const bool sharded = h->last_drawn.z_index != nn - 1 || h->last_drawn.base != 0;
-    if (sharded)
-      hipLaunchKernelGGL(rbpf_sample_normals, dim3(blocks), dim3(256), 0, h->stream, nn - 1, h->last_drawn.seed, h->last_drawn.scan, h->d_normals,
-                         (const double2*)nullptr, (double2*)nullptr, 0, (size_t)0, (size_t)0, h->last_drawn.base, h->last_drawn.z_index, nn - 1);
-    else
-      hipLaunchKernelGGL(rbpf_sample_normals, dim3(blocks), dim3(256), 0, h->stream, nn, h->last_drawn.seed, h->last_drawn.scan, h->d_normals,
-                         (const double2*)nullptr, (double2*)nullptr, 0, (size_t)0, (size_t)0, (size_t)0, ~(size_t)0, (size_t)0);
-    TBNAV_HIP(hipGetLastError());
+    TBNAV_TRY(launch_sample_normals(h, nn, h->last_drawn.seed, h->last_drawn.scan, sharded, h->last_drawn.base, h->last_drawn.z_index,
+                                    nullptr, nullptr, 0));
     TBNAV_HIP(hipStreamSynchronize(h->stream));
     TBNAV_HIP(hipMemcpy(out, h->d_normals, sizeof(double) * n, hipMemcpyDeviceToHost));
     return TBNAV_OK;

@@ -207,12 +207,7 @@ int tbnav_rbpf_set_option(tbnav_rbpf* h, int32_t option, int32_t value) {
       if (h->ref) h->ref->set_reach(value);
       return TBNAV_OK;
     case TBNAV_RBPF_OPT_RAYCAST_ORDERED:
-      if (value) h->tile_cap = 0;
-      else {
-        const double reach = (double)h->p.range_max + std::hypot(h->p.Trs[1], h->p.Trs[2]);
-        const long side = 2 * ((long)std::ceil(reach / h->p.resolution) + 2) + 1;
-        h->tile_cap = (side * side <= 30000) ? (int)(side * side) : 0;
-      }
+      h->tile_cap = value ? 0 : tile_cap_for((double)h->p.range_max, h->p.Trs, h->p.resolution);
       return TBNAV_OK;
     case TBNAV_RBPF_OPT_RAYCAST_THREADS:
       if (value != 0 && value != 256 && value != 512 && value != 1024) return TBNAV_ERR_INVALID_ARG;
@@ -274,13 +269,15 @@ int tbnav_rbpf_set_timing(tbnav_rbpf* h, int32_t enable) {
 
 int tbnav_rbpf_last_kernel_names(const tbnav_rbpf* h, char* propose, int32_t propose_cap, char* raycast, int32_t raycast_cap, int32_t* raycast_workgroups) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
-  if (propose && propose_cap > 0) { if (h->lk_propose) snprintf(propose, (size_t)propose_cap, "rbpf_propose<%d, %s>", h->lk_propose, h->lk_propose_dn ? "true" : "false"); else propose[0] = 0; }
+  const ProposePlan& pp = h->last_propose;
+  const RaycastPlan& rp = h->last_raycast;
+  if (propose && propose_cap > 0) { if (pp.threads) snprintf(propose, (size_t)propose_cap, "rbpf_propose<%d, %s>", pp.threads, pp.dn ? "true" : "false"); else propose[0] = 0; }
   if (raycast && raycast_cap > 0) {
-    if (h->lk_raycast > 0) snprintf(raycast, (size_t)raycast_cap, "rbpf_raycast_box<%d, %d, %s, %d>", h->lk_raycast, h->lk_raycast_wps, h->lk_raycast_c16 ? "true" : "false", h->lk_raycast_ev);
-    else if (h->lk_raycast == 0) snprintf(raycast, (size_t)raycast_cap, "rbpf_raycast");
+    if (rp.box()) snprintf(raycast, (size_t)raycast_cap, "rbpf_raycast_box<%d, %d, %s, %d>", rp.threads, rp.wps, rp.c16 ? "true" : "false", rp.ev);
+    else if (rp.threads == 0) snprintf(raycast, (size_t)raycast_cap, "rbpf_raycast");
     else raycast[0] = 0;
   }
-  if (raycast_workgroups) *raycast_workgroups = h->lk_raycast_grid;
+  if (raycast_workgroups) *raycast_workgroups = rp.grid;
   return TBNAV_OK;
 }
 
@@ -297,8 +294,8 @@ int tbnav_rbpf_last_field_kernels(tbnav_rbpf* h, int32_t* tier, int32_t* cols) {
 
 int tbnav_rbpf_raycast_box_cells(const tbnav_rbpf* h, int32_t* need_cells, int32_t* array_cells) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
-  if (need_cells) *need_cells = h->lk_box_need;
-  if (array_cells) *array_cells = h->lk_box_cap;
+  if (need_cells) *need_cells = h->last_raycast.need;   // (the value the launch's selection used)
+  if (array_cells) *array_cells = h->last_raycast.box() ? (int32_t)h->last_raycast.cap_win : 0;   // (the beam-ordered kernel has no array)
   return TBNAV_OK;
 }
 

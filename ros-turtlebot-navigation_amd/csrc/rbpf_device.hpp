@@ -18,29 +18,23 @@
 
 #include "common.hpp"
 #include "tbnav_rbpf.h"
+#include "rbpf_plan.hpp"   // the constants and size formulas the host's selection shares with the kernels
 
 namespace tbnav_rk {
 
 constexpr double kPI = 3.14159265358979323846;  // rigid2d.hpp:13
-constexpr int kWave = 64;
-#ifndef TBNAV_PROPOSE_THREADS
-#define TBNAV_PROPOSE_THREADS 256
-#endif
 #ifndef TBNAV_PROPOSE_WAVES
 #define TBNAV_PROPOSE_WAVES 4  // four workgroups of four waves per CU (what its LDS allows): 128 VGPRs
 #endif
 #ifndef TBNAV_PROPOSE_KSB
 #define TBNAV_PROPOSE_KSB 1
 #endif
-constexpr int kProposeThreads = TBNAV_PROPOSE_THREADS;
-constexpr int kUnCap = 16;  // unstable beams handled by the per-pair path of the proposal kernel
 static_assert(kProposeThreads >= 128 && kProposeThreads % 64 == 0, "wave 0 samples, the other waves look the beams up");
 constexpr uint16_t kCodeUnreached = 0xFFFF;
 // reference-field mode only (ref_field.hpp): the particle's brushfire has not written this cell yet — a lookup that reads it is
 // reported to the host (DistSrc::pend), which resumes that brushfire and has the proposal run again.  The largest real code is
 // cell_radius^2 = 40 000.
 constexpr uint16_t kCodePending = 0xFFFE;
-constexpr int kMaxLds = 160 * 1024;
 
 // ---- small math shared by host and device ----------------------------------------------------------
 __host__ __device__ inline bool almost_equal(double a, double b, double eps = 1.0e-12) { return fabs(a - b) < eps; }
@@ -291,7 +285,7 @@ __device__ __forceinline__ double uniform_d(double v) {
 }
 
 // ---- proposal side: what the host needs of it (the lookups are in rbpf_lookup.hpp, likelihoods and the kernels' helpers in rbpf_propose.hip) ----
-constexpr int kMixLut = 1024, kMixLds = 128;
+constexpr int kMixLds = 128;   // (kMixLut: rbpf_plan.hpp)
 struct Trace {
   double *sampled, *p_scan, *p_pose, *mu, *sigma, *eta, *new_pose, *weight_raw;
 };
@@ -326,25 +320,13 @@ struct NormOut { double sum_w, sq_sum; int neff, resampled; };
 // that i because U_m and c[] are both non-decreasing), found by binary search, clamped to N-1.
 // Any N: the weights pass through LDS in chunks of kNormChunk (parallel loads / divisions, the one lane carries its
 // running sums from chunk to chunk); the prefix c[] lives in LDS when one chunk holds it, else in a global scratch.
-constexpr int kNormChunk = 2048;
 constexpr int kScanSlots = 4;  // per-scan host-visible results (error flags, normalisation result, staged beams): a ring
 struct NormArgs { int N; const double* zp; const double* weight; double* weight_out; double* cs; int* parent; NormOut* out;
                   int* gate; const int* gate_prev; unsigned int* seq; unsigned int seq_val; int* children; };
-constexpr int kBoxEv = 8;     // events a slot holds before it is replayed exhaustively
+// (kBoxEv, kBoxEvFour, box_lds_bytes, box16_*, kBoxStaticLds: rbpf_plan.hpp)
 constexpr int kHotSide = 7;   // the kHotSide x kHotSide cells round the robot are candidates for a lane of their own ...
 constexpr int kHotMin = 16;   // ... when they collect at least this many free adds
 constexpr int kVeryHot = 80;  // ... and from this many on they are worked out without the chain of adds (add_repeated)
-// tile u32[cap] | ev u16[bv][kBoxEv] (a slot's first 8 bytes become its replayed value once its events are read) | hot values f64[64] | exy i32[bv] | ecnt u16[bv]
-constexpr int kBoxEvFour = 4; // ... in the four-workgroups-per-CU form (8 bytes a slot: exactly the replayed value; the bench room's box fits with them)
-__host__ __device__ constexpr size_t box_lds_bytes(size_t cap, size_t bv, size_t ev = kBoxEv) { return 4 * cap + 2 * ev * bv + 8 * 64 + 4 * bv + 2 * ((bv + 1) & ~(size_t)1); }
-// the 16-bit cell form: half the cell array + the slot table (hash_words u32, a power of two >= 2 x (bv + 64) slots)
-__host__ __device__ constexpr size_t box16_hash_words(size_t bv) { size_t h = 256; while (h < 2 * (bv + 64)) h *= 2; return h; }
-__host__ __device__ constexpr size_t box16_lds_bytes(size_t cap, size_t bv, size_t ev = kBoxEv) { return box_lds_bytes(cap, bv, ev) - 2 * cap + 4 * box16_hash_words(bv); }
-constexpr size_t kBoxStaticLds = 896;  // the kernel's __shared__ variables (tools/kernel_resources.py rbpf_raycast: 856 B since mt_src, round 5), rounded up
-// (512 threads: three workgroups = 24 waves per CU when the LDS array is sized by what the boxes need, see launch_raycast —
-//  6 waves per SIMD leave 80 registers a lane: the kernel needs 77 and spills nothing; 1024 threads: two workgroups = 32 waves, 64)
-
-
 
 struct EdtJob { const int4* win; const int* skip; int p0; };
 
@@ -606,6 +588,9 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
                                                                 double* __restrict__ weight, Trace tr, double* __restrict__ sens,
                                                                 int* __restrict__ err, const int* __restrict__ gate_prev,
                                                                 const double* __restrict__ mixlut, NoiseSrc ns, int* __restrict__ pend = nullptr);
+// Every form of it that exists, once: X(NT, DN).  The explicit instantiations (rbpf_propose.hip, in this order), the launch dispatch
+// and create's LDS attributes (rbpf.hip) are all made from this list; a plan (rbpf_plan.hpp) that names another form is refused.
+#define TBNAV_PROPOSE_FORMS(X) X(kProposeThreads, false) X(kProposeThreads, true) X(2 * kProposeThreads, false) X(2 * kProposeThreads, true)
 // rbpf_raycast.hip
 __global__ __launch_bounds__(kWave) void rbpf_raycast(ScanC c, TilePool P, MapT M, const double2* __restrict__ beams,
                                                      const double* __restrict__ pose, int* __restrict__ trow_occ,
@@ -625,6 +610,8 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
                                                           int* __restrict__ trow_occ, int* __restrict__ n_occ, int* __restrict__ err,
                                                           int tile_cap, unsigned long long* __restrict__ touched, NormArgs nz,
                                                           int* __restrict__ box_need, int* __restrict__ box_need_host, int need_slot, int hash_words);
+// ... and of the box kernel: X(NT, WPS, C16, EV), used like TBNAV_PROPOSE_FORMS (what plan_raycast can name and cannot: tests/raycast_cases.py UNREACHABLE)
+#define TBNAV_RAYCAST_BOX_FORMS(X) X(512, 6, false, 8) X(512, 6, true, 8) X(512, 8, false, 8) X(512, 8, false, 4) X(512, 8, true, 8) X(1024, 8, false, 8)
 // rbpf_field.hip
 __global__ __launch_bounds__(256) void rbpf_densify(GridC g, int p0, TilePool P, MapT M, const int* __restrict__ trow_occ,
                                                     unsigned long long* __restrict__ bitmap, int* __restrict__ row_count);

@@ -5,6 +5,8 @@
 //   rbpf_sharded.hip   the sharded filter inside the library: sharded_scan, tbnav_rbpf_attach_comm, tbnav_rbpf_group_*
 //   rbpf_io.hip        particle blobs (export / import, one and many), particles / log-odds / distance fields in and out
 //   rbpf_api.hip       queries and options: trace, best state / map, one-particle GridMapper calls, tbnav_rbpf_set_option, measurement hooks
+//   rbpf_pool.hip      the tile pool's free lists on their own (self-test)
+//   rbpf_plan.hpp      which kernel form a launch gets and with how much LDS, as plain host arithmetic (no HIP: tests/test_rbpf_plan.py)
 // Kernels and launch structs: rbpf_device.hpp.  Everything in namespace tbnav_rh is internal to libtbnav_hip.so.
 #ifndef TBNAV_RBPF_HOST_HPP
 #define TBNAV_RBPF_HOST_HPP
@@ -29,8 +31,6 @@
 #include "ref_field.hpp"
 #include "tbnav_rbpf.h"
 #include "rbpf_device.hpp"
-
-using namespace tbnav_rk;  // the launch-argument structs and the kernels (rbpf_device.hpp)
 
 using namespace tbnav_rk;  // the launch-argument structs and the kernels (rbpf_device.hpp)
 
@@ -109,7 +109,8 @@ struct tbnav_rbpf {
   std::vector<double2> beams_tmp;
   int raycast_band_rows = 0;   // > 0: cap the LDS array of rbpf_raycast_box at about this many box rows (TBNAV_RBPF_OPT_RAYCAST_BAND_ROWS, tests)
   int raycast_cell16 = 1;      // 0: never the 16-bit cell form; 1: where it buys a higher residency (default); 2: wherever it can run (TBNAV_RBPF_OPT_RAYCAST_CELL16)
-  int lk_raycast = -1, lk_raycast_wps = 0, lk_raycast_c16 = 0, lk_raycast_ev = 8, lk_raycast_grid = 0, lk_propose = 0, lk_propose_dn = 0, lk_box_need = 0, lk_box_cap = 0;  // the instantiations the last launches were (tbnav_rbpf_last_kernel_names): raycast threads (0 = beam-ordered), its workgroups, propose threads
+  RaycastPlan last_raycast;    // what the last map-update launch was, with its grid (tbnav_rbpf_last_kernel_names, tbnav_rbpf_raycast_box_cells)
+  ProposePlan last_propose;    // ... and the last proposal launch
   double* d_sens = nullptr;    // [N][4] sensor transform (X, Y, sin, cos) of each particle's new pose, left by the proposal kernel
   uint64_t seed = 0x5EEDull, scan_index = 0;  // device noise source (normals == NULL)
   uint64_t rng_first = 0, rng_n_global = 0;   // sharded filters: this handle's particles are [rng_first, rng_first + N) of rng_n_global (0 = unsharded)
@@ -117,7 +118,7 @@ struct tbnav_rbpf {
   // normalise / select run on a SECOND stream beside the local map update
   tbnav_comm* comm = nullptr;
   hipStream_t stream2 = nullptr;
-  hipEvent_t ev_w = nullptr, ev_g = nullptr;   // "the proposal kernel has left the weights" / (ev_g: unused since round 5 — the weights come back on the main stream)
+  hipEvent_t ev_w = nullptr;   // "the proposal kernel has left the weights"
   int shard_latched = TBNAV_OK;                // a rank-local failure after a scan's last agreement: carried into the next scan's, where every rank stops with it
   double* d_gw_raw = nullptr;                  // [n_global] all-gathered raw weights
   char* d_sendbuf = nullptr; char* d_recvbuf = nullptr; size_t send_cap = 0, recv_cap = 0;   // particle blobs of a cross-rank resample
@@ -225,7 +226,6 @@ double find_occ_cut(double l_occ_nominal, double p_occ);
 int export_value_host(double l);
 double bisect_first(double lo, double hi, bool (*pred)(double, int), int arg);
 ExportCuts derive_export_cuts(double cut_occ);
-size_t edt_lds_bytes(int xs, int words, int C);
 bool mixture_consts(const tbnav_rbpf* h, ScanC& c);
 int build_scan_consts(tbnav_rbpf* h, ScanC& c, const float* scan, int n_beams, const double u[3],
                       const double cur_odom[3], const double prev_odom[3], int icp_ok, const double T_icp[3],
@@ -263,9 +263,6 @@ int slot_tiles(tbnav_rbpf* h, int slot, std::vector<uint32_t>& tidx, std::vector
 int count_batch(tbnav_rbpf* h, int32_t n, const int32_t* slots);
 int ensure_shard_state(tbnav_rbpf* h);
 int grow(char*& buf, size_t& cap, size_t need);
-int sharded_scan(int n, tbnav_rbpf* const* hs, const float* scan, int n_beams, const double u[3], const double cur_odom[3],
-                 const double prev_odom[3], int icp_ok, const double T_icp[3], const double* const* normals, tbnav_rbpf_stats* out,
-                 tbnav_rbpf_stats* local_out);
 int one_particle_consts(tbnav_rbpf* h, int32_t particle, const float* scan, int32_t n_beams, ScanC& c);
 int sharded_scan(int n, tbnav_rbpf* const* hs, const float* scan, int n_beams, const double u[3], const double cur_odom[3],
                  const double prev_odom[3], int icp_ok, const double T_icp[3], const double* const* normals, tbnav_rbpf_stats* out,

@@ -10,7 +10,6 @@ int ensure_shard_state(tbnav_rbpf* h) {
   const size_t ng = (size_t)P * h->N;
   if (!h->stream2) TBNAV_HIP(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
   if (!h->ev_w) TBNAV_HIP(hipEventCreateWithFlags(&h->ev_w, hipEventDisableTiming));
-  if (!h->ev_g) TBNAV_HIP(hipEventCreateWithFlags(&h->ev_g, hipEventDisableTiming));
   if (ng > h->g_cap || !h->d_gw_raw) {
     TBNAV_HIP(hipStreamSynchronize(h->stream));
     TBNAV_HIP(hipStreamSynchronize(h->stream2));

@@ -1,5 +1,5 @@
 """The case table of the RBPF proposal kernel (csrc/rbpf_propose.hip: rbpf_propose<NT, DN>, four instantiations, six phases).  Plain
-data, the host expressions of csrc/rbpf.hip::slam_impl that choose the instantiation and the staging form, restated, and the
+data, the host expressions of csrc/rbpf_plan.hpp::plan_propose that choose the instantiation and the staging form, restated, and the
 kernel's own rules restated in float64 over the oracle's numbers: which beams a particle's samples can move out of the centre's cell
 (U_true), which the kernel's bound calls unstable (U_rule), the per-wave segment counts of its list, and which query-mode lookups
 the 7 x 7 look settles.  tests/test_propose_cases.py proves the table on the CPU with the oracle alone;
@@ -26,7 +26,7 @@ import scanmatch_cases as smc
 ZERO = (0.0, 0.0, 0.0)
 START = (0.01, 0.012, 0.007)       # (from (0, 0, 0) beam 0 of the first scan ends ON the border y = 0 of its cell)
 RES = 0.05
-K_UNCAP = 16                      # rbpf_device.hpp: kUnCap
+K_UNCAP = 16                      # rbpf_plan.hpp: kUnCap
 K_MAX_LDS = 160 * 1024            # kMaxLds
 K_PROPOSE_THREADS = 256           # kProposeThreads (TBNAV_PROPOSE_THREADS)
 K_WAVE = 64
@@ -176,7 +176,7 @@ def runs_of(case):
     return [(s, n) for s in case.sources for n in case.noises]
 
 
-# ---- the host expressions of csrc/rbpf.hip::slam_impl, restated -----------------------------------------------------------------------
+# ---- the host expressions of csrc/rbpf_plan.hpp::plan_propose, restated (tests/test_rbpf_plan.py runs the C++ against these) -----------------------------------------------------------------------
 def occ_half(case, source):
     """Half-width of the LDS slice of the occupancy bitmap; 0: none.  (scanmatch_cases.slice_regime is the restated loop; the handle's
     distance-field mode decides whether it runs: an injected field does not change the mode, `window` and `full` do.)"""

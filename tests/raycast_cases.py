@@ -1,5 +1,5 @@
 """The case table of the RBPF map update (csrc/rbpf_raycast.hip: the six instantiations of rbpf_raycast_box and the beam-ordered
-rbpf_raycast) and launch_raycast's selection (csrc/rbpf.hip), restated.  Plain data and host arithmetic, no device.
+rbpf_raycast) and the host's selection among them (csrc/rbpf_plan.hpp: plan_raycast, tile_cap_for), restated.  Plain data and host arithmetic, no device.
 tests/test_raycast_cases.py proves on the CPU, with the oracle's GridMapper alone, that every case reaches what it names;
 tests/test_raycast_gpu.py runs the table through tbnav_rbpf_integrate_scan_many and compares every particle's map with `==`.
 
@@ -38,7 +38,7 @@ FORMS = {
     "box512w8ev4": dict(opts=dict(ADAPT=3), warm=2),
     "box512w8c16": dict(opts=dict(ADAPT=1, CELL16=2), warm=2),
     "ordered":     dict(opts=dict(ORDERED=1), warm=0),
-    "threads256":  dict(opts=dict(THREADS=256), warm=0),   # accepted, and selects the beam-ordered kernel (launch_raycast wants nt >= 512)
+    "threads256":  dict(opts=dict(THREADS=256), warm=0),   # accepted, and selects the beam-ordered kernel (plan_raycast wants nt >= 512)
 }
 BOX_FORMS = ("box1024", "box512w6", "box512w6c16", "box512w8", "box512w8ev4", "box512w8c16")
 ALL_FORMS = BOX_FORMS + ("ordered",)
@@ -60,7 +60,7 @@ UNREACHABLE = {
 }
 
 
-# ---- launch_raycast's selection, restated (csrc/rbpf.hip) ------------------------------------------------------------------------------
+# ---- plan_raycast's selection, restated (csrc/rbpf_plan.hpp; tests/test_rbpf_plan.py runs the C++ against this) ------------------------------------------------------------------------------
 def box_lds_bytes(cap, bv, ev=kBoxEv):
     return 4 * cap + 2 * ev * bv + 8 * 64 + 4 * bv + 2 * ((bv + 1) & ~1)
 
@@ -81,7 +81,7 @@ def _trunc_div(a, b):
 
 
 def tile_cap_of(range_max, trs, ordered):
-    """create's rule (and TBNAV_RBPF_OPT_RAYCAST_ORDERED's): 0 = the box kernel is never used."""
+    """create's rule (and TBNAV_RBPF_OPT_RAYCAST_ORDERED's; csrc/rbpf_plan.hpp: tile_cap_for): 0 = the box kernel is never used."""
     reach = float(np.float32(range_max)) + math.hypot(trs[1], trs[2])
     side = 2 * (int(math.ceil(reach / RES)) + 2) + 1
     return side * side if (side * side <= 30000 and not ordered) else 0

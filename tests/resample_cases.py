@@ -13,7 +13,7 @@ lets a shape such as `every-once` (margins of 1 / N^2) survive the scan.  The ch
 No library is imported at module level (numpy alone)."""
 import numpy as np
 
-K_NORM_CHUNK = 2048               # rbpf_device.hpp: kNormChunk
+K_NORM_CHUNK = 2048               # rbpf_plan.hpp: kNormChunk
 K_RESAMPLE_THREADS = 1024         # kResampleThreads
 K_RESAMPLE_BLOCKS = 8192          # resample_on_device: the table loop's workgroups, at most
 K_TS = 32                         # kTS: 32 x 32-cell tiles
@@ -44,7 +44,7 @@ def chunks(N):
 
 
 def normalise_home(form):
-    """Where normalize_body runs for a handle set up as `form` (csrc/rbpf.hip: scan_enqueue's `overlap`, launch_raycast): riding as
+    """Where normalize_body runs for a handle set up as `form` (csrc/rbpf.hip: scan_enqueue's `overlap`, launch_raycast; csrc/rbpf_plan.hpp: plan_raycast): riding as
     workgroup 0 of rbpf_raycast_box when overlap holds and the box kernel runs; else rbpf_normalize, a launch of its own.
     Returns (home, the raycast kernel's name — whole for the beam-ordered kernel, up to the thread count for the box —, raycast workgroups minus N)."""
     timing = form == "own-timing"

@@ -1,6 +1,6 @@
 """The case table of the RBPF scan matcher (csrc/rbpf_propose.hip: rbpf_scanmatch, with the lookups it makes through csrc/rbpf_lookup.hpp's
 lookup_code / nearest_code_query_body and its per-beam cell cache).  Plain data and the two host expressions that decide which lookup path a case takes,
-restated: slam_impl's window half-width and the LDS bitmap slice.  tests/test_scanmatch_cases.py proves the table on the CPU with the
+restated: the window half-width and the LDS bitmap slice (csrc/rbpf_plan.hpp: lookup_half_cells, sampling_spread, plan_propose).  tests/test_scanmatch_cases.py proves the table on the CPU with the
 oracle alone (the matcher really moves, leaves the slice / the window, wraps, hits the move cap where a case says so, and no
 decision of any matcher call is nearer than 5e-10 to going the other way); tests/test_rbpf_scanmatch_gpu.py runs it on the device,
 nothing injected.
@@ -115,7 +115,7 @@ CASE = {c.id: c for c in CASES}
 MODE_CASES = ("modes-query", "modes-window", "modes-full")
 
 
-# ---- the two host expressions, restated (csrc/rbpf.hip, slam_impl) ------------------------------------------------------------------
+# ---- the two host expressions, restated (csrc/rbpf_plan.hpp: lookup_half_cells, plan_propose) ------------------------------------------------------------------
 def _spread():
     return 8.0 * math.sqrt(max(SAMPLE_RANGE[1], SAMPLE_RANGE[2], MOTION_NOISE[1], MOTION_NOISE[2]))
 

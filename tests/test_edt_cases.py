@@ -17,7 +17,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 MAX_LDS = 160 * 1024
 
 
-# ---- create's rules, restated (csrc/rbpf.hip, create_impl) --------------------------------------------------------------------------
+# ---- create's rules, restated (csrc/rbpf.hip: create_impl; csrc/rbpf_plan.hpp: edt_lds_bytes, edt_cols_for) --------------------------------------------------------------------------
 def lds_bytes(xsize, cols):
     """Bitmap rows as u64 words, and per row and column of the tile a u16 stack row, an i16 stack start and a u8 row distance."""
     return xsize * ((xsize + 63) // 64) * 8 + xsize * cols * 5

@@ -59,7 +59,7 @@ def test_committed_profiles_have_a_row_for_every_kernel_the_bench_lines_point_at
     for kernel, grid, wl in (("mppi_rollout_fused<2, 8, 1, 2>", None, None), ("mppi_rollout_prefix<1>", 65536, "mppi_K65536_T100"), ("mppi_partials", None, "mppi_K65536_T100")):
         r = bp.rocprof_row(kernel, grid, wl)
         assert r is not None and r["avg_us"] > 0 and r["source"].startswith("profiles/"), kernel
-    # the map update's instantiation is chosen per launch (launch_raycast): the committed bench line names the one that ran
+    # the map update's instantiation is chosen per launch (plan_raycast, csrc/rbpf_plan.hpp): the committed bench line names the one that ran
     # (round 6: the line is the compact record the driver parses — bench.compact_line — and carries the same names)
     line_path = os.path.join(ROOT, "profiles", src.split("/")[-1].replace("kernel_stats.md", "bench_line.json"))
     with open(line_path) as f:

@@ -138,16 +138,19 @@ def test_the_restated_literals_are_the_host_code_s_and_the_kernel_s():
     dev = open(os.path.join(CSRC, "rbpf_device.hpp")).read()
     ker = open(os.path.join(CSRC, "rbpf_propose.hip")).read() + open(os.path.join(CSRC, "rbpf_lookup.hpp")).read()   # (its lookups)
     api = open(os.path.join(CSRC, "rbpf_api.hip")).read()
-    for src, pieces in ((host, ("sizeof(double) * ((12 + kUnCap) * h->k + 3 * (c.Bv > 0 ? c.Bv : 1)) + sizeof(unsigned int) * 4 * (c.Bv > 0 ? c.Bv : 1);",
-                                "if (h->df_mode == 2) {\n    // LDS copy of the occupancy bitmap",
-                                "if (bytes <= 48 * 1024) { occ_half = half; propose_lds += bytes; break; }",
-                                "if (propose_lds > (size_t)kMaxLds - 3072) return TBNAV_ERR_UNSUPPORTED;",
-                                "h->lk_propose = (propose_lds + 3072 > (size_t)kMaxLds / 4) ? 2 * kProposeThreads : kProposeThreads;",
-                                "if (propose_lds + 3072 > (size_t)kMaxLds / 4) { if (dn) TBNAV_PROPOSE(2 * kProposeThreads, true); else TBNAV_PROPOSE(2 * kProposeThreads, false); }",
-                                "else { if (dn) TBNAV_PROPOSE(kProposeThreads, true); else TBNAV_PROPOSE(kProposeThreads, false); }",
+    plan = open(os.path.join(CSRC, "rbpf_plan.hpp")).read()       # (plan_propose: tests/test_rbpf_plan.py runs it against these restatements)
+    for src, pieces in ((plan, ("const size_t bvn = in.Bv > 0 ? in.Bv : 1;",
+                                "p.lds = sizeof(double) * ((12 + kUnCap) * (size_t)in.k + 3 * bvn) + sizeof(unsigned int) * 4 * bvn + p.slice_bytes;",
+                                "if (in.df_mode == 2) {\n    // LDS copy of the occupancy bitmap",
+                                "if (bytes <= 48 * 1024) { p.occ_half = half; p.slice_bytes = bytes; break; }",
+                                "p.fits = p.lds <= (size_t)kMaxLds - 3072;",
+                                "p.threads = (p.lds + 3072 > (size_t)kMaxLds / 4) ? 2 * kProposeThreads : kProposeThreads;",
+                                "constexpr int kUnCap = 16;", "constexpr int kMaxLds = 160 * 1024;", "#define TBNAV_PROPOSE_THREADS 256",
+                                "constexpr int kWave = 64;", "constexpr int kMixLut = 1024;")),
+                        (host, ("if (!pp.fits) return TBNAV_ERR_UNSUPPORTED;", "if (pp.threads == NT_ && pp.dn == DN_) {", "pp.dn = noise.in_kernel;",
+                                "return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have)",
                                 "h->TW = (xsize + kTS - 1) / kTS;")),
-                        (dev, ("constexpr int kUnCap = 16;", "constexpr int kMaxLds = 160 * 1024;", "#define TBNAV_PROPOSE_THREADS 256",
-                               "constexpr int kWave = 64;", "constexpr int kTS = 32, kTSh = 5,", "constexpr int kMixLut = 1024, kMixLds = 128;")),
+                        (dev, ("constexpr int kTS = 32, kTSh = 5,", "constexpr int kMixLds = 128;")),
                         (ker, ("tt_all <= NT && tt_all <= 256;", "constexpr int kStC = 12, kStIds = 256;",
                                "ntc = min(2 * nW, ds.occ.TW - tc0), n_ids = ((R1 >> kTSh) - tr0 + 1) * ntc;",
                                "if (ntc <= kStC && (whole_table || n_ids <= kStIds)) {",
@@ -158,12 +161,17 @@ def test_the_restated_literals_are_the_host_code_s_and_the_kernel_s():
                                "mg = __double2float_rd(fmin(fmin(ex - x_lo, x_hi - ex), fmin(ey - y_lo, y_hi - ey)));",
                                "const int seg = (c.Bv + kPW - 1) / kPW;", "constexpr int kPW = NT / kWave;",
                                "if (L.lds && cd < kMixLds) return L.lds[cd];", "if (L.glob && cd < kMixLut) return L.glob[cd];")),
-                        (api, ('"rbpf_propose<%d, %s>", h->lk_propose, h->lk_propose_dn ? "true" : "false"',))):
+                        (api, ('"rbpf_propose<%d, %s>", pp.threads, pp.dn ? "true" : "false"', "const ProposePlan& pp = h->last_propose;"))):
         for piece in pieces:
             assert piece in src, (f"the source no longer writes `{piece}`: if the rule changed, change its restatement in tests/propose_cases.py "
                                   "(and the cases' claims) with it; if only its spelling changed, update this list")
-    # the four names are exactly the four explicit instantiations
-    inst = re.findall(r"^template __global__ void rbpf_propose<([^,]+), (true|false)>", ker, flags=re.M)
+    # the four names are exactly the four explicit instantiations: the kernel file makes them from the one list of forms
+    # (rbpf_device.hpp: TBNAV_PROPOSE_FORMS), which the launch dispatch and create's LDS attributes are made from too
+    assert "#define TBNAV_X(NT_, DN_) template __global__ void rbpf_propose<NT_, DN_>(" in ker and ker.count("TBNAV_PROPOSE_FORMS(TBNAV_X)") == 1
+    assert host.count("TBNAV_PROPOSE_FORMS(TBNAV_X)") == 2 and "template __global__ void rbpf_propose<k" not in ker
+    forms = re.search(r"^#define TBNAV_PROPOSE_FORMS\(X\) (.*)$", dev, flags=re.M).group(1)
+    inst = re.findall(r"X\(([^,]+), (true|false)\)", forms)
+    assert " ".join(f"X({nt}, {dn})" for nt, dn in inst) == forms.strip()
     spelled = {"kProposeThreads": pc.K_PROPOSE_THREADS, "2 * kProposeThreads": 2 * pc.K_PROPOSE_THREADS}
     got = sorted(pc.name(spelled[nt], dn == "true") for nt, dn in inst)
     assert len(inst) == 4 and got == sorted(pc.name(nt, dn) for nt in (256, 512) for dn in (False, True))

@@ -379,23 +379,24 @@ def test_the_hot_counts_do_not_collapse_into_one_product(refs):
 
 # ---- the selector --------------------------------------------------------------------------------------------------------------------------
 def test_the_restated_selector_is_the_host_code_s():
-    """The literals of launch_raycast as csrc/rbpf.hip writes them: a change there must come to raycast_cases.select too."""
-    src = open(os.path.join(CSRC, "rbpf.hip")).read()
-    for piece in ("const long side = (long)std::floor(2.0 * reach / h->p.resolution) + 3;", "cap_win = (side * ((side + 2) & ~1L) + 7) & ~7L;",
+    """The literals of plan_raycast as csrc/rbpf_plan.hpp writes them (and of its launch, csrc/rbpf.hip): a change there must come to
+    raycast_cases.select too.  (tests/test_rbpf_plan.py runs the compiled plan_raycast against `select`; this pins the spelling.)"""
+    src = open(os.path.join(CSRC, "rbpf_plan.hpp")).read()
+    for piece in ("const long side = (long)std::floor(2.0 * reach / in.resolution) + 3;", "cap_win = (side * ((side + 2) & ~1L) + 7) & ~7L;",
                   "((78L * 1024 - (long)box_lds_bytes(0, (size_t)bvn) - (long)kBoxStaticLds) / 4) & ~7L;",
                   "if (cap_win > cap_fit) cap_win = std::max(cap_fit, (side + 9) & ~7L);",
-                  "cap_win = std::min(cap_win, (h->raycast_band_rows * ((side + 2) & ~1L) + 7) & ~7L);",
-                  "const long want = ((long)need + need / 8 + 512 + 7) & ~7L;", "cap4 = std::max(((long)need + 256 + 7) & ~7L, (side + 9) & ~7L);",
-                  "(size_t)R * (std::max(bytes, nz_lds) + kBoxStaticLds) <= (size_t)kMaxLds", "h->raycast_adapt != 2 && cap4 > 0 && cap4 <= cap_win;",
-                  "h->raycast_cell16 != 0 && cap_win > 0 && cap_win < 65528 && c.Bv + 64 < 32768;", "const bool force4 = h->raycast_adapt == 3;",
-                  "if (h->raycast_cell16 == 2 && c16_ok && nt == 512) c16 = true;",
-                  "c.Bv < 32768 - kWave && nt >= 512 && lds_win <= (size_t)kMaxLds - 4096", "h->tile_cap = (side * side <= 30000) ? (int)(side * side) : 0;",
-                  "const int need_slot = (int)(h->rc_launches++ % 3u);"):
-        assert piece in src, f"csrc/rbpf.hip no longer writes `{piece}`: restate the change in tests/raycast_cases.py (select) or update this list"
+                  "cap_win = std::min(cap_win, (in.band_rows * ((side + 2) & ~1L) + 7) & ~7L);",
+                  "const long want = ((long)p.need + p.need / 8 + 512 + 7) & ~7L;", "cap4 = std::max(((long)p.need + 256 + 7) & ~7L, (side + 9) & ~7L);",
+                  "(size_t)R * (bytes + kBoxStaticLds) <= (size_t)kMaxLds", "in.adapt != 2 && cap4 > 0 && cap4 <= cap_win;",
+                  "in.cell16 != 0 && cap_win > 0 && cap_win < 65528 && in.Bv + 64 < 32768;", "const bool force4 = in.adapt == 3;",
+                  "if (in.cell16 == 2 && c16_ok && nt == 512) c16 = true;",
+                  "in.Bv < 32768 - kWave && nt >= 512 && p.lds <= (size_t)kMaxLds - 4096", "return (side * side <= 30000) ? (int)(side * side) : 0;",
+                  "return 4 * cap + 2 * ev * bv + 8 * 64 + 4 * bv + 2 * ((bv + 1) & ~(size_t)1);", "size_t h = 256; while (h < 2 * (bv + 64)) h *= 2;",
+                  "constexpr size_t kBoxStaticLds = 896;", "constexpr int kMaxLds = 160 * 1024;", "constexpr int kBoxEv = 8;", "constexpr int kBoxEvFour = 4;"):
+        assert piece in src, f"csrc/rbpf_plan.hpp no longer writes `{piece}`: restate the change in tests/raycast_cases.py (select) or update this list"
+    assert "const int need_slot = (int)(h->rc_launches++ % 3u);" in open(os.path.join(CSRC, "rbpf.hip")).read()
     dev = open(os.path.join(CSRC, "rbpf_device.hpp")).read()
-    for piece in ("return 4 * cap + 2 * ev * bv + 8 * 64 + 4 * bv + 2 * ((bv + 1) & ~(size_t)1);", "size_t h = 256; while (h < 2 * (bv + 64)) h *= 2;",
-                  "constexpr size_t kBoxStaticLds = 896;", "constexpr int kMaxLds = 160 * 1024;", "constexpr int kHotMin = 16;", "constexpr int kVeryHot = 80;",
-                  "constexpr int kBoxEv = 8;", "constexpr int kBoxEvFour = 4;", "constexpr int kHotSide = 7;", "constexpr int kBoxSideMax = 176;",
+    for piece in ("constexpr int kHotMin = 16;", "constexpr int kVeryHot = 80;", "constexpr int kHotSide = 7;", "constexpr int kBoxSideMax = 176;",
                   "constexpr int kMapTilesMax = 64;"):
         assert piece in dev, piece
     ray = open(os.path.join(CSRC, "rbpf_raycast.hip")).read()

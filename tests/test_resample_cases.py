@@ -28,7 +28,8 @@ def table(pkg):
 
 def test_the_restated_literals_are_the_sources():
     read = lambda name: open(os.path.join(CSRC, name)).read()
-    for src, pieces in ((read("rbpf_device.hpp"), ("constexpr int kNormChunk = 2048;", "constexpr int kResampleThreads = 1024;", "constexpr int kTS = 32, kTSh = 5,")),
+    for src, pieces in ((read("rbpf_plan.hpp"), ("constexpr int kNormChunk = 2048;",)),
+                        (read("rbpf_device.hpp"), ("constexpr int kResampleThreads = 1024;", "constexpr int kTS = 32, kTSh = 5,")),
                         (read("rbpf_normalize.hpp"), ("const int neff = (int)(1.0 / sq);", "const int res = (neff < (N / 2)) ? 1 : 0;",
                                                       "constexpr int kSeqBlk = NTHR == 256 ? 32 : 16;", "const bool one_chunk = N <= kNormChunk;",
                                                       "const bool plain = one_chunk || !PAR;", "int lo = 0, hi = N - 1;",
@@ -39,9 +40,10 @@ def test_the_restated_literals_are_the_sources():
                                                      "if (ov > sv[threadIdx.x] || (ov == sv[threadIdx.x] && oi < si[threadIdx.x]))")),
                         (read("rbpf_batch.hip"), ("out->neff = static_cast<int>(1.0 / sq);", "out->resampled = (out->neff < (N / 2)) ? 1 : 0;")),
                         (read("rbpf.hip"), ("const bool overlap = !local_only && !h->timing;",
-                                            "rc = launch_raycast(h, c, h->N, h->d_sens, overlap ? &nz : nullptr, d_err, beams_dev);",
-                                            "if (!local_only && !overlap) {\n    rc = launch_normalize(st);",
-                                            "const int blocks = count + (nz ? 1 : 0);",
+                                            "TBNAV_TRY(launch_raycast(h, c, h->N, h->d_sens, overlap ? &nz : nullptr, d_err, beams_dev));",
+                                            "if (!local_only && !overlap)   // (no gate, no flag: see above)\n    TBNAV_TRY(launch_normalize(h, NormArgs{",
+                                            "p.grid = count + (p.box() && nz ? 1 : 0);",
+                                            "return nz ? launch_normalize(h, *nz) : TBNAV_OK;",
                                             "const int blocks = (int)std::min<size_t>((n + kResampleThreads - 1) / kResampleThreads, 8192);",
                                             "const int chunks = (int)std::min<size_t>(std::max<size_t>(work / 2048, 1), 64);")),
                         (read("rbpf_api.hip"), ('"rbpf_raycast_box<%d, %d, %s, %d>"', 'snprintf(raycast, (size_t)raycast_cap, "rbpf_raycast");',

@@ -88,17 +88,22 @@ def test_the_slice_regimes_are_what_the_restated_expression_gives():
 
 
 def test_the_restated_expressions_are_the_host_code_s():
-    """The literals of the two expressions as csrc/rbpf.hip writes them: a change there must come here too."""
-    src = open(os.path.join(CSRC, "rbpf.hip")).read()
-    for piece in ("for (int margin : {48, 16, 0})", "if (bytes <= 48 * 1024)", "std::min(h->xsize, 2 * half + 1)",
-                  "std::min(h->words, (2 * half + 1 + 63) / 64 + 1)", "(size_t)rows * nw * 8 + (size_t)rows * 4",
-                  "(int)std::ceil(((double)h->p.range_max + 8.0 * std::sqrt(sig)) / h->p.resolution) + 2",
+    """The literals of the two expressions as csrc/rbpf_plan.hpp writes them (sampling_spread, lookup_half_cells, plan_propose) and
+    as csrc/rbpf.hip hands them their inputs: a change there must come here too."""
+    src = open(os.path.join(CSRC, "rbpf_plan.hpp")).read()
+    for piece in ("for (int margin : {48, 16, 0})", "if (bytes <= 48 * 1024)", "std::min(in.xsize, 2 * half + 1)",
+                  "std::min(in.words, (2 * half + 1 + 63) / 64 + 1)", "(size_t)rows * nw * 8 + (size_t)rows * 4",
+                  "return 8.0 * std::sqrt(sig);", "(int)std::ceil((in.range_max + in.spread) / in.resolution) + 2",
                   "std::max(std::hypot(T_icp[1], T_icp[2]), std::fabs(u[1]))",
-                  "(double)h->p.range_max + std::hypot(h->p.Trs[1], h->p.Trs[2]) + move + 8.0 * std::sqrt(sig)",
-                  "if (h->sm_on && c.icp_ok) half += h->sm.max_moves * h->sm.lstep;",
-                  "(int)std::ceil(half / h->p.resolution) + 3", "if (h->full_edt || half_cells > h->xsize) half_cells = h->xsize;"):
-        assert piece in src, (f"csrc/rbpf.hip no longer writes `{piece}`: if the window or slice rule changed, change half_cells / slice_regime in "
+                  "range_max + std::hypot(Trs[1], Trs[2]) + move + spread;",
+                  "if (matcher_travel > 0.0) half += matcher_travel;",
+                  "(int)std::ceil(half / resolution) + 3", "return (whole_map || half_cells > xsize) ? xsize : half_cells;"):
+        assert piece in src, (f"csrc/rbpf_plan.hpp no longer writes `{piece}`: if the window or slice rule changed, change half_cells / slice_regime in "
                               "tests/scanmatch_cases.py (and the cases' claimed values) with it; if only its spelling changed, update this list")
+    host = open(os.path.join(CSRC, "rbpf.hip")).read()
+    for piece in ("const bool matching = h->sm_on && c.icp_ok;", "matching ? h->sm.max_moves * h->sm.lstep : 0.0,", "h->p.resolution, h->full_edt, h->xsize);",
+                  "(double)h->p.range_max, spread, h->p.resolution}", "sampling_spread(h->p.sample_range, h->p.motion_noise);"):
+        assert piece in host, f"csrc/rbpf.hip no longer writes `{piece}`: see above"
     api = open(os.path.join(CSRC, "rbpf_api.hip")).read()
     assert f"h->sm.max_moves = {smc.MAX_MOVES};" in api
 
