@@ -309,6 +309,14 @@ int tbnav_mppi_debug_sincos(const double* x_host, int32_t n, double* sin_host, d
  * *used_reciprocal = 0 when this lambda takes the plain division (reciprocal not normal, or lambda's significand all ones). */
 int tbnav_mppi_debug_div_lambda(const double* x_host, int32_t n, double lambda, double* out_host, int32_t* used_reciprocal);
 
+/* The last tick's combine once more, by the GENERAL form of mppi_combine (the text the sharded ticks run) over the same records
+ * and the same warm start, into a scratch vector: u_host [2][T] receives the updated controls BEFORE the shift (column 0 is what
+ * the tick returned, column i + 1 what tbnav_mppi_get_controls gives as column i) — lets the tests hold the straight-line form of
+ * the latency-bound ticks to the general one bit for bit.  Reads the handle, changes nothing of it.  Only after a plain
+ * (not replayed) tick on this handle whose combine was mppi_combine<KEEP, 0> over one group of at most KEEP * 64 records and
+ * before anything else touches the handle's controls; TBNAV_ERR_INVALID_ARG otherwise. */
+int tbnav_mppi_debug_combine_general(tbnav_mppi* h, double* u_host);
+
 /* ---- measurement hook -------------------------------------------------------------------------- */
 
 /* One tick with a hipEvent pair around each kernel, recorded on `stream` (the stream the kernels

@@ -80,6 +80,38 @@ __device__ __forceinline__ double lane63(double v) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
 }
 __device__ __forceinline__ double wave_sum_dpp(double v) { return lane63(wave_scan_incl(v, 0)); }
+// N wave sums at once, for a wave that has its SIMD to itself (the time-step waves of mppi_combine's straight-line form): nothing
+// else fills its issue slots, so every instruction issued is paid for (measured: about 4 cycles each, docs/lab_notebook.md, Round 23).
+//  * Only the TOTAL is wanted, and it is read from lane 63.  Lane 63's sum is wave_scan_incl's, stage for stage:
+//    ((x + shr1) + shr2) + shr3, then row_shr:4, row_shr:8, row_bcast:15, row_bcast:31 — the same bits as wave_sum_dpp.  What the
+//    scan's row and bank masks do is keep `old` = 0 in lanes that must not receive.  For row_shr:4 / 8 those are exactly the lanes
+//    whose source lies outside the row, where bound_ctrl writes the same +0.0.  For the two row_bcast they are rows that lane 63
+//    never reads afterwards: row_bcast:15 reaches lane 63 from lane 47 and lane 31 from lane 15, row_bcast:31 lane 63 from lane 31.
+//    So every stage is a full-mask move with bound_ctrl (dpp_shift_or_zero) and none has a `v_mov_b32 v, 0` in front of each half;
+//    the lanes below 63 do NOT hold prefix sums.
+//  * Stage s of every value, then stage s + 1: one sum's DPP moves stand between another's add and the moves that read it, where
+//    six scans in a row had an `s_nop` for the DPP hazard in most stages.
+// v[n] comes back as the total, broadcast.
+template <int CTRL, int N>
+__device__ __forceinline__ void wave_sums_stage(double (&out)[N], const double (&src)[N]) {
+#pragma unroll
+  for (int n = 0; n < N; ++n) out[n] += dpp_shift_or_zero<CTRL>(src[n]);
+}
+template <int N>
+__device__ __forceinline__ void wave_sums_dpp(double (&v)[N]) {
+  double out[N];
+#pragma unroll
+  for (int n = 0; n < N; ++n) out[n] = v[n];
+  wave_sums_stage<0x111>(out, v);    // row_shr:1 .. 3 read the lane's own value
+  wave_sums_stage<0x112>(out, v);
+  wave_sums_stage<0x113>(out, v);
+  wave_sums_stage<0x114>(out, out);  // row_shr:4
+  wave_sums_stage<0x118>(out, out);  // row_shr:8: lane 15 of each row holds the row's sum
+  wave_sums_stage<0x142>(out, out);  // row_bcast:15
+  wave_sums_stage<0x143>(out, out);  // row_bcast:31
+#pragma unroll
+  for (int n = 0; n < N; ++n) v[n] = lane63(out[n]);
+}
 template <int CTRL, int ROW_MASK, int BANK_MASK>
 __device__ __forceinline__ double dpp_or_inf(double src) {
   const double inf = __builtin_huge_val();

@@ -198,6 +198,7 @@ int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipS
 #undef TBNAV_COMBINE_KEEP
 #undef TBNAV_COMBINE
   TBNAV_HIP(hipGetLastError());
+  h->lk_records = direct ? nullptr : d_records; h->lk_S = S; h->lk_G = G; h->lk_ushift = usrc.shift;
   ++h->seq;
   if (h->publish_next) h->published = h->seq;
   h->ucur = 1 - h->ucur;       // the freshly written vector is current ...
@@ -981,6 +982,35 @@ int tbnav_mppi_debug_div_lambda(const double* x_host, int32_t n, double lambda, 
   if (e == hipSuccess) { hipLaunchKernelGGL(mppi_debug_div_lambda, dim3((n + 255) / 256), dim3(256), 0, nullptr, n, dx, lam, dy); e = hipGetLastError(); }
   if (e == hipSuccess) e = hipMemcpy(out_host, dy, sizeof(double) * n, hipMemcpyDeviceToHost);
   (void)hipFree(dx); (void)hipFree(dy);
+  TBNAV_HIP(e);
+  return TBNAV_OK;
+}
+
+int tbnav_mppi_debug_combine_general(tbnav_mppi* h, double* u_host) {
+  if (!h || !u_host) return TBNAV_ERR_INVALID_ARG;
+  const int keep = h->lk_combine[0], S = h->lk_S, T = h->T;
+  if (h->lk_combine[1] != 0 || (keep != 2 && keep != 4 && keep != 8) || !h->lk_records || h->lk_G != 1 || S > keep * kWave) return TBNAV_ERR_INVALID_ARG;
+  DeviceGuard guard(h->device);
+  // launch_combine's arithmetic for one group; the tick's input controls are the vector that is no longer current (the tick wrote
+  // the other one), read with the shift the tick read them with
+  int tpr_log2 = 0;
+  while ((1 << tpr_log2) < S && (1 << tpr_log2) < kWave) ++tpr_log2;
+  const int steps_per_block = TBNAV_COMBINE_WAVES * (kWave >> tpr_log2), blocks = (T + steps_per_block - 1) / steps_per_block;
+  const DirectSrc ds{nullptr, 0ull, nullptr, nullptr, 0u};
+  const RngArgs off{0, 0, 0.0, 0.0};
+  double* d = nullptr;   // [2][T] controls, then the two to apply
+  TBNAV_HIP(hipDeviceSynchronize());
+  hipError_t e = hipMalloc((void**)&d, sizeof(double) * (2 * (size_t)T + 2));
+#define TBNAV_GENERAL(KEEP) hipLaunchKernelGGL((mppi_combine<KEEP, 1>), dim3(blocks), dim3(TBNAV_COMBINE_WAVES * kWave), 0, nullptr, h->lk_records, (const double*)h->d_u[1 - h->ucur], (double*)nullptr, \
+                                               (const uint64_t*)nullptr, T, S, h->lk_ushift, blocks, 1, tpr_log2, (uint64_t*)nullptr, lam_of(h), h->p.max_wheel_vel, h->uinit[0], h->uinit[1], d, d + 2 * (size_t)T, \
+                                               (double*)nullptr, 0.0, ds, rng_rest(off))
+  if (e == hipSuccess) {
+    if (keep == 2) TBNAV_GENERAL(2); else if (keep == 4) TBNAV_GENERAL(4); else TBNAV_GENERAL(8);
+    e = hipGetLastError();
+  }
+#undef TBNAV_GENERAL
+  if (e == hipSuccess) e = hipMemcpy(u_host, d, sizeof(double) * 2 * (size_t)T, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
   TBNAV_HIP(e);
   return TBNAV_OK;
 }

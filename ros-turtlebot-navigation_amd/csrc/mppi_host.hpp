@@ -22,6 +22,8 @@ struct tbnav_mppi {
   int T = 0, K = 0, S = 0, device = 0;
   int lk_rollout[5] = {0, 0, 0, 0, 0};  // the instantiation the last rollout launch picked: kind (1 fused, 2 scan, 3 prefix, 4 cost, 5 field), template arguments
   int lk_combine[2] = {0, 0};           // ... and the last combine: KEEP, DIRECT  (tbnav_mppi_last_kernel_names)
+  const double* lk_records = nullptr;   // ... what that combine read: its records, S, G and whether it read the controls shifted
+  int lk_S = 0, lk_G = 0, lk_ushift = 0;   //     (tbnav_mppi_debug_combine_general)
   double xd[3] = {0, 0, 0};
   double uinit[2] = {0, 0};
   double* d_u[2] = {nullptr, nullptr};  // [2][T] each; d_u[ucur] holds the controls, d_u[1-ucur] receives the next update

@@ -370,6 +370,13 @@ __device__ __forceinline__ void combine_steps(const double* __restrict__ records
       }
     }
   }
+  if constexpr (STRAIGHT) {
+    // the six sums side by side, every stage without a zeroed `old` (tbnav::wave_sums_dpp): each the same bits as wave_sum_dpp
+    // (tests/test_mppi_combine_chains_gpu.py); six whole scans one after the other issue 84 `v_mov_b32 v, 0` and 27 `s_nop` more
+    double s[6] = {W, NL, NR, SD, SE, SN};
+    tbnav::wave_sums_dpp(s);
+    W = s[0]; NL = s[1]; NR = s[2]; SD = s[3]; SE = s[4]; SN = s[5];
+  } else   // (the general form, as it was)
   if (tpr == kWave) {
     W = tbnav::wave_sum_dpp(W); NL = tbnav::wave_sum_dpp(NL); NR = tbnav::wave_sum_dpp(NR);
     SD = tbnav::wave_sum_dpp(SD); SE = tbnav::wave_sum_dpp(SE); SN = tbnav::wave_sum_dpp(SN);

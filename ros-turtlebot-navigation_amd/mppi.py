@@ -266,6 +266,12 @@ class MPPI:
         capi.check(self._L.tbnav_mppi_get_controls(self._h, u.ctypes.data), "get_controls")
         return u
 
+    def debugCombineGeneral(self) -> np.ndarray:
+        """The last tick's combine once more by the general form of mppi_combine: [2][T], before the shift (tbnav_mppi.h)."""
+        u = np.empty((2, self.steps))
+        capi.check(self._L.tbnav_mppi_debug_combine_general(self._h, u.ctypes.data), "debug_combine_general")
+        return u
+
     def setControls(self, u: np.ndarray):
         u = np.ascontiguousarray(u, dtype=np.float64)
         assert u.shape == (2, self.steps)

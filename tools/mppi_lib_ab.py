@@ -3,12 +3,13 @@ and over 20-tick batches of plain launches (what the driver's --steps 20 times).
 Each library is loaded in a process of its own.
   --dump DIR   no timing: every library writes DIR/<its position>/<shape>.npz instead — after three device-noise ticks (seed 42) the
                control sequence, the controls to apply, J of the last tick, and the K-slice records of a fourth tick — for (K, T) =
-               (1024, 50), (1000, 50), (100, 50), (1024, 100), (2048, 30), (1024, 65) and the arc dynamics at (1024, 50), (1024, 100),
-               (1024, 65); the files of any two
+               (1024, 50), (1000, 50), (100, 50), (1024, 100), (2048, 30), (1024, 65), (2048, 50) and the arc dynamics at (1024, 50),
+               (1024, 100), (1024, 65); the files of any two
                libraries are then compared array by array, bit for bit (exit code 1 on a difference)."""
 import os, subprocess, sys, time
 DUMP_SHAPES = [(1024, 50, "rk4"), (1000, 50, "rk4"), (100, 50, "rk4"), (1024, 100, "rk4"), (2048, 30, "rk4"), (1024, 50, "arc"),
-               (1024, 100, "arc"), (1024, 65, "rk4"), (1024, 65, "arc")]   # (T = 65: two steps per lane, the last live lane half padding)
+               (1024, 100, "arc"), (1024, 65, "rk4"), (1024, 65, "arc"),   # (T = 65: two steps per lane, the last live lane half padding)
+               (2048, 50, "rk4")]                                          # (the straight-line mppi_combine<4, 0> at the shipped horizon)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, ROOT)
