@@ -203,7 +203,10 @@ int tbnav_rbpf_pool_selftest(uint32_t cap_tiles, int32_t rounds, int32_t callers
 int tbnav_rbpf_gather_local(tbnav_rbpf* h, const int32_t* local_parent /*[N], -1 = leave*/);
 /* A particle as one device buffer: header, state (pose, prev_pose, weight), the indices and 8 KB payloads of the
  * tiles (log-odds + occupancy bits) it does not share with the empty map, its tile-row counts, and its stored distance field if
- * that is authoritative (injected).  export_size: bytes the export of `slot` needs now. */
+ * that is authoritative (injected).  export_size: bytes the export of `slot` needs now.  import_particle_dev is
+ * import_batch_dev with n = 1 and the blob at d_buf: the same refusals, and the same contract when the pool runs out — either
+ * nothing is touched, or the slot is left with the EMPTY map (no tiles, occupied counts 0, no stored field, every distance
+ * unreached; pose, prev_pose and weight stay the slot's own), never with a part of the blob's map. */
 int tbnav_rbpf_export_size(tbnav_rbpf* h, int32_t slot, uint64_t* bytes);
 int tbnav_rbpf_export_particle_dev(tbnav_rbpf* h, int32_t slot, void* d_buf, uint64_t capacity, uint64_t* bytes);
 int tbnav_rbpf_import_particle_dev(tbnav_rbpf* h, int32_t slot, const void* d_buf, uint64_t bytes);
@@ -213,7 +216,9 @@ int tbnav_rbpf_import_particle_dev(tbnav_rbpf* h, int32_t slot, const void* d_bu
  * receivers.  import: slot slots[i] (each at most once) takes the blob at d_buf + offsets[i] (several slots may name the
  * same blob).  Two launches each, whatever n.  import returns TBNAV_ERR_POOL_EXHAUSTED with NOTHING touched when the incoming
  * tiles exceed the free tiles plus every tile the destination slots name; inside that bound the slots are released first and an
- * exhaustion found while unpacking leaves those slots with empty maps (a sharded driver must then stop on every rank). */
+ * exhaustion found while unpacking leaves every listed slot either with its blob's particle, whole, or with the EMPTY map (no
+ * tiles, occupied counts 0, no stored field, every distance unreached; its pose, prev_pose and weight as before the call) — a
+ * sharded driver must then stop on every rank. */
 int tbnav_rbpf_export_batch_sizes(tbnav_rbpf* h, int32_t n, const int32_t* slots, uint64_t* sizes_out /*[n]*/);
 int tbnav_rbpf_export_batch_dev(tbnav_rbpf* h, int32_t n, const int32_t* slots, void* d_buf, uint64_t capacity,
                                 uint64_t* offsets_out /*[n + 1]*/);

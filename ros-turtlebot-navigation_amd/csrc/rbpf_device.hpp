@@ -635,13 +635,9 @@ __global__ __launch_bounds__(kResampleThreads) void rbpf_resample_apply(int N, i
 __global__ __launch_bounds__(256) void rbpf_tiles_to_dense(int xs, size_t G, TilePool P, MapT M, int p, double* __restrict__ out);
 __global__ __launch_bounds__(kWave) void rbpf_dense_to_tiles(int xs, double cut_occ, TilePool P, MapT M, int p, const double* __restrict__ in,
                                                              int* __restrict__ trow_occ, int* __restrict__ n_occ, int* __restrict__ err);
-__global__ __launch_bounds__(256) void rbpf_release_slot(TilePool P, MapT M, int p);
 // rbpf_migrate.hip
 __global__ __launch_bounds__(256) void rbpf_pack_tiles(TilePool P, const unsigned int* __restrict__ ids, double* __restrict__ out,
                                                        unsigned int* __restrict__ out_bm);
-__global__ __launch_bounds__(256) void rbpf_unpack_tiles(TilePool P, MapT M, int p, const unsigned int* __restrict__ tidx,
-                                                         const double* __restrict__ in, const unsigned int* __restrict__ in_bm,
-                                                         int* __restrict__ err);
 __global__ __launch_bounds__(256) void rbpf_count_tiles(MapT M, const int* __restrict__ slots, const int* __restrict__ fstate, int2* __restrict__ out);
 __global__ __launch_bounds__(256) void rbpf_pack_batch(TilePool P, MapT M, const double* __restrict__ pose, const double* __restrict__ prev,
                                                        const double* __restrict__ weight, const int* __restrict__ trow, const int* __restrict__ nocc,

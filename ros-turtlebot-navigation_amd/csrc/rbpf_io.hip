@@ -74,42 +74,9 @@ int tbnav_rbpf_export_particle_dev(tbnav_rbpf* h, int32_t slot, void* d_buf, uin
 }
 
 int tbnav_rbpf_import_particle_dev(tbnav_rbpf* h, int32_t slot, const void* d_buf, uint64_t bytes) {
-  if (!h || !d_buf || slot < 0 || slot >= h->N || bytes < sizeof(BlobHeader)) return TBNAV_ERR_INVALID_ARG;
-  DeviceGuard guard(h->device);
-  hipStream_t st = h->stream;
-  const char* b = static_cast<const char*>(d_buf);
-  BlobHeader hd{};
-  TBNAV_HIP(hipStreamSynchronize(st));
-  TBNAV_HIP(hipMemcpy(&hd, b, sizeof hd, hipMemcpyDeviceToHost));
-  if (hd.magic != kBlobMagic || hd.xsize != (uint32_t)h->xsize || hd.TT != (uint32_t)h->TT || hd.n_tiles > (uint32_t)h->TT) return TBNAV_ERR_INVALID_ARG;
-  const BlobLayout L = blob_layout(h, hd.n_tiles, hd.has_codes != 0);
-  if (L.total > bytes) return TBNAV_ERR_INVALID_ARG;
-  if (hd.has_codes) { const int rc = ensure_codes(h); if (rc != TBNAV_OK) return rc; }
-  const MapT M = map_of(h);
-  for (int q = 0; q < 4; ++q) h->h_err[q] = 0;
-  hipLaunchKernelGGL(rbpf_release_slot, dim3((h->TT + 255) / 256), dim3(256), 0, st, h->pool, M, slot);
-  TBNAV_HIP(hipGetLastError());
-  if (hd.n_tiles) {
-    hipLaunchKernelGGL(rbpf_unpack_tiles, dim3(hd.n_tiles), dim3(256), 0, st, h->pool, M, slot, reinterpret_cast<const unsigned int*>(b + L.tidx),
-                       reinterpret_cast<const double*>(b + L.tiles), reinterpret_cast<const unsigned int*>(b + L.tile_bm), h->d_err);
-    TBNAV_HIP(hipGetLastError());
-  }
-  StatePtrs sp = state_ptrs(h->d_state[h->cur], h->N);
-  const double* bs = reinterpret_cast<const double*>(b + L.state);
-  TBNAV_HIP(hipMemcpyAsync(sp.pose + (size_t)slot * 3, bs, sizeof(double) * 3, hipMemcpyDeviceToDevice, st));
-  TBNAV_HIP(hipMemcpyAsync(sp.prev + (size_t)slot * 3, bs + 3, sizeof(double) * 3, hipMemcpyDeviceToDevice, st));
-  TBNAV_HIP(hipMemcpyAsync(sp.weight + slot, bs + 6, sizeof(double), hipMemcpyDeviceToDevice, st));
-  TBNAV_HIP(hipMemcpyAsync(h->d_trow[h->cur] + (size_t)slot * h->TW, b + L.trow, sizeof(int) * h->TW, hipMemcpyDeviceToDevice, st));
-  TBNAV_HIP(hipMemcpyAsync(h->d_nocc[h->cur] + slot, &hd.nocc, sizeof(int), hipMemcpyHostToDevice, st));
-  const int fs = hd.has_codes ? 2 : 0;
-  if (hd.has_codes) {
-    TBNAV_HIP(hipMemcpyAsync(h->d_code[h->cur] + (size_t)slot * h->G, b + L.codes, sizeof(uint16_t) * h->G, hipMemcpyDeviceToDevice, st));
-    h->fstate_dirty = true;
-  }
-  TBNAV_HIP(hipMemcpyAsync(h->d_fstate + slot, &fs, sizeof(int), hipMemcpyHostToDevice, st));
-  TBNAV_HIP(hipStreamSynchronize(st));  // hd / fs are locals
-  if (h->h_err[3] & 8) return TBNAV_ERR_POOL_EXHAUSTED;
-  return TBNAV_OK;
+  if (!h || !d_buf) return TBNAV_ERR_INVALID_ARG;
+  const uint64_t at = 0;   // a batch of one: the same checks, the same two launches, the same contract when the pool runs out
+  return tbnav_rbpf_import_batch_dev(h, 1, &slot, d_buf, bytes, &at);
 }
 
 // ---- the same for many particles at once (what a cross-rank resample needs: hundreds of particles per rank) ------------

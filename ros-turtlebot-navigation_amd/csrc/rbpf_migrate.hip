@@ -14,23 +14,6 @@ __global__ __launch_bounds__(256) void rbpf_pack_tiles(TilePool P, const unsigne
   for (int i = threadIdx.x; i < kTileCells / 2; i += blockDim.x) dst[i] = src[i];
   if (threadIdx.x < kTS) out_bm[(size_t)blockIdx.x * kTS + threadIdx.x] = P.bm[(size_t)ids[blockIdx.x] * kTS + threadIdx.x];
 }
-// one workgroup per received tile: take a free tile, name it in the (released) slot's table, fill it
-__global__ __launch_bounds__(256) void rbpf_unpack_tiles(TilePool P, MapT M, int p, const unsigned int* __restrict__ tidx,
-                                                         const double* __restrict__ in, const unsigned int* __restrict__ in_bm,
-                                                         int* __restrict__ err) {
-  __shared__ unsigned int sid;
-  if (threadIdx.x == 0) {
-    const unsigned int id = tile_pop(P, blockIdx.x);
-    if (id) { P.ref[id] = 1; M.table[(size_t)p * M.TT + tidx[blockIdx.x]] = id; } else atomicOr(&err[3], 8);
-    sid = id;
-  }
-  __syncthreads();
-  if (sid == 0u) return;
-  const double2* src = reinterpret_cast<const double2*>(in + (size_t)blockIdx.x * kTileCells);
-  double2* dst = reinterpret_cast<double2*>(P.lo + (size_t)sid * kTileCells);
-  for (int i = threadIdx.x; i < kTileCells / 2; i += blockDim.x) dst[i] = src[i];
-  if (threadIdx.x < kTS) P.bm[(size_t)sid * kTS + threadIdx.x] = in_bm[(size_t)blockIdx.x * kTS + threadIdx.x];
-}
 // tiles named by each listed slot's table, and the slot's field state
 __global__ __launch_bounds__(256) void rbpf_count_tiles(MapT M, const int* __restrict__ slots, const int* __restrict__ fstate, int2* __restrict__ out) {
   __shared__ int tot;
@@ -158,7 +141,10 @@ __global__ __launch_bounds__(256) void rbpf_unpack_batch(TilePool P, MapT M, dou
       if (sb == kPoolScattered) tab[tidx[j]] = 0u;
       if (id) { P.ref[id] = 1; M.shed[(size_t)slot * M.TT + tidx[j]] = id; }
     }
-    if (tid == 0) atomicOr(&err[3], 8);
+    // the empty map's counts and field: nothing occupied, no stored field, every cell unreached (the state stays the slot's own)
+    for (int r = tid; r < M.TW; r += 256) trow[(size_t)slot * M.TW + r] = 0;
+    if (codes) for (size_t i = tid; i < G; i += 256) codes[(size_t)slot * G + i] = kCodeUnreached;
+    if (tid == 0) { nocc[slot] = 0; fstate[slot] = 0; atomicOr(&err[3], 8); }
     return;
   }
   const double2* src = reinterpret_cast<const double2*>(b + L.tiles);

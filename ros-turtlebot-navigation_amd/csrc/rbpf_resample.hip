@@ -74,18 +74,6 @@ __global__ __launch_bounds__(kWave) void rbpf_dense_to_tiles(int xs, double cut_
   }
   if (lane == 0 && n_occ_tile) { atomicAdd(&trow_occ[(size_t)p * M.TW + ti], n_occ_tile); atomicAdd(&n_occ[p], n_occ_tile); }
 }
-// Drop every tile reference of slot p (table and shed) and leave it with the empty map: the slot is about to receive
-// an imported particle (tbnav_rbpf_import_particle_dev).
-__global__ __launch_bounds__(256) void rbpf_release_slot(TilePool P, MapT M, int p) {
-  unsigned int* tab = M.table + (size_t)p * M.TT;
-  unsigned int* shed = M.shed + (size_t)p * M.TT;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < M.TT; t += gridDim.x * blockDim.x) {
-    const unsigned int id = tab[t], sh = shed[t];
-    if (id && atomicSub(&P.ref[id], 1) == 1) tile_push(P, id);
-    if (sh && atomicSub(&P.ref[sh], 1) == 1) tile_push(P, sh);
-    tab[t] = 0u; shed[t] = 0u;
-  }
-}
 __global__ __launch_bounds__(256) void rbpf_gather_weights(int N, const double* __restrict__ gw, const int* __restrict__ parent, double* __restrict__ weight) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m < N) weight[m] = gw[parent[m]];

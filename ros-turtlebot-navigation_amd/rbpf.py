@@ -170,6 +170,14 @@ class ParticleFilter:
         assert par.size == self.N
         capi.check(self._L.tbnav_rbpf_gather_local(self._h, par.ctypes.data), "gather_local")
 
+    def copyParticle(self, dst_slot: int, src: "ParticleFilter", src_slot: int, check=True) -> int:
+        """Slot dst_slot of this filter becomes a deep copy of slot src_slot of `src` (tbnav_rbpf_copy_particle; `src` may be
+        this filter): same device, grid and distance-field mode."""
+        rc = self._L.tbnav_rbpf_copy_particle(self._h, int(dst_slot), src._h, int(src_slot))
+        if check:
+            capi.check(rc, "tbnav_rbpf_copy_particle")
+        return rc
+
     # ---- state access ----
     def particles(self):
         pose = np.empty((self.N, 3)); prev = np.empty((self.N, 3)); w = np.empty(self.N)
