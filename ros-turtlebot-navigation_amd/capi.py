@@ -76,6 +76,7 @@ class NavSolveInfo(C.Structure):
 
 
 NAV_MAX_SIDE, NAV_MAX_COST, NAV_UNREACHED = 2048, 64, 0xFFFFFFFF
+NAV_MAX_REACH, NAV_BEST_PARTICLE = 32, -1
 
 
 class RbpfParams(C.Structure):
@@ -259,6 +260,12 @@ def lib() -> C.CDLL:
         "tbnav_nav_last_solve": (C.c_int, [vp, C.POINTER(NavSolveInfo), C.c_char_p, i32]),
         "tbnav_nav_apply_to_mppi": (C.c_int, [vp, vp, dbl, dbl]),
         "tbnav_nav_apply_to_mppi_group": (C.c_int, [vp, vp, dbl, dbl]),
+        "tbnav_nav_get_cost": (C.c_int, [vp, vp]),
+        "tbnav_nav_inflation_tables": (C.c_int, [dbl, dbl, dbl, dbl, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]),
+        "tbnav_nav_set_cost_from_rbpf": (C.c_int, [vp, vp, i32, dbl, dbl, dbl]),
+        "tbnav_nav_profile_cost_from_rbpf": (C.c_int, [vp, vp, i32, dbl, dbl, dbl, i32, C.POINTER(C.c_float)]),
+        "tbnav_mppi_set_cost_field_from_rbpf": (C.c_int, [vp, vp, i32, dbl, dbl, dbl]),
+        "tbnav_nav_last_cost_kernel": (C.c_int, [vp, C.c_char_p, i32]),
         # communicators (include/tbnav_comm.h) and the sharded MPPI tick
         "tbnav_comm_unique_id": (C.c_int, [vp]),
         "tbnav_comm_unique_id_ipc": (C.c_int, [vp]),

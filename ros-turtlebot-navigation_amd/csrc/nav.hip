@@ -9,7 +9,7 @@
 #include <vector>
 
 #include "mppi_host.hpp"
-#include "tbnav_nav.h"
+#include "nav_host.hpp"
 
 namespace tbnav_nk {
 
@@ -147,21 +147,6 @@ __global__ void nav_field(const unsigned* __restrict__ d, int n, double resoluti
 using namespace tbnav_nk;
 using tbnav_mh::DeviceGuard;
 
-struct tbnav_nav {
-  tbnav_nav_params p;
-  int device = 0, n = 0, tiles_x = 0, tiles_y = 0;
-  double inv = 0.0;                 // 1.0 / resolution (G1)
-  uint8_t* d_cost = nullptr;        // [nx][ny] what the next solve uses
-  unsigned* d_d = nullptr;          // [nx][ny] the last solve's cost-to-go
-  float* d_field = nullptr;         // [nx][ny] G5 of the last get_field / apply
-  unsigned* d_flags = nullptr;      // [2][tiles] active tiles of even and odd rounds
-  unsigned* d_rec = nullptr;        // [batch][2] a batch's round records
-  std::vector<uint8_t> cost, cost_solved;   // host copies: the grid set last, and the one the last solve used (G6 walks over it)
-  std::vector<unsigned> d_host;     // the downloaded cost-to-go (filled at its first use after a solve)
-  bool cost_set = false, solved = false, d_host_valid = false;
-  tbnav_nav_solve_info info{0, {0, 0}, 0, 0, {0, 0}, 0};
-};
-
 namespace {
 // Rounds per batch: in open space the front crosses about a tile per round, so half the tiles along both sides is a batch or two
 // per solve; at least 4 (a host read costs several launches), at most kMaxBatch (what a finished solve wastes on launches that find
@@ -181,6 +166,15 @@ int download(tbnav_nav* h) {
   h->d_host.resize((size_t)h->n);
   TBNAV_HIP(hipMemcpy(h->d_host.data(), h->d_d, sizeof(unsigned) * (size_t)h->n, hipMemcpyDeviceToHost));
   h->d_host_valid = true;
+  return TBNAV_OK;
+}
+int download_cost_solved(tbnav_nav* h) {
+  if (h->cost_solved_valid) return TBNAV_OK;
+  DeviceGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  h->cost_solved.resize((size_t)h->n);
+  TBNAV_HIP(hipMemcpy(h->cost_solved.data(), h->d_cost_solved, (size_t)h->n, hipMemcpyDeviceToHost));
+  h->cost_solved_valid = true;
   return TBNAV_OK;
 }
 bool cap_ok(double cap) { return std::isfinite(cap) && cap > 0.0; }
@@ -225,6 +219,8 @@ int tbnav_nav_create(const tbnav_nav_params* params, tbnav_nav** out) {
   h->tiles_y = (p.ny + kTile - 1) / kTile;
   h->info.tiles[0] = h->tiles_x; h->info.tiles[1] = h->tiles_y;
   hipError_t e = hipMalloc((void**)&h->d_cost, (size_t)h->n);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->d_cost_solved, (size_t)h->n);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->d_infl, (size_t)kInflEntries);
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_d, sizeof(unsigned) * (size_t)h->n);
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_field, sizeof(float) * (size_t)h->n);
   if (e == hipSuccess) e = hipMalloc((void**)&h->d_flags, sizeof(unsigned) * 2 * (size_t)h->tiles_x * h->tiles_y);
@@ -239,7 +235,7 @@ void tbnav_nav_destroy(tbnav_nav* h) {
   {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(h->d_cost); (void)hipFree(h->d_d); (void)hipFree(h->d_field); (void)hipFree(h->d_flags); (void)hipFree(h->d_rec);
+    (void)hipFree(h->d_cost); (void)hipFree(h->d_cost_solved); (void)hipFree(h->d_infl); (void)hipFree(h->d_d); (void)hipFree(h->d_field); (void)hipFree(h->d_flags); (void)hipFree(h->d_rec);
   }
   delete h;
 }
@@ -251,16 +247,32 @@ int tbnav_nav_set_cost(tbnav_nav* h, const uint8_t* cost_host) {
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   TBNAV_HIP(hipMemcpy(h->d_cost, cost_host, (size_t)h->n, hipMemcpyHostToDevice));   // (solves are synchronous: nothing reads d_cost now)
   h->cost.assign(cost_host, cost_host + h->n);
-  h->cost_set = true;
+  h->cost_set = true; h->cost_host_valid = true;
+  return TBNAV_OK;
+}
+
+int tbnav_nav_get_cost(tbnav_nav* h, uint8_t* cost_host) {
+  if (!h || !cost_host || !h->cost_set) return TBNAV_ERR_INVALID_ARG;
+  if (!h->cost_host_valid) {
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+    h->cost.resize((size_t)h->n);
+    TBNAV_HIP(hipMemcpy(h->cost.data(), h->d_cost, (size_t)h->n, hipMemcpyDeviceToHost));
+    h->cost_host_valid = true;
+  }
+  std::memcpy(cost_host, h->cost.data(), (size_t)h->n);
   return TBNAV_OK;
 }
 
 int tbnav_nav_solve(tbnav_nav* h, int32_t goal_ix, int32_t goal_iy) {
   if (!h || !h->cost_set || !in_grid(h, goal_ix, goal_iy)) return TBNAV_ERR_INVALID_ARG;
   const int goal = goal_ix * h->p.ny + goal_iy;
-  if (h->cost[(size_t)goal] == 0) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  uint8_t at_goal = 0;   // a grid set on the device has no host copy yet: the goal's cell alone is read back
+  if (h->cost_host_valid) at_goal = h->cost[(size_t)goal];
+  else TBNAV_HIP(hipMemcpy(&at_goal, h->d_cost + goal, 1, hipMemcpyDeviceToHost));
+  if (at_goal == 0) return TBNAV_ERR_INVALID_ARG;
   h->solved = false; h->d_host_valid = false;   // from here on the last solution is being overwritten
   const int tiles = h->tiles_x * h->tiles_y, B = batch_rounds(h);
   hipLaunchKernelGGL(nav_reset, dim3(256), dim3(256), 0, nullptr, h->d_d, h->n, h->p.ny, goal_ix, goal_iy, h->d_flags, tiles, h->tiles_y);
@@ -287,7 +299,10 @@ int tbnav_nav_solve(tbnav_nav* h, int32_t goal_ix, int32_t goal_iy) {
       if (rec[2 * r + 1] == 0) rounds = r0 + r + 1;   // nothing changed, so nothing was marked: every later round finds no tile
     }
   }
-  h->cost_solved = h->cost;
+  // what G6 walks over: the host copy where there is one, else kept on the device until a path is asked for
+  if (h->cost_host_valid) h->cost_solved = h->cost;
+  else TBNAV_HIP(hipMemcpy(h->d_cost_solved, h->d_cost, (size_t)h->n, hipMemcpyDeviceToDevice));
+  h->cost_solved_valid = h->cost_host_valid;
   h->solved = true;
   h->info.solved = 1; h->info.goal[0] = goal_ix; h->info.goal[1] = goal_iy;
   h->info.rounds = rounds; h->info.launches = launches; h->info.tile_visits = visits;
@@ -322,7 +337,8 @@ int tbnav_nav_get_field(tbnav_nav* h, double cap, float* out) {
 
 int tbnav_nav_path(tbnav_nav* h, int32_t start_ix, int32_t start_iy, int32_t* cells, int32_t cells_cap, int32_t* n) {
   if (!h || !n || cells_cap < 0 || (cells_cap > 0 && !cells) || !h->solved || !in_grid(h, start_ix, start_iy)) return TBNAV_ERR_INVALID_ARG;
-  const int rc = download(h);
+  int rc = download(h);
+  if (rc == TBNAV_OK) rc = download_cost_solved(h);
   if (rc != TBNAV_OK) return rc;
   const int ny = h->p.ny;
   const std::vector<unsigned>& d = h->d_host;

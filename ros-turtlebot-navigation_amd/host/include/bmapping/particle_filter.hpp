@@ -26,6 +26,8 @@
 
 struct tbnav_rbpf;        // C-ABI handle
 struct tbnav_rbpf_group;  // the same over several GPUs (include/tbnav_rbpf.h)
+namespace planner { class GoalField; }   // planner/goal_field.hpp, controller/mppi.hpp: both take a cost grid / a cost field from
+namespace controller { class MPPI; }     // the best particle's map on the device, through the filter's handle
 
 namespace bmapping {
 
@@ -73,6 +75,8 @@ class ParticleFilter {
   bool resampledLastScan() const { return last_resampled_; }
 
  private:
+  friend class planner::GoalField;
+  friend class controller::MPPI;
   tbnav_rbpf* h_ = nullptr;         // n_gpus == 1
   tbnav_rbpf_group* g_ = nullptr;   // n_gpus > 1
   bool reference_field_ = false;

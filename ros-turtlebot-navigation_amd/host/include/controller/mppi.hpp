@@ -18,6 +18,7 @@
 struct tbnav_mppi;        // C-ABI handle
 struct tbnav_mppi_group;  // the same over several GPUs (include/tbnav_mppi.h)
 namespace planner { class GoalField; }  // planner/goal_field.hpp: hands its field to the controller's handle on the device
+namespace bmapping { class ParticleFilter; }  // bmapping/particle_filter.hpp: setCostFieldFrom reads its best particle's map on the device
 
 namespace controller {
 
@@ -78,6 +79,11 @@ class MPPI {
   /// field the library rejects (sizes outside 2 .. 4096, a non-finite number), and the field in force stays.
   void setCostField(const CostField& field);
   void clearCostField();
+  /// The field costFieldFromDistance would give for the distance field of the filter's best particle, with the filter's geometry
+  /// and `weight`, formed on the device from that particle's occupancy bits (include/tbnav_nav.h G7-G9): no distance field is
+  /// stored or moved.  Throws std::runtime_error for a filter or a controller built with n_gpus > 1 and where r_inflate reaches
+  /// further than 31 cells, std::invalid_argument unless 0 <= r_robot < r_inflate <= 10; the field in force then stays.
+  void setCostFieldFrom(bmapping::ParticleFilter& filter, double r_robot, double r_inflate, double weight);
   int steps() const { return steps_; }
   int rollouts() const { return rollouts_; }
   int gpus() const;

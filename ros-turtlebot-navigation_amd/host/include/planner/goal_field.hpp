@@ -6,6 +6,8 @@
 //     planner::GoalField nav(nx, ny, xmin, ymin, resolution);
 //     nav.setCost(planner::navCostFromDistance(occ_dist, nx, ny, r_robot, r_inflate, k));
 //     nav.solve(goal.x, goal.y);  nav.applyTo(mppi, cap, weight);
+// and one that owns the filter itself replaces the second line by nav.setCostFrom(filter, r_robot, r_inflate, k): the grid comes from
+// the best particle's map on the device (G7-G9).
 // and links libtbnav_host.so + libtbnav_hip.so.
 #ifndef TBNAV_PLANNER_GOAL_FIELD_HPP
 #define TBNAV_PLANNER_GOAL_FIELD_HPP
@@ -17,6 +19,7 @@
 #include "controller/mppi.hpp"
 
 struct tbnav_nav;  // C-ABI handle
+namespace bmapping { class ParticleFilter; }  // bmapping/particle_filter.hpp
 
 namespace planner {
 
@@ -38,6 +41,11 @@ class GoalField {
 
   /// G2: nx * ny costs, 0 = blocked, 1 .. 64 the multiplier a move pays for entering the cell; what the next solve uses.
   void setCost(const std::vector<std::uint8_t>& cost);
+  /// G7-G9: the grid navCostFromDistance would give for the distance field of the filter's best particle, formed on the device from
+  /// that particle's occupancy bits — no distance field is stored, nothing crosses the host.  This grid must be the filter's (side,
+  /// xmin, ymin, resolution), else std::invalid_argument, as for r_robot, r_inflate, k outside 0 <= r_robot < r_inflate <= 10,
+  /// 0 <= k <= 63.  Throws std::runtime_error for a filter built with n_gpus > 1 and where r_inflate reaches further than 31 cells.
+  void setCostFrom(bmapping::ParticleFilter& filter, double r_robot, double r_inflate, double k);
   /// G3-G4 with the goal at the cell of the world position (x, y).  Throws std::invalid_argument when that position is outside the
   /// grid (the reference's "NOT in the bounds of the world") or its cell is blocked; the last solution then stays.
   void solve(double x, double y);

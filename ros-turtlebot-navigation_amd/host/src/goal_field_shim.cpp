@@ -5,6 +5,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "bmapping/particle_filter.hpp"
 #include "planner/goal_field.hpp"
 #include "tbnav_nav.h"
 
@@ -48,6 +49,10 @@ GoalField::GoalField(GoalField&& o) noexcept : h_(o.h_), nx_(o.nx_), ny_(o.ny_) 
 void GoalField::setCost(const std::vector<std::uint8_t>& cost) {
   if (cost.size() != (size_t)nx_ * (size_t)ny_) throw std::invalid_argument("setCost: cost.size() != nx * ny");
   check(tbnav_nav_set_cost(h_, cost.data()), "setCost");
+}
+void GoalField::setCostFrom(bmapping::ParticleFilter& filter, double r_robot, double r_inflate, double k) {
+  if (filter.g_) throw std::runtime_error("setCostFrom: a filter over several GPUs is not supported");
+  check(tbnav_nav_set_cost_from_rbpf(h_, filter.h_, TBNAV_NAV_BEST_PARTICLE, r_robot, r_inflate, k), "setCostFrom");
 }
 std::array<int, 2> GoalField::cellOf(double x, double y) const {
   int32_t ix = 0, iy = 0;

@@ -4,9 +4,11 @@
 #include <stdexcept>
 #include <string>
 
+#include "bmapping/particle_filter.hpp"
 #include "controller/mppi.hpp"
 #include "rigid2d/utilities.hpp"
 #include "tbnav_mppi.h"
+#include "tbnav_nav.h"
 
 namespace controller {
 namespace {
@@ -70,6 +72,11 @@ void MPPI::setCostField(const CostField& f) {
 }
 void MPPI::clearCostField() {
   check(g_ ? tbnav_mppi_group_set_cost_field(g_, nullptr, nullptr) : tbnav_mppi_set_cost_field(h_, nullptr, nullptr), "clearCostField");
+}
+
+void MPPI::setCostFieldFrom(bmapping::ParticleFilter& filter, double r_robot, double r_inflate, double weight) {
+  if (g_ || filter.g_) throw std::runtime_error("setCostFieldFrom: a controller or a filter over several GPUs is not supported");
+  check(tbnav_mppi_set_cost_field_from_rbpf(h_, filter.h_, TBNAV_NAV_BEST_PARTICLE, r_robot, r_inflate, weight), "setCostFieldFrom");
 }
 
 std::vector<float> costFieldFromDistance(const std::vector<double>& occ_dist, int nx, int ny, double r_robot, double r_inflate) {

@@ -164,6 +164,14 @@ class MPPI:
     def clearCostField(self):
         capi.check(self._L.tbnav_mppi_set_cost_field(self._h, None, None), "set_cost_field(clear)")
 
+    def setCostFieldFrom(self, pf, r_robot: float, r_inflate: float, weight: float = 1.0, particle=None):
+        """tbnav_mppi_set_cost_field_from_rbpf: the field cost_field_from_distance(pf.occDist(p), r_robot, r_inflate) of a particle
+        of an rtn_amd.rbpf.ParticleFilter (None: the best one), with the filter's geometry, formed on the device from the
+        particle's occupancy bits (tbnav_nav.h G7-G9)."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        capi.check(self._L.tbnav_mppi_set_cost_field_from_rbpf(self._h, pf._h, p, r_robot, r_inflate, weight),
+                   "tbnav_mppi_set_cost_field_from_rbpf")
+
     def costField(self):
         """None, or the geometry in force as a dict (nx, ny, xmin, ymin, resolution, weight)."""
         on, g = C.c_int32(), capi.MppiCostField()

@@ -25,6 +25,20 @@ def nav_cost_from_distance(dist, r_robot: float, r_inflate: float, k: float) -> 
     return np.where(d <= r_robot, 0.0, 1.0 + np.rint(k * t * t)).astype(np.uint8)
 
 
+def inflation_tables(resolution: float, r_robot: float, r_inflate: float, k: float):
+    """tbnav_nav_inflation_tables (tbnav_nav.h G7; no GPU needed): (cost, field, reach) — cost uint8 and field float32 by squared
+    cell distance c = 0 .. reach**2, each FOLLOWED BY its open value (so reach**2 + 2 values)."""
+    L = capi.lib()
+    n, reach = C.c_int32(), C.c_int32()
+    capi.check(L.tbnav_nav_inflation_tables(resolution, r_robot, r_inflate, k, None, None, 0, C.byref(n), C.byref(reach)),
+               "tbnav_nav_inflation_tables")
+    cost, field = np.empty(n.value + 1, dtype=np.uint8), np.empty(n.value + 1, dtype=np.float32)
+    capi.check(L.tbnav_nav_inflation_tables(resolution, r_robot, r_inflate, k, cost.ctypes.data, field.ctypes.data, n.value + 1,
+                                            C.byref(n), C.byref(reach)), "tbnav_nav_inflation_tables")
+    assert n.value + 1 == cost.size
+    return cost, field, reach.value
+
+
 class GoalField:
     """tbnav_nav on one MI355X.  Cells are (ix, iy), arrays [nx][ny]."""
 
@@ -53,6 +67,32 @@ class GoalField:
             raise ValueError("setCost: cost must be an integer array of shape [nx][ny] with values 0 .. 255")
         c = np.ascontiguousarray(c, dtype=np.uint8)
         capi.check(self._L.tbnav_nav_set_cost(self._h, c.ctypes.data), "tbnav_nav_set_cost")
+
+    def setCostFrom(self, pf, r_robot: float, r_inflate: float, k: float, particle=None):
+        """G7-G9: the cost grid from the occupancy bits of a particle of an rtn_amd.rbpf.ParticleFilter (None: the best one, found
+        on the device), formed on the device: nav_cost_from_distance(pf.occDist(p), ...) without the distance field or the host."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        capi.check(self._L.tbnav_nav_set_cost_from_rbpf(self._h, pf._h, p, r_robot, r_inflate, k), "tbnav_nav_set_cost_from_rbpf")
+
+    def profileCostFrom(self, pf, r_robot: float, r_inflate: float, k: float, launches: int, particle=None) -> float:
+        """setCostFrom with the kernel launched `launches` times between two events: microseconds per launch (a measurement hook)."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        ms = C.c_float()
+        capi.check(self._L.tbnav_nav_profile_cost_from_rbpf(self._h, pf._h, p, r_robot, r_inflate, k, launches, C.byref(ms)),
+                   "tbnav_nav_profile_cost_from_rbpf")
+        return ms.value * 1e3
+
+    def cost(self) -> np.ndarray:
+        """The grid the next solve uses, however it was set."""
+        c = np.empty((self.nx, self.ny), dtype=np.uint8)
+        capi.check(self._L.tbnav_nav_get_cost(self._h, c.ctypes.data), "tbnav_nav_get_cost")
+        return c
+
+    def lastCostKernel(self) -> str:
+        """The kernel setCostFrom launched, as a profiler prints it; "" until that route has run."""
+        name = C.create_string_buffer(64)
+        capi.check(self._L.tbnav_nav_last_cost_kernel(self._h, name, 64), "tbnav_nav_last_cost_kernel")
+        return name.value.decode()
 
     def solve(self, ix: int, iy: int):
         capi.check(self._L.tbnav_nav_solve(self._h, ix, iy), "tbnav_nav_solve")
