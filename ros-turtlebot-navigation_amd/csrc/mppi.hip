@@ -1,8 +1,10 @@
 // mppi.hip — MI355X (gfx950) implementation of controller::MPPI::newControls behind the C-ABI of include/tbnav_mppi.h: the handle,
-// which kernel a (K, T) takes, the launchers and the single-GPU entry points.  Reference: controller/src/controller/mppi.cpp:72-140,
-// rk4.cpp:49-115, controller/include/controller/mppi.hpp:41-105 (paths relative to the reference tree).
+// the launchers and the single-GPU entry points.  Which kernel a (K, T) takes and which instantiation a tick launches is decided in
+// mppi_plan.hpp (plain arithmetic, no HIP); the launchers here fill its inputs from the handle, launch what comes back, update the
+// handle.  Reference: controller/src/controller/mppi.cpp:72-140, rk4.cpp:49-115, controller/include/controller/mppi.hpp:41-105
+// (paths relative to the reference tree).
 // Kernels: mppi_rollout.hip (four rollout families), mppi_softmin.hip (records, combine, exchange words, noise) over mppi_device.hpp;
-// communicator attachment, the sharded tick and groups: mppi_sharded.hip; the handle: mppi_host.hpp.
+// the cost field: mppi_field.hip; communicator attachment, the sharded tick and groups: mppi_sharded.hip; the handle: mppi_host.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,6 +31,11 @@ Lam lam_of(double lambda) {
 }  // namespace tbnav_mh
 
 namespace {
+using TickGraph = tbnav_mppi::TickGraph;
+void drop_graph(TickGraph& g) {
+  if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  if (g.graph) { (void)hipGraphDestroy(g.graph); g.graph = nullptr; }
+}
 
 // the publication the sharded tick has asked for, taken over by the launch that can carry it out (see pub_pending)
 DirectPub take_pub(tbnav_mppi* h) {
@@ -36,71 +43,6 @@ DirectPub take_pub(tbnav_mppi* h) {
   h->pub_pending = false;
   return h->pub_next;
 }
-
-int launch_rollout(tbnav_mppi* h, const double x0[3], const double* d_duL, const double* d_duR,
-                   hipStream_t st) {
-  RolloutArgs a;
-  a.half_r = h->p.wheel_radius / 2.0;
-  a.r_over_b = h->p.wheel_radius / h->p.wheel_base;
-  a.r_d = h->p.wheel_radius * (1 / h->p.wheel_base);
-  a.h = h->p.dt;
-  a.h6 = h->p.dt / 6.0;
-  for (int c = 0; c < 3; ++c) { a.x0[c] = x0[c]; a.xd[c] = h->xd[c]; a.Q[c] = h->p.Q[c]; a.P1[c] = h->p.P1[c]; }
-  a.R[0] = h->p.R[0]; a.R[1] = h->p.R[1];
-  a.T = h->T; a.K = h->K;
-  const dim3 grid((h->K + kWave - 1) / kWave), block(kWave);
-  const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
-  if (h->field_on) return launch_rollout_field(h, a, usrc, d_duL, d_duR, st);   // (a cost field: its own kernel, whatever the handle's choice)
-  if (h->scan_tc > 0 && h->dyn == 0) {  // (the arc dynamics live in the fused and the sequential kernels)
-    h->prefix_rows = 0;
-    const int TCv = h->scan_tc, C = (h->T + TCv - 1) / TCv;
-    const size_t lds = ((size_t)2 * h->T + (size_t)4 * C * kWave) * sizeof(double);
-    const dim3 blk(kWave, C);
-#define TBNAV_SCAN(TR, TCC, MW) do { h->lk_rollout[0] = 2; h->lk_rollout[1] = TR; h->lk_rollout[2] = TCC; h->lk_rollout[3] = MW; \
-                                 hipLaunchKernelGGL((mppi_rollout_scan<TR, TCC, MW>), grid, blk, lds, st, a, d_duL, d_duR, usrc, h->d_J); } while (0)
-#define TBNAV_SCAN_TC(TR)                                                                                          \
-  switch (TCv) {                                                                                                   \
-    case 4: if (C > 12) TBNAV_SCAN(TR, 4, 16); else TBNAV_SCAN(TR, 4, 12); break;                                  \
-    case 5: TBNAV_SCAN(TR, 5, 12); break;   case 6: TBNAV_SCAN(TR, 6, 12); break;                                  \
-    case 7: TBNAV_SCAN(TR, 7, 16); break;                                                                          \
-    case 8: if (C > 12) TBNAV_SCAN(TR, 8, 16); else TBNAV_SCAN(TR, 8, 12); break;                                  \
-    case 10: TBNAV_SCAN(TR, 10, 12); break; case 12: TBNAV_SCAN(TR, 12, 12); break;                                \
-    case 16: TBNAV_SCAN(TR, 16, 12); break; default: TBNAV_SCAN(TR, 20, 12); break;                                \
-  }
-    // (TRIG 2 — a fresh sincos every step — is an A-B setting of the sequential / fused kernels; here it takes the three-evaluation form:
-    //  its eleven instantiations spilled up to 1.2 KB per lane and nothing selected them)
-    if (h->trig == 1) { TBNAV_SCAN_TC(1) } else { TBNAV_SCAN_TC(3) }
-#undef TBNAV_SCAN_TC
-#undef TBNAV_SCAN
-  } else {
-    if (h->prefix_rg > 0 && h->dyn == 0 && h->trig == 1) {
-      const size_t ldsp = (size_t)2 * h->T * sizeof(double);
-      a.lds_from = 0;
-      h->lk_rollout[0] = 3; h->lk_rollout[1] = h->prefix_rg < 3 ? h->prefix_rg : 3;
-      switch (h->prefix_rg) {
-        case 1: hipLaunchKernelGGL((mppi_rollout_prefix<1>), grid, block, ldsp, st, a, d_duL, d_duR, usrc, h->d_J, h->d_total); break;
-        case 2: hipLaunchKernelGGL((mppi_rollout_prefix<2>), grid, block, ldsp, st, a, d_duL, d_duR, usrc, h->d_J, h->d_total); break;
-        default: hipLaunchKernelGGL((mppi_rollout_prefix<3>), grid, block, ldsp, st, a, d_duL, d_duR, usrc, h->d_J, h->d_total); break;
-      }
-      TBNAV_HIP(hipGetLastError());
-      h->j_valid = true;
-      h->prefix_rows = h->T - kGroup * h->prefix_rg;
-      return TBNAV_OK;
-    }
-    h->prefix_rows = 0;
-    const size_t lds = (size_t)2 * h->T * sizeof(double) + (size_t)(h->T - h->lds_from) * kWave * sizeof(double);
-    a.lds_from = h->lds_from;
-    h->lk_rollout[0] = 4; h->lk_rollout[1] = h->dyn == 1 ? 4 : (h->trig >= 1 && h->trig <= 2 ? h->trig : 3);
-    if (h->dyn == 1) hipLaunchKernelGGL((mppi_rollout_cost<4>), grid, block, lds, st, a, d_duL, d_duR, usrc, h->d_J);
-    else if (h->trig == 1) hipLaunchKernelGGL((mppi_rollout_cost<1>), grid, block, lds, st, a, d_duL, d_duR, usrc, h->d_J);
-    else if (h->trig == 2) hipLaunchKernelGGL((mppi_rollout_cost<2>), grid, block, lds, st, a, d_duL, d_duR, usrc, h->d_J);
-    else hipLaunchKernelGGL((mppi_rollout_cost<3>), grid, block, lds, st, a, d_duL, d_duR, usrc, h->d_J);
-  }
-  TBNAV_HIP(hipGetLastError());
-  h->j_valid = true;
-  return TBNAV_OK;
-}
-
 
 RolloutArgs rollout_args(const tbnav_mppi* h, const double x0[3]) {
   RolloutArgs a;
@@ -116,41 +58,58 @@ RolloutArgs rollout_args(const tbnav_mppi* h, const double x0[3]) {
   return a;
 }
 
-size_t fused_lds_bytes(int T, int R) { return (size_t)3 * T * (R + 1) * sizeof(double); }
+// the rollout kernel of the three-kernel tick: plan_rollout names the form, the family's list gives the instantiation
+int launch_rollout(tbnav_mppi* h, const double x0[3], const double* d_duL, const double* d_duR, hipStream_t st) {
+  const RolloutPlan p = plan_rollout(RolloutIn{h->T, h->K, h->dyn, h->trig, h->scan_tc, h->prefix_rg, h->lds_from, h->field_on});
+  RolloutArgs a = rollout_args(h, x0);
+  a.lds_from = p.lds_from;
+  const USrc usrc = usrc_of(h);
+  const dim3 grid(p.grid), block(kWave, p.block_y);
+  const KernelForm& f = p.form;
+  auto launched = [&]() {
+    TBNAV_HIP(hipGetLastError());
+    h->lk_rollout = f;
+    h->j_valid = true;
+    h->prefix_rows = p.prefix_rows;
+    return (int)TBNAV_OK;
+  };
+  if (f.family == kField) { const int rc = launch_rollout_field(h, p, a, usrc, d_duL, d_duR, st); return rc != TBNAV_OK ? rc : launched(); }
+#define TBNAV_X(TR, TC, MW) if (f.is(kScan, TR, TC, MW)) { hipLaunchKernelGGL((mppi_rollout_scan<TR, TC, MW>), grid, block, p.lds, st, a, d_duL, d_duR, usrc, h->d_J); return launched(); }
+  TBNAV_MPPI_SCAN_FORMS(TBNAV_X)
+#undef TBNAV_X
+#define TBNAV_X(RG) if (f.is(kPrefix, RG)) { hipLaunchKernelGGL((mppi_rollout_prefix<RG>), grid, block, p.lds, st, a, d_duL, d_duR, usrc, h->d_J, h->d_total); return launched(); }
+  TBNAV_MPPI_PREFIX_FORMS(TBNAV_X)
+#undef TBNAV_X
+#define TBNAV_X(TR) if (f.is(kCost, TR)) { hipLaunchKernelGGL((mppi_rollout_cost<TR>), grid, block, p.lds, st, a, d_duL, d_duR, usrc, h->d_J); return launched(); }
+  TBNAV_MPPI_COST_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have: never another form in its place)
+}
 
 // rollout + partial records in one launch (small K); the caller follows with launch_combine(..., fused_S)
 int launch_fused(tbnav_mppi* h, const double x0[3], const double* d_duL, const double* d_duR, hipStream_t st,
                  const RngArgs* rng = nullptr) {
+  const FusedPlan p = plan_fused(FusedIn{h->T, h->K, h->dyn, h->trig, h->sampler, h->fused_r, h->fused_S, rng != nullptr});
   const RolloutArgs a = rollout_args(h, x0);
-  const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
-  const int R = h->fused_r, TL = (h->T + kWave - 1) / kWave;
-  const dim3 grid(h->fused_S), block(kWave * R);
-  const size_t lds = fused_lds_bytes(h->T, R);
+  const USrc usrc = usrc_of(h);
   const RngArgs g = rng ? *rng : RngArgs{0, 0, 0.0, 0.0};
-#define TBNAV_FUSED(TR, RR, TLL, RG) do { h->lk_rollout[0] = 1; h->lk_rollout[1] = TR; h->lk_rollout[2] = RR; h->lk_rollout[3] = TLL; h->lk_rollout[4] = RG;     \
-                                     hipLaunchKernelGGL((mppi_rollout_fused<TR, RR, TLL, RG>), grid, block, lds, st, usrc.p, (const double*)g.ahead, (const uint64_t*)g.ahead_tag, g.tick0, \
-                                                        usrc.shift, h->T, h->K, h->fused_S, h->d_records_f, h->keep_j ? h->d_J : nullptr, a, usrc.init_l, usrc.init_r, \
-                                                        lam_of(h), d_duL, d_duR, rng_rest(g)); } while (0)
-#define TBNAV_FUSED_R(TR)                                                                                \
-  if (R == 8) { if (TL == 1) TBNAV_FUSED(TR, 8, 1, 0); else TBNAV_FUSED(TR, 8, 2, 0); }          \
-  else if (R == 4) { if (TL == 1) TBNAV_FUSED(TR, 4, 1, 0); else TBNAV_FUSED(TR, 4, 2, 0); }     \
-  else { if (TL == 1) TBNAV_FUSED(TR, 16, 1, 0); else TBNAV_FUSED(TR, 16, 2, 0); }
-#define TBNAV_FUSED_RNG(TR, RG)                                                                              \
-  if (R == 16) { if (TL == 1) TBNAV_FUSED(TR, 16, 1, RG); else TBNAV_FUSED(TR, 16, 2, RG); }                   \
-  else { if (TL == 1) TBNAV_FUSED(TR, 8, 1, RG); else TBNAV_FUSED(TR, 8, 2, RG); }
-  if (rng) {  // in-kernel noise: instantiated for 8 and 16 rollouts per workgroup (the handle's own choices) — the caller checks
-    // (RNG 2 = the fp64 sampler, the handle's default; RNG 1 = the fp32 one, TBNAV_MPPI_OPT_SAMPLER = 0)
-    if (h->sampler == 1) {
-      if (h->dyn == 1) { TBNAV_FUSED_RNG(4, 2); } else if (h->trig == 3) { TBNAV_FUSED_RNG(3, 2); } else { TBNAV_FUSED_RNG(2, 2); }
-    } else if (h->dyn == 1) { TBNAV_FUSED_RNG(4, 1); } else if (h->trig == 3) { TBNAV_FUSED_RNG(3, 1); } else { TBNAV_FUSED_RNG(2, 1); }
-  } else if (h->dyn == 1) { TBNAV_FUSED_R(4) } else if (h->trig == 3) { TBNAV_FUSED_R(3) } else { TBNAV_FUSED_R(2) }
-#undef TBNAV_FUSED_RNG
-#undef TBNAV_FUSED_R
-#undef TBNAV_FUSED
-  TBNAV_HIP(hipGetLastError());
-  h->j_valid = h->keep_j;
-  h->prefix_rows = 0;
-  return TBNAV_OK;
+  auto launched = [&]() {
+    TBNAV_HIP(hipGetLastError());
+    h->lk_rollout = p.form;
+    h->j_valid = h->keep_j;
+    h->prefix_rows = 0;
+    return (int)TBNAV_OK;
+  };
+#define TBNAV_X(TR, RR, TL, RG)                                                                                                                       \
+  if (p.form.is(kFused, TR, RR, TL, RG)) {                                                                                                            \
+    hipLaunchKernelGGL((mppi_rollout_fused<TR, RR, TL, RG>), dim3(p.grid), dim3(p.block), p.lds, st, usrc.p, (const double*)g.ahead,                  \
+                       (const uint64_t*)g.ahead_tag, g.tick0, usrc.shift, h->T, h->K, h->fused_S, h->d_records_f, h->keep_j ? h->d_J : nullptr, a,    \
+                       usrc.init_l, usrc.init_r, lam_of(h), d_duL, d_duR, rng_rest(g));                                                               \
+    return launched();                                                                                                                                \
+  }
+  TBNAV_MPPI_FUSED_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have)
 }
 
 int launch_partials(tbnav_mppi* h, const double* d_duL, const double* d_duR, double* d_records, hipStream_t st) {
@@ -164,46 +123,40 @@ int launch_partials(tbnav_mppi* h, const double* d_duL, const double* d_duR, dou
 int tbnav_mh::launch_combine(tbnav_mppi* h, const double* d_records, int G, hipStream_t st, int S, const DirectSrc* direct,
                              const RngArgs* next) {
   if (S < 0) S = h->S;
-  // lanes per time step (the power of two >= the record count, at most a wave) and the time steps' blocks are formed here, once,
-  // and handed to the kernel: they are launch-uniform, and used to head its chain as a loop and an integer division
-  int tpr_log2 = 0;
-  while ((1 << tpr_log2) < G * S && (1 << tpr_log2) < kWave) ++tpr_log2;
-  const int tpr = 1 << tpr_log2;
-  const int wpb = TBNAV_COMBINE_WAVES;  // waves per workgroup
-  const int steps_per_block = wpb * (kWave / tpr);
-  const int blocks = (h->T + steps_per_block - 1) / steps_per_block;
-  // noise ahead (the one-group form only): sampler blocks behind the time steps' blocks, TBNAV_AHEAD_PAIRS pairs per lane
-  const RngArgs nx = next ? *next : RngArgs{0, 0, 0.0, 0.0};
-  const int pairs_per_block = wpb * kWave * TBNAV_AHEAD_PAIRS;
-  const int ahead_blocks = nx.ahead ? (h->K * h->T + pairs_per_block - 1) / pairs_per_block : 0;
-  const RngArgs off{0, 0, 0.0, 0.0};
-  const USrc usrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]};
+  const USrc usrc = usrc_of(h);
   // (records that came through an all-gather: only the error words — a poisoned record raises them, see mppi_combine)
   const DirectSrc ds = direct ? *direct : DirectSrc{nullptr, 0ull, (G > 1 && h->comm) ? h->d_dx_err : nullptr, (G > 1 && h->comm) ? h->d_dx_dead : nullptr, 0u};
-#define TBNAV_COMBINE(KEEP, MODE) do { h->lk_combine[0] = KEEP; h->lk_combine[1] = MODE; hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(blocks + (MODE == 0 ? ahead_blocks : 0)), dim3(wpb * kWave), 0, st, d_records, usrc.p, MODE == 0 ? nx.ahead : nullptr, MODE == 0 ? nx.tick0 : nullptr, \
-                                                    h->T, S, usrc.shift, blocks, G, tpr_log2, MODE == 0 ? nx.ahead_tag : nullptr, lam_of(h), h->p.max_wheel_vel, usrc.init_l, usrc.init_r, \
-                                                    h->d_u[1 - h->ucur], h->d_out, h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1), ds, rng_rest(MODE == 0 ? nx : off)); } while (0)
-#define TBNAV_COMBINE_KEEP(MODE) do { if (G * S > 4 * kWave && G * S <= 8 * kWave) TBNAV_COMBINE(8, MODE); else if (G * S > 2 * kWave && G * S <= 4 * kWave) TBNAV_COMBINE(4, MODE); \
-                                      else TBNAV_COMBINE(2, MODE); } while (0)
-  // (which form: the direct exchange polls; records that came through an all-gather may carry a failed rank's poison; one group has neither —
-  //  and with more than 256 records per step, the fused kernel's at K = 4097 ... 8192, it gets four waves per time step)
-  if (direct) TBNAV_COMBINE_KEEP(2);
-  else if (G > 1 && ds.err) TBNAV_COMBINE_KEEP(1);
-  else if (G == 1 && S > 4 * kWave && S <= 16 * kWave && h->wide_combine) {
-    h->lk_combine[0] = -4; h->lk_combine[1] = 0;
-    hipLaunchKernelGGL(mppi_combine_wide, dim3(h->T), dim3(4 * kWave), 0, st, h->T, S, lam_of(h), h->p.max_wheel_vel, usrc, d_records, h->d_u[1 - h->ucur], h->d_out,
-                       h->publish_next ? h->d_out_host : nullptr, (double)(h->seq + 1));
+  // noise ahead (the one-group form only): sampler blocks behind the time steps' blocks
+  const RngArgs off{0, 0, 0.0, 0.0};
+  const RngArgs nx = next ? *next : off;
+  const CombinePlan p = plan_combine(h->T, h->K, G, S, direct != nullptr, ds.err != nullptr, h->wide_combine, nx.ahead != nullptr);
+  double* const out_host = h->publish_next ? h->d_out_host : nullptr;
+  const double seq = (double)(h->seq + 1);
+  auto launched = [&]() {
+    TBNAV_HIP(hipGetLastError());
+    h->lk_combine = p.form;
+    h->lk_records = direct ? nullptr : d_records; h->lk_S = S; h->lk_G = G; h->lk_ushift = usrc.shift;
+    ++h->seq;
+    if (h->publish_next) h->published = h->seq;
+    h->ucur = 1 - h->ucur;       // the freshly written vector is current ...
+    h->pending_shift = true;     // ... and its shift is still owed
+    return (int)TBNAV_OK;
+  };
+  if (p.form.family == kCombineWide) {
+    hipLaunchKernelGGL(mppi_combine_wide, dim3(p.grid), dim3(p.block), 0, st, h->T, S, lam_of(h), h->p.max_wheel_vel, usrc, d_records, h->d_u[1 - h->ucur], h->d_out,
+                       out_host, seq);
+    return launched();
   }
-  else TBNAV_COMBINE_KEEP(0);
-#undef TBNAV_COMBINE_KEEP
-#undef TBNAV_COMBINE
-  TBNAV_HIP(hipGetLastError());
-  h->lk_records = direct ? nullptr : d_records; h->lk_S = S; h->lk_G = G; h->lk_ushift = usrc.shift;
-  ++h->seq;
-  if (h->publish_next) h->published = h->seq;
-  h->ucur = 1 - h->ucur;       // the freshly written vector is current ...
-  h->pending_shift = true;     // ... and its shift is still owed
-  return TBNAV_OK;
+#define TBNAV_X(KEEP, MODE)                                                                                                                           \
+  if (p.form.is(kCombine, KEEP, MODE)) {                                                                                                              \
+    hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(p.grid), dim3(p.block), 0, st, d_records, usrc.p, MODE == 0 ? nx.ahead : nullptr,             \
+                       MODE == 0 ? nx.tick0 : nullptr, h->T, S, usrc.shift, p.blocks, G, p.tpr_log2, MODE == 0 ? nx.ahead_tag : nullptr, lam_of(h),   \
+                       h->p.max_wheel_vel, usrc.init_l, usrc.init_r, h->d_u[1 - h->ucur], h->d_out, out_host, seq, ds, rng_rest(MODE == 0 ? nx : off)); \
+    return launched();                                                                                                                                \
+  }
+  TBNAV_MPPI_COMBINE_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have)
 }
 namespace {
 
@@ -233,15 +186,17 @@ bool pick_noise(tbnav_mppi* h, const double*& d_duL, const double*& d_duR) {
   return d_duL && d_duR;
 }
 
-// the perturbations can be drawn inside the fused kernel: its in-kernel form exists for 8 and 16 rollouts per workgroup (either sampler)
-bool rng_in_kernel(const tbnav_mppi* h) {
-  return fused_rng(h) && (h->fused_r == 8 || h->fused_r == 16);
-}
-
-// Noise ahead (TBNAV_MPPI_OPT_NOISE_AHEAD) where the tick is latency-bound: 8 rollouts per workgroup (K <= 2048 at 256 CUs), the
-// single-GPU combine (one group of K / 8 records per step: never the four-wave form) with most of the chip idle beside it.
-bool ahead_wanted(const tbnav_mppi* h) { return h->fused_rng && h->fused_r == 8; }
+// the plan's predicates on this handle (a handle with a cost field takes neither the fused kernel nor the noise-ahead draw)
+bool rng_in_kernel(const tbnav_mppi* h) { return tbnav_mk::rng_in_kernel(fused_rng(h), h->fused_r); }
+bool ahead_wanted(const tbnav_mppi* h) { return tbnav_mk::ahead_wanted(h->fused_rng, h->fused_r); }
 bool ahead_on(const tbnav_mppi* h) { return h->noise_ahead && h->d_ahead && ahead_wanted(h) && !h->comm; }
+// the device noise source of tick `tick` under `seed` ...
+RngArgs rng_args(const tbnav_mppi* h, uint64_t seed, uint64_t tick) { return RngArgs{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)}; }
+// ... and with the noise-ahead fields: the pair buffer, its tag and what a tag must say to be this launch's
+RngArgs with_ahead(const tbnav_mppi* h, RngArgs g) {
+  g.ahead = h->d_ahead; g.ahead_tag = h->d_ahead_tag; g.epoch = h->cfg_epoch; g.kind = h->sampler == 1 ? 2 : 1; g.K = h->K;
+  return g;
+}
 // (re)allocate the pair buffer and its tag for the handle's kernel choice; a fresh tag matches no tick
 hipError_t ahead_alloc(tbnav_mppi* h) {
   (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag);
@@ -257,12 +212,34 @@ hipError_t ahead_alloc(tbnav_mppi* h) {
 // its own and the combine draws the next tick's (the tick after `g`: the counters of one tick further on, same tick0 word)
 int rng_tick(tbnav_mppi* h, const double x0[3], RngArgs g, hipStream_t st) {
   const bool ahead = ahead_on(h);
-  if (ahead) { g.ahead = h->d_ahead; g.ahead_tag = h->d_ahead_tag; g.epoch = h->cfg_epoch; g.kind = h->sampler == 1 ? 2 : 1; g.K = h->K; }
+  if (ahead) g = with_ahead(h, g);
   const int rc = launch_fused(h, x0, h->d_duL, h->d_duR, st, &g);
   if (rc != TBNAV_OK) return rc;
   RngArgs nx = g;
   nx.base += (uint64_t)h->T * h->k_global;
   return launch_combine(h, h->d_records_f, 1, st, h->fused_S, nullptr, ahead ? &nx : nullptr);
+}
+
+// the fused kernel's fine records folded into the K-slice records that the ranks exchange (published by the kernel itself when the
+// sharded tick has asked for it)
+int launch_merge(tbnav_mppi* h, double* d_records_out, hipStream_t st) {
+  hipLaunchKernelGGL(mppi_merge_records, dim3(h->S, h->T), dim3(kWave), 0, st, h->T, h->fused_S, kSlice / h->fused_r, h->S,
+                     lam_of(h), h->d_records_f, d_records_out, take_pub(h));
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+
+// `launch(r)`, r = 0 .. reps-1, back to back between ONE pair of events; ms[which] = the mean.  Nothing runs once rc is an error.
+template <class Launch>
+void timed(hipEvent_t (&ev)[2], hipStream_t st, int reps, float* ms, int which, int& rc, Launch&& launch) {
+  if (rc != TBNAV_OK) return;
+  if (hipEventRecord(ev[0], st) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
+  for (int r = 0; r < reps && rc == TBNAV_OK; ++r) rc = launch(r);
+  if (rc != TBNAV_OK) return;
+  float t = 0.f;
+  if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
+      hipEventElapsedTime(&t, ev[0], ev[1]) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
+  ms[which] = t / (float)reps;
 }
 
 }  // namespace
@@ -294,70 +271,16 @@ int tbnav_mppi_create(const tbnav_mppi_params* params, tbnav_mppi** out) {
   h->p = *params;
   h->T = T;
   h->K = params->rollouts;
-  h->S = (h->K + kSlice - 1) / kSlice;
   h->device = dev;
   {
-    // How many steps' losses fit in LDS while the whole grid stays resident in ONE round:
-    // blocks per CU needed = ceil(blocks / CUs) (at most 8 considered), LDS budget per block = 160 KB / that.
+    // which kernel this (K, T) takes on this chip: mppi_plan.hpp (plan_create: the rules, the measurements behind them)
     hipDeviceProp_t prop;
     int cus = 256;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    const long blocks = (params->rollouts + kWave - 1) / kWave;
-    long per_cu = (blocks + cus - 1) / cus;
-    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    const long budget = (long)kMaxLdsBytes / per_cu - 512 - (long)(2 * T * sizeof(double));
-    long steps_in_lds = budget > 0 ? budget / (long)(kWave * sizeof(double)) : 0;
-    if (steps_in_lds > T) steps_in_lds = T;
-    h->lds_from = T - (int)steps_in_lds;
-    h->lds_from = ((h->lds_from + 3) / 4) * 4;  // whole groups of 4 steps switch staging together
-    if (h->lds_from > T) h->lds_from = T;
-    // round 3: the prefix-form kernel takes the streaming shape whenever a late region of 1, 2 or 3 groups leaves whole rounds
-    // of three groups (one of the three always does) and at least one round — whatever T: it stages nothing in LDS
-    if (T % 4 == 0 && blocks >= 2 * cus)
-      for (int rg : {1, 2, 3}) if ((T / 4 - rg) % kRoundGroups == 0 && T / 4 - rg >= kRoundGroups) { h->prefix_rg = rg; break; }
+    const CreatePlan c = plan_create(h->K, T, cus);
+    h->S = c.S; h->lds_from = c.lds_from; h->prefix_rg = c.prefix_rg; h->scan_tc = c.scan_tc;
+    h->fused_dev = c.fused_dev; h->fused_rng = c.fused_rng; h->fused_r = c.fused_r; h->fused_S = c.fused_S;
   }
-  // time-parallel kernel: up to 16 chunks (waves) per workgroup
-  h->scan_tc = 0;
-  for (int tc : {4, 5, 6, 8, 10, 12, 16, 20})
-    if ((T + tc - 1) / tc <= 12) { h->scan_tc = tc; break; }
-  {
-    // The time-parallel kernel exists to create waves when the rollout count alone cannot fill the chip;
-    // once K/64 one-wave workgroups cover >= 2 waves per CU-SIMD pair the sequential kernel (fewer
-    // registers, no chunk barriers) is faster (measured on MI355X: K=65536,T=100 87 us vs 121 us;
-    // K=1024,T=50 32 us vs 11 us).
-    hipDeviceProp_t prop;
-    int cus = 256;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-    // Measured on MI355X (tools/mppi_size_sweep.py, T = 25 / 50 / 100, tick in us, resident noise):
-    //   K        fused<8>      time-parallel     sequential
-    //   2048     11.3          15.2              29.4            (T = 50)
-    //   4096     20.1          20.5              49.2            (T = 100)
-    //   8192     32.9          23.6              52.1
-    //   16384    54.6          29.3              56.1
-    //   32768    100           47.1              55.1
-    //   49152    -             66.2              62.1
-    //   65536    165 (T = 50)  86.6              76.1
-    // one wave per rollout (fused) costs 5x the instructions of one lane per rollout and only pays while the chip is
-    // otherwise empty; the time-parallel kernel carries the middle; the sequential one takes over once K/64 one-wave
-    // workgroups are ~2.5 per CU.  (Round 1 switched fused -> sequential at 2 per CU and never used the middle kernel
-    // below T = 129: K = 16384 ran at half speed.)
-    const long waves = (params->rollouts + kWave - 1) / kWave;
-    if (2 * waves > 5 * cus) h->scan_tc = 0;
-    // fused rollout + partials (lanes = time): T must fit two steps per lane.  With the perturbations drawn inside it the
-    // fused kernel saves the sample kernel's launch and 16 B per rollout-step, so device-noise ticks stay with it longer
-    // (K = 8192, T = 100: 33.1 us against 36.1 for sample + time-parallel; K = 12288, T = 50: 38.9 against 29.7).
-    const bool fused_ok = T <= 2 * kWave && h->scan_tc > 0;
-    // (re-measured after the combine learnt to keep a lane's records in registers and to spread over one-wave workgroups —
-    //  the fused kernel's many records were what made it lose earlier: K = 8192, T = 100: fused with 16 rollouts per workgroup
-    //  20.4 us, time-parallel 22.6; with device noise 21.3 against 35.5)
-    h->fused_dev = fused_ok && 2 * waves <= cus;        // K <= 8192 at 256 CUs
-    h->fused_rng = fused_ok && 2 * waves <= cus;
-    // rollouts per workgroup: 8 spreads K = 1024 over 128 CUs (9.0 us against 10.0 with 16: latency-bound); from ~2048 up the
-    // chip is covered anyway and 16 halve the records the combine reads (K = 2048: 11.6 -> 10.7 us, 3072: 14.7 -> 12.1,
-    // 4096, T = 100: 20.1 -> 15.6)
-    h->fused_r = (h->fused_dev || h->fused_rng) ? (8 * waves <= cus ? 8 : 16) : 0;   // 8 up to K = 2048 (K = 2048, T = 50: 9.2 us against 10.0; 3072: 11.6 against 10.5)
-  }
-  h->fused_S = h->fused_r ? (h->K + h->fused_r - 1) / h->fused_r : 0;
   h->k_global = (uint64_t)h->K;
   const size_t tk = (size_t)T * h->K;
   hipError_t e = hipSuccess;
@@ -380,16 +303,11 @@ int tbnav_mppi_create(const tbnav_mppi_params* params, tbnav_mppi** out) {
   if (e == hipSuccess) e = hipMemset(h->d_J, 0, tk * sizeof(double));
   if (e == hipSuccess) e = hipMemset(h->d_duL, 0, tk * sizeof(double));
   if (e == hipSuccess) e = hipMemset(h->d_duR, 0, tk * sizeof(double));
-  if (e == hipSuccess) {
-    const int lds_max = (int)((size_t)2 * T * sizeof(double) + (size_t)(T - h->lds_from) * kWave * sizeof(double));
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_cost<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_cost<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_cost<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_cost<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-  }
+  // dynamic LDS beyond the 64 KB default for every form of the sequential kernel (lds_from only ever grows afterwards)
+  const int lds_max = (int)staged_lds_bytes(T, h->lds_from);
+#define TBNAV_X(TR) if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_cost<TR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  TBNAV_MPPI_COST_FORMS(TBNAV_X)
+#undef TBNAV_X
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     const int rc = tbnav::hip_fail(e, "tbnav_mppi_create allocation", __FILE__, __LINE__);
@@ -416,7 +334,7 @@ void tbnav_mppi_destroy(tbnav_mppi* h) {
   (void)hipFree(h->d_raw); (void)hipFree(h->d_records); (void)hipFree(h->d_records_f); (void)hipFree(h->d_out);
   (void)hipFree(h->d_ahead); (void)hipFree(h->d_ahead_tag); (void)hipFree(h->d_field);
   if (h->h_out) (void)hipHostFree(h->h_out);
-  for (auto* g : {&h->tg, &h->tgs}) { if (g->exec) (void)hipGraphExecDestroy(g->exec); if (g->graph) (void)hipGraphDestroy(g->graph); }
+  drop_graph(h->tg); drop_graph(h->tgs);
   (void)hipFree(h->d_tick0);
   delete h;
 }
@@ -472,25 +390,12 @@ int tbnav_mppi_set_option(tbnav_mppi* h, int32_t option, int32_t value) {
       return TBNAV_OK;
     case TBNAV_MPPI_OPT_KERNEL: {
       // 0: mppi_rollout_cost (sequential); n > 0: mppi_rollout_scan with n steps per thread; -4 / -8 / -16: fused, that many rollouts per workgroup
-      int fused = 0, tc = 0;
-      if (value < 0) {
-        fused = -value;
-        if (!(T <= 2 * kWave && (fused == 4 || fused == 8 || fused == 16))) return TBNAV_ERR_INVALID_ARG;
-      } else if (value > 0) {
-        const int cmax = (value == 4 || value == 7 || value == 8) ? 16 : 12;
-        bool known = false;
-        for (int t : {4, 5, 6, 7, 8, 10, 12, 16, 20}) known |= t == value;
-        if (!known || (T + value - 1) / value > cmax) return TBNAV_ERR_INVALID_ARG;
-        tc = value;
-      }
-      h->scan_tc = tc;
-      h->fused_r = fused;
-      h->fused_dev = fused > 0;          // a forced choice holds for both kinds of tick (in-kernel noise exists for 8 and 16:
-      h->fused_rng = fused == 8 || fused == 16;  //  a 4-rollout workgroup samples first)
-      h->fused_S = fused ? (h->K + fused - 1) / fused : 0;
+      const KernelOption o = plan_kernel_option(T, h->K, value);   // (which values a horizon admits: mppi_plan.hpp)
+      if (!o.ok) return TBNAV_ERR_INVALID_ARG;
+      h->scan_tc = o.scan_tc; h->fused_r = o.fused_r; h->fused_dev = o.fused_dev; h->fused_rng = o.fused_rng; h->fused_S = o.fused_S;
       (void)hipFree(h->d_records_f);
       h->d_records_f = nullptr;
-      if (fused) TBNAV_HIP(hipMalloc((void**)&h->d_records_f, sizeof(double) * (size_t)T * h->fused_S * TBNAV_MPPI_REC));
+      if (o.fused_r) TBNAV_HIP(hipMalloc((void**)&h->d_records_f, sizeof(double) * (size_t)T * h->fused_S * TBNAV_MPPI_REC));
       TBNAV_HIP(hipDeviceSynchronize());   // (a queued tick may still read the old pair buffer)
       TBNAV_HIP(ahead_alloc(h));
       return TBNAV_OK;
@@ -563,11 +468,7 @@ int tbnav_mppi_shard_partials(tbnav_mppi* h, const double x0[3], const double* d
     // small K: the fused rollout+partials kernel, then its fine records folded into the K-slice records that the
     // ranks exchange (two short launches instead of three)
     const int rcf = launch_fused(h, x0, d_duL, d_duR, st);
-    if (rcf != TBNAV_OK) return rcf;
-    hipLaunchKernelGGL(mppi_merge_records, dim3(h->S, h->T), dim3(kWave), 0, st, h->T, h->fused_S, kSlice / h->fused_r, h->S,
-                       lam_of(h), h->d_records_f, d_records_out, take_pub(h));
-    TBNAV_HIP(hipGetLastError());
-    return TBNAV_OK;
+    return rcf != TBNAV_OK ? rcf : launch_merge(h, d_records_out, st);
   }
   int rc = launch_rollout(h, x0, d_duL, d_duR, st);
   if (rc != TBNAV_OK) return rc;
@@ -584,13 +485,9 @@ int tbnav_mppi_shard_partials_rng(tbnav_mppi* h, const double x0[3], uint64_t se
   }
   DeviceGuard guard(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const RngArgs g{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
+  const RngArgs g = rng_args(h, seed, tick);
   const int rcf = launch_fused(h, x0, h->d_duL, h->d_duR, st, &g);
-  if (rcf != TBNAV_OK) return rcf;
-  hipLaunchKernelGGL(mppi_merge_records, dim3(h->S, h->T), dim3(kWave), 0, st, h->T, h->fused_S, kSlice / h->fused_r, h->S,
-                     lam_of(h), h->d_records_f, d_records_out, take_pub(h));
-  TBNAV_HIP(hipGetLastError());
-  return TBNAV_OK;
+  return rcf != TBNAV_OK ? rcf : launch_merge(h, d_records_out, st);
 }
 
 int tbnav_mppi_shard_combine(tbnav_mppi* h, const double* d_records_all, int32_t n_shards, void* stream) {
@@ -656,24 +553,14 @@ int tbnav_mppi_profile_kernels(tbnav_mppi* h, const double x0[3], const double* 
   hipEvent_t ev[2];
   for (auto& e : ev) TBNAV_HIP(hipEventCreate(&e));
   int rc = TBNAV_OK;
-  auto timed = [&](int which, auto&& launch) {
-    if (rc != TBNAV_OK) return;
-    if (hipEventRecord(ev[0], st) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
-    for (int r = 0; r < reps && rc == TBNAV_OK; ++r) rc = launch();
-    if (rc != TBNAV_OK) return;
-    float t = 0.f;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&t, ev[0], ev[1]) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
-    ms[which] = t / (float)reps;
-  };
   for (int i = 0; i < TBNAV_MPPI_NKERNELS; ++i) ms[i] = 0.f;
   if (fused_dev(h)) {
-    timed(0, [&] { return launch_fused(h, x0, d_duL, d_duR, st); });
-    timed(2, [&] { return launch_combine(h, h->d_records_f, 1, st, h->fused_S); });
+    timed(ev, st, reps, ms, 0, rc, [&](int) { return launch_fused(h, x0, d_duL, d_duR, st); });
+    timed(ev, st, reps, ms, 2, rc, [&](int) { return launch_combine(h, h->d_records_f, 1, st, h->fused_S); });
   } else {
-    timed(0, [&] { return launch_rollout(h, x0, d_duL, d_duR, st); });
-    timed(1, [&] { return launch_partials(h, d_duL, d_duR, h->d_records, st); });
-    timed(2, [&] { return launch_combine(h, h->d_records, 1, st); });
+    timed(ev, st, reps, ms, 0, rc, [&](int) { return launch_rollout(h, x0, d_duL, d_duR, st); });
+    timed(ev, st, reps, ms, 1, rc, [&](int) { return launch_partials(h, d_duL, d_duR, h->d_records, st); });
+    timed(ev, st, reps, ms, 2, rc, [&](int) { return launch_combine(h, h->d_records, 1, st); });
   }
   for (auto& e : ev) (void)hipEventDestroy(e);
   return rc;
@@ -692,32 +579,22 @@ int tbnav_mppi_profile_kernels_rng(tbnav_mppi* h, const double x0[3], uint64_t s
   hipEvent_t ev[2];
   for (auto& e : ev) TBNAV_HIP(hipEventCreate(&e));
   int rc = TBNAV_OK;
-  auto timed = [&](int which, auto&& launch) {
-    if (rc != TBNAV_OK) return;
-    if (hipEventRecord(ev[0], st) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
-    for (int r = 0; r < reps && rc == TBNAV_OK; ++r) rc = launch(r);
-    if (rc != TBNAV_OK) return;
-    float t = 0.f;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&t, ev[0], ev[1]) != hipSuccess) { rc = TBNAV_ERR_HIP; return; }
-    ms[which] = t / (float)reps;
-  };
   for (int i = 0; i < TBNAV_MPPI_NKERNELS; ++i) ms[i] = 0.f;
   // the launches of tbnav_mppi_enqueue_rng, kernel by kernel, in the form the steady-state tick runs them: the in-kernel-noise
   // instantiation of the fused kernel and, with noise ahead, that kernel finding its pairs drawn (one untimed tick `tick` draws
   // tick + 1's; every timed launch is tick + 1 and hits) and the combine with its sampler blocks (drawing tick + 2 + r)
   const bool ahead = ahead_on(h);
-  RngArgs g{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
+  RngArgs g = rng_args(h, seed, tick);
   if (ahead) {
     rc = rng_tick(h, x0, g, st);
-    g.ahead = h->d_ahead; g.ahead_tag = h->d_ahead_tag; g.epoch = h->cfg_epoch; g.kind = h->sampler == 1 ? 2 : 1; g.K = h->K;
+    g = with_ahead(h, g);
   }
-  timed(0, [&](int r) {
+  timed(ev, st, reps, ms, 0, rc, [&](int r) {
     RngArgs gr = g;
     gr.base = rng_base(h, ahead ? tick + 1 : tick + (uint64_t)r);
     return launch_fused(h, x0, h->d_duL, h->d_duR, st, &gr);
   });
-  timed(2, [&](int r) {
+  timed(ev, st, reps, ms, 2, rc, [&](int r) {
     RngArgs nx = g;
     nx.base = rng_base(h, tick + 2 + (uint64_t)r);
     return launch_combine(h, h->d_records_f, 1, st, h->fused_S, nullptr, ahead ? &nx : nullptr);
@@ -728,22 +605,8 @@ int tbnav_mppi_profile_kernels_rng(tbnav_mppi* h, const double x0[3], uint64_t s
 
 int tbnav_mppi_last_kernel_names(const tbnav_mppi* h, char* rollout, int32_t rollout_cap, char* combine, int32_t combine_cap) {
   if (!h) return TBNAV_ERR_INVALID_ARG;
-  const int* k = h->lk_rollout;
-  if (rollout && rollout_cap > 0) {
-    switch (k[0]) {
-      case 1: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_fused<%d, %d, %d, %d>", k[1], k[2], k[3], k[4]); break;   // (as the profiler spells the instantiation)
-      case 2: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_scan<%d, %d, %d>", k[1], k[2], k[3]); break;
-      case 3: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_prefix<%d>", k[1]); break;
-      case 4: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_cost<%d>", k[1]); break;
-      case 5: snprintf(rollout, (size_t)rollout_cap, "mppi_rollout_field<%d>", k[1]); break;
-      default: rollout[0] = 0;
-    }
-  }
-  if (combine && combine_cap > 0) {
-    if (h->lk_combine[0] == -4) snprintf(combine, (size_t)combine_cap, "mppi_combine_wide");
-    else if (h->lk_combine[0]) snprintf(combine, (size_t)combine_cap, "mppi_combine<%d, %d>", h->lk_combine[0], h->lk_combine[1]);
-    else combine[0] = 0;
-  }
+  if (rollout && rollout_cap > 0) form_name(h->lk_rollout, rollout, (size_t)rollout_cap);   // (as the profiler spells the instantiation)
+  if (combine && combine_cap > 0) form_name(h->lk_combine, combine, (size_t)combine_cap);
   return TBNAV_OK;
 }
 
@@ -822,15 +685,10 @@ int tbnav_mppi_enqueue_rng(tbnav_mppi* h, const double x0[3], uint64_t seed, uin
   }
   DeviceGuard guard(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return rng_tick(h, x0, RngArgs{seed, rng_base(h, tick), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)}, st);
+  return rng_tick(h, x0, rng_args(h, seed, tick), st);
 }
 
 namespace {
-using TickGraph = tbnav_mppi::TickGraph;
-void drop_graph(TickGraph& g) {
-  if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-  if (g.graph) { (void)hipGraphDestroy(g.graph); g.graph = nullptr; }
-}
 bool graph_usable(const tbnav_mppi* h, const TickGraph& g, const double* x0, uint64_t seed, hipStream_t st) {
   return g.exec && g.epoch == h->cfg_epoch && g.seed == seed && g.stream == st && std::memcmp(g.x0, x0, sizeof g.x0) == 0;
 }
@@ -846,7 +704,7 @@ void build_graph(tbnav_mppi* h, TickGraph& g, int len, const double* x0, uint64_
   const int ucur0 = h->ucur; const uint64_t seq0 = h->seq;
   int rc = TBNAV_OK;
   for (int t = 0; t < len && rc == TBNAV_OK; ++t) {
-    RngArgs ra{seed, rng_base(h, (uint64_t)t), std::sqrt(h->p.ul_var), std::sqrt(h->p.ur_var)};
+    RngArgs ra = rng_args(h, seed, (uint64_t)t);
     ra.tick0 = h->d_tick0; ra.per_tick = (uint64_t)h->T * h->k_global;
     rc = rng_tick(h, x0, ra, st);   // (the last tick's combine draws the first tick of the next replay: the tag holds the resolved counters)
   }
@@ -883,9 +741,8 @@ int tbnav_mppi_enqueue_rng_batch(tbnav_mppi* h, const double* x0s, int32_t x0_st
   constexpr int kGraphTicks = 100;  // (even: the controls' double buffer is back where it was after a chunk)
   constexpr int kShortMin = 8;      // the shortest batch worth a graph of its own
   hipStream_t st = static_cast<hipStream_t>(stream);
-  // (only where the tick is short enough for the launches themselves to matter: K = 1024: 8.25 -> 8.15 us per tick on a fast host, 8.9 -> 8.3
-  //  on a slower one; from K = 2048 up the device is the bound and the replay is 1-3 % slower than plain launches)
-  if (h->graph_on && !h->comm && x0_stride == 0 && st != nullptr && rng_in_kernel(h) && h->fused_r == 8 && h->K <= 1536 && n_ticks >= 2) {
+  // (only where the tick is short enough for the launches themselves to matter: graph_worth_it, mppi_plan.hpp)
+  if (h->graph_on && !h->comm && x0_stride == 0 && st != nullptr && graph_worth_it(rng_in_kernel(h), h->fused_r, h->K, n_ticks)) {
     DeviceGuard guard(h->device);
     // (the chunk graph is built by the first batch call that could use one, however short — a warm-up call, typically — so that a
     //  later long call does not pay the ~1 ms of capture + instantiation)
@@ -988,27 +845,30 @@ int tbnav_mppi_debug_div_lambda(const double* x_host, int32_t n, double lambda, 
 
 int tbnav_mppi_debug_combine_general(tbnav_mppi* h, double* u_host) {
   if (!h || !u_host) return TBNAV_ERR_INVALID_ARG;
-  const int keep = h->lk_combine[0], S = h->lk_S, T = h->T;
-  if (h->lk_combine[1] != 0 || (keep != 2 && keep != 4 && keep != 8) || !h->lk_records || h->lk_G != 1 || S > keep * kWave) return TBNAV_ERR_INVALID_ARG;
+  const KernelForm last = h->lk_combine;
+  const int keep = last.arg[0], S = h->lk_S, T = h->T;
+  if (last.family != kCombine || last.arg[1] != 0 || !h->lk_records || h->lk_G != 1 || S > keep * kWave) return TBNAV_ERR_INVALID_ARG;
   DeviceGuard guard(h->device);
-  // launch_combine's arithmetic for one group; the tick's input controls are the vector that is no longer current (the tick wrote
-  // the other one), read with the shift the tick read them with
-  int tpr_log2 = 0;
-  while ((1 << tpr_log2) < S && (1 << tpr_log2) < kWave) ++tpr_log2;
-  const int steps_per_block = TBNAV_COMBINE_WAVES * (kWave >> tpr_log2), blocks = (T + steps_per_block - 1) / steps_per_block;
+  // the last tick's own geometry (one group, nothing drawn ahead), run by the general form <KEEP, 1>; the tick's input controls are
+  // the vector that is no longer current (the tick wrote the other one), read with the shift the tick read them with
+  const CombinePlan p = plan_combine(T, h->K, 1, S, false, false, false, false);
   const DirectSrc ds{nullptr, 0ull, nullptr, nullptr, 0u};
   const RngArgs off{0, 0, 0.0, 0.0};
   double* d = nullptr;   // [2][T] controls, then the two to apply
   TBNAV_HIP(hipDeviceSynchronize());
   hipError_t e = hipMalloc((void**)&d, sizeof(double) * (2 * (size_t)T + 2));
-#define TBNAV_GENERAL(KEEP) hipLaunchKernelGGL((mppi_combine<KEEP, 1>), dim3(blocks), dim3(TBNAV_COMBINE_WAVES * kWave), 0, nullptr, h->lk_records, (const double*)h->d_u[1 - h->ucur], (double*)nullptr, \
-                                               (const uint64_t*)nullptr, T, S, h->lk_ushift, blocks, 1, tpr_log2, (uint64_t*)nullptr, lam_of(h), h->p.max_wheel_vel, h->uinit[0], h->uinit[1], d, d + 2 * (size_t)T, \
-                                               (double*)nullptr, 0.0, ds, rng_rest(off))
   if (e == hipSuccess) {
-    if (keep == 2) TBNAV_GENERAL(2); else if (keep == 4) TBNAV_GENERAL(4); else TBNAV_GENERAL(8);
-    e = hipGetLastError();
+    e = hipErrorInvalidDeviceFunction;   // (a KEEP the list does not have)
+#define TBNAV_X(KEEP, MODE)                                                                                                                            \
+    if (MODE == 1 && keep == KEEP) {                                                                                                                   \
+      hipLaunchKernelGGL((mppi_combine<KEEP, MODE>), dim3(p.blocks), dim3(p.block), 0, nullptr, h->lk_records, (const double*)h->d_u[1 - h->ucur],    \
+                         (double*)nullptr, (const uint64_t*)nullptr, T, S, h->lk_ushift, p.blocks, 1, p.tpr_log2, (uint64_t*)nullptr, lam_of(h),       \
+                         h->p.max_wheel_vel, h->uinit[0], h->uinit[1], d, d + 2 * (size_t)T, (double*)nullptr, 0.0, ds, rng_rest(off));                \
+      e = hipGetLastError();                                                                                                                           \
+    }
+    TBNAV_MPPI_COMBINE_FORMS(TBNAV_X)
+#undef TBNAV_X
   }
-#undef TBNAV_GENERAL
   if (e == hipSuccess) e = hipMemcpy(u_host, d, sizeof(double) * 2 * (size_t)T, hipMemcpyDeviceToHost);
   (void)hipFree(d);
   TBNAV_HIP(e);

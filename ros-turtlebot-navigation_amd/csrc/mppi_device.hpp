@@ -2,8 +2,8 @@
 // combine, exchange words, noise) and the host side (mppi.hip: handle, launches, C-ABI; mppi_sharded.hip: exchange set-up,
 // sharded tick, groups) share: the launch-argument structs, the rollout arithmetic (device trig, RK4 / exact-arc steps, losses),
 // the Philox noise source and the declaration of every kernel.  Kernels are defined in their family's file and launched from the
-// host files; the template kernels are explicitly instantiated where they are defined.  All four are compiled with
-// -ffp-contract=fast-honor-pragmas (csrc/Makefile says why).
+// host files; the template kernels are explicitly instantiated where they are defined, from mppi_plan.hpp's lists of forms.
+// All four are compiled with -ffp-contract=fast-honor-pragmas (csrc/Makefile says why).
 // Reference: controller/src/controller/mppi.cpp:72-140, rk4.cpp:49-115, controller/include/controller/mppi.hpp:41-105.
 #ifndef TBNAV_MPPI_DEVICE_HPP
 #define TBNAV_MPPI_DEVICE_HPP
@@ -13,23 +13,10 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "mppi_plan.hpp"   // the sizes the kernels and the selection share, the lists of forms
 #include "tbnav_mppi.h"
 
 namespace tbnav_mk {
-
-constexpr int kWave = 64;
-constexpr int kSliceThreads = 256;
-constexpr int kSliceItems = 8;
-constexpr int kSlice = kSliceThreads * kSliceItems;  // rollouts per K-slice record
-constexpr int kMaxLdsBytes = 160 * 1024;
-constexpr int kGroup = 4;        // steps per group of the one-lane-per-rollout kernels (independent trig chains)
-constexpr int kRoundGroups = 3;  // groups per round of mppi_rollout_prefix
-#ifndef TBNAV_AHEAD_PAIRS
-#define TBNAV_AHEAD_PAIRS 1  // noise pairs per lane of the combine's sampler blocks (TBNAV_MPPI_OPT_NOISE_AHEAD; 1, 2, 4 measured: docs/lab_notebook.md)
-#endif
-#ifndef TBNAV_COMBINE_WAVES
-#define TBNAV_COMBINE_WAVES 1  // one wave per workgroup: the groups spread over as many CUs as there are time steps (K = 1024 tick 8.9 -> 8.4 us against four waves)
-#endif
 
 // The warm-start controls as the kernels see them.  A tick leaves its updated, UNSHIFTED controls in `p`;
 // the shift of mppi.cpp:134-137 (u(:,i) <- u(:,i+1), last <- uinit) is applied on read by the next tick

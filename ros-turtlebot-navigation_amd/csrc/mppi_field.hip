@@ -166,10 +166,10 @@ __global__ __launch_bounds__(kWave) void mppi_rollout_field(RolloutArgs a, Field
     Jk[(size_t)i * K] = acc;
   }
 }
-// (TRIG 2 — a fresh sincos every step, an A-B setting — takes the three-evaluation form here, as in the time-parallel kernel)
-template __global__ void mppi_rollout_field<1>(RolloutArgs, FieldArgs, const double* __restrict__, const double* __restrict__, USrc, double* __restrict__);
-template __global__ void mppi_rollout_field<3>(RolloutArgs, FieldArgs, const double* __restrict__, const double* __restrict__, USrc, double* __restrict__);
-template __global__ void mppi_rollout_field<4>(RolloutArgs, FieldArgs, const double* __restrict__, const double* __restrict__, USrc, double* __restrict__);
+// (mppi_plan.hpp's list of forms: TRIG 2 takes the three-evaluation form here, as in the time-parallel kernel)
+#define TBNAV_X(TR) template __global__ void mppi_rollout_field<TR>(RolloutArgs, FieldArgs, const double* __restrict__, const double* __restrict__, USrc, double* __restrict__);
+TBNAV_MPPI_FIELD_FORMS(TBNAV_X)
+#undef TBNAV_X
 
 // the test hook's kernel: F2 through the rollout kernel's own two functions
 __global__ void mppi_field_lookup(FieldArgs f, int n, const double* __restrict__ xy, double* __restrict__ out) {
@@ -188,38 +188,32 @@ namespace {
 FieldArgs field_args(const tbnav_mppi* h) {
   return FieldArgs{h->d_field, h->field.xmin, h->field.ymin, 1.0 / h->field.resolution, h->field.weight, h->field.nx, h->field.ny};
 }
-size_t field_lds_bytes(const tbnav_mppi* h, int lds_from) {
-  return (size_t)2 * h->T * sizeof(double) + (size_t)(h->T - lds_from) * kWave * sizeof(double);
-}
 bool geom_ok(const tbnav_mppi_cost_field& g) {
   return g.nx >= 2 && g.nx <= TBNAV_MPPI_FIELD_MAX_SIDE && g.ny >= 2 && g.ny <= TBNAV_MPPI_FIELD_MAX_SIDE && std::isfinite(g.xmin) &&
          std::isfinite(g.ymin) && std::isfinite(g.resolution) && g.resolution > 0.0 && std::isfinite(g.weight);
 }
 }  // namespace
 
-int tbnav_mh::launch_rollout_field(tbnav_mppi* h, RolloutArgs a, const USrc& usrc, const double* d_duL, const double* d_duR, hipStream_t st) {
-  const dim3 grid((h->K + kWave - 1) / kWave), block(kWave);
-  a.lds_from = h->lds_from;
-  const size_t lds = field_lds_bytes(h, h->lds_from);
-  const FieldArgs f = field_args(h);
-  h->prefix_rows = 0;
-  h->lk_rollout[0] = 5; h->lk_rollout[1] = h->dyn == 1 ? 4 : (h->trig == 1 ? 1 : 3);
-  if (h->dyn == 1) hipLaunchKernelGGL((mppi_rollout_field<4>), grid, block, lds, st, a, f, d_duL, d_duR, usrc, h->d_J);
-  else if (h->trig == 1) hipLaunchKernelGGL((mppi_rollout_field<1>), grid, block, lds, st, a, f, d_duL, d_duR, usrc, h->d_J);
-  else hipLaunchKernelGGL((mppi_rollout_field<3>), grid, block, lds, st, a, f, d_duL, d_duR, usrc, h->d_J);
-  TBNAV_HIP(hipGetLastError());
-  h->j_valid = true;
-  return TBNAV_OK;
+int tbnav_mh::launch_rollout_field(tbnav_mppi* h, const RolloutPlan& p, const RolloutArgs& a, const USrc& usrc, const double* d_duL, const double* d_duR, hipStream_t st) {
+#define TBNAV_X(TR)                                                                                                                         \
+  if (p.form.is(kField, TR)) {                                                                                                              \
+    hipLaunchKernelGGL((mppi_rollout_field<TR>), dim3(p.grid), dim3(kWave), p.lds, st, a, field_args(h), d_duL, d_duR, usrc, h->d_J);       \
+    TBNAV_HIP(hipGetLastError());                                                                                                           \
+    return TBNAV_OK;                                                                                                                        \
+  }
+  TBNAV_MPPI_FIELD_FORMS(TBNAV_X)
+#undef TBNAV_X
+  return TBNAV_ERR_UNSUPPORTED;  // (a form the plan names and the list does not have: never another form in its place)
 }
 
 namespace {
 // what both stagings share: the kernel's dynamic LDS allowed for this handle, and room for the values on its device (current here)
 int field_alloc(tbnav_mppi* h, size_t n, float** d) {
   // the kernel's dynamic LDS, as tbnav_mppi_create allows it for mppi_rollout_cost (lds_from only ever grows afterwards)
-  const int lds_max = (int)field_lds_bytes(h, h->lds_from);
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-  TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  const int lds_max = (int)staged_lds_bytes(h->T, h->lds_from);
+#define TBNAV_X(TR) TBNAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_rollout_field<TR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+  TBNAV_MPPI_FIELD_FORMS(TBNAV_X)
+#undef TBNAV_X
   TBNAV_HIP(hipMalloc((void**)d, n * sizeof(float)));
   return TBNAV_OK;
 }

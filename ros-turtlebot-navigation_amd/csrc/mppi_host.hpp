@@ -1,5 +1,6 @@
-// mppi_host.hpp — the MPPI handle and what the two host files share (mppi.hip: create / options / launchers / single-GPU C-ABI;
-// mppi_sharded.hip: communicator attachment, direct exchange, sharded tick, groups).  Kernels and launch structs: mppi_device.hpp.
+// mppi_host.hpp — the MPPI handle and what the host files share (mppi.hip: create / options / launchers / single-GPU C-ABI;
+// mppi_field.hip: the cost field; mppi_sharded.hip: communicator attachment, direct exchange, sharded tick, groups).  Kernels and
+// launch structs: mppi_device.hpp; what a handle decides and which instantiation a tick launches: mppi_plan.hpp.
 #ifndef TBNAV_MPPI_HOST_HPP
 #define TBNAV_MPPI_HOST_HPP
 #include <hip/hip_runtime.h>
@@ -20,8 +21,7 @@ using tbnav_mk::DirectPub;
 struct tbnav_mppi {
   tbnav_mppi_params p;
   int T = 0, K = 0, S = 0, device = 0;
-  int lk_rollout[5] = {0, 0, 0, 0, 0};  // the instantiation the last rollout launch picked: kind (1 fused, 2 scan, 3 prefix, 4 cost, 5 field), template arguments
-  int lk_combine[2] = {0, 0};           // ... and the last combine: KEEP, DIRECT  (tbnav_mppi_last_kernel_names)
+  tbnav_mk::KernelForm lk_rollout, lk_combine;   // the instantiations the last rollout launch and the last combine picked (tbnav_mppi_last_kernel_names)
   const double* lk_records = nullptr;   // ... what that combine read: its records, S, G and whether it read the controls shifted
   int lk_S = 0, lk_G = 0, lk_ushift = 0;   //     (tbnav_mppi_debug_combine_general)
   double xd[3] = {0, 0, 0};
@@ -136,8 +136,10 @@ struct DeviceGuard {
 // which ticks take the fused kernel (resident noise / noise drawn inside it): never a handle with a cost field
 inline bool fused_dev(const tbnav_mppi* h) { return h->fused_dev && !h->field_on; }
 inline bool fused_rng(const tbnav_mppi* h) { return h->fused_rng && !h->field_on; }
-// (mppi_field.hip) the rollout launch of a handle with a cost field; a's lds_from and the kernel's name are set there
-int launch_rollout_field(tbnav_mppi* h, RolloutArgs a, const USrc& usrc, const double* d_duL, const double* d_duR, hipStream_t st);
+// the warm-start controls as the next launch reads them
+inline USrc usrc_of(const tbnav_mppi* h) { return USrc{h->d_u[h->ucur], h->pending_shift ? 1 : 0, h->uinit[0], h->uinit[1]}; }
+// (mppi_field.hip) the rollout launch of a handle with a cost field: the form plan_rollout named, over the field's list
+int launch_rollout_field(tbnav_mppi* h, const RolloutPlan& p, const RolloutArgs& a, const USrc& usrc, const double* d_duL, const double* d_duR, hipStream_t st);
 // the two halves of tbnav_mppi_set_cost_field, apart so that a group can stage every member's copy before any member changes:
 // field_stage checks F1 and uploads the values (*d_new = nullptr for geom == nullptr); field_commit waits for the device and swaps
 int field_stage(tbnav_mppi* h, const tbnav_mppi_cost_field* geom, const float* values_host, float** d_new);

@@ -1,5 +1,5 @@
 // mppi_rollout.hip — the rollout half of controller::MPPI::newControls (mppi.cpp:81-109; rk4.cpp:49-115; mppi.hpp:41-105), four
-// kernel families (all fp64; which one a handle takes: tbnav_mppi_create in mppi.hip):
+// kernel families (all fp64; which one a handle takes: plan_create in mppi_plan.hpp):
 //   mppi_rollout_fused   small K (K/64 < 2 x CUs, T <= 128): one wave per rollout with its lanes over TIME, DPP wave scans for
 //                        heading / position / cost-to-go, and the soft-min partial record of every time step over the workgroup's
 //                        rollouts in the same launch; the perturbations drawn in-kernel (RNG = 1: fp32 Box-Muller, 2: fp64)
@@ -653,39 +653,23 @@ __global__ __launch_bounds__(kWave * R) void mppi_rollout_fused(const double* __
   }
 }
 
-// ---- explicit instantiations: exactly what mppi.hip's launchers name -------------------------------------------------------------
+// ---- explicit instantiations: mppi_plan.hpp's lists of forms, which the launchers of mppi.hip dispatch over -------------------------
 #define TBNAV_ARGS_ROLLOUT RolloutArgs, const double* __restrict__, const double* __restrict__, USrc, double* __restrict__
-template __global__ void mppi_rollout_cost<1>(TBNAV_ARGS_ROLLOUT);
-template __global__ void mppi_rollout_cost<2>(TBNAV_ARGS_ROLLOUT);
-template __global__ void mppi_rollout_cost<3>(TBNAV_ARGS_ROLLOUT);
-template __global__ void mppi_rollout_cost<4>(TBNAV_ARGS_ROLLOUT);
-template __global__ void mppi_rollout_prefix<1>(TBNAV_ARGS_ROLLOUT, double* __restrict__);
-template __global__ void mppi_rollout_prefix<2>(TBNAV_ARGS_ROLLOUT, double* __restrict__);
-template __global__ void mppi_rollout_prefix<3>(TBNAV_ARGS_ROLLOUT, double* __restrict__);
-#define TBNAV_INST_SCAN(TR) \
-  template __global__ void mppi_rollout_scan<TR, 4, 16>(TBNAV_ARGS_ROLLOUT); template __global__ void mppi_rollout_scan<TR, 4, 12>(TBNAV_ARGS_ROLLOUT);   \
-  template __global__ void mppi_rollout_scan<TR, 5, 12>(TBNAV_ARGS_ROLLOUT); template __global__ void mppi_rollout_scan<TR, 6, 12>(TBNAV_ARGS_ROLLOUT);   \
-  template __global__ void mppi_rollout_scan<TR, 7, 16>(TBNAV_ARGS_ROLLOUT); template __global__ void mppi_rollout_scan<TR, 8, 16>(TBNAV_ARGS_ROLLOUT);   \
-  template __global__ void mppi_rollout_scan<TR, 8, 12>(TBNAV_ARGS_ROLLOUT); template __global__ void mppi_rollout_scan<TR, 10, 12>(TBNAV_ARGS_ROLLOUT);  \
-  template __global__ void mppi_rollout_scan<TR, 12, 12>(TBNAV_ARGS_ROLLOUT); template __global__ void mppi_rollout_scan<TR, 16, 12>(TBNAV_ARGS_ROLLOUT); \
-  template __global__ void mppi_rollout_scan<TR, 20, 12>(TBNAV_ARGS_ROLLOUT);
-TBNAV_INST_SCAN(1)
-TBNAV_INST_SCAN(3)
-#undef TBNAV_INST_SCAN
-#define TBNAV_ARGS_FUSED const double* __restrict__, const double* __restrict__, const uint64_t* __restrict__, const uint64_t* __restrict__, int, int, int, int, \
-                         double* __restrict__, double* __restrict__, RolloutArgs, double, double, Lam, const double* __restrict__, const double* __restrict__, RngRest
-#define TBNAV_INST_FUSED(TR, RR, RG) \
-  template __global__ void mppi_rollout_fused<TR, RR, 1, RG>(TBNAV_ARGS_FUSED); template __global__ void mppi_rollout_fused<TR, RR, 2, RG>(TBNAV_ARGS_FUSED);
-#define TBNAV_INST_FUSED_TR(TR) \
-  TBNAV_INST_FUSED(TR, 4, 0) TBNAV_INST_FUSED(TR, 8, 0) TBNAV_INST_FUSED(TR, 16, 0) TBNAV_INST_FUSED(TR, 8, 1) TBNAV_INST_FUSED(TR, 16, 1)
-TBNAV_INST_FUSED_TR(2)
-TBNAV_INST_FUSED_TR(3)
-TBNAV_INST_FUSED_TR(4)
-// the fp64 sampler (round 6: the handle's default, TBNAV_MPPI_OPT_SAMPLER = 1) in every dynamics' kernel
-TBNAV_INST_FUSED(2, 8, 2) TBNAV_INST_FUSED(2, 16, 2) TBNAV_INST_FUSED(3, 8, 2) TBNAV_INST_FUSED(3, 16, 2) TBNAV_INST_FUSED(4, 8, 2) TBNAV_INST_FUSED(4, 16, 2)
-#undef TBNAV_INST_FUSED_TR
-#undef TBNAV_INST_FUSED
-#undef TBNAV_ARGS_FUSED
+#define TBNAV_X(TR) template __global__ void mppi_rollout_cost<TR>(TBNAV_ARGS_ROLLOUT);
+TBNAV_MPPI_COST_FORMS(TBNAV_X)
+#undef TBNAV_X
+#define TBNAV_X(RG) template __global__ void mppi_rollout_prefix<RG>(TBNAV_ARGS_ROLLOUT, double* __restrict__);
+TBNAV_MPPI_PREFIX_FORMS(TBNAV_X)
+#undef TBNAV_X
+#define TBNAV_X(TR, TC, MW) template __global__ void mppi_rollout_scan<TR, TC, MW>(TBNAV_ARGS_ROLLOUT);
+TBNAV_MPPI_SCAN_FORMS(TBNAV_X)
+#undef TBNAV_X
+#define TBNAV_X(TR, RR, TL, RG)                                                                                                                          \
+  template __global__ void mppi_rollout_fused<TR, RR, TL, RG>(const double* __restrict__, const double* __restrict__, const uint64_t* __restrict__,      \
+                                                              const uint64_t* __restrict__, int, int, int, int, double* __restrict__, double* __restrict__, \
+                                                              RolloutArgs, double, double, Lam, const double* __restrict__, const double* __restrict__, RngRest);
+TBNAV_MPPI_FUSED_FORMS(TBNAV_X)
+#undef TBNAV_X
 #undef TBNAV_ARGS_ROLLOUT
 
 }  // namespace tbnav_mk

@@ -593,10 +593,9 @@ __global__ void mppi_sample_noise(int T, int K, uint64_t seed, uint64_t base, do
   }
 }
 
-#define TBNAV_INST_COMBINE(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(const double* __restrict__, const double* __restrict__, double* __restrict__, const uint64_t* __restrict__, int, int, int, int, int, int, uint64_t* __restrict__, Lam, double, double, double, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc, RngRest);
-TBNAV_INST_COMBINE(2, 0) TBNAV_INST_COMBINE(4, 0) TBNAV_INST_COMBINE(8, 0)
-TBNAV_INST_COMBINE(2, 1) TBNAV_INST_COMBINE(4, 1) TBNAV_INST_COMBINE(8, 1)
-TBNAV_INST_COMBINE(2, 2) TBNAV_INST_COMBINE(4, 2) TBNAV_INST_COMBINE(8, 2)
-#undef TBNAV_INST_COMBINE
+// ---- explicit instantiations: mppi_plan.hpp's list of forms, which launch_combine (mppi.hip) dispatches over ----------------------
+#define TBNAV_X(KEEP, MODE) template __global__ void mppi_combine<KEEP, MODE>(const double* __restrict__, const double* __restrict__, double* __restrict__, const uint64_t* __restrict__, int, int, int, int, int, int, uint64_t* __restrict__, Lam, double, double, double, double* __restrict__, double* __restrict__, double* __restrict__, double, DirectSrc, RngRest);
+TBNAV_MPPI_COMBINE_FORMS(TBNAV_X)
+#undef TBNAV_X
 
 }  // namespace tbnav_mk

@@ -180,6 +180,137 @@ OVERFLOW_PRODUCERS = (
 OVERFLOW_DEFAULT = (1025, 50, "mppi_rollout_fused<2, 8, 1, 0>")    # K % 8 == 1 at the handle's own choice: rollout 1024 overflows
 
 
+# ---- what a handle picks by itself and what a tick then launches, restated from the rules in words -----------------------------
+# (csrc/mppi_plan.hpp is the C++; tests/test_mppi_plan.py holds the two against each other with `==` on the CPU, and
+#  tests/test_mppi_gpu.py holds the launched kernels' names against this file on the device's own CU count)
+LDS_BYTES = 160 * 1024
+Choice = namedtuple("Choice", "K T S lds_from prefix_rg scan_tc fused_dev fused_rng fused_r fused_S")
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def default_choice(K, T, cus):
+    """What tbnav_mppi_create decides for K rollouts of T steps on a chip of `cus` CUs."""
+    waves = _ceil(K, WAVE)                      # one-wave workgroups of the one-lane-per-rollout kernels
+    # losses staged in LDS: the whole grid is to be resident in one round, so the (1 .. 8) workgroups a CU gets share its 160 KB;
+    # each keeps 512 B spare and both control rows (16 B a step), and a staged step takes a wave of doubles.  The steps that do
+    # not fit come first, in whole groups of four
+    share = LDS_BYTES // min(max(_ceil(waves, cus), 1), 8)
+    staged = min(max(share - 512 - 16 * T, 0) // (8 * WAVE), T)
+    lds_from = min(_ceil(T - staged, 4) * 4, T)
+    # the prefix form: whole groups of four steps, two workgroups per CU or more, and a late region of 1, 2 or 3 groups that
+    # leaves whole rounds of three groups, at least one
+    prefix_rg = 0
+    if T % 4 == 0 and waves >= 2 * cus:
+        prefix_rg = next((rg for rg in (1, 2, 3) if (T // 4 - rg) % 3 == 0 and T // 4 - rg >= 3), 0)
+    # the time-parallel kernel: the fewest steps per thread that give at most 12 chunks; not past 2.5 workgroups per CU
+    scan_tc = next((tc for tc in (4, 5, 6, 8, 10, 12, 16, 20) if _ceil(T, tc) <= 12), 0)
+    if waves > 2.5 * cus:
+        scan_tc = 0
+    # the fused kernel: two steps per lane at most, where the time-parallel kernel could run, up to half a workgroup per CU;
+    # 8 rollouts per workgroup up to an eighth of a workgroup per CU, 16 beyond
+    fused = T <= 2 * WAVE and scan_tc > 0 and waves <= cus / 2
+    fused_r = (8 if waves <= cus / 8 else 16) if fused else 0
+    return Choice(K, T, _ceil(K, 2048), lds_from, prefix_rg, scan_tc, fused, fused, fused_r, _ceil(K, fused_r) if fused_r else 0)
+
+
+SCAN_MAX_CHUNKS = {4: 16, 5: 12, 6: 12, 7: 16, 8: 16, 10: 12, 12: 12, 16: 12, 20: 12}
+
+
+def kernel_option(choice, value):
+    """`choice` after TBNAV_MPPI_OPT_KERNEL = value, or None where the value is refused (and the handle stays as it was)."""
+    K, T = choice.K, choice.T
+    if value < 0:
+        if -value not in (4, 8, 16) or T > 2 * WAVE:
+            return None
+        return choice._replace(scan_tc=0, fused_dev=True, fused_rng=-value in (8, 16), fused_r=-value, fused_S=_ceil(K, -value))
+    if value > 0 and (value not in SCAN_MAX_CHUNKS or _ceil(T, value) > SCAN_MAX_CHUNKS[value]):
+        return None
+    return choice._replace(scan_tc=value, fused_dev=False, fused_rng=False, fused_r=0, fused_S=0)
+
+
+def staged_lds(T, lds_from):
+    return 16 * T + (T - lds_from) * 8 * WAVE
+
+
+def rollout_launch(choice, trig, dyn, field):
+    """The rollout kernel of the three-kernel tick: (name, workgroups, waves per workgroup, dynamic LDS bytes, the lds_from the
+    kernel is told, rows of J left as exclusive prefixes)."""
+    K, T = choice.K, choice.T
+    grid, arc = _ceil(K, WAVE), dyn == "arc"
+    if field:               # a cost field: its own kernel, whatever else the handle chose; TRIG 2 has no form there
+        return f"mppi_rollout_field<{4 if arc else 1 if trig == 1 else 3}>", grid, 1, staged_lds(T, choice.lds_from), choice.lds_from, 0
+    if choice.scan_tc and not arc:      # TRIG 2 has no time-parallel form either
+        tc = choice.scan_tc
+        chunks = _ceil(T, tc)
+        return f"mppi_rollout_scan<{1 if trig == 1 else 3}, {tc}, {scan_mw(tc, T)}>", grid, chunks, 8 * (2 * T + 4 * chunks * WAVE), 0, 0
+    if choice.prefix_rg and not arc and trig == 1:
+        return f"mppi_rollout_prefix<{choice.prefix_rg}>", grid, 1, 16 * T, 0, T - 4 * choice.prefix_rg
+    return f"mppi_rollout_cost<{4 if arc else trig}>", grid, 1, staged_lds(T, choice.lds_from), choice.lds_from, 0
+
+
+def fused_launch(choice, trig, dyn, in_kernel_noise, sampler):
+    """The fused kernel of a handle that runs it: (name, workgroups, threads, dynamic LDS bytes).  sampler: TBNAV_MPPI_OPT_SAMPLER."""
+    R, T = choice.fused_r, choice.T
+    tr = 4 if dyn == "arc" else 3 if trig == 3 else 2
+    rg = (2 if sampler == 1 else 1) if in_kernel_noise else 0
+    return f"mppi_rollout_fused<{tr}, {R}, {1 if T <= WAVE else 2}, {rg}>", choice.fused_S, WAVE * R, 24 * T * (R + 1)
+
+
+def in_kernel_noise_runs(choice, field):
+    """A device-noise tick draws its perturbations inside the fused kernel (otherwise it samples first and runs the resident-noise tick)."""
+    return choice.fused_rng and not field and choice.fused_r in (8, 16)
+
+
+def noise_ahead_wanted(choice):
+    return choice.fused_rng and choice.fused_r == 8
+
+
+def rollout_name(choice, trig, dyn, field, in_kernel_noise, sampler):
+    """The rollout kernel of one tick: in_kernel_noise = a device-noise tick (tbnav_mppi_enqueue_rng), else resident noise."""
+    if in_kernel_noise and in_kernel_noise_runs(choice, field):
+        return fused_launch(choice, trig, dyn, True, sampler)[0]
+    if choice.fused_dev and not field:
+        return fused_launch(choice, trig, dyn, False, sampler)[0]
+    return rollout_launch(choice, trig, dyn, field)[0]
+
+
+def combine_plan(T, K, G, S, direct, err, wide, ahead):
+    """The combine of G groups of S records per step: (name, log2 of the lanes per time step, workgroups for the time steps,
+    sampler workgroups behind them, workgroups launched, threads).  direct: the direct exchange; err: the exchange's error words
+    exist (a communicator is attached); wide: TBNAV_MPPI_OPT_WIDE_COMBINE; ahead: the next tick's noise is drawn in this launch."""
+    n = G * S
+    log2 = 0
+    while (1 << log2) < min(n, WAVE):         # lanes per time step: the power of two that holds the records, a wave at most
+        log2 += 1
+    blocks = _ceil(T, WAVE >> log2)           # one wave per workgroup
+    mode = 2 if direct else 1 if (G > 1 and err) else 0
+    if mode == 0 and G == 1 and combine_name(S, wide) == "mppi_combine_wide":
+        return "mppi_combine_wide", log2, blocks, 0, T, 4 * WAVE
+    ahead_blocks = _ceil(K * T, WAVE) if (ahead and mode == 0) else 0        # one pair per lane
+    return combine_name(n).replace(", 0>", f", {mode}>"), log2, blocks, ahead_blocks, blocks + ahead_blocks, WAVE
+
+
+def tick_names(choice, opts, dyn, device_noise=False, comm=False):
+    """(rollout, combine) of a single-GPU tick of a handle that started as `choice` and had `opts` (a case's, in order) set."""
+    o = dict(TRIG=1, SAMPLER=1, WIDE_COMBINE=1, NOISE_AHEAD=1)
+    for name, v in opts:
+        if name == "KERNEL":
+            choice = kernel_option(choice, v) or choice
+        elif name == "NO_LDS_STAGING" and v:
+            choice = choice._replace(lds_from=choice.T, prefix_rg=0)
+        elif name == "PREFIX_FORM" and not v:
+            choice = choice._replace(prefix_rg=0)
+        else:
+            o[name] = v
+    rollout = rollout_name(choice, o["TRIG"], dyn, False, device_noise, o["SAMPLER"])
+    fused = "fused" in rollout
+    ahead = device_noise and in_kernel_noise_runs(choice, False) and noise_ahead_wanted(choice) and bool(o["NOISE_AHEAD"]) and not comm
+    return rollout, combine_plan(choice.T, choice.K, 1, choice.fused_S if fused else choice.S, False, comm, bool(o["WIDE_COMBINE"]), ahead)[0]
+
+
 # ---- which kernels the table names ------------------------------------------------------------------------------------------------
 def all_cases():
     return fused_resident_cases() + fused_rng_cases() + scan_cases() + sequential_cases() + combine_tick_cases()

@@ -31,7 +31,7 @@ def shipped_kernels():
 
 def test_every_shipped_instantiation_has_a_case_or_a_stated_exclusion(shipped_kernels):
     held = {k for k in shipped_kernels if any(re.match(f, k) for f in mc.HELD_FAMILIES)}
-    # what the launchers of csrc/mppi.hip can name: 42 fused, 22 time-parallel, 4 sequential, 3 single-process combines
+    # what the launchers of csrc/mppi.hip can name (the lists of forms of csrc/mppi_plan.hpp): 42 fused, 22 time-parallel, 4 sequential, 3 single-process combines
     assert [sum(1 for k in held if k.startswith(p)) for p in ("mppi_rollout_fused<", "mppi_rollout_scan<", "mppi_rollout_cost<", "mppi_combine<")] \
         == [42, 22, 4, 3], sorted(held)
     covered = mc.covered_kernels()

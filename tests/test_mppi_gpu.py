@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mppi_cases as mc
 import oracle_api as orc
 from cases import WAYPOINTS, make_mppi, mppi_cfg, rel_err
 
@@ -615,12 +616,17 @@ def test_default_kernel_choice_by_ensemble_size_against_the_oracle(gpu_pkg, K, h
     T = orc.mppi_steps(d)
     m.setWaypoint(*WAYPOINTS[1])
     ref = _check_tick(m, d, np.zeros((2, T)), (0, 0), WAYPOINTS[1], (0.01, 0.0, 0.05), _noise(7, K, T))
+    # the exact instantiations, as tests/mppi_cases.py restates the handle's choice for this device's own CU count
+    import torch
+    choice = mc.default_choice(K, T, torch.cuda.get_device_properties(0).multi_processor_count)
+    assert m.lastKernelNames() == mc.tick_names(choice, (), "rk4"), (m.lastKernelNames(), choice)
     # production tick: in-kernel noise (K <= 8192) or sample + tick — either way the values tbnav_mppi_sample_noise writes
     m2 = make_mppi(gpu_pkg, d); m2.setWaypoint(*WAYPOINTS[1]); m2.setControls(m.getControls())
     m.sampleNoise(11, 3)
     a = m.newControlsDev((0.02, 0.0, 0.06), 0, 0)
     b = m2.newControlsRng((0.02, 0.0, 0.06), 11, 3)
     assert np.array_equal(np.array(a), np.array(b)) and np.array_equal(m.getControls(), m2.getControls())  # same kernels on both sides
+    assert m.lastKernelNames() == mc.tick_names(choice, (), "rk4") and m2.lastKernelNames() == mc.tick_names(choice, (), "rk4", device_noise=True)
 
 
 @pytest.mark.parametrize("K,horizon", [(1024, 0.5), (1500, 0.25), (4096, 1.0)])
