@@ -340,8 +340,11 @@ __device__ __forceinline__ void device_noise(const Rng& g, int T, int i, int k, 
     dl = g.sig_l * (rad * cs);
     dr = g.sig_r * (rad * sn);
   } else {
-    const float u1 = ((float)(r[0] >> 8) + 0.5f) * 0x1.0p-24f;  // (0, 1)
-    const float u2 = ((float)(r[1] >> 8) + 0.5f) * 0x1.0p-24f;  // [0, 1) turns
+    // (0, 1], not (0, 1): from r >> 8 = 2^23 on a float cannot hold the half and the sum rounds to even, so the top value gives
+    // exactly 1.0f.  Harmless: u1 = 1 is log 0, rad = -0, and the pair is (-+0, -+0); no NaN or infinity for any input
+    // (tests/test_noise_restatement.py).
+    const float u1 = ((float)(r[0] >> 8) + 0.5f) * 0x1.0p-24f;  // (0, 1]
+    const float u2 = ((float)(r[1] >> 8) + 0.5f) * 0x1.0p-24f;  // (0, 1] turns
     const float rad = __builtin_sqrtf(-2.0f * 0.69314718056f * __builtin_amdgcn_logf(u1));  // v_log_f32 is log2
     dl = g.sig_l * (double)(rad * __builtin_amdgcn_cosf(u2));
     dr = g.sig_r * (double)(rad * __builtin_amdgcn_sinf(u2));

@@ -127,6 +127,8 @@ __device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned l
 }
 // Box-Muller pair number P of scan `scan` under `seed`: normals 2P and 2P + 1 of the scan's stream (fp64: 53-bit uniforms, log, sqrt,
 // sincospi).  What rbpf_sample_normals stores and what rbpf_propose draws in place: one definition.
+// The uniforms are in (0, 1], not (0, 1): from 2^52 on a double cannot hold the half, the sum rounds to even and the top value gives
+// exactly 1.0 — log 0, rad = -0 and a pair of zeros there; no NaN or infinity for any input (tests/test_noise_restatement.py).
 __device__ __forceinline__ void normal_pair(unsigned long long seed, unsigned long long scan, size_t P, double& a_out, double& b_out) {
   unsigned int r[4];
   philox4x32_10((scan << 40) + P, seed, r);
