@@ -73,6 +73,14 @@ typedef struct tbnav_rbpf_params {
   int32_t device;                      /* HIP device ordinal, -1 = current                */
   double z_hit, z_short, z_max, z_rand, sigma_hit;
   double Trs[3];                       /* robot -> laser (theta, x, y)                    */
+  /* The grid: cell size (metres) and the world's extent.  side = ceil((max - min) / resolution) per axis; a last
+   * cell that sticks out past xmax / ymax is a cell like any other (a point ON xmax belongs to it).  Admitted:
+   *   - resolution > 0, xmax > xmin, ymax > ymin                         (else TBNAV_ERR_INVALID_ARG);
+   *   - the brushfire radius ceil(10 / resolution) at most 254, i.e. resolution >= 0.0394 m to four digits
+   *     (distances along a row are stored in a byte)                     (else TBNAV_ERR_UNSUPPORTED);
+   *   - a square map whose side is even, at least 4 and at most 32000    (else TBNAV_ERR_UNSUPPORTED).
+   * create leaves *out NULL in every refused case.  Held against the reference's GridMapper at 0.05 m and at
+   * 0.0394, 0.0625, 0.07, 0.3 and 0.5 m (tests/raycast_cases.py, propose_cases.py: group `res`). */
   double resolution, xmin, xmax, ymin, ymax;
   double pose0[3];                     /* initial pose (theta, x, y)                      */
 } tbnav_rbpf_params;

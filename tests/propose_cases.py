@@ -25,7 +25,7 @@ import scanmatch_cases as smc
 
 ZERO = (0.0, 0.0, 0.0)
 START = (0.01, 0.012, 0.007)       # (from (0, 0, 0) beam 0 of the first scan ends ON the border y = 0 of its cell)
-RES = 0.05
+RES = 0.05                        # the shipped cell size, and the default of a case's `res`
 K_UNCAP = 16                      # rbpf_plan.hpp: kUnCap
 K_MAX_LDS = 160 * 1024            # kMaxLds
 K_PROPOSE_THREADS = 256           # kProposeThreads (TBNAV_PROPOSE_THREADS)
@@ -45,19 +45,19 @@ ROOM_TIERS = (-2.9, 1.8, -1.5, 1.3)         # walls 38, 16, 14 and 8 cells beyon
 # var = sample_range; clamps; icp = per-scan icp_ok; u_at = {scan: (w, vx)} handed over instead of the true twist's; resample_at;
 # shard = (first, extra) for setRngShard(first, N + extra); window of the oracle's maps; walls_at = {first scan: room};
 # reset_at = scans before which every particle is put on the true pose; threads = the workgroup size the case must launch;
-# expect = what else the case claims (see the CPU test).
+# expect = what else the case claims (see the CPU test); res = the cell size.
 Case = namedtuple("Case", "id group half cells room range_max trs start inc N k beams sources noises n_scans seed valid var clamps icp "
-                          "u_at resample_at shard window walls_at reset_at threads expect")
+                          "u_at resample_at shard window walls_at reset_at threads expect res", defaults=(RES,))
 
 
 def _case(id, group, half=2.0, room=rc.ROOM_SMALL, range_max=3.5, trs=ZERO, start=START, inc=(0.04, 0.03, 0.02), N=4, k=10, beams=360,
           sources=("inj", "query"), noises=("host",), n_scans=3, seed=5, valid=None, var=DEFAULT_VAR, clamps=DEFAULT_CLAMPS, icp=True,
-          u_at=None, resample_at=None, shard=None, window=None, walls_at=None, reset_at=(), threads=256, expect=None):
+          u_at=None, resample_at=None, shard=None, window=None, walls_at=None, reset_at=(), threads=256, expect=None, res=RES):
     icp = (icp,) * n_scans if isinstance(icp, bool) else tuple(icp)
     assert len(icp) == n_scans
-    return Case(id, group, half, int(math.ceil(2 * half / RES)), room, range_max, trs, start, inc, N, k, beams, tuple(sources), tuple(noises),
+    return Case(id, group, half, int(math.ceil(2 * half / res)), room, range_max, trs, start, inc, N, k, beams, tuple(sources), tuple(noises),
                 n_scans, seed, valid or {}, tuple(var), tuple(clamps), icp, u_at or {}, resample_at, shard, window, walls_at or {},
-                tuple(reset_at), threads, expect or {})
+                tuple(reset_at), threads, expect or {}, res)
 
 
 _ALL = (4e-4, 4e-3, 4e-3)          # tests/test_rbpf_gpu.py's widest spread: sigma 6 cm against 5 cm cells, every beam unstable
@@ -164,8 +164,56 @@ CASES = tuple(_sizes() + _beams() + [
     _case("rng-shard-even", "geometry", k=10, noises=("dn",), shard=(3, 5)),
     _case("rng-shard-odd", "geometry", k=11, noises=("dn",), shard=(3, 5)),
 ])
+
+
+# ---- other cell sizes (group `res`): the quantities the kernel counts in cells — the slice's reach and margin, the mixture table's codes, the
+# 7 x 7 look, the stable-beam bound against a cell's width — at the sizes of raycast_cases.RES_TABLE.  One case with the shipped spread and
+# one with _ALL's (sigma 6 cm: 1.5 cells at 0.0394 m, an eighth of a cell at 0.5 m), each in every field source and noise form; what each
+# claims (expect: unstable = (least, most) unstable beams of a particle after the first scan; tiers = the tiers of mix_term its lookups take;
+# centre_settled = whether the 7 x 7 look settles every / some / no centre lookup; margin = the slice margin plan_propose ends on) was counted
+# by tests/test_propose_cases.py from the oracle's numbers.
+RES_SIZES = (0.0394, 0.0625, 0.07, 0.3, 0.5)
+ROOM_RES = (-1.2, 1.1, -1.0, 1.3)           # on the +-2 m map with 0.6 m to spare: _ALL's samples (sigma 6 cm) keep every end point inside
+_EVERY = dict(sources=("inj", "query", "window", "full"), noises=("host", "dn"))
+ROOM_0394_IN, ROOM_0394_OUT = (-0.5, 0.5, -0.4, 0.45), (-1.85, 0.75, -0.4, 0.95)    # walls 34, 6, 0 and 13 cells of 0.0394 m beyond the first room's
+RES_EXPECT = {
+    "res-0p0394": dict(unstable=(3, 11), tiers=("lds",), centre_settled="every", margin=48),
+    "res-0p0394-wide": dict(unstable=(360, 360), tiers=("lds",), centre_settled="every", margin=48),
+    "res-0p0625": dict(unstable=(3, 7), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p0625-wide": dict(unstable=(360, 360), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p07": dict(unstable=(2, 10), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p07-wide": dict(unstable=(360, 360), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p3": dict(unstable=(0, 5), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p3-wide": dict(unstable=(356, 360), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p5": dict(unstable=(1, 2), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p5-wide": dict(unstable=(275, 360), tiers=("lds",), centre_settled="some", margin=48),
+    "res-0p07-k110": dict(unstable=(360, 360), tiers=("lds",), centre_settled="some", margin=48),
+    # the one size at which a +-2 m map holds codes of all three tiers (32 cells are 1.26 m): lut-tiers' method
+    "res-0p0394-tiers": dict(tiers_at=3, unsettled_centre_at=(3,), margin=48),
+}
+
+
+def res_tag(res):
+    return repr(res).replace(".", "p")
+
+
+def _res_cases():
+    out = []
+    for res in RES_SIZES:
+        tag = res_tag(res)
+        out.append(_case(f"res-{tag}", "res", res=res, room=ROOM_RES, expect=RES_EXPECT.get(f"res-{tag}"), **_EVERY))
+        out.append(_case(f"res-{tag}-wide", "res", res=res, room=ROOM_RES, var=_ALL, expect=RES_EXPECT.get(f"res-{tag}-wide"), **_EVERY))
+    # (the 512-thread instantiations at a cell size whose reciprocal is no double)
+    out.append(_case("res-0p07-k110", "res", res=0.07, room=ROOM_RES, k=110, threads=512, var=_ALL, sources=("inj", "query"), noises=("host", "dn"),
+                     expect=RES_EXPECT.get("res-0p07-k110")))
+    out.append(_case("res-0p0394-tiers", "res", res=0.0394, room=ROOM_0394_IN, inc=(0.05, 0.03, 0.02), n_scans=5, walls_at={3: ROOM_0394_OUT},
+                     sources=("query",), expect=RES_EXPECT.get("res-0p0394-tiers")))
+    return out
+
+
+CASES = CASES + tuple(_res_cases())
 CASE = {c.id: c for c in CASES}
-GROUPS = ("sizes", "beams", "split", "lookups", "icp-failed", "clamps", "geometry")
+GROUPS = ("sizes", "beams", "split", "lookups", "icp-failed", "clamps", "geometry", "res")
 
 
 _Slice = namedtuple("_Slice", "cells range_max res")     # what scanmatch_cases.slice_regime reads of a case
@@ -180,7 +228,7 @@ def runs_of(case):
 def occ_half(case, source):
     """Half-width of the LDS slice of the occupancy bitmap; 0: none.  (scanmatch_cases.slice_regime is the restated loop; the handle's
     distance-field mode decides whether it runs: an injected field does not change the mode, `window` and `full` do.)"""
-    return smc.slice_regime(_Slice(case.cells, case.range_max, RES))[1] if source in ("inj", "query") else 0
+    return smc.slice_regime(_Slice(case.cells, case.range_max, case.res))[1] if source in ("inj", "query") else 0
 
 
 def slice_bytes(case, source):
@@ -243,9 +291,9 @@ def sensor_xy(case, pose):
 
 def cells_of(case, xy):
     """grid_mapper.cpp:852-887 for points inside the world: (i, j) and the distance of each point from its cell's nearest border."""
-    d = (xy + case.half) / RES
+    d = (xy + case.half) / case.res
     ij = np.minimum(np.floor(d), case.cells - 1).astype(np.int64)
-    border = np.abs(d - np.round(d)).min(-1) * RES
+    border = np.abs(d - np.round(d)).min(-1) * case.res
     return ij, border
 
 
@@ -267,8 +315,8 @@ def unstable_sets(case, centre, centre_xy, samples, samples_xy, z_theta, sensor_
     sens_s = sensor_xy(case, samples) if sensor_from == "sensor" else samples[:, 1:]
     sdxy = float(np.abs(sens_s - sens_c[None]).max()) if len(samples) else 0.0
     sdth = float(np.abs(math.sqrt(case.var[0]) * z_theta).max()) if (angular and len(samples)) else 0.0
-    lo = centre_xy - (np.floor((centre_xy + case.half) / RES) * RES - case.half)
-    marg = np.minimum(lo, RES - lo).min(-1)
+    lo = centre_xy - (np.floor((centre_xy + case.half) / case.res) * case.res - case.half)
+    marg = np.minimum(lo, case.res - lo).min(-1)
     marg32 = marg.astype(np.float32)
     marg32 = np.where(marg32.astype(np.float64) > marg, np.nextafter(marg32, np.float32(-1.0)), marg32).astype(np.float64)
     beam = centre_xy - sensor_xy(case, centre)[None]
@@ -311,7 +359,7 @@ def look7_settles(case, ij, occ, box):
     d2 = np.where((np.abs(di) <= 3) & (np.abs(dj) <= 3), di * di + dj * dj, 1 << 30).min(1)
     ci, cj = flat[:, 0], flat[:, 1]
     fit = look7_fits(case, flat, box)
-    clear = np.full(ci.shape, 201)
+    clear = np.full(ci.shape, int(math.ceil(10.0 / case.res)) + 1)          # (cell_radius + 1: 201 at 0.05 m)
     if R0 > 0:
         clear = np.minimum(clear, ci - R0 + 1)
     if R1 < case.cells - 1:
@@ -327,7 +375,7 @@ def look7_settles(case, ij, occ, box):
 def common_params(case):
     lo = tuple(a - b for a, b in zip(case.start, case.inc))
     return dict(N=case.N, k=case.k, map_min=-case.half, map_max=case.half, pose0=lo, beam_delta_deg=360.0 / case.beams,
-                range_max=case.range_max, Trs=list(case.trs), sample_range=list(case.var))
+                range_max=case.range_max, Trs=list(case.trs), sample_range=list(case.var), resolution=case.res)
 
 
 def oracle_params(case):
@@ -383,13 +431,13 @@ def _handmade(kind, case, pose, scan):
         if b in near:
             ax = 0 if abs(dirv[0]) >= abs(dirv[1]) else 1
             at = sens[ax] + float(scan[b]) * dirv[ax]                                  # where the room's own range ends along that axis
-            line = math.floor((at + case.half) / RES) * RES - case.half             # the border of that cell on the sensor's side
+            line = math.floor((at + case.half) / case.res) * case.res - case.half   # the border of that cell on the sensor's side
             out[b] = np.float32((line + 5e-5 * np.sign(dirv[ax]) - sens[ax]) / dirv[ax])
         else:
             r = float(scan[b]) + offs
-            lo = (sens[None] + r[:, None] * dirv[None] + case.half) / RES
-            lo = (lo - np.floor(lo)) * RES
-            out[b] = np.float32(r[int(np.argmax(np.minimum(lo, RES - lo).min(-1)))])
+            lo = (sens[None] + r[:, None] * dirv[None] + case.half) / case.res
+            lo = (lo - np.floor(lo)) * case.res
+            out[b] = np.float32(r[int(np.argmax(np.minimum(lo, case.res - lo).min(-1)))])
     return out
 
 

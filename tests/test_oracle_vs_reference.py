@@ -90,8 +90,13 @@ def test_arc_plant_step_bit_exact():
     assert abs(pa[2]) <= np.pi
 
 
+# the cell sizes the map-update and proposal tables run at beside 0.05 m (tests/raycast_cases.py: RES_TABLE): (res, map half, cells a side)
+RES_GEOMETRIES = ((0.0394, 2.0, 102), (0.0625, 2.0, 64), (0.07, 2.0, 58), (0.3, 2.0, 14), (0.5, 2.0, 8), (0.5, 3.0, 12))
+
+
 @pytest.mark.parametrize("grid,delta", [((0.05, -2.0, 2.0, -2.0, 2.0), 1.0), ((0.05, -3.0, 3.0, -3.0, 3.0), 1.0),
-                                        ((0.05, -10.0, 10.0, -10.0, 10.0), 1.0), ((0.1, -5.0, 5.0, -5.0, 5.0), 1.0 / 3.0)])
+                                        ((0.05, -10.0, 10.0, -10.0, 10.0), 1.0), ((0.1, -5.0, 5.0, -5.0, 5.0), 1.0 / 3.0)]
+                         + [((res, -half, half, -half, half), 1.0) for res, half, _ in RES_GEOMETRIES])
 def test_grid_mapper_scan_sequences_bit_exact(grid, delta):
     """integrateScan (raycast, log-odds, states, occupied set in hash order, brushfire distances),
     likelihoodFieldModel, gridMap, laserEndPoints — 8 noisy scans along a trajectory."""
@@ -144,6 +149,33 @@ def test_bresenham_all_octants_and_degenerate_rays():
     assert go.world2rowmajor(0, 2.01) == gr.world2rowmajor(0, 2.01) == -1
     for x, y in [(-2.0, -2.0), (2.0, 2.0), (0.0, 0.0), (1.99999, -0.00001), (0.05, 0.1), (0.15, 0.15000000000000002)]:
         assert go.world2rowmajor(x, y) == gr.world2rowmajor(x, y)
+    go.close(); gr.close()
+    # the other cell sizes: every cell border as the doubles nearest to it (at 0.0625 m the border itself is a double: the point ON it,
+    # and one ulp either side), the ragged last cell from its lower border up to xmax itself (where the clamp `i == xsize` binds on a map
+    # that is a whole number of cells wide and does not on one that is not), one ulp past xmax, and rays into that last cell
+    for res, half, cells in RES_GEOMETRIES:
+        go, gr = _pair(grid=(res, -half, half, -half, half))
+        assert go.xsize == gr.xsize == go.ysize == gr.ysize == cells
+        edges = [-half + i * res for i in range(cells + 1) if -half + i * res <= half]
+        xs = [v for e in edges for v in (np.nextafter(e, -np.inf), e, np.nextafter(e, np.inf)) if -half <= v <= half]
+        xs += list(np.linspace(-half + (cells - 1) * res, half, 9)) + [half, float(np.nextafter(half, np.inf)), float(np.nextafter(-half, -np.inf))]
+        xs += list(rng.uniform(-half, half, 40))
+        idx = set()
+        for n, x in enumerate(xs):
+            for y in (xs[(7 * n + 3) % len(xs)], half, -half, 0.013):
+                a = go.world2rowmajor(x, y)
+                assert a == gr.world2rowmajor(x, y), (res, x, y)
+                assert go.world2rowmajor(y, x) == gr.world2rowmajor(y, x), (res, y, x)
+                idx.add(a)
+        assert -1 in idx and cells * cells - 1 in idx and 0 in idx, res           # outside, the upper corner's cell, the lower corner's
+        if res == 0.0625:       # exact borders: i * res - half is the border, and the point on it belongs to the cell above
+            assert all(go.world2rowmajor(-half + i * res, -half) == i * cells for i in range(cells)), res
+        last = -half + (cells - 0.5) * res if -half + cells * res <= half else 0.5 * (half + (-half + (cells - 1) * res))
+        pose = (0.3, 0.013, -0.021)
+        for pt in [(last, last), (half, half), (half, -half), (-half, half), (last, 0.013), (0.013, half)] + [tuple(p) for p in rng.uniform(-half, half, (60, 2))]:
+            a, b = go.free_index(pt, pose), gr.free_index(pt, pose)
+            assert a is not None and np.array_equal(a, b), (res, pt)
+        go.close(); gr.close()
 
 
 def test_out_of_world_scan_reports_the_same_error():

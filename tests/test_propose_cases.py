@@ -21,7 +21,7 @@ STATUS_OUT_OF_WORLD, STATUS_ETA_ZERO = 4, 5
 
 def _analyse(c, kind, pf, sc, before, after, occ, tr):
     """One scan of one oracle run, per particle: the restated kernel rules over the oracle's numbers."""
-    lookups = c.group == "lookups"
+    lookups = c.group in ("lookups", "res")
     half = pc.occ_half(c, "query")
     Bv = pc.n_valid(c, sc.scan)
     row = dict(s=sc.s, rc=tr["rc"], Bv=Bv, icp_ok=sc.icp_ok, nocc=[len(o) for o in occ], border=np.inf, parts=[], eta=tr["eta"].copy(),
@@ -300,7 +300,7 @@ def test_the_lookup_cases_reach_the_paths_they_name(runs):
     for (cid, kind), rows in runs.items():
         c = pc.CASE[cid]
         e = c.expect
-        if c.group != "lookups" or kind != "exact":
+        if c.group not in ("lookups", "res") or kind != "exact":
             continue
         for r in rows[1:]:
             for p, part in enumerate(r["parts"]):
@@ -361,6 +361,65 @@ def test_the_clamp_and_geometry_cases_reach_what_they_name(runs):
     c = pc.CASE["eta-zero"]
     assert c.k * c.clamps[1] * c.clamps[3] <= 0.5e-12 and c.expect["status_at"] == {0: STATUS_ETA_ZERO}
     assert pc.CASE["sample-out-of-world"].expect["status_at"] == {2: STATUS_OUT_OF_WORLD}
+
+
+# ---- other cell sizes ---------------------------------------------------------------------------------------------------------------------
+def test_the_cases_at_0p05_are_byte_for_byte_what_they_were():
+    """The table took a cell size (Case.res, default 0.05): the fields, runs, slices and every scan's inputs of these cases hash to what
+    tests/golden/make_case_digests.py recorded before it did."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("make_case_digests", os.path.join(ROOT, "tests", "golden", "make_case_digests.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "case_digests.json")))["propose"]
+    assert set(want) == set(mk.PROPOSE_IDS) and len(want) >= 8
+    for cid in mk.PROPOSE_IDS:
+        assert pc.CASE[cid].res == pc.RES == 0.05 and mk.propose_digest(cid) == want[cid], cid
+    assert all((c.res == pc.RES) == (c.group != "res") for c in pc.CASES)
+
+
+def test_the_cell_size_cases_reach_what_they_name(runs):
+    """Per case of group `res`, from the oracle's numbers (host noise): the least and most unstable beams of a particle by the kernel's
+    rule, the tiers of mix_term its lookups take, whether the 7 x 7 look settles the centre lookups, and the slice margin."""
+    sigma = np.sqrt(pc._ALL[1])
+    assert sigma / 0.0394 > 1.5 and sigma / 0.5 < 0.13          # the wide spread: a cell and a half, an eighth of a cell
+    for res in pc.RES_SIZES:
+        tag = pc.res_tag(res)
+        for cid, var in ((f"res-{tag}", pc.DEFAULT_VAR), (f"res-{tag}-wide", pc._ALL)):
+            c = pc.CASE[cid]
+            assert (c.res, c.N, c.k, c.beams, c.var, c.half, c.cells) == (res, 4, 10, 360, var, 2.0, int(np.ceil(4.0 / res))) and c.cells % 2 == 0, cid
+            assert len(pc.runs_of(c)) == 8 and c.threads == 256, cid
+    for c in pc.CASES:
+        if c.group != "res":
+            continue
+        e = c.expect
+        margin, half = smc.slice_regime(pc._Slice(c.cells, c.range_max, c.res))
+        assert margin == e["margin"] == 48 and half >= c.cells and pc.occ_half(c, "query") == half, c.id      # every map here is inside its slice
+        if "unstable" not in e:
+            continue
+        for kind in ("plain", "exact"):
+            rows = runs[c.id, kind]
+            un = [int(part["u_rule"].sum()) for r in rows[1:] for part in r["parts"]]
+            assert len(un) == 2 * c.N and (min(un), max(un)) == e["unstable"], (c.id, kind, min(un), max(un))
+        rows = runs[c.id, "exact"]
+        parts = [part for r in rows[1:] for part in r["parts"]]
+        assert all(part["staging"] == "whole_table" for part in parts), c.id
+        cd = np.concatenate([part["codes"] for part in parts])
+        tiers = tuple(t for t, hit in (("lds", (cd < pc.K_MIX_LDS).any()), ("lut", ((cd >= pc.K_MIX_LDS) & (cd < pc.K_MIX_LUT)).any()),
+                                       ("beyond", (cd >= pc.K_MIX_LUT).any())) if hit)
+        assert tiers == e["tiers"], (c.id, tiers, int(cd.max()))
+        frac = [part["centre_settled"].mean() for part in parts]
+        kind = "every" if min(frac) == 1.0 else "none" if max(frac) == 0.0 else "some"
+        assert kind == e["centre_settled"] and (kind != "some" or (0.05 < min(frac) and max(frac) < 0.95)), (c.id, min(frac), max(frac))
+    # either side of the kUnCap = 16 unstable beams of the per-pair path: the shipped spread stays in one chunk at every size, the wide
+    # one takes more than two
+    for res in pc.RES_SIZES:
+        tag = pc.res_tag(res)
+        assert pc.CASE[f"res-{tag}"].expect["unstable"][1] <= pc.K_UNCAP and pc.CASE[f"res-{tag}-wide"].expect["unstable"][0] > 2 * pc.K_UNCAP, res
+    # what a size cannot reach: a code is at most 2 (cells - 1)^2 — below kMixLds on the 8-cell map, below kMixLut on the 14-cell one
+    assert 2 * 7 * 7 < pc.K_MIX_LDS and 2 * 13 * 13 < pc.K_MIX_LUT < 2 * 57 * 57
+    assert pc.CASE["res-0p0394-tiers"].expect["tiers_at"] == 3 and pc.CASE["res-0p0394-tiers"].res == 0.0394
 
 
 # ---- margins --------------------------------------------------------------------------------------------------------------------------

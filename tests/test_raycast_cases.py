@@ -3,8 +3,11 @@ world2rowmajor, integrate_scan) and a restatement of "the events of each cell, i
 the order-sensitive cases are order-sensitive, the restated selector names exactly the instantiations csrc/rbpf_raycast.hip
 ships, every instantiation has a case of every group that applies to it, and no case leaves its map.  No device."""
 import importlib.util
+import json
+import math
 import os
 import re
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -66,8 +69,9 @@ def test_the_table_is_within_the_sizes_it_may_use():
     want |= {f"events_{k}" for k in (3, 4, 5, 7, 8, 9)} | {f"hot_{k}" for k in (15, 16, 79, 80)} | {f"band_rows_{r}" for r in (1, 3, 4, 5)}
     assert want <= set(IDS), sorted(want - set(IDS))
     for c in CASES:
-        assert 18 <= c.N <= 32 and len(c.steps) <= 8 and rcs.cells_of(c) in (80, 200), c.id
-        assert c.group in ("bv", "slots", "hot", "bands", "cow", "toggle") and set(c.forms) <= set(rcs.FORMS), c.id
+        assert 18 <= c.N <= 32 and len(c.steps) <= 8 and rcs.cells_of(c) in ((80, 200) if c.group != "res" else (102, 64, 58, 20, 14, 12, 8)), c.id
+        assert (c.res == rcs.RES) == (c.group != "res") and rcs.cells_of(c) % 2 == 0, c.id
+        assert c.group in ("bv", "slots", "hot", "bands", "cow", "toggle", "res") and set(c.forms) <= set(rcs.FORMS), c.id
         assert c.steps[-1].mark and all((s.scan is None) != (s.gather is None) for s in c.steps), c.id
     assert rcs.cells_of(rcs.case("bands_natural_4p2m")) == 200
     # no odd-sided map: create refuses one (its vectorised copies want G % 4 == 0), so the pair past a map's last column does not exist
@@ -108,6 +112,183 @@ def test_the_restated_events_give_the_oracle_s_bits(refs):
                 assert np.array_equal(want, e["after"]), (c.id, s, p)
                 checked += len(e["events"])
     assert checked > 100000
+
+
+def test_the_cases_at_0p05_are_byte_for_byte_what_they_were():
+    """The table took a cell size (Case.res, default 0.05): scans, poses, the oracle's boxes, end points and maps at every marked step and
+    the restated plans of these cases hash to what tests/golden/make_case_digests.py recorded before it did."""
+    spec = importlib.util.spec_from_file_location("make_case_digests", os.path.join(ROOT, "tests", "golden", "make_case_digests.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "case_digests.json")))["raycast"]
+    assert set(want) == set(mk.RAYCAST_IDS) and len(want) >= 10
+    for cid in mk.RAYCAST_IDS:
+        assert rcs.case(cid).res == rcs.RES == 0.05 and mk.raycast_digest(cid) == want[cid], cid
+
+
+# ---- other cell sizes ------------------------------------------------------------------------------------------------------------------------
+RES_CASES = [c for c in CASES if c.group == "res"]
+
+
+def _counts(e, ends, robot, cells):
+    """Of one particle's step: (end-point cells past kBoxEv events, hot cells, very hot cells, hot cells outside the 7 x 7 window, slots
+    replayed exhaustively with eight-event slots) — `hot` as the kernel's hot path means it: a cell without an end point, not the robot's."""
+    ev, eset = e["events"], set(ends.tolist())
+    rx, ry = divmod(int(robot), cells)
+    free = [q for q in ev if q not in eset and q != robot]
+    hot = [q for q in free if len(ev[q]) >= rcs.kHotMin]
+    return (sum(len(ev[q]) > rcs.kBoxEv for q in eset), len(hot), sum(len(ev[q]) >= rcs.kVeryHot for q in free),
+            sum(max(abs(q // cells - rx), abs(q % cells - ry)) > rcs.kHotSide // 2 for q in hot), len(_overflowed(ev, ends, robot, rcs.kBoxEv)))
+
+
+def test_the_cell_sizes_are_the_admitted_range_s_edges_and_kinds():
+    by_cells = {0.0394: 102, 0.0625: 64, 0.07: 58, 0.3: 14, 0.5: 8}
+    assert set(rcs.RES_TABLE) == set(by_cells)
+    src = open(os.path.join(CSRC, "rbpf.hip")).read()
+    assert "std::ceil((10.0 - 0.0) / P->resolution)" in src and "if (radius > 254) return TBNAV_ERR_UNSUPPORTED;" in src     # create's brushfire radius and its limit
+    for res, cells in by_cells.items():
+        radius = int(math.ceil(10.0 / res))
+        assert 4 <= radius <= 254 and int(math.ceil(4.0 / res)) == cells and cells % 2 == 0, res
+        inv = 1 / Fraction(res)                                                      # the exact reciprocal of the double `res`
+        exact = inv.denominator & (inv.denominator - 1) == 0 and inv.numerator.bit_length() - (inv.numerator & -inv.numerator).bit_length() < 53
+        assert exact == (res in (0.0625, 0.5)) and (Fraction(4) / Fraction(res)).denominator != 1 or res in (0.0625, 0.5), res
+        assert (cells * Fraction(res) > 4) == (res in rcs.RAGGED), res                # the last cell sticks out past xmax
+        tag = rcs.res_tag(res)
+        want = {f"res_{tag}_room", f"res_{tag}_trs"} | ({f"res_{tag}_corner", f"res_{tag}_edge"} if res in rcs.RAGGED else set())
+        assert want <= set(IDS), sorted(want - set(IDS))
+        for cid in want:
+            c = rcs.case(cid)
+            assert (c.res, rcs.cells_of(c), c.N, len(c.steps), c.forms) == (res, cells, 18, 2, rcs.ALL_FORMS), cid
+            assert c.trs == (rcs.TRS_OFFSET if cid.endswith("_trs") else (0.0, 0.0, 0.0)), cid
+    assert int(math.ceil(10.0 / 0.0394)) == 254 and int(math.ceil(10.0 / 0.0393)) == 255         # the finest admitted, to four digits
+    assert int(math.ceil(10.0 / 0.5)) == 20 and (rcs.cells_of(rcs.case("res_0p5_room_12")), rcs.cells_of(rcs.case("res_0p3_wide_20"))) == (12, 20)
+    # the room scans are align's / sensor_offset's: the same scan, poses a whole number of cells apart and turned, two steps
+    assert all(np.array_equal(rcs.case(f"res_{rcs.res_tag(r)}_room").steps[0].scan, rcs.case("sensor_offset").steps[0].scan) for r in by_cells)
+
+
+def test_the_finest_size_hands_over_by_cell_size_alone(plans):
+    """0.0394 m: range_max 3.5 is a box side of 183 > sqrt(30000): tile cap 0, every form launches rbpf_raycast; 3.3 is side 173, the
+    largest cap the rule admits, and the forms launch the box kernels `select` names (plan side 170 against kBoxSideMax 176)."""
+    f32 = lambda x: float(np.float32(x))      # noqa: E731
+    assert 2 * (int(math.ceil(f32(3.5) / 0.0394)) + 2) + 1 == 183 and 2 * (int(math.ceil(f32(3.3) / 0.0394)) + 2) + 1 == 173
+    assert 173 * 173 <= 30000 < 175 * 175 and int(math.floor(2.0 * f32(3.3) / 0.0394)) + 3 == 170 <= rcs.kBoxSideMax
+    for cid in ("res_0p0394_room", "res_0p0394_trs", "res_0p0394_corner", "res_0p0394_edge"):
+        c = rcs.case(cid)
+        assert c.range_max == 3.5 and rcs.tile_cap_of(c.range_max, c.trs, 0, c.res) == 0 and rcs.tile_cap_of(c.range_max, c.trs, 0) > 0, cid
+        assert all(x == ("rbpf_raycast", None, 0) for pl in plans[cid].values() for x in pl), cid
+    c = rcs.case("res_0p0394_room_3p3")
+    assert c.range_max == 3.3 and rcs.tile_cap_of(c.range_max, c.trs, 0, c.res) == c.claims["tile_cap"] == 29929
+    assert np.array_equal(c.steps[0].scan, rcs.case("res_0p0394_room").steps[0].scan) and np.array_equal(c.steps[0].poses, rcs.case("res_0p0394_room").steps[0].poses)
+    for form, pl in plans[c.id].items():
+        assert [x[0] for x in pl] == [rcs.FORM_KERNEL[form]] * 2 and all((x[1] is not None) == (form != "ordered") for x in pl), (form, pl)
+
+
+def test_the_ragged_cases_sit_on_the_map_s_borders_and_in_its_partial_cell(refs):
+    for res in rcs.RAGGED:
+        tag, cells = rcs.res_tag(res), int(math.ceil(4.0 / res))
+        lower_border = -2.0 + (cells - 1) * res                                     # of the last, partial cell
+        assert lower_border < 2.0 < lower_border + res
+        c = rcs.case(f"res_{tag}_corner")
+        po = c.steps[0].poses
+        assert {(x, y) for _, x, y in po[:4]} == {(-2.0, -2.0), (-2.0, 2.0), (2.0, -2.0), (2.0, 2.0)}          # ON the corners: xmin / xmax themselves
+        assert sum(lower_border < v < 2.0 for _, x, y in po for v in (x, y)) >= 4                              # inside the partial cell
+        for r in refs[c.id]["steps"]:
+            robots = {divmod(int(q), cells) for q in r["robots"]}
+            assert {(0, 0), (0, cells - 1), (cells - 1, 0), (cells - 1, cells - 1)} <= robots and len(robots) >= 12, (c.id, sorted(robots))
+            assert all(b[2] * b[3] >= max(4, int(0.3 / res) ** 2) for b in r["boxes"]), c.id                   # a real fan, inside
+        c = rcs.case(f"res_{tag}_edge")
+        po = c.steps[0].poses
+        assert sum(y == 2.0 for _, _, y in po) == c.N // 2 and sum(lower_border < y < 2.0 for _, _, y in po) == c.N // 2
+        for r in refs[c.id]["steps"]:
+            for p, (minx, miny, bh, bw) in enumerate(r["boxes"]):
+                assert int(r["robots"][p]) % cells == c.claims["last_column"] == cells - 1 == miny + bw - 1, (c.id, p)     # the box's last pair is the map's
+                assert len(set((r["ends"][p] // cells).tolist())) >= 3 and (r["ends"][p] % cells).min() < cells - 1, (c.id, p)
+
+
+def test_the_sensor_offset_moves_the_sensor_to_another_cell_at_every_size_that_can_show_it():
+    for res in rcs.RES_TABLE:
+        c = rcs.case(f"res_{rcs.res_tag(res)}_trs")
+        g = rcs.oracle_grid(c)
+        far = 0
+        for th, x, y in c.steps[0].poses:
+            sx = x + np.cos(th) * c.trs[1] - np.sin(th) * c.trs[2]
+            sy = y + np.sin(th) * c.trs[1] + np.cos(th) * c.trs[2]
+            far += g.world2rowmajor(sx, sy) != g.world2rowmajor(x, y)
+        g.close()
+        # |Trs| = 5.4 cm: more than half a cell up to 0.07 m; a small fraction of a cell at 0.3 and 0.5 m (the offset then shows in the end points alone)
+        assert far >= (c.N // 2 if res <= 0.07 else 0), (res, far)
+
+
+def test_the_exact_border_case_puts_end_points_and_sensors_on_borders(refs):
+    c = rcs.case("res_0p0625_borders")
+    cells, res = 64, 0.0625
+    assert c.res == res and c.trs == (0.0, 0.0, 0.0) and float(np.float32(8 * res)) == 0.5 == float(c.steps[0].scan[c.claims["border_beam"]])
+    g = rcs.oracle_grid(c)
+    for s, st in enumerate(c.steps):
+        assert (st.poses[:, 0] == 0.0).all() and ((st.poses[:, 1:] + 2.0) / res == np.round((st.poses[:, 1:] + 2.0) / res)).all(), s    # theta 0, on lattice points
+        if s == 1:
+            assert st.scan[0] == 0.0                                                # beam 0 invalid: the corner particle's +x beam would leave the world
+    st = c.steps[0]
+    for p in range(c.N):
+        pts = g.end_points(st.scan, st.poses[p])
+        x0, y0 = st.poses[p, 1], st.poses[p, 2]
+        assert pts[0][0] == x0 + 0.5 and pts[0][1] == y0, (p, pts[0])                  # the oracle's end point of beam 0: exactly the lattice point 8 cells on
+        i, j = int((x0 + 2.0) / res) + 8, int((y0 + 2.0) / res)
+        assert g.world2rowmajor(*pts[0]) == min(i, cells - 1) * cells + min(j, cells - 1) == refs[c.id]["steps"][0]["ends"][p][0], p    # ... in the cell ABOVE the border, the clamp aside
+        for b in (1, 2):                                                            # the other two valid beams end inside cells
+            q = (pts[b] + 2.0) / res
+            assert (np.abs(q - np.round(q)) > 1e-3).all(), (p, b)
+    p = c.claims["end_on_corner"]
+    assert tuple(g.end_points(st.scan, st.poses[p])[0]) == (2.0, 2.0) and refs[c.id]["steps"][0]["ends"][p][0] == cells * cells - 1     # the clamp, both indices
+    p = c.claims["robot_on_corner"]
+    assert tuple(c.steps[1].poses[p, 1:]) == (2.0, 2.0) and refs[c.id]["steps"][1]["robots"][p] == cells * cells - 1
+    assert {tuple(q) for q in c.steps[1].poses[:3, 1:]} == {(2.0, 2.0), (2.0, 2.0 - res), (2.0 - res, 2.0)}
+    # a corner of four cells, inside: the robot's cell is the one above and to the right
+    assert tuple(c.steps[0].poses[5, 1:]) == (0.0, 0.0) and refs[c.id]["steps"][0]["robots"][5] == 32 * cells + 32
+    g.close()
+
+
+def test_the_lattice_cases_stand_where_the_reciprocal_and_the_division_disagree(refs):
+    """cell_floor multiplies by fl(1 / res) and falls back to the division within 1e-9 of a border.  These robots stand where
+    floor(d * fl(1 / res)) is NOT the reference's floor(d / res): the oracle's cell is the division's, for every particle in x, y or
+    both — a kernel without the fallback starts its rays one cell off."""
+    assert rcs.reciprocal_traps(0.0625) == [] == rcs.reciprocal_traps(0.5) and len(rcs.reciprocal_traps(0.05)) > 0       # (0.05 m has them too)
+    for res in (0.0394, 0.07):
+        c = rcs.case(f"res_{rcs.res_tag(res)}_lattice")
+        cells, inv = rcs.cells_of(c), 1.0 / res
+        assert c.claims["traps"] >= 2 and c.res == res and c.trs == (0.0, 0.0, 0.0)
+        axes = set()
+        for p, (_, x, y) in enumerate(c.steps[0].poses):
+            di, dj = x + 2.0, y + 2.0
+            by_div, by_mul = (math.floor(di / res), math.floor(dj / res)), (math.floor(di * inv), math.floor(dj * inv))
+            assert by_div != by_mul and max(abs(by_div[0] - by_mul[0]), abs(by_div[1] - by_mul[1])) == 1, (c.id, p)
+            assert refs[c.id]["steps"][0]["robots"][p] == by_div[0] * cells + by_div[1] != by_mul[0] * cells + by_mul[1], (c.id, p)
+            for q, m in ((di, by_mul[0]), (dj, by_mul[1])):
+                fr = q * inv - m
+                assert fr == 0.0 or abs(fr - 0.5) <= 0.5 - 1e-6, (c.id, p, fr)     # on the border to the last bit, or well inside: nothing near the 1e-9 threshold itself
+            axes.add((by_div[0] != by_mul[0], by_div[1] != by_mul[1]))
+        assert axes == {(True, False), (False, True), (True, True)}, (c.id, axes)
+
+
+def test_the_coarse_cases_reach_the_counts_they_name(refs):
+    """What a 360-beam room scan reaches by itself at 0.3 and 0.5 m (raycast_cases.COARSE_COUNTS): per particle and step, counted with
+    the table's own events."""
+    assert set(rcs.COARSE_COUNTS) == {c.id for c in RES_CASES if c.res >= 0.3 and ("room" in c.id or c.id.endswith("_trs") or "wide" in c.id)}
+    for cid in rcs.COARSE_COUNTS:
+        c = rcs.case(cid)
+        cells = refs[cid]["cells"]
+        got = []
+        for r in refs[cid]["steps"]:
+            assert sorted(r["ev"]) == list(range(c.N)), cid                         # every particle
+            got += [_counts(r["ev"][p], r["ends"][p], r["robots"][p], cells) for p in range(c.N)]
+            assert not any(r["robots"][p] in set(r["ends"][p].tolist()) for p in range(c.N)), cid
+        for n, key in enumerate(("count_past_ev", "count_hot", "count_very_hot", "count_hot_outside", "count_overflowed")):
+            col = [g[n] for g in got]
+            assert (min(col), max(col)) == tuple(c.claims[key]), (cid, key, min(col), max(col))
+        assert max(g[4] for g in got) < rcs.kWave                                   # the overflow list never fills on these maps
+    wide, small = rcs.case("res_0p3_wide_20").claims, rcs.case("res_0p3_room").claims
+    assert wide["count_hot_outside"][0] > 0 and small["count_hot_outside"] == (0, 0) and small["count_very_hot"][1] > 0
+    assert small["count_past_ev"][0] >= 14 and rcs.case("res_0p5_room").claims["count_hot"] == (0, 0)
 
 
 # ---- every case does what it names ---------------------------------------------------------------------------------------------------------
@@ -431,6 +612,9 @@ def test_every_form_runs_the_kernel_it_is_for_and_no_unreachable_combination_is_
     why_not = {"all_zero_length", "zero_length_but_one",            # no long beam: the array is smaller than need + 256
                "bands_natural_4p2m", "bv_lds_last", "bv_lds_first_ordered",   # too large for four (three) workgroups per CU
                "band_rows_1", "band_rows_3", "band_rows_4", "band_rows_5", "robot_in_last_band", "cow_across_bands"}   # BAND_ROWS caps the array below need + 256
+    why_not |= {c.id for c in RES_CASES if rcs.tile_cap_of(c.range_max, c.trs, 0, c.res) == 0}      # 0.0394 m with range_max 3.5: no box kernel at all
+    why_not |= {c.id for c in RES_CASES if c.res >= 0.3}                                              # a few cells of reach: the array is smaller than need + 256
+    why_not |= {"res_0p07_lattice"}                                                                   # its small room, near the map's edge: the same
     for c in CASES:
         for form, pl in plans[c.id].items():
             last = pl[-1][0]

@@ -93,3 +93,24 @@ def test_integrate_scan_many_rejects_what_it_cannot_do(gpu_pkg):
     assert pf.integrateScanMany(st.scan, st.poses, check=False) == capi.ERR_UNSUPPORTED                          # stored fields: one particle at a time
     assert not pf.logOdds(0).any()
     pf.close()
+
+
+def test_create_admits_the_cell_sizes_the_header_states(gpu_pkg):
+    """include/tbnav_rbpf.h on `resolution`: radius ceil(10 / res) <= 254 (0.0394 m is admitted, 0.0393 m is not), an even square side,
+    res > 0 — and *out stays NULL where create refuses."""
+    import ctypes as C
+    from rtn_amd import capi
+    from rtn_amd.rbpf import default_params
+    L = capi.lib()
+    for kw, want in ((dict(resolution=0.0394), 0), (dict(resolution=0.5), 0), (dict(resolution=0.0393), capi.ERR_UNSUPPORTED),
+                     (dict(resolution=0.01), capi.ERR_UNSUPPORTED), (dict(resolution=0.0), capi.ERR_INVALID_ARG), (dict(resolution=-0.05), capi.ERR_INVALID_ARG),
+                     (dict(resolution=0.3, map_max=2.2), capi.ERR_UNSUPPORTED),          # fl(4.2 / 0.3) is just above 14: 15 cells, odd
+                     (dict(resolution=0.5, map_max=0.4), capi.ERR_UNSUPPORTED)):         # 4.8 -> 5 cells, odd
+        p, h = default_params(N=2, k=4, **kw), C.c_void_p()
+        side = int(np.ceil((p.xmax - p.xmin) / p.resolution)) if p.resolution > 0 else None
+        if want == capi.ERR_UNSUPPORTED and kw["resolution"] >= 0.0394:
+            assert side % 2 == 1, (kw, side)                                             # refused for its odd side, nothing else
+        rc = L.tbnav_rbpf_create(C.byref(p), C.byref(h))
+        assert rc == want and bool(h.value) == (want == 0), (kw, rc, h.value)
+        if h.value:
+            L.tbnav_rbpf_destroy(h)

@@ -124,6 +124,40 @@ def test_un_injected_run_with_empty_scans(gpu_pkg, mode):
     pf_d.close()
 
 
+@pytest.mark.parametrize("mode", ["reference", "query"])
+@pytest.mark.parametrize("res", [0.0394, 0.0625, 0.07, 0.3, 0.5])
+def test_un_injected_run_at_other_cell_sizes(gpu_pkg, res, mode):
+    """Whole scans at the cell sizes of raycast_cases.RES_TABLE (102, 64, 58, 14 and 8 cells for +-2.0 m; brushfire radius 254, 160, 143,
+    34 and 20): 24 particles, k = 20, six scans, a forced resampling after the third, nothing injected, both distance-field modes against
+    their oracle.  Every stage at _assert_every_stage's bounds; every particle's log-odds with `==`, in reference mode the distance field
+    too; every particle's exported map and the best particle's (newMap) are the oracle's gridMap."""
+    import math
+    N = 24
+    radius = int(math.ceil(10.0 / res))
+    assert 20 <= radius <= 254 and (radius == 254) == (res == 0.0394) and (radius == 20) == (res == 0.5)
+    pf_o, pf_d, rows = _free_run(gpu_pkg, mode, N=N, k=20, map_half=2.0, walls=rc.ROOM_SMALL, n_scans=6, inc=(0.04, 0.03, 0.02), seed=5,
+                                 force_resample_at=3, oracle_exact_field=(mode == "query"), resolution=res)
+    cells = int(math.ceil(4.0 / res))
+    assert (pf_d.xsize, pf_d.ysize) == (cells, cells) == (pf_o.grid(0).xsize, pf_o.grid(0).ysize)
+    assert rows[3]["resampled"] == (1, 1)
+    print(f"\n[res {res} {mode}] " + ", ".join(f"{key}={max(r[key] for r in rows):.3g}" for key in ("sampled", "p_scan", "p_pose", "eta", "mu", "new_pose", "w_raw", "w")))
+    _assert_every_stage(rows)
+    if mode == "reference":
+        st = pf_d.referenceFieldStats()
+        assert st["passes"] > 0, (res, st)                                     # the brushfire ran, at this radius
+    for p in range(N):
+        g = pf_o.grid(p)
+        d = g.dump()
+        assert np.array_equal(pf_d.logOdds(p), d["log_odds"]), p
+        if mode == "reference":
+            assert np.array_equal(pf_d.occDist(p), d["occ_dist"]), p
+        assert np.array_equal(pf_d.particleMap(p), g.grid_map()), p
+    (_, best) = pf_d.getRobotState()
+    assert best == pf_o.best() and np.array_equal(pf_d.newMap(), pf_o.grid(best).grid_map())
+    pf_d.close()
+    pf_o.close()
+
+
 def test_reference_mode_shares_one_brushfire_among_particles_in_the_same_state(gpu_pkg):
     """The reference's field is a function of (occupied set with its history, stale field, the scan's insert / erase sequence), and
     the product runs ONE brushfire per distinct such triple instead of one per particle (csrc/ref_field.hpp).  With the shipped

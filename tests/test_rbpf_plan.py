@@ -40,8 +40,8 @@ def ask(tmp_path_factory):
 
 
 # ---- the map update ----------------------------------------------------------------------------------------------------------------------
-def _raycast_line(range_max, trs, opts, bv, rmax, need):
-    return (f"R {_f32(range_max)!r} {int(bool(opts.get('ORDERED', 0)))} {RES!r} {float(trs[1])!r} {float(trs[2])!r} {float(rmax)!r} {bv} {need} "
+def _raycast_line(range_max, trs, opts, bv, rmax, need, res=RES):
+    return (f"R {_f32(range_max)!r} {int(bool(opts.get('ORDERED', 0)))} {res!r} {float(trs[1])!r} {float(trs[2])!r} {float(rmax)!r} {bv} {need} "
             f"{opts.get('THREADS', 0)} {opts.get('ADAPT', 1)} {opts.get('CELL16', 1)} {opts.get('BAND_ROWS', 0)} 0")
 
 
@@ -72,6 +72,31 @@ def test_plan_raycast_is_the_restated_selector_over_the_sweep(ask):
     assert not set(seen) & set(rcs.UNREACHABLE)
 
 
+def test_plan_raycast_is_the_restated_selector_at_other_cell_sizes(ask):
+    """tile_cap_for and plan_raycast form the box side from reach / resolution: the sweep again at the cell sizes of raycast_cases.RES_TABLE,
+    with the pair of range_max either side of the hand-over at the finest admitted size (3.3 m: side 173, the largest cap; 3.5 m: none)."""
+    tuples = []
+    for res, range_max, trs, bv, f, need, nt, adapt, c16, rows in itertools.product(
+            tuple(rcs.RES_TABLE), (3.3, 3.5, 12), ((0, 0, 0), (0, 0.1, 0.05)), (0, 1, 64, 360, 1080, 4096), (0.03, 0.3, 0.999),
+            (0, 1, 40, 2000, 8272, 30000), (0, 512, 1024), (0, 1, 3), (0, 1, 2), (0, 3)):
+        tuples.append((range_max, trs, dict(THREADS=nt, ADAPT=adapt, CELL16=c16, BAND_ROWS=rows), bv, f * range_max, need, res))
+    got = ask([_raycast_line(*t) for t in tuples])
+    caps, seen = {}, {}
+    for t, g in zip(tuples, got):
+        tile_cap, name, cap, need = _raycast_answer(g)
+        assert (name, cap) == rcs.select(*t), (t, g)
+        assert tile_cap == rcs.tile_cap_of(t[0], t[1], 0, t[6]), (t, g)
+        assert need == (t[5] if t[2]["ADAPT"] else 0), (t, g)
+        if t[1] == (0, 0, 0):
+            caps[(t[6], t[0])] = tile_cap
+        seen.setdefault(t[6], set()).add(name)
+    assert (caps[(0.0394, 3.3)], caps[(0.0394, 3.5)], caps[(0.0394, 12)]) == (173 * 173, 0, 0) and caps[(0.07, 3.5)] == 105 * 105
+    assert caps[(0.5, 12)] == 53 * 53 and caps[(0.3, 12)] == 85 * 85 and caps[(0.0625, 3.5)] == 117 * 117
+    for res in rcs.RES_TABLE:          # every size reaches all six box forms; the fine ones the beam-ordered kernel too (tile cap 0, or the LDS limit)
+        assert seen[res] >= set(BOX_NAMES), (res, seen[res])
+    assert seen[0.0394] == seen[0.0625] == seen[0.07] == set(BOX_NAMES) | {"rbpf_raycast"}
+
+
 def test_plan_raycast_is_the_restated_selector_on_the_case_tables(ask):
     """Every (case, form, step) of tests/raycast_cases.py, with the need its Need class predicts for the launch."""
     keys, lines, want = [], [], []
@@ -83,7 +108,7 @@ def test_plan_raycast_is_the_restated_selector_on_the_case_tables(ask):
                     continue
                 bv, rmax = rcs.scan_stats(c.steps[s].scan, c.range_max)
                 keys.append((c.id, form, s))
-                lines.append(_raycast_line(c.range_max, c.trs, opts, bv, rmax, x[2]))
+                lines.append(_raycast_line(c.range_max, c.trs, opts, bv, rmax, x[2], c.res))
                 want.append(x)
     assert len(lines) > 300
     names = set()
@@ -93,7 +118,7 @@ def test_plan_raycast_is_the_restated_selector_on_the_case_tables(ask):
         if cap is not None:
             assert gneed == need, (key, g)
         c = rcs.case(key[0])
-        assert tile_cap == rcs.tile_cap_of(c.range_max, c.trs, rcs.form_opts(c, key[1]).get("ORDERED", 0)), (key, g)
+        assert tile_cap == rcs.tile_cap_of(c.range_max, c.trs, rcs.form_opts(c, key[1]).get("ORDERED", 0), c.res), (key, g)
         names.add(gname)
     assert names == set(BOX_NAMES) | {"rbpf_raycast"}, names
 
@@ -108,8 +133,8 @@ def _spread_of(ask, var):
     return float(s)
 
 
-def _propose_line(k, bv, df_mode, cells, range_max, spread):
-    return f"P {k} {bv} {df_mode} {cells} {(cells + 63) // 64} {_f32(range_max)!r} {spread!r} {RES!r}"
+def _propose_line(k, bv, df_mode, cells, range_max, spread, res=RES):
+    return f"P {k} {bv} {df_mode} {cells} {(cells + 63) // 64} {_f32(range_max)!r} {spread!r} {res!r}"
 
 
 def _check_propose(key, text, k, bv, half, slice_b):
@@ -136,7 +161,7 @@ def test_plan_propose_is_the_restatement_on_every_case_and_source(ask):
             bv = pc.n_valid(c, sc.scan)
             for src in c.sources:
                 keys.append((c, src, sc.s, bv))
-                lines.append(_propose_line(c.k, bv, DF_MODE[src], c.cells, c.range_max, spread))
+                lines.append(_propose_line(c.k, bv, DF_MODE[src], c.cells, c.range_max, spread, c.res))
     seen = set()
     for (c, src, s, bv), g in zip(keys, ask(lines)):
         nt, fits = _check_propose((c.id, src, s), g, c.k, bv, pc.occ_half(c, src), pc.slice_bytes(c, src))
@@ -169,7 +194,10 @@ def test_plan_propose_over_sizes_and_slice_regimes(ask):
 def test_lookup_half_cells_is_the_restated_window_rule(ask):
     spread = _spread_of(ask, smc.SAMPLE_RANGE)
     keys, lines = [], []
-    for c in smc.CASES:
+    # (every case of the table, and its first query-, window- and full-mode cases again at the cell sizes of raycast_cases.RES_TABLE on a +-2 m map)
+    firsts = [next(c for c in smc.CASES if c.mode == m) for m in ("query", "window", "full")]
+    resized = [c._replace(id=f"{c.id}@{res}", half=2.0, res=res, cells=int(math.ceil(4.0 / res))) for c in firsts for res in rcs.RES_TABLE]
+    for c in list(smc.CASES) + resized:
         for guess, u, matching in itertools.product(((0.0, 0.0, 0.0), (0.02, 0.03, -0.02), (0.0, -0.4, 0.0)), ((0.0, 0.0, 0.0), (0.1, 0.5, 0.0), (0.0, -0.05, 0.0)),
                                                     (False, True)):
             keys.append((c, guess, u, matching))
@@ -178,6 +206,11 @@ def test_lookup_half_cells_is_the_restated_window_rule(ask):
                          f"{c.res!r} {int(c.mode == 'full')} {c.cells}")
     for (c, guess, u, matching), g in zip(keys, ask(lines)):
         assert int(g) == smc.half_cells(c, guess, u, matching), (c.id, guess, u, matching, g)
+    got = {c.id.split("@")[1]: set() for c in resized}
+    for (c, guess, u, matching), g in zip(keys, ask(lines)):
+        if "@" in c.id:
+            got[c.id.split("@")[1]].add(int(g) == c.cells)
+    assert got["0.0394"] == {False, True} and got["0.5"] == {True}, got       # the finest map is wider than some windows; the coarsest is inside every one
 
 
 def test_edt_cols_is_the_restated_create_rule(ask):

@@ -2,7 +2,7 @@
 
 usage: python tools/fuzz_parity.py [n_mppi] [n_rbpf] [seed] [only] [n_batch]
 (n_batch: cases of the pipelined replay, tbnav_rbpf_slam_batch, against one synchronous call per scan — bit for bit)
-Every case draws its own sizes, gains, start poses (incl. headings near +-pi), sensor offsets, sampling spreads,
+Every case draws its own sizes, gains, start poses (incl. headings near +-pi), cell sizes, sensor offsets, sampling spreads,
 gated beams, dynamics model, scan-matching on/off ...; the assertions are the test suite's.  Prints one line per
 failing case with the parameters needed to reproduce it.
 """
@@ -73,8 +73,14 @@ def rbpf_case(i):
     icp_ok = bool(rng.random() < 0.8)
     sm = bool(rng.random() < 0.25) and icp_ok
     mode = str(rng.choice(["query", "query", "window", "full"]))
-    desc = dict(N=N, k=k, half=half, bd=bd, spread=spread, trs=trs, icp_ok=icp_ok, sm=sm, mode=mode)
-    extra = dict(sample_range=[spread * 0.1, spread, spread], Trs=trs)
+    # the cell size: the shipped one, or one of tests/raycast_cases.py's RES_TABLE (its own stream: the other draws stay as they were);
+    # create wants an even side: a half-extent that gives an odd one at the drawn size falls back to 2.0 m, which is even at all of them
+    res = float(np.random.default_rng([seed, 6, i]).choice([0.05, 0.05, 0.0394, 0.0625, 0.07, 0.3, 0.5]))
+    if int(np.ceil(2 * half / res)) % 2:
+        half = 2.0
+    assert int(np.ceil(2 * half / res)) % 2 == 0
+    desc = dict(N=N, k=k, half=half, res=res, bd=bd, spread=spread, trs=trs, icp_ok=icp_ok, sm=sm, mode=mode)
+    extra = dict(sample_range=[spread * 0.1, spread, spread], Trs=trs, resolution=res)
     n_beams = int(round(360 / bd))
     # the matcher in query mode: on half of those cases nothing is injected and the oracle reads the exact field itself (its own
     # stream: the other draws stay as they were) — the matcher's lookups then go through the bitmap query, not a stored array
@@ -137,7 +143,7 @@ def rbpf_case(i):
                         c0, s0 = np.cos(th), np.sin(th)
                         X, Y = c0 * trs[1] - s0 * trs[2] + x, s0 * trs[1] + c0 * trs[2] + y
                         ex, ey = X + scan * np.cos(ang), Y + scan * np.sin(ang)
-                        qx, qy = (ex + half) / 0.05, (ey + half) / 0.05
+                        qx, qy = (ex + half) / res, (ey + half) / res
                         near = np.argsort(np.minimum(np.abs(qx - np.round(qx)), np.abs(qy - np.round(qy))))[:3]
                         print("   nearest-to-border beams:", [(int(b), float(scan[b]), float(qx[b]), float(qy[b])) for b in near])
                         raise AssertionError(("log-odds", s, p, desc, "cells", [(int(b // xs), int(b % xs), float(lo_d[b]), float(lo_o[b])) for b in bad[:8]], len(bad),
