@@ -6,9 +6,10 @@
  * it enters, 1 or sqrt(2) cells or an occupied-cell cost, at :444-461) — but its controller never sees it: MPPI's pull towards the
  * waypoint is the quadratic distance (controller/include/controller/mppi.hpp:87-105), which points straight through whatever
  * stands in the way.  A cost field (tbnav_mppi.h, COST FIELD) that holds METRES TO GO ROUND THE WALLS instead pulls the rollouts
- * out of a pocket.  Not built: D* Lite's incremental repair (every solve starts afresh), several goals, heading-dependent costs.
+ * out of a pocket.  Not built: D* Lite's incremental repair (every solve starts afresh), heading-dependent costs.
  *
- * This section is the whole specification; tests/nav_restatement.py restates G1-G6 in Python integers, tests/nav_from_map_restatement.py G7-G8.
+ * This section is the whole specification; tests/nav_restatement.py restates G1-G6 in Python integers, tests/nav_from_map_restatement.py G7-G8,
+ * tests/nav_frontier_restatement.py G10-G16.
  *
  * G1. Grid.  nx, ny in 2 .. TBNAV_NAV_MAX_SIDE; (xmin, ymin), finite, are the world coordinates of the OUTER corner of cell (0, 0);
  *     resolution finite and > 0.  Cell (ix, iy) is at index ix*ny + iy (x is the slow index): the cost field's layout and, for the
@@ -77,6 +78,60 @@
  * 0, 1, .. R either side, finds the nearest set bit left and right of its column with clz / ffs, keeps min(dr^2 + dc^2) and stops at
  * the first dr with dr^2 >= that minimum; then one look into the table, held in LDS.  Integers only, no atomics, no waiting.
  *
+ * EXPLORATION FRONTIERS AS GOALS (csrc/nav_frontier.hip; an option like everything here).  A robot that is building its map has a source
+ * of goals of its own: the border between what it has seen to be free and what it has not seen at all.  Everything below is integer or
+ * order-free, so the tests' bar stays ==.
+ *
+ * G10. Classes.  A cell of a particle's map is UNKNOWN or FREE exactly where GridMapper::gridMap (tbnav_rbpf_particle_map) exports -1 or
+ *     0, by the cuts the filter handle holds for that export: UNKNOWN where half_lo <= l <= half_hi (probability exactly 0.5), FREE where
+ *     l <= free_cut (probability <= 0.35).  A tile nobody has written (table id 0) is unknown throughout; a cell outside the map is
+ *     neither.  The nav grid's cell (ix, iy) is the filter's cell (ci, cj) = (ix, iy), as in G8; the exported int8 map is that grid
+ *     TRANSPOSED.
+ * G11. Frontier cell: FREE, and passable (cost != 0 in the grid the next solve would use, however that grid was set), and not visited
+ *     (G14), and at least one of its FOUR edge neighbours inside the grid is UNKNOWN.  Four and not eight: the mapper's walls are only
+ *     8-connected, and a diagonal look leaks through them.
+ * G12. Clusters.  A cluster is an 8-connected component of frontier cells (no corner rule: this is connectivity of a set, not a move).
+ *     A cell's label is the least index ix*ny + iy in its component; a cell that is no frontier cell has the label TBNAV_NAV_UNREACHED.
+ *     A cluster's size is its number of cells.
+ * G13. Seeds.  A seed is any cell of a cluster of size >= min_cells; min_cells >= 1, anything else is TBNAV_ERR_INVALID_ARG.
+ *     tbnav_nav_find_frontiers runs G10-G13 for a slot of the filter or TBNAV_NAV_BEST_PARTICLE.  Grid and device must match as in G8,
+ *     with G8's rejections, and TBNAV_ERR_INVALID_ARG while no cost grid is set.  It is enqueued on the filter's stream (G9) and returns
+ *     when done.  Anything rejected changes nothing.
+ * G14. Visited mask.  One bit per cell, owned by the handle, empty at create.  tbnav_nav_mark_visited adds the disc
+ *     dix^2 + diy^2 <= radius^2 round (ix, iy), cut at the grid; 0 <= radius <= TBNAV_NAV_MAX_VISIT_RADIUS and a centre inside the grid,
+ *     else TBNAV_ERR_INVALID_ARG.  tbnav_nav_clear_visited empties it; there is no other way to take a mark back.  The host holds the
+ *     mask and uploads it when it changed: marking is not a kernel.  Why it is part of this and not left to the caller: the reference's
+ *     mapper drops a beam without a return (sensor_model.cpp:43-112), so standing on a frontier does not clear it when the wall behind
+ *     it is out of range, and a robot without the mask sits on such a seed for ever.
+ * G15. Several goals.  tbnav_nav_solve_goals: d = 0 at every listed cell, G3-G4 otherwise, so d is the cost-to-go to the NEAREST goal.
+ *     n >= 1; a cell listed twice is harmless; one blocked or outside cell is TBNAV_ERR_INVALID_ARG and the last solution stays.  With
+ *     n = 1 it equals tbnav_nav_solve bit for bit, tbnav_nav_last_solve's info included.  tbnav_nav_solve_frontiers: the same with the
+ *     seeds of the last find as goals, taken from the device with no list crossing the host; TBNAV_ERR_UNSUPPORTED when that find left no
+ *     seed — nothing left to explore — and the last solution stays; TBNAV_ERR_INVALID_ARG before any find, or when the cost grid or the
+ *     visited mask was set again since (every successful set, mark or clear counts, whatever it changed).  Everything that reads a
+ *     solution works unchanged (G5, G6, the hand-over); G6's walk stops at the first d == 0, which is the seed reached.
+ *     tbnav_nav_solve_info.goal is the first listed goal for solve_goals and (-1, -1) for solve_frontiers.
+ * G16. Results for people.  tbnav_nav_get_frontier_labels returns G12; tbnav_nav_frontier_list one record per cluster in ascending label
+ *     order — a host loop over the downloaded labels, like G6, not a kernel; a buffer too small is TBNAV_ERR_INVALID_ARG with *n set.
+ *     Both are TBNAV_ERR_INVALID_ARG before the first find and keep the last find's results whatever is set afterwards.
+ *
+ * The kernels.  nav_frontier_mark: one workgroup of 256 per 32 x 32 tile (nav_cost_from_occ's tiling) reads the tile's 1024 log-odds
+ * through the particle's tile table (8 KB, rows contiguous) and the facing row or column of its four edge neighbours, classifies them
+ * against the cuts passed by value, packs UNKNOWN / FREE / passable into row words with wave ballots (a wave64 is two rows of 32), forms
+ * each row's frontier word with shifts and ORs of the unknown words above, below and either side, ANDs in the visited word, writes
+ * frontier[nx][TW] (the pool's bm layout), the initial labels (own index or UNREACHED) and zeros for the sizes, and sets the tile's active
+ * flag when any bit is set; a tile nobody has written holds no FREE cell, writes zeros and UNREACHED and leaves early; one count per
+ * workgroup is its only atomic.  nav_frontier_label: minimum-label propagation over the 8 neighbours in the shape of nav_relax_tiles (an
+ * active tile with a one-cell halo in LDS, sweeps to the tile's own fixed point under the same bound, the interior written back, a changed
+ * rim wakes the neighbours, a round is a launch, the host stops at the first round that changed nothing).  nav_frontier_sizes: one integer
+ * atomicAdd per frontier cell into size[label] — order-free, hence exact.  nav_frontier_seeds: the seed words by ballot, and the counts.
+ * nav_reset_goals: a solve's start from the seed words or from an uploaded list, active the tiles that see a goal (nav_reset's rule).  No
+ * kernel waits for another workgroup; every loop is bounded by the tile.
+ *
+ * Not built here: sharded filters and handles on different devices; information gain or any ranking of frontiers other than nearest;
+ * clearing along beams without a return (the mapper's behaviour stays the reference's); incremental updates between scans; a time-out for
+ * marks.
+ *
  * Not thread-safe; one handle per planner object; the handle owns all device memory.  Bad arguments return before any device call.
  */
 #ifndef TBNAV_NAV_H
@@ -96,6 +151,7 @@ extern "C" {
 #define TBNAV_NAV_UNREACHED 0xFFFFFFFFu
 #define TBNAV_NAV_MAX_REACH 32 /* G7's R: one tile of halo round a workgroup's tile */
 #define TBNAV_NAV_BEST_PARTICLE (-1)
+#define TBNAV_NAV_MAX_VISIT_RADIUS 64 /* G14, cells */
 
 typedef struct tbnav_nav_params {
   int32_t nx, ny;     /* cells along x (slow index) and y, each 2 .. TBNAV_NAV_MAX_SIDE */
@@ -171,6 +227,48 @@ int tbnav_nav_last_solve(const tbnav_nav* h, tbnav_nav_solve_info* info, char* k
 int tbnav_nav_apply_to_mppi(tbnav_nav* h, tbnav_mppi* mppi, double cap, double weight);
 /* Every member of the group receives the field, or none does. */
 int tbnav_nav_apply_to_mppi_group(tbnav_nav* h, tbnav_mppi_group* group, double cap, double weight);
+
+/* What the last find left (G13). */
+typedef struct tbnav_nav_frontier_info {
+  int32_t found;          /* 1 once a find has succeeded on this handle                                    */
+  int32_t min_cells;      /* its threshold                                                                   */
+  int32_t cells;          /* frontier cells (G11)                                                            */
+  int32_t clusters;       /* clusters (G12)                                                                  */
+  int32_t seed_clusters;  /* clusters of size >= min_cells                                                   */
+  int32_t seed_cells;     /* their cells: the goals of tbnav_nav_solve_frontiers                             */
+  int32_t rounds;         /* the labelling's rounds up to and including the first that changed nothing       */
+  int32_t launches;       /* launches of nav_frontier_label (>= rounds)                                      */
+  int64_t tile_visits;    /* workgroups that found their tile active, over all rounds                        */
+} tbnav_nav_frontier_info;
+
+/* One cluster (G16). */
+typedef struct tbnav_nav_frontier {
+  int32_t root[2];        /* the cell whose index is the label                                               */
+  int32_t size;           /* cells                                                                           */
+  int32_t seeds;          /* 1 where size >= the find's min_cells                                            */
+  int32_t box[4];         /* ix_min, iy_min, ix_max, iy_max                                                  */
+  int64_t sum_ix, sum_iy; /* over the cells: the centroid is (sum_ix / size, sum_iy / size)                  */
+} tbnav_nav_frontier;
+
+/* G10-G13.  info may be null. */
+int tbnav_nav_find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info);
+/* Measurement hook (tools/nav_frontier_time.py): the same find with events on the filter's stream between its stages; stage_ms[4] = mark,
+ * the label rounds with the host's reads of their records, sizes, seeds. */
+int tbnav_nav_profile_find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info, float* stage_ms);
+/* The last find's info (found = 0 before the first). */
+int tbnav_nav_last_frontiers(const tbnav_nav* h, tbnav_nav_frontier_info* info);
+/* The kernels of a find, spelled as a profiler prints them and separated by ';'; "" before the first find. */
+int tbnav_nav_last_frontier_kernels(const tbnav_nav* h, char* kernels, int32_t kernels_cap);
+/* G14.  tbnav_nav_get_visited: nx*ny bytes, 1 = visited. */
+int tbnav_nav_mark_visited(tbnav_nav* h, int32_t ix, int32_t iy, int32_t radius_cells);
+int tbnav_nav_clear_visited(tbnav_nav* h);
+int tbnav_nav_get_visited(tbnav_nav* h, uint8_t* visited_host);
+/* G15, synchronous like tbnav_nav_solve.  cells: n pairs (ix, iy). */
+int tbnav_nav_solve_goals(tbnav_nav* h, const int32_t* cells, int32_t n);
+int tbnav_nav_solve_frontiers(tbnav_nav* h);
+/* G16.  labels_host: nx*ny values.  out: room for cap records (may be null when cap is 0: *n is then the number needed). */
+int tbnav_nav_get_frontier_labels(tbnav_nav* h, uint32_t* labels_host);
+int tbnav_nav_frontier_list(tbnav_nav* h, tbnav_nav_frontier* out, int32_t cap, int32_t* n);
 
 #ifdef __cplusplus
 }

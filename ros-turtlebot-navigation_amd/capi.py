@@ -77,6 +77,19 @@ class NavSolveInfo(C.Structure):
 
 NAV_MAX_SIDE, NAV_MAX_COST, NAV_UNREACHED = 2048, 64, 0xFFFFFFFF
 NAV_MAX_REACH, NAV_BEST_PARTICLE = 32, -1
+NAV_MAX_VISIT_RADIUS = 64
+
+
+class NavFrontierInfo(C.Structure):
+    """tbnav_nav_frontier_info (G13)."""
+    _fields_ = [("found", C.c_int32), ("min_cells", C.c_int32), ("cells", C.c_int32), ("clusters", C.c_int32), ("seed_clusters", C.c_int32),
+                ("seed_cells", C.c_int32), ("rounds", C.c_int32), ("launches", C.c_int32), ("tile_visits", C.c_int64)]
+
+
+class NavFrontier(C.Structure):
+    """tbnav_nav_frontier (G16)."""
+    _fields_ = [("root", C.c_int32 * 2), ("size", C.c_int32), ("seeds", C.c_int32), ("box", C.c_int32 * 4), ("sum_ix", C.c_int64),
+                ("sum_iy", C.c_int64)]
 
 
 class RbpfParams(C.Structure):
@@ -266,6 +279,17 @@ def lib() -> C.CDLL:
         "tbnav_nav_profile_cost_from_rbpf": (C.c_int, [vp, vp, i32, dbl, dbl, dbl, i32, C.POINTER(C.c_float)]),
         "tbnav_mppi_set_cost_field_from_rbpf": (C.c_int, [vp, vp, i32, dbl, dbl, dbl]),
         "tbnav_nav_last_cost_kernel": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_nav_find_frontiers": (C.c_int, [vp, vp, i32, i32, C.POINTER(NavFrontierInfo)]),
+        "tbnav_nav_profile_find_frontiers": (C.c_int, [vp, vp, i32, i32, C.POINTER(NavFrontierInfo), C.POINTER(C.c_float)]),
+        "tbnav_nav_last_frontiers": (C.c_int, [vp, C.POINTER(NavFrontierInfo)]),
+        "tbnav_nav_last_frontier_kernels": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_nav_mark_visited": (C.c_int, [vp, i32, i32, i32]),
+        "tbnav_nav_clear_visited": (C.c_int, [vp]),
+        "tbnav_nav_get_visited": (C.c_int, [vp, vp]),
+        "tbnav_nav_solve_goals": (C.c_int, [vp, vp, i32]),
+        "tbnav_nav_solve_frontiers": (C.c_int, [vp]),
+        "tbnav_nav_get_frontier_labels": (C.c_int, [vp, vp]),
+        "tbnav_nav_frontier_list": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
         # communicators (include/tbnav_comm.h) and the sharded MPPI tick
         "tbnav_comm_unique_id": (C.c_int, [vp]),
         "tbnav_comm_unique_id_ipc": (C.c_int, [vp]),

@@ -147,16 +147,26 @@ __global__ void nav_field(const unsigned* __restrict__ d, int n, double resoluti
 using namespace tbnav_nk;
 using tbnav_mh::DeviceGuard;
 
-namespace {
-// Rounds per batch: in open space the front crosses about a tile per round, so half the tiles along both sides is a batch or two
-// per solve; at least 4 (a host read costs several launches), at most kMaxBatch (what a finished solve wastes on launches that find
-// no active tile).  Doubling the batch while a solve goes on was measured and lost: the serpentine's 100 rounds are bound by their
-// sweeps, not by the host's reads (5.5 against 5.7 ms), and the 400 x 400 solves paid 13 more empty launches (0.65 against 0.61 ms).
-constexpr int kMaxBatch = 32;
-int batch_rounds(const tbnav_nav* h) {
-  const int b = (h->tiles_x + h->tiles_y) / 2;
-  return b < 4 ? 4 : (b > kMaxBatch ? kMaxBatch : b);
+// the rounds of a solve (the batches and the stop rule: nav_host.hpp, run_rounds) and what a finished solve leaves in the handle
+int tbnav_nk::relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy) {
+  int rounds = 0, launches = 0;
+  long long visits = 0;
+  const int rc = run_rounds(h, h->d_flags, h->d_rec, nullptr, [&](unsigned* cur, unsigned* nxt, unsigned* rec) {
+    const RelaxArgs a{h->d_cost, h->d_d, cur, nxt, rec, h->p.nx, h->p.ny, h->tiles_y};
+    hipLaunchKernelGGL(nav_relax_tiles, dim3(h->tiles_y, h->tiles_x), dim3(kThreads), 0, nullptr, a);
+  }, &rounds, &launches, &visits);
+  if (rc != TBNAV_OK) return rc;
+  // what G6 walks over: the host copy where there is one, else kept on the device until a path is asked for
+  if (h->cost_host_valid) h->cost_solved = h->cost;
+  else TBNAV_HIP(hipMemcpy(h->d_cost_solved, h->d_cost, (size_t)h->n, hipMemcpyDeviceToDevice));
+  h->cost_solved_valid = h->cost_host_valid;
+  h->solved = true;
+  h->info.solved = 1; h->info.goal[0] = goal_ix; h->info.goal[1] = goal_iy;
+  h->info.rounds = rounds; h->info.launches = launches; h->info.tile_visits = visits;
+  return TBNAV_OK;
 }
+
+namespace {
 bool in_grid(const tbnav_nav* h, int ix, int iy) { return ix >= 0 && ix < h->p.nx && iy >= 0 && iy < h->p.ny; }
 
 int download(tbnav_nav* h) {
@@ -236,6 +246,9 @@ void tbnav_nav_destroy(tbnav_nav* h) {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
     (void)hipFree(h->d_cost); (void)hipFree(h->d_cost_solved); (void)hipFree(h->d_infl); (void)hipFree(h->d_d); (void)hipFree(h->d_field); (void)hipFree(h->d_flags); (void)hipFree(h->d_rec);
+    // nav_frontier.hip's (null where its calls were never made)
+    (void)hipFree(h->d_front); (void)hipFree(h->d_seed); (void)hipFree(h->d_visited); (void)hipFree(h->d_label); (void)hipFree(h->d_size);
+    (void)hipFree(h->d_fflags); (void)hipFree(h->d_frec); (void)hipFree(h->d_fcount); (void)hipFree(h->d_goals);
   }
   delete h;
 }
@@ -248,6 +261,7 @@ int tbnav_nav_set_cost(tbnav_nav* h, const uint8_t* cost_host) {
   TBNAV_HIP(hipMemcpy(h->d_cost, cost_host, (size_t)h->n, hipMemcpyHostToDevice));   // (solves are synchronous: nothing reads d_cost now)
   h->cost.assign(cost_host, cost_host + h->n);
   h->cost_set = true; h->cost_host_valid = true;
+  ++h->cost_epoch;
   return TBNAV_OK;
 }
 
@@ -274,39 +288,10 @@ int tbnav_nav_solve(tbnav_nav* h, int32_t goal_ix, int32_t goal_iy) {
   else TBNAV_HIP(hipMemcpy(&at_goal, h->d_cost + goal, 1, hipMemcpyDeviceToHost));
   if (at_goal == 0) return TBNAV_ERR_INVALID_ARG;
   h->solved = false; h->d_host_valid = false;   // from here on the last solution is being overwritten
-  const int tiles = h->tiles_x * h->tiles_y, B = batch_rounds(h);
+  const int tiles = h->tiles_x * h->tiles_y;
   hipLaunchKernelGGL(nav_reset, dim3(256), dim3(256), 0, nullptr, h->d_d, h->n, h->p.ny, goal_ix, goal_iy, h->d_flags, tiles, h->tiles_y);
   TBNAV_HIP(hipGetLastError());
-  // a relaxation that moved one cell per round would need fewer than n rounds; this one never needs more
-  const long long round_cap = (long long)h->n + kMaxBatch;
-  unsigned rec[2 * kMaxBatch];
-  int rounds = 0, launches = 0;
-  long long visits = 0;
-  for (int r0 = 0; rounds == 0; r0 += B) {
-    if (r0 > round_cap) return TBNAV_ERR_UNSUPPORTED;
-    TBNAV_HIP(hipMemsetAsync(h->d_rec, 0, sizeof(unsigned) * 2 * B, nullptr));
-    for (int r = 0; r < B; ++r) {
-      unsigned* cur = h->d_flags + ((r0 + r) & 1) * tiles;
-      unsigned* nxt = h->d_flags + ((r0 + r + 1) & 1) * tiles;
-      const RelaxArgs a{h->d_cost, h->d_d, cur, nxt, h->d_rec + 2 * r, h->p.nx, h->p.ny, h->tiles_y};
-      hipLaunchKernelGGL(nav_relax_tiles, dim3(h->tiles_y, h->tiles_x), dim3(kThreads), 0, nullptr, a);
-    }
-    TBNAV_HIP(hipGetLastError());
-    launches += B;
-    TBNAV_HIP(hipMemcpy(rec, h->d_rec, sizeof(unsigned) * 2 * B, hipMemcpyDeviceToHost));   // waits for the batch
-    for (int r = 0; r < B && rounds == 0; ++r) {
-      visits += rec[2 * r];
-      if (rec[2 * r + 1] == 0) rounds = r0 + r + 1;   // nothing changed, so nothing was marked: every later round finds no tile
-    }
-  }
-  // what G6 walks over: the host copy where there is one, else kept on the device until a path is asked for
-  if (h->cost_host_valid) h->cost_solved = h->cost;
-  else TBNAV_HIP(hipMemcpy(h->d_cost_solved, h->d_cost, (size_t)h->n, hipMemcpyDeviceToDevice));
-  h->cost_solved_valid = h->cost_host_valid;
-  h->solved = true;
-  h->info.solved = 1; h->info.goal[0] = goal_ix; h->info.goal[1] = goal_iy;
-  h->info.rounds = rounds; h->info.launches = launches; h->info.tile_visits = visits;
-  return TBNAV_OK;
+  return relax_from_start(h, goal_ix, goal_iy);
 }
 
 int tbnav_nav_cell_of(const tbnav_nav* h, double x, double y, int32_t* ix, int32_t* iy) {

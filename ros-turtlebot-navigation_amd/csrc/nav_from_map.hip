@@ -215,6 +215,7 @@ int tbnav_nav_profile_cost_from_rbpf(tbnav_nav* h, tbnav_rbpf* pf, int32_t parti
   TBNAV_HIP(e);
   h->cost_set = true; h->cost_host_valid = false;   // (the host copy is fetched when somebody asks: tbnav_nav_get_cost)
   h->from_map = true;
+  ++h->cost_epoch;
   return TBNAV_OK;
 }
 

@@ -1,5 +1,6 @@
-// nav_host.hpp — the goal field's handle and what its two host files share (nav.hip: create / solve / results / hand-over of the solved
-// field; nav_from_map.hip: the cost grid taken from a filter's occupancy bits on the device, tbnav_nav.h G7-G9).
+// nav_host.hpp — the goal field's handle and what its host files share (nav.hip: create / solve / results / hand-over of the solved
+// field; nav_from_map.hip: the cost grid taken from a filter's occupancy bits on the device, tbnav_nav.h G7-G9; nav_frontier.hip: the
+// frontiers of a particle's map, their clusters, and the solves that start from several goals, G10-G16).
 #ifndef TBNAV_NAV_HOST_HPP
 #define TBNAV_NAV_HOST_HPP
 #include <hip/hip_runtime.h>
@@ -7,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "common.hpp"
 #include "tbnav_nav.h"
 
 struct tbnav_nav {
@@ -28,11 +30,76 @@ struct tbnav_nav {
   bool cost_set = false, solved = false, d_host_valid = false, cost_host_valid = false, cost_solved_valid = false;
   bool from_map = false;            // tbnav_nav_set_cost_from_rbpf has run on this handle (tbnav_nav_last_cost_kernel)
   tbnav_nav_solve_info info{0, {0, 0}, 0, 0, {0, 0}, 0};
+  // G10-G16 (nav_frontier.hip).  Everything below is allocated at the first use of that file's calls, never at create.
+  unsigned* d_front = nullptr;      // [nx][tiles_y] frontier bits: row ix, word iy >> 5, bit iy & 31 (TilePool::bm's layout)
+  unsigned* d_seed = nullptr;       // [nx][tiles_y] ... of the seeds
+  unsigned* d_visited = nullptr;    // [nx][tiles_y] ... of the visited mask
+  unsigned* d_label = nullptr;      // [nx][ny] G12's labels
+  unsigned* d_size = nullptr;       // [nx][ny] cells per cluster, at the cluster's root
+  unsigned* d_fflags = nullptr;     // [2][tiles] active tiles of the labelling's even and odd rounds
+  unsigned* d_frec = nullptr;       // [batch][2] its round records
+  unsigned* d_fcount = nullptr;     // [4] frontier cells, clusters, seed clusters, seed cells
+  int* d_goals = nullptr;           // [goals_cap][2] the list of tbnav_nav_solve_goals
+  int goals_cap = 0;
+  std::vector<unsigned> visited;    // host side of d_visited: the mask lives here (G14) and is uploaded when it changed
+  bool visited_dirty = true;
+  std::vector<unsigned> label_host; // the downloaded labels (filled at their first use after a find)
+  bool label_host_valid = false;
+  // a find's seeds are goals only while the grid and the mask it saw are the ones in force: every successful set of either counts
+  uint64_t cost_epoch = 0, visited_epoch = 0, found_cost_epoch = 0, found_visited_epoch = 0;
+  tbnav_nav_frontier_info finfo{0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace tbnav_nk {
 // room for a table of TBNAV_NAV_MAX_REACH^2 + 1 entries and the open value
 constexpr int kInflEntries = TBNAV_NAV_MAX_REACH * TBNAV_NAV_MAX_REACH + 2;
+
+// Rounds per batch: in open space the front crosses about a tile per round, so half the tiles along both sides is a batch or two
+// per solve; at least 4 (a host read costs several launches), at most kMaxBatch (what a finished solve wastes on launches that find
+// no active tile).  Doubling the batch while a solve goes on was measured and lost: the serpentine's 100 rounds are bound by their
+// sweeps, not by the host's reads (5.5 against 5.7 ms), and the 400 x 400 solves paid 13 more empty launches (0.65 against 0.61 ms).
+constexpr int kMaxBatch = 32;
+inline int batch_rounds(const tbnav_nav* h) {
+  const int b = (h->tiles_x + h->tiles_y) / 2;
+  return b < 4 ? 4 : (b > kMaxBatch ? kMaxBatch : b);
+}
+
+// The host side of a tiled fixed-point iteration (nav_relax_tiles, nav_frontier_label): rounds are enqueued in batches on `stream`,
+// launch(cur, nxt, rec) being one round over the active tiles of `flags` ([2][tiles]: even and odd rounds; the even array holds round
+// 0's tiles, the odd one is zero); one record per batch is read (rec[0] tiles visited, rec[1] tiles in which something changed) and the
+// first round that changed nothing ends it — the proof of the fixed point.
+template <class Launch>
+int run_rounds(tbnav_nav* h, unsigned* flags, unsigned* d_rec, hipStream_t stream, Launch launch, int* rounds_out, int* launches_out, long long* visits_out) {
+  const int tiles = h->tiles_x * h->tiles_y, B = batch_rounds(h);
+  // an iteration that moved one cell per round would need fewer than n rounds; these never need more
+  const long long round_cap = (long long)h->n + kMaxBatch;
+  unsigned rec[2 * kMaxBatch];
+  int rounds = 0, launches = 0;
+  long long visits = 0;
+  for (int r0 = 0; rounds == 0; r0 += B) {
+    if (r0 > round_cap) return TBNAV_ERR_UNSUPPORTED;
+    TBNAV_HIP(hipMemsetAsync(d_rec, 0, sizeof(unsigned) * 2 * B, stream));
+    for (int r = 0; r < B; ++r) launch(flags + ((r0 + r) & 1) * tiles, flags + ((r0 + r + 1) & 1) * tiles, d_rec + 2 * r);
+    TBNAV_HIP(hipGetLastError());
+    launches += B;
+    if (stream) {
+      TBNAV_HIP(hipMemcpyAsync(rec, d_rec, sizeof(unsigned) * 2 * B, hipMemcpyDeviceToHost, stream));
+      TBNAV_HIP(hipStreamSynchronize(stream));
+    } else {
+      TBNAV_HIP(hipMemcpy(rec, d_rec, sizeof(unsigned) * 2 * B, hipMemcpyDeviceToHost));   // waits for the batch
+    }
+    for (int r = 0; r < B && rounds == 0; ++r) {
+      visits += rec[2 * r];
+      if (rec[2 * r + 1] == 0) rounds = r0 + r + 1;   // nothing changed, so nothing was marked: every later round finds no tile
+    }
+  }
+  *rounds_out = rounds; *launches_out = launches; *visits_out = visits;
+  return TBNAV_OK;
+}
+
+// nav.hip: the rounds of nav_relax_tiles from whatever start d_d and d_flags hold (nav_reset / nav_reset_goals have been enqueued on the
+// null stream; the handle's device is current), and what a finished solve leaves in the handle.  h->solved is false while it runs.
+int relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy);
 }  // namespace tbnav_nk
 
 #endif

@@ -7,7 +7,10 @@
 //     nav.setCost(planner::navCostFromDistance(occ_dist, nx, ny, r_robot, r_inflate, k));
 //     nav.solve(goal.x, goal.y);  nav.applyTo(mppi, cap, weight);
 // and one that owns the filter itself replaces the second line by nav.setCostFrom(filter, r_robot, r_inflate, k): the grid comes from
-// the best particle's map on the device (G7-G9).
+// the best particle's map on the device (G7-G9).  A node that EXPLORES has no waypoint to type: it replaces the solve by
+//     nav.findFrontiers(filter);  if (!nav.solveToFrontiers()) { /* nothing left to explore */ }
+// — the goals are the frontiers of the best particle's map, the border between what it has seen to be free and what it has not seen
+// (G10-G16) — and calls nav.markVisited(x, y, radius) where it arrives at a frontier that its scans do not clear.
 // and links libtbnav_host.so + libtbnav_hip.so.
 #ifndef TBNAV_PLANNER_GOAL_FIELD_HPP
 #define TBNAV_PLANNER_GOAL_FIELD_HPP
@@ -29,6 +32,15 @@ namespace planner {
 /// occ_dist.size() == nx * ny.
 std::vector<std::uint8_t> navCostFromDistance(const std::vector<double>& occ_dist, int nx, int ny, double r_robot, double r_inflate, double k);
 
+/// One cluster of frontier cells (tbnav_nav.h G12, G16).
+struct Frontier {
+  std::array<int, 2> root{};   ///< the cell whose index ix * ny + iy is the cluster's label: its least
+  int size = 0;                ///< cells
+  bool seeds = false;          ///< size >= the find's min_cells: its cells are goals of solveToFrontiers
+  std::array<int, 4> box{};    ///< ix_min, iy_min, ix_max, iy_max
+  double cx = 0.0, cy = 0.0;   ///< the centroid in world coordinates (the mean of the cells' centres)
+};
+
 class GoalField {
  public:
   /// G1: nx x ny cells of `resolution` metres, (xmin, ymin) the outer corner of cell (0, 0).  Throws std::invalid_argument on a grid
@@ -49,6 +61,21 @@ class GoalField {
   /// G3-G4 with the goal at the cell of the world position (x, y).  Throws std::invalid_argument when that position is outside the
   /// grid (the reference's "NOT in the bounds of the world") or its cell is blocked; the last solution then stays.
   void solve(double x, double y);
+  /// G10-G13 on the map of the filter's best particle: frontier cells, their 8-connected clusters, and as seeds the cells of the
+  /// clusters of at least min_cells cells.  Returns one Frontier per cluster in ascending label order.  Needs a cost grid (setCost /
+  /// setCostFrom) and this grid to be the filter's, else std::invalid_argument, as for min_cells < 1; std::runtime_error for a filter
+  /// built with n_gpus > 1.
+  std::vector<Frontier> findFrontiers(bmapping::ParticleFilter& filter, int min_cells = 8);
+  /// G14: the disc of radius_m (rounded to cells, at most 64) round the cell of (x, y) joins the visited mask: no cell of it is a
+  /// frontier cell any more.  Throws std::invalid_argument for a position outside the grid or a radius outside 0 .. 64 cells.
+  void markVisited(double x, double y, double radius_m);
+  void clearVisited();
+  /// G15: the cost-to-go to the NEAREST of the world positions (x, y).  Throws like solve where one of them is outside or blocked.
+  void solveGoals(const std::vector<std::array<double, 2>>& goals);
+  /// G15 with the seeds of the last findFrontiers as goals, taken from the device.  false where that find left no seed — nothing left
+  /// to explore; the last solution then stays.  Throws std::invalid_argument before any find, or when the cost grid or the visited
+  /// mask was set again since.
+  bool solveToFrontiers();
   std::vector<std::uint32_t> costToGo();           ///< G4, [nx][ny]; 0xFFFFFFFF = blocked or unreached
   std::vector<float> field(double cap);            ///< G5, metres to go capped at `cap`
   /// G6 from the cell of (x, y): (ix, iy) pairs, start and goal included.  Throws std::runtime_error from a blocked or unreached start.
@@ -65,6 +92,7 @@ class GoalField {
   std::array<int, 2> cellOf(double x, double y) const;
   tbnav_nav* h_ = nullptr;
   int nx_ = 0, ny_ = 0;
+  double xmin_ = 0.0, ymin_ = 0.0, resolution_ = 1.0;
 };
 
 }  // namespace planner

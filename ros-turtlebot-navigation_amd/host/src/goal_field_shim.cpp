@@ -38,13 +38,15 @@ std::vector<std::uint8_t> navCostFromDistance(const std::vector<double>& occ_dis
   return c;
 }
 
-GoalField::GoalField(int nx, int ny, double xmin, double ymin, double resolution) : nx_(nx), ny_(ny) {
+GoalField::GoalField(int nx, int ny, double xmin, double ymin, double resolution)
+    : nx_(nx), ny_(ny), xmin_(xmin), ymin_(ymin), resolution_(resolution) {
   tbnav_nav_params p{};
   p.nx = nx; p.ny = ny; p.xmin = xmin; p.ymin = ymin; p.resolution = resolution; p.device = -1;
   check(tbnav_nav_create(&p, &h_), "planner::GoalField");
 }
 GoalField::~GoalField() { tbnav_nav_destroy(h_); }
-GoalField::GoalField(GoalField&& o) noexcept : h_(o.h_), nx_(o.nx_), ny_(o.ny_) { o.h_ = nullptr; }
+GoalField::GoalField(GoalField&& o) noexcept
+    : h_(o.h_), nx_(o.nx_), ny_(o.ny_), xmin_(o.xmin_), ymin_(o.ymin_), resolution_(o.resolution_) { o.h_ = nullptr; }
 
 void GoalField::setCost(const std::vector<std::uint8_t>& cost) {
   if (cost.size() != (size_t)nx_ * (size_t)ny_) throw std::invalid_argument("setCost: cost.size() != nx * ny");
@@ -62,6 +64,48 @@ std::array<int, 2> GoalField::cellOf(double x, double y) const {
 void GoalField::solve(double x, double y) {
   const auto c = cellOf(x, y);
   check(tbnav_nav_solve(h_, c[0], c[1]), "solve");
+}
+std::vector<Frontier> GoalField::findFrontiers(bmapping::ParticleFilter& filter, int min_cells) {
+  if (filter.g_) throw std::runtime_error("findFrontiers: a filter over several GPUs is not supported");
+  tbnav_nav_frontier_info info{};
+  check(tbnav_nav_find_frontiers(h_, filter.h_, TBNAV_NAV_BEST_PARTICLE, min_cells, &info), "findFrontiers");
+  std::vector<tbnav_nav_frontier> recs((size_t)info.clusters);
+  int32_t n = 0;
+  if (info.clusters > 0) check(tbnav_nav_frontier_list(h_, recs.data(), info.clusters, &n), "findFrontiers");
+  std::vector<Frontier> out((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const tbnav_nav_frontier& r = recs[(size_t)i];
+    Frontier& f = out[(size_t)i];
+    f.root = {r.root[0], r.root[1]};
+    f.size = r.size;
+    f.seeds = r.seeds != 0;
+    f.box = {r.box[0], r.box[1], r.box[2], r.box[3]};
+    f.cx = xmin_ + ((double)r.sum_ix / (double)r.size + 0.5) * resolution_;
+    f.cy = ymin_ + ((double)r.sum_iy / (double)r.size + 0.5) * resolution_;
+  }
+  return out;
+}
+void GoalField::markVisited(double x, double y, double radius_m) {
+  const auto c = cellOf(x, y);
+  const double cells = std::rint(radius_m / resolution_);
+  if (!(cells >= 0.0 && cells <= (double)TBNAV_NAV_MAX_VISIT_RADIUS)) throw std::invalid_argument("markVisited: the radius must be 0 .. 64 cells");
+  check(tbnav_nav_mark_visited(h_, c[0], c[1], (int32_t)cells), "markVisited");
+}
+void GoalField::clearVisited() { check(tbnav_nav_clear_visited(h_), "clearVisited"); }
+void GoalField::solveGoals(const std::vector<std::array<double, 2>>& goals) {
+  std::vector<int32_t> cells;
+  cells.reserve(2 * goals.size());
+  for (const auto& g : goals) {
+    const auto c = cellOf(g[0], g[1]);
+    cells.push_back(c[0]); cells.push_back(c[1]);
+  }
+  check(tbnav_nav_solve_goals(h_, cells.data(), (int32_t)goals.size()), "solveGoals");
+}
+bool GoalField::solveToFrontiers() {
+  const int rc = tbnav_nav_solve_frontiers(h_);
+  if (rc == TBNAV_ERR_UNSUPPORTED) return false;   // the find left no seed
+  check(rc, "solveToFrontiers");
+  return true;
 }
 std::vector<std::uint32_t> GoalField::costToGo() {
   std::vector<std::uint32_t> d((size_t)nx_ * ny_);

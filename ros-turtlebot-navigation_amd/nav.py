@@ -1,6 +1,6 @@
 """Python mirror of planner::GoalField over the C-ABI of include/tbnav_nav.h (tests / tools plumbing): the exact cost-to-go to a
 goal cell over a cost grid, solved on the device, and its hand-over to an MPPI handle as a cost field.  The header is the
-specification (G1-G6); the shipped host surface for ROS nodes is the C++ class in host/include/planner/goal_field.hpp.
+specification (G1-G16); the shipped host surface for ROS nodes is the C++ class in host/include/planner/goal_field.hpp.
 """
 from __future__ import annotations
 
@@ -100,6 +100,83 @@ class GoalField:
     def solveAt(self, x: float, y: float):
         """solve with the goal given in world coordinates."""
         self.solve(*self.cellOf(x, y))
+
+    # ---- exploration frontiers as goals (tbnav_nav.h G10-G16) ----
+    @staticmethod
+    def _frontier_info(info) -> dict:
+        return dict(found=bool(info.found), min_cells=info.min_cells, cells=info.cells, clusters=info.clusters,
+                    seed_clusters=info.seed_clusters, seed_cells=info.seed_cells, rounds=info.rounds, launches=info.launches,
+                    tile_visits=int(info.tile_visits))
+
+    def findFrontiers(self, pf, min_cells: int = 8, particle=None) -> dict:
+        """G10-G13 for a particle of an rtn_amd.rbpf.ParticleFilter (None: the best one, found on the device): the counts of frontier
+        cells, clusters, seed clusters and seed cells, and the labelling's rounds, launches and tile visits."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        info = capi.NavFrontierInfo()
+        capi.check(self._L.tbnav_nav_find_frontiers(self._h, pf._h, p, int(min_cells), C.byref(info)), "tbnav_nav_find_frontiers")
+        return self._frontier_info(info)
+
+    def profileFindFrontiers(self, pf, min_cells: int = 8, particle=None):
+        """findFrontiers with events between its stages: (info, microseconds of mark / label rounds / sizes / seeds) (a measurement hook)."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        info, ms = capi.NavFrontierInfo(), (C.c_float * 4)()
+        capi.check(self._L.tbnav_nav_profile_find_frontiers(self._h, pf._h, p, int(min_cells), C.byref(info), ms), "tbnav_nav_profile_find_frontiers")
+        return self._frontier_info(info), dict(zip(("mark", "label", "sizes", "seeds"), (v * 1e3 for v in ms)))
+
+    def lastFrontiers(self) -> dict:
+        info = capi.NavFrontierInfo()
+        capi.check(self._L.tbnav_nav_last_frontiers(self._h, C.byref(info)), "tbnav_nav_last_frontiers")
+        return self._frontier_info(info)
+
+    def frontierLabels(self) -> np.ndarray:
+        """G12: uint32 [nx][ny], the least index ix*ny + iy of the cell's cluster; NAV_UNREACHED where the cell is no frontier cell."""
+        lab = np.empty((self.nx, self.ny), dtype=np.uint32)
+        capi.check(self._L.tbnav_nav_get_frontier_labels(self._h, lab.ctypes.data), "tbnav_nav_get_frontier_labels")
+        return lab
+
+    def frontiers(self) -> list:
+        """G16: one dict per cluster in ascending label order: root, size, seeds, box (ix_min, iy_min, ix_max, iy_max), sum_ix, sum_iy."""
+        n = C.c_int32(0)
+        rc = self._L.tbnav_nav_frontier_list(self._h, None, 0, C.byref(n))
+        if n.value <= 0:
+            capi.check(rc, "tbnav_nav_frontier_list")
+            return []
+        recs = (capi.NavFrontier * n.value)()
+        capi.check(self._L.tbnav_nav_frontier_list(self._h, recs, n.value, C.byref(n)), "tbnav_nav_frontier_list")
+        return [dict(root=(r.root[0], r.root[1]), size=r.size, seeds=bool(r.seeds), box=tuple(r.box), sum_ix=int(r.sum_ix), sum_iy=int(r.sum_iy))
+                for r in recs[:n.value]]
+
+    def markVisited(self, ix: int, iy: int, radius_cells: int):
+        """G14: the disc of radius_cells round (ix, iy) joins the visited mask."""
+        capi.check(self._L.tbnav_nav_mark_visited(self._h, int(ix), int(iy), int(radius_cells)), "tbnav_nav_mark_visited")
+
+    def clearVisited(self):
+        capi.check(self._L.tbnav_nav_clear_visited(self._h), "tbnav_nav_clear_visited")
+
+    def visited(self) -> np.ndarray:
+        v = np.empty((self.nx, self.ny), dtype=np.uint8)
+        capi.check(self._L.tbnav_nav_get_visited(self._h, v.ctypes.data), "tbnav_nav_get_visited")
+        return v
+
+    def solveGoals(self, cells):
+        """G15: the cost-to-go to the nearest of the listed cells, [(ix, iy), ...]."""
+        c = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        capi.check(self._L.tbnav_nav_solve_goals(self._h, c.ctypes.data, c.shape[0]), "tbnav_nav_solve_goals")
+
+    def solveFrontiers(self) -> bool:
+        """G15 with the last find's seeds as goals, taken from the device.  False where that find left no seed: nothing left to
+        explore, and the last solution stays."""
+        rc = self._L.tbnav_nav_solve_frontiers(self._h)
+        if rc == capi.ERR_UNSUPPORTED:
+            return False
+        capi.check(rc, "tbnav_nav_solve_frontiers")
+        return True
+
+    def lastFrontierKernels(self) -> list:
+        """The kernels a find launches, as a profiler prints them; [] before the first find."""
+        name = C.create_string_buffer(160)
+        capi.check(self._L.tbnav_nav_last_frontier_kernels(self._h, name, 160), "tbnav_nav_last_frontier_kernels")
+        return [k for k in name.value.decode().split(";") if k]
 
     def cellOf(self, x: float, y: float) -> tuple:
         ix, iy = C.c_int32(), C.c_int32()
