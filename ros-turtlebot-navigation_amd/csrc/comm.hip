@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -71,11 +72,7 @@ struct LocalGroup {
   std::vector<int> device;
 };
 
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int d) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(d); }
-  ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
+using tbnav::DeviceGuard;  // (no call site here looks at .ok: a device that cannot be made current shows in the call that follows)
 
 // ---- the IPC transport: processes of one node whose ranks may SHARE a device (RCCL refuses two ranks on one device) ----------
 // A POSIX shared-memory segment carries a barrier and, per rank, the table of what it sends this round (destination, bytes);
@@ -148,7 +145,7 @@ namespace {
 // [i * kIpcMailbox, (i + 1) * kIpcMailbox) through the mailbox.
 int ipc_round(tbnav_comm* c, const std::vector<tbnav::P2P>& sends, const std::vector<tbnav::P2P>& recvs, hipStream_t st) {
   IpcState& I = *c->ipc;
-  DevGuard dg(c->device);
+  DeviceGuard dg(c->device);
   const int P = c->nranks, me = c->rank;
   int rc = TBNAV_OK;
   auto note = [&](bool ok, const char* what) { if (!ok && rc == TBNAV_OK) rc = I.fail(what); return ok; };
@@ -213,7 +210,7 @@ int ipc_round(tbnav_comm* c, const std::vector<tbnav::P2P>& sends, const std::ve
 // the mailboxes: allocate and export mine, map everybody else's (called once, by tbnav_comm_create)
 int ipc_open_mailboxes(tbnav_comm* c) {
   IpcState& I = *c->ipc;
-  DevGuard dg(c->device);
+  DeviceGuard dg(c->device);
   int rc = TBNAV_OK;
   if (hipMalloc((void**)&I.mailbox, kIpcMailbox) != hipSuccess) rc = I.fail("hipMalloc of the mailbox");
   if (rc == TBNAV_OK && hipIpcGetMemHandle(&I.sh->slot[c->rank].mailbox, I.mailbox) != hipSuccess) rc = I.fail("hipIpcGetMemHandle");
@@ -230,7 +227,7 @@ int ipc_open_mailboxes(tbnav_comm* c) {
 void ipc_close(tbnav_comm* c) {
   IpcState* I = c->ipc;
   if (!I) return;
-  DevGuard dg(c->device);
+  DeviceGuard dg(c->device);
   (void)hipDeviceSynchronize();
   for (int q = 0; q < c->nranks; ++q) if (q != c->rank && I->peer[q]) (void)hipIpcCloseMemHandle(I->peer[q]);
   if (I->mailbox) (void)hipFree(I->mailbox);
@@ -266,7 +263,7 @@ int comm_all_gather(int n, tbnav_comm* const* comms, const void* const* send, vo
     std::vector<P2P> sends{P2P{-1, const_cast<void*>(send[0]), bytes}}, recvs;
     for (int q = 0; q < c->nranks; ++q) if (q != c->rank) recvs.push_back(P2P{q, static_cast<char*>(recv[0]) + (size_t)q * bytes, bytes});
     char* own = static_cast<char*>(recv[0]) + (size_t)c->rank * bytes;
-    if (own != send[0]) { DevGuard dg(c->device); TBNAV_HIP(hipMemcpyAsync(own, send[0], bytes, hipMemcpyDeviceToDevice, streams[0])); }
+    if (own != send[0]) { DeviceGuard dg(c->device); TBNAV_HIP(hipMemcpyAsync(own, send[0], bytes, hipMemcpyDeviceToDevice, streams[0])); }
     return ipc_round(c, sends, recvs, streams[0]);
   }
   if (!g || g->use_rccl) {
@@ -274,7 +271,7 @@ int comm_all_gather(int n, tbnav_comm* const* comms, const void* const* send, vo
     if (!R.ok) return TBNAV_ERR_UNSUPPORTED;
     if (n > 1) TBNAV_NCCL(R.GroupStart());
     for (int r = 0; r < n; ++r) {
-      DevGuard dg(comms[r]->device);
+      DeviceGuard dg(comms[r]->device);
       const ncclResult_t e = R.AllGather(send[r], recv[r], bytes, ncclChar, comms[r]->nccl, streams[r]);
       if (e != ncclSuccess) { if (n > 1) (void)R.GroupEnd(); return rccl_fail(e, "ncclAllGather"); }
     }
@@ -282,9 +279,9 @@ int comm_all_gather(int n, tbnav_comm* const* comms, const void* const* send, vo
     return TBNAV_OK;
   }
   // copy transport: rank q's block goes to every rank's recv + q * bytes, on the RECEIVER's stream behind the sender's "ready"
-  for (int r = 0; r < n; ++r) { DevGuard dg(g->device[r]); TBNAV_HIP(hipEventRecord(g->ready[r], streams[r])); }
+  for (int r = 0; r < n; ++r) { DeviceGuard dg(g->device[r]); TBNAV_HIP(hipEventRecord(g->ready[r], streams[r])); }
   for (int d = 0; d < n; ++d) {
-    DevGuard dg(g->device[d]);
+    DeviceGuard dg(g->device[d]);
     for (int q = 0; q < n; ++q) {
       char* dst = static_cast<char*>(recv[d]) + (size_t)q * bytes;
       if (dst == send[q]) continue;  // in place
@@ -295,7 +292,7 @@ int comm_all_gather(int n, tbnav_comm* const* comms, const void* const* send, vo
   }
   // nobody rewrites its send buffer before every reader is through with it
   for (int r = 0; r < n; ++r) {
-    DevGuard dg(g->device[r]);
+    DeviceGuard dg(g->device[r]);
     for (int d = 0; d < n; ++d) if (d != r) TBNAV_HIP(hipStreamWaitEvent(streams[r], g->done[d], 0));
   }
   return TBNAV_OK;
@@ -319,7 +316,7 @@ int comm_exchange(int n, tbnav_comm* const* comms, const std::vector<P2P>* sends
     TBNAV_NCCL(R.GroupStart());
     ncclResult_t e = ncclSuccess;
     for (int r = 0; r < n && e == ncclSuccess; ++r) {
-      DevGuard dg(comms[r]->device);
+      DeviceGuard dg(comms[r]->device);
       for (const P2P& m : sends[r]) if (m.bytes && e == ncclSuccess) e = R.Send(m.ptr, m.bytes, ncclChar, m.peer, comms[r]->nccl, streams[r]);
       for (const P2P& m : recvs[r]) if (m.bytes && e == ncclSuccess) e = R.Recv(m.ptr, m.bytes, ncclChar, m.peer, comms[r]->nccl, streams[r]);
     }
@@ -329,9 +326,9 @@ int comm_exchange(int n, tbnav_comm* const* comms, const std::vector<P2P>* sends
     return TBNAV_OK;
   }
   // copy transport: message i from q to d = the i-th send of q naming d and the i-th receive of d naming q
-  for (int r = 0; r < n; ++r) { DevGuard dg(g->device[r]); TBNAV_HIP(hipEventRecord(g->ready[r], streams[r])); }
+  for (int r = 0; r < n; ++r) { DeviceGuard dg(g->device[r]); TBNAV_HIP(hipEventRecord(g->ready[r], streams[r])); }
   for (int d = 0; d < n; ++d) {
-    DevGuard dg(g->device[d]);
+    DeviceGuard dg(g->device[d]);
     for (int q = 0; q < n; ++q) {
       size_t is = 0;
       bool waited = q == d;
@@ -350,7 +347,7 @@ int comm_exchange(int n, tbnav_comm* const* comms, const std::vector<P2P>* sends
     TBNAV_HIP(hipEventRecord(g->done[d], streams[d]));
   }
   for (int r = 0; r < n; ++r) {
-    DevGuard dg(g->device[r]);
+    DeviceGuard dg(g->device[r]);
     for (int d = 0; d < n; ++d) if (d != r) TBNAV_HIP(hipStreamWaitEvent(streams[r], g->done[d], 0));
   }
   return TBNAV_OK;
@@ -360,7 +357,7 @@ bool comm_is_multiprocess(const tbnav_comm* c) { return c && !c->group && c->nra
 
 int comm_all_gather_host(tbnav_comm* c, const void* send_host, void* recv_host, size_t bytes) {
   if (!c || !send_host || !recv_host || bytes == 0 || (c->group && c->nranks != 1)) return TBNAV_ERR_INVALID_ARG;
-  DevGuard dg(c->device);
+  DeviceGuard dg(c->device);
   hipStream_t st = nullptr;
   char *d_send = nullptr, *d_recv = nullptr;
   auto done = [&](int code) { if (st) (void)hipStreamDestroy(st); (void)hipFree(d_send); (void)hipFree(d_recv); return code; };
@@ -403,10 +400,7 @@ int tbnav_comm_unique_id_ipc(uint8_t id[TBNAV_COMM_ID_BYTES]) {
 int tbnav_comm_create(const uint8_t id[TBNAV_COMM_ID_BYTES], int32_t nranks, int32_t rank, int32_t device, tbnav_comm** out) {
   if (!id || !out || nranks <= 0 || rank < 0 || rank >= nranks) return TBNAV_ERR_INVALID_ARG;
   *out = nullptr;
-  int ndev = 0;
-  { const hipError_t e = hipGetDeviceCount(&ndev); if (e != hipSuccess || ndev <= 0) return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__); }
-  if (device < 0) TBNAV_HIP(hipGetDevice(&device));
-  if (device >= ndev) return TBNAV_ERR_INVALID_ARG;
+  if (const int rc = tbnav::pick_device(device, &device)) return rc;
   if (std::memcmp(id, kIpcMagic, sizeof kIpcMagic) == 0) {  // an id drawn by tbnav_comm_unique_id_ipc: the IPC transport
     if (nranks > kIpcMaxRanks) return TBNAV_ERR_INVALID_ARG;
     char name[48] = "/tbnav_";
@@ -434,7 +428,7 @@ int tbnav_comm_create(const uint8_t id[TBNAV_COMM_ID_BYTES], int32_t nranks, int
   tbnav_comm* c = new (std::nothrow) tbnav_comm();
   if (!c) return TBNAV_ERR_INVALID_ARG;
   c->rank = rank; c->nranks = nranks; c->device = device;
-  DevGuard dg(device);
+  DeviceGuard dg(device);
   ncclUniqueId u;
   std::memcpy(&u, id, sizeof u);
   const ncclResult_t e = R.CommInitRank(&c->nccl, nranks, u, rank);
@@ -446,13 +440,12 @@ int tbnav_comm_create(const uint8_t id[TBNAV_COMM_ID_BYTES], int32_t nranks, int
 int tbnav_comm_create_local(int32_t n, const int32_t* devices, tbnav_comm** out) {
   if (n <= 0 || !out) return TBNAV_ERR_INVALID_ARG;
   for (int r = 0; r < n; ++r) out[r] = nullptr;
-  int ndev = 0;
-  { const hipError_t e = hipGetDeviceCount(&ndev); if (e != hipSuccess || ndev <= 0) return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__); }
   std::vector<int> dev(n);
   std::set<int> distinct;
   for (int r = 0; r < n; ++r) {
-    dev[r] = devices ? devices[r] : r;
-    if (dev[r] < 0 || dev[r] >= ndev) return TBNAV_ERR_INVALID_ARG;
+    // a list of ranks has no "current device": a negative index is refused as one past the count is
+    const int want = devices ? devices[r] : r;
+    if (const int rc = tbnav::pick_device(want < 0 ? INT_MAX : want, &dev[r])) return rc;
     distinct.insert(dev[r]);
   }
   LocalGroup* g = new (std::nothrow) LocalGroup();
@@ -468,7 +461,7 @@ int tbnav_comm_create_local(int32_t n, const int32_t* devices, tbnav_comm** out)
   } else {
     g->ready.resize(n); g->done.resize(n);
     for (int r = 0; r < n; ++r) {
-      DevGuard dg(dev[r]);
+      DeviceGuard dg(dev[r]);
       if (hipEventCreateWithFlags(&g->ready[r], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&g->done[r], hipEventDisableTiming) != hipSuccess) {
         delete g;  // (events created so far leak with a failing runtime: nothing else can be done about them here)
         return TBNAV_ERR_HIP;
@@ -486,11 +479,11 @@ int tbnav_comm_create_local(int32_t n, const int32_t* devices, tbnav_comm** out)
 
 void tbnav_comm_destroy(tbnav_comm* c) {
   if (!c) return;
-  if (c->nccl) { DevGuard dg(c->device); (void)rccl().CommDestroy(c->nccl); }
+  if (c->nccl) { DeviceGuard dg(c->device); (void)rccl().CommDestroy(c->nccl); }
   ipc_close(c);
   if (LocalGroup* g = c->group) {
     if (--g->alive == 0) {
-      for (size_t r = 0; r < g->ready.size(); ++r) { DevGuard dg(g->device[r]); (void)hipEventDestroy(g->ready[r]); (void)hipEventDestroy(g->done[r]); }
+      for (size_t r = 0; r < g->ready.size(); ++r) { DeviceGuard dg(g->device[r]); (void)hipEventDestroy(g->ready[r]); (void)hipEventDestroy(g->done[r]); }
       delete g;
     }
   }
@@ -507,7 +500,7 @@ int tbnav_comm_selftest(tbnav_comm* c, uint64_t bytes) {
   // a one-process group is driven as a whole from its member 0 — which this library never keeps a list of: only the multi-process
   // form and groups of one are tested here (the groups' exchanges are exercised through tbnav_mppi_group_* / tbnav_rbpf_group_*)
   if (c->group && P != 1) return TBNAV_ERR_UNSUPPORTED;
-  DevGuard dg(c->device);
+  DeviceGuard dg(c->device);
   hipStream_t st = nullptr;
   TBNAV_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   unsigned char *d_send = nullptr, *d_all = nullptr, *d_recv = nullptr;

@@ -526,15 +526,9 @@ int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
       !std::isfinite(params->max_corr_dist * params->max_corr_dist) || !(params->transform_eps >= 0.0) ||
       !(params->fitness_eps >= 0.0))
     return TBNAV_ERR_INVALID_ARG;
-  int ndev = 0;
-  {
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__);
-  }
-  int dev = params->device;
-  if (dev < 0) TBNAV_HIP(hipGetDevice(&dev));
-  if (dev >= ndev) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(dev);
+  int dev = 0;
+  if (const int rc = tbnav::pick_device(params->device, &dev)) return rc;
+  DeviceGuard guard(dev);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   tbnav_icp* h = new (std::nothrow) tbnav_icp();
   if (!h) return TBNAV_ERR_INVALID_ARG;
@@ -567,7 +561,7 @@ int tbnav_icp_create(const tbnav_icp_params* params, tbnav_icp** out) {
 void tbnav_icp_destroy(tbnav_icp* h) {
   if (!h) return;
   {
-    DevGuard guard(h->device);
+    DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->d_table);
     for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out}) b->release();
@@ -608,7 +602,7 @@ int tbnav_icp_get_metric(const tbnav_icp* h, int32_t* metric, int32_t* normal_wi
 
 int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* nxy, int32_t* has) {
   if (!h || !scan || !nxy || !has || n_beams <= 0 || n_beams > TBNAV_ICP_LINE_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
   int* d_has;
@@ -625,7 +619,7 @@ int tbnav_icp_normals(tbnav_icp* h, const float* scan, int32_t n_beams, float* n
 
 int tbnav_icp_cloud(tbnav_icp* h, const float* scan, int32_t n_beams, float* xy, int32_t* n_points) {
   if (!h || !scan || !xy || !n_points || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
   int* d_valid;
@@ -650,7 +644,7 @@ int tbnav_icp_match(tbnav_icp* h, const float* target_scan, const float* source_
                     double T_out[3], tbnav_icp_info* info) {
   if (!h || !target_scan || !source_scan || !T_init || !T_out || !info || !beams_ok(h, n_beams))
     return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
   if (int rc = h->d_scans.reserve(sizeof(float) * 2 * (size_t)n_beams)) return rc;
@@ -671,7 +665,7 @@ int tbnav_icp_step(tbnav_icp* h, const float* scan, int32_t n_beams, const doubl
                    tbnav_icp_info* info) {
   if (!h || !scan || !T_init || !T_out || !ok || !beams_ok(h, n_beams)) return TBNAV_ERR_INVALID_ARG;
   if (h->have_stored && n_beams != h->stored_beams) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (!h->have_stored) {  // cloud_alignment.cpp:64-68
     if (int rc = store_scan(h, nullptr, scan, n_beams)) return rc;
@@ -703,7 +697,7 @@ int tbnav_icp_step_batch(tbnav_icp* h, const float* scans, int32_t n_beams, int3
   if (!h || !scans || !T_init || !ok || !T_out || !beams_ok(h, n_beams) || n_scans <= 0)
     return TBNAV_ERR_INVALID_ARG;
   if (h->have_stored && n_beams != h->stored_beams) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
   if (int rc = h->d_scans.reserve(sizeof(float) * (size_t)n_beams * (size_t)n_scans)) return rc;

@@ -50,12 +50,7 @@ __device__ __forceinline__ bool cloud_point(float r, float2 cs, const IcpConst& 
   return true;
 }
 
-struct DevGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DevGuard(int d) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(d) == hipSuccess) ok = true; }
-  ~DevGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
-};
+using tbnav::DeviceGuard;
 
 // a device buffer that only grows and forgets its contents when it does: every user writes it before reading it
 struct DevBuf {

@@ -501,7 +501,7 @@ int search_one(tbnav_icp* h, const float* target_scan, const float* source_scan,
                uint32_t* wide_scores = nullptr) {
   if (!h || !target_scan || !source_scan || !T_init || !T_out || !info || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS)
     return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (int rc = ensure_table(h, n_beams)) return rc;
   if (int rc = h->d_scans.reserve(sizeof(float) * 2 * (size_t)n_beams)) return rc;
@@ -548,7 +548,7 @@ int tbnav_icp_search_wide_scores(tbnav_icp* h, const float* target_scan, const f
 
 int tbnav_icp_search_table(tbnav_icp* h, const float* scan, int32_t n_beams, uint8_t* table) {
   if (!h || !scan || !table || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS) return TBNAV_ERR_INVALID_ARG;
-  DevGuard guard(h->device);
+  DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   IcpSearch& S = h->search;
   const SearchConst sc = make_const(S.p);

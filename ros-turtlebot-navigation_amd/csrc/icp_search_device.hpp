@@ -1,6 +1,6 @@
 // icp_search_device.hpp — what the correlative search's kernels (icp_search.hip) and the kernel that measures the shape of
 // its score volume (icp_search_shape.hip) share: the by-value constants, the per-pair input and result, the cell of a
-// coordinate, the wave reductions and the scoring front (load_table, base_cells, slow_read: what icp_search_score and
+// coordinate, the names of the wave reductions they use (wave.hpp) and the scoring front (load_table, base_cells, slow_read: what icp_search_score and
 // icp_search_shape do before they score, and how either reads a table byte for a point of the slow list).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,26 +39,7 @@ __device__ __forceinline__ bool cell_of(double v, double E, double inv, int& c) 
   return true;
 }
 
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, kWave);
-  return v;
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
+using tbnav::wave_max_u64; using tbnav::wave_sum_u32; using tbnav::wave_sum_i64;   // (wave.hpp)
 
 // ---- the scoring front.  Dynamic LDS of a scoring kernel: the padded table, then uint16 cells[n_beams], the fast list
 // growing up from 0 and the slow list down from n_beams - 1 (compacted by atomics: a sum of integers has no order) ----

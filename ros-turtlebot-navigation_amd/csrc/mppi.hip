@@ -254,15 +254,8 @@ int tbnav_mppi_create(const tbnav_mppi_params* params, tbnav_mppi** out) {
     return TBNAV_ERR_INVALID_ARG;
   const int T = static_cast<int>(params->horizon / params->dt);  // mppi.cpp:47
   if (T <= 0) return TBNAV_ERR_INVALID_ARG;
-  int ndev = 0;
-  {
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__);
-  }
-  int dev = params->device;
-  if (dev < 0) TBNAV_HIP(hipGetDevice(&dev));
-  if (dev >= ndev) return TBNAV_ERR_INVALID_ARG;
+  int dev = 0;
+  if (const int rc = tbnav::pick_device(params->device, &dev)) return rc;
   DeviceGuard guard(dev);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
 

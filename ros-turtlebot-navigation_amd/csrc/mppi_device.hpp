@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "common.hpp"
+#include "philox.hpp"
 #include "mppi_plan.hpp"   // the sizes the kernels and the selection share, the lists of forms
 #include "tbnav_mppi.h"
 
@@ -273,27 +274,6 @@ __device__ __forceinline__ double terminal_loss(const RolloutArgs& a, double x, 
   return ((e0 * a.P1[0]) * e0 + (e1 * a.P1[1]) * e1) + (e2 * a.P1[2]) * e2;
 }
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ __forceinline__ void philox4x32_10(uint64_t ctr, uint64_t key, uint32_t (&out)[4]) {
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c[0]; out[1] = c[1]; out[2] = c[2]; out[3] = c[3];
-}
-
 // One (duL, duR) pair of the device noise source: Philox4x32-10 keyed by the seed, counter = tick*T*K + k*T + i, then
 // Box-Muller.  mppi_sample_noise fills the [T][K] arrays with it; the fused kernel can call it in place of the loads.
 struct RngArgs {  // base = tick * T * K_global + k0 * T
@@ -328,7 +308,7 @@ enum { kTagSeed = 0, kTagBase = 1, kTagKind = 2, kTagEpoch = 3, kTagWords = 4 };
 template <bool WIDE, class Rng /* RngArgs or RngRest: seed, base, sig_l, sig_r */>
 __device__ __forceinline__ void device_noise(const Rng& g, int T, int i, int k, double& dl, double& dr) {
   uint32_t r[4];
-  philox4x32_10(g.base + (uint64_t)k * T + i, g.seed, r);
+  tbnav::philox4x32_10(g.base + (uint64_t)k * T + i, g.seed, r);
   if constexpr (WIDE) {
     const uint64_t b1 = ((uint64_t)r[0] << 20) | (uint64_t)(r[1] >> 12);   // 52 bits
     const uint64_t b2 = ((uint64_t)r[2] << 20) | (uint64_t)(r[3] >> 12);

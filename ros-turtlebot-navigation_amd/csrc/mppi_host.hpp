@@ -124,14 +124,7 @@ struct tbnav_mppi_group {
 namespace tbnav_mh {
 using namespace tbnav_mk;
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) ok = true;
-  }
-  ~DeviceGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
-};
+using tbnav::DeviceGuard;
 
 // which ticks take the fused kernel (resident noise / noise drawn inside it): never a handle with a cost field
 inline bool fused_dev(const tbnav_mppi* h) { return h->fused_dev && !h->field_on; }

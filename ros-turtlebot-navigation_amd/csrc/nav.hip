@@ -145,7 +145,7 @@ __global__ void nav_field(const unsigned* __restrict__ d, int n, double resoluti
 }  // namespace tbnav_nk
 
 using namespace tbnav_nk;
-using tbnav_mh::DeviceGuard;
+using tbnav::DeviceGuard;
 
 // the rounds of a solve (the batches and the stop rule: nav_host.hpp, run_rounds) and what a finished solve leaves in the handle
 int tbnav_nk::relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy) {
@@ -209,14 +209,8 @@ int tbnav_nav_create(const tbnav_nav_params* params, tbnav_nav** out) {
   if (p.nx < 2 || p.nx > TBNAV_NAV_MAX_SIDE || p.ny < 2 || p.ny > TBNAV_NAV_MAX_SIDE || !std::isfinite(p.xmin) || !std::isfinite(p.ymin) ||
       !std::isfinite(p.resolution) || !(p.resolution > 0.0))
     return TBNAV_ERR_INVALID_ARG;
-  int ndev = 0;
-  {
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__);
-  }
-  int dev = p.device;
-  if (dev < 0) TBNAV_HIP(hipGetDevice(&dev));
-  if (dev >= ndev) return TBNAV_ERR_INVALID_ARG;
+  int dev = 0;
+  if (const int rc = tbnav::pick_device(p.device, &dev)) return rc;
   DeviceGuard guard(dev);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   tbnav_nav* h = new (std::nothrow) tbnav_nav();

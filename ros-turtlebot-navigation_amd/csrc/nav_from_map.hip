@@ -191,7 +191,7 @@ int tbnav_nav_profile_cost_from_rbpf(tbnav_nav* h, tbnav_rbpf* pf, int32_t parti
   if (rc != TBNAV_OK) return rc;
   if (h->device != pf->device) return TBNAV_ERR_UNSUPPORTED;
   const int n_tab = R * R + 1;
-  tbnav_rh::DeviceGuard guard(pf->device);
+  tbnav::DeviceGuard guard(pf->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   h->infl.resize((size_t)n_tab + 1);
   for (int c = 0; c <= n_tab; ++c) h->infl[(size_t)c] = infl_cost(infl_dist(c, n_tab, pf->p.resolution), r_robot, r_inflate, k);
@@ -232,7 +232,7 @@ int tbnav_mppi_set_cost_field_from_rbpf(tbnav_mppi* mppi, tbnav_rbpf* pf, int32_
   for (int c = 0; c <= n_tab; ++c) tab[(size_t)c] = infl_field(infl_dist(c, n_tab, pf->p.resolution), r_robot, r_inflate);
   float* d_tmp = nullptr;   // the values, then the table
   {
-    tbnav_rh::DeviceGuard guard(pf->device);
+    tbnav::DeviceGuard guard(pf->device);
     if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
     TBNAV_HIP(hipMalloc((void**)&d_tmp, sizeof(float) * (pf->G + tab.size())));
     hipError_t e = hipMemcpyAsync(d_tmp + pf->G, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice, pf->stream);
@@ -244,7 +244,7 @@ int tbnav_mppi_set_cost_field_from_rbpf(tbnav_mppi* mppi, tbnav_rbpf* pf, int32_
   // every value is 0 .. 1: tbnav_mppi.h F1's finiteness holds by construction
   float* d_new = nullptr;
   const int rc_s = tbnav_mh::field_stage_device(mppi, geom, d_tmp, pf->device, &d_new);
-  { tbnav_rh::DeviceGuard guard(pf->device); (void)hipFree(d_tmp); }
+  { tbnav::DeviceGuard guard(pf->device); (void)hipFree(d_tmp); }
   return rc_s != TBNAV_OK ? rc_s : tbnav_mh::field_commit(mppi, &geom, d_new);
 }
 

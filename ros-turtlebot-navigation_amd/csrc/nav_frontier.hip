@@ -304,7 +304,7 @@ int find(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbna
       h->p.resolution != pf->p.resolution || !h->cost_set)
     return TBNAV_ERR_INVALID_ARG;
   if (h->device != pf->device) return TBNAV_ERR_UNSUPPORTED;
-  tbnav_rh::DeviceGuard guard(pf->device);
+  tbnav::DeviceGuard guard(pf->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   int rc = ensure_buffers(h);
   if (rc != TBNAV_OK) return rc;
@@ -363,7 +363,7 @@ int find(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbna
 
 int download_labels(tbnav_nav* h) {
   if (h->label_host_valid) return TBNAV_OK;
-  tbnav_rh::DeviceGuard guard(h->device);
+  tbnav::DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   h->label_host.resize((size_t)h->n);
   TBNAV_HIP(hipMemcpy(h->label_host.data(), h->d_label, sizeof(unsigned) * (size_t)h->n, hipMemcpyDeviceToHost));
@@ -478,7 +478,7 @@ int tbnav_nav_frontier_list(tbnav_nav* h, tbnav_nav_frontier* out, int32_t cap, 
 int tbnav_nav_solve_goals(tbnav_nav* h, const int32_t* cells, int32_t n) {
   if (!h || !cells || n < 1 || !h->cost_set) return TBNAV_ERR_INVALID_ARG;
   for (int i = 0; i < n; ++i) if (!in_grid(h, cells[2 * i], cells[2 * i + 1])) return TBNAV_ERR_INVALID_ARG;
-  tbnav_rh::DeviceGuard guard(h->device);
+  tbnav::DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   if (!h->cost_host_valid) {   // a grid set on the device: fetched to look at the goals' cells
     h->cost.resize((size_t)h->n);
@@ -501,7 +501,7 @@ int tbnav_nav_solve_goals(tbnav_nav* h, const int32_t* cells, int32_t n) {
 int tbnav_nav_solve_frontiers(tbnav_nav* h) {
   if (!h || !h->finfo.found || h->found_cost_epoch != h->cost_epoch || h->found_visited_epoch != h->visited_epoch) return TBNAV_ERR_INVALID_ARG;
   if (h->finfo.seed_cells == 0) return TBNAV_ERR_UNSUPPORTED;   // nothing left to explore
-  tbnav_rh::DeviceGuard guard(h->device);
+  tbnav::DeviceGuard guard(h->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
   return solve_from_goals(h, 0, -1, -1);
 }

@@ -809,15 +809,8 @@ int create_impl(const tbnav_rbpf_params* P, uint64_t max_pool_bytes, tbnav_rbpf*
   if (P->num_particles > (1 << 20)) return TBNAV_ERR_UNSUPPORTED;
   const int radius = (int)static_cast<unsigned int>(std::ceil((10.0 - 0.0) / P->resolution));         // cell_radius_, grid_mapper.cpp:50
   if (radius > 254) return TBNAV_ERR_UNSUPPORTED;  // row-pass distances are stored as u8 (and radius^2 must fit the u16 code)
-  int ndev = 0;
-  {
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      return tbnav::hip_fail(e == hipSuccess ? hipErrorNoDevice : e, "hipGetDeviceCount", __FILE__, __LINE__);
-  }
-  int dev = P->device;
-  if (dev < 0) TBNAV_HIP(hipGetDevice(&dev));
-  if (dev >= ndev) return TBNAV_ERR_INVALID_ARG;
+  int dev = 0;
+  if (const int rc = tbnav::pick_device(P->device, &dev)) return rc;
   DeviceGuard guard(dev);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
 

@@ -1,5 +1,5 @@
 // rbpf_device.hpp — what the RBPF kernel files and the host side (rbpf_host.hpp + rbpf*.hip: handle, launches, C-ABI) share: the launch-argument
-// structs, the tiled copy-on-write map's accessors, world -> cell, wave reductions, the exact-transform / resampling / migration
+// structs, the tiled copy-on-write map's accessors, world -> cell, the names of the wave reductions it uses (wave.hpp), the exact-transform / resampling / migration
 // helpers and the declarations of every kernel.  What only one family needs lives in that family's file: the distance lookups
 // in rbpf_lookup.hpp, the likelihoods in rbpf_propose.hip, rays and add_repeated in rbpf_raycast.hip; the normalise / selection body, which runs in
 // a kernel of its own AND as workgroup 0 of the map update, in rbpf_normalize.hpp.  Kernels are defined in their family's file
@@ -258,26 +258,10 @@ __device__ __forceinline__ double pdf_normal(double a, double b) {
   return sqrt_inv * exp(var);
 }
 
-// Wave-wide reductions of doubles without LDS round trips (__shfl_xor is ds_bpermute: six dependent LDS-latency steps per
-// reduction, two permutes each for a double): an inclusive scan inside each row of 16 lanes by DPP shifts, then the row
-// totals carried down the rows (row_bcast:15 / :31); lane 63 holds the result, which is handed to every lane.  A fixed
-// order of operations, the same on every call (the proposal kernel's sums and products are compared with the oracle at
-// 1e-9, not bit for bit).
-#define TBNAV_DPP_D(v, ident, ctrl, rmask)                                                                                      \
-  __hiloint2double(__builtin_amdgcn_update_dpp(__double2hiint(ident), __double2hiint(v), ctrl, rmask, 0xf, false),              \
-                   __builtin_amdgcn_update_dpp(__double2loint(ident), __double2loint(v), ctrl, rmask, 0xf, false))
-template <class Op> __device__ __forceinline__ double wave_reduce_dpp_d(double v, double ident, Op op) {
-  v = op(v, TBNAV_DPP_D(v, ident, 0x111, 0xf));  // row_shr:1
-  v = op(v, TBNAV_DPP_D(v, ident, 0x112, 0xf));  // row_shr:2
-  v = op(v, TBNAV_DPP_D(v, ident, 0x114, 0xf));  // row_shr:4
-  v = op(v, TBNAV_DPP_D(v, ident, 0x118, 0xf));  // row_shr:8
-  v = op(v, TBNAV_DPP_D(v, ident, 0x142, 0xa));  // row_bcast:15 into rows 1, 3
-  v = op(v, TBNAV_DPP_D(v, ident, 0x143, 0xc));  // row_bcast:31 into rows 2, 3
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
-}
-__device__ __forceinline__ double wave_max_d(double v) { return wave_reduce_dpp_d(v, -1.0e300, [](double a, double b) { return fmax(a, b); }); }
-__device__ __forceinline__ double wave_sum_d(double v) { return wave_reduce_dpp_d(v, 0.0, [](double a, double b) { return a + b; }); }
-__device__ __forceinline__ double wave_prod(double v) { return wave_reduce_dpp_d(v, 1.0, [](double a, double b) { return a * b; }); }
+// the wave-wide reductions the filter's kernels use (wave.hpp)
+using tbnav::wave_sum_i; using tbnav::wave_min_i;                                   // __shfl_xor butterflies
+using tbnav::wave_max_d; using tbnav::wave_sum_d; using tbnav::wave_prod;           // doubles on the DPP network
+using tbnav::wave_min_dpp; using tbnav::wave_max_dpp; using tbnav::wave_sum_dpp;    // ints on the DPP network (the map update)
 // A value every lane of the workgroup holds alike (the particle's pose, what is derived from it): into scalar registers — the
 // proposal kernel lives at its 128-VGPR ceiling, and these are a dozen doubles that stay live across its phases.
 __device__ __forceinline__ double uniform_d(double v) {
@@ -294,21 +278,6 @@ constexpr int kMatchThreads = 6 * kWave;
 // ---- map update: what the host needs of it (the kernels and their device helpers are in rbpf_raycast.hip) ----
 struct OccLog { int* ev; int* count; int cap; };
 constexpr int kMapTilesMax = 64;  // map tiles a scan's bounding box can span: (ceil(175 / 32) + 1)^2 = 49 for tile_cap 30000
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off, 64); v = o < v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
-  return v;
-}
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 constexpr int kBoxSideMax = 176;  // rows a scan's bounding box can have (tile_cap <= 30000 -> side <= 173)
 // ---- normalise / Neff / low-variance selection (sequential order = the reference's) ---------------
 struct NormOut { double sum_w, sq_sum; int neff, resampled; };

@@ -193,12 +193,7 @@ struct tbnav_rbpf_group {
 
 namespace tbnav_rh {
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(dev) == hipSuccess) ok = true; }
-  ~DeviceGuard() { if (ok && prev >= 0) (void)hipSetDevice(prev); }
-};
+using tbnav::DeviceGuard;
 
 // state layout helpers: the kernels take pose / prev_pose / weight pointers with [N][3] / [N] strides,
 // so the 7-double record is split into three arrays inside one allocation.

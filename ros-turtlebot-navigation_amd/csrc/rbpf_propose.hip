@@ -3,26 +3,15 @@
 // one-pose likelihood (bmapping::GridMapper::likelihoodFieldModel), the per-particle scan matcher (option N1) and
 // rbpf_propose itself — one workgroup per particle: k samples, one lookup per beam at their centre, stable-beam collapse,
 // Gaussian proposal, new pose, weight *= eta.  Where a lookup gets its distance code from: rbpf_lookup.hpp.
+#include "kernel_trace.hpp"
+#include "philox.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_lookup.hpp"
 
 namespace tbnav_rk {
 
-// Development build (-DTBNAV_PHASE_PROF): per-phase wall-clock stamps inside the proposal and raycast kernels, summed
-// over workgroups and printed by tbnav_rbpf_destroy.  The stamps add barriers and global atomics — the kernels
-// run measurably slower with them; the numbers are for comparing phases, not for the bench.
-#ifdef TBNAV_PHASE_PROF
-static __device__ unsigned long long g_trace_p[2][4][16];  // [which][wave][stamp] of TWO proposal workgroups (blockIdx.x == 96, 100: XCCs 0 and 4)
-#define TRACE_P(i) do { if ((blockIdx.x == 96 || blockIdx.x == 100) && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < 4) g_trace_p[blockIdx.x == 100][threadIdx.x >> 6][i] = wall_clock64(); } while (0)
-static __device__ unsigned long long g_wgp[4096][3];   // [workgroup] entry, exit (10 ns ticks), XCC_ID << 32 | HW_ID of the LAST proposal launch
-#define WGP_IN() do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_wgp[blockIdx.x][0] = wall_clock64(); \
-  g_wgp[blockIdx.x][2] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned int)__builtin_amdgcn_s_getreg(63492); } } while (0)
-#define WGP_OUT() do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_wgp[blockIdx.x][1] = wall_clock64(); } while (0)
-#else
-#define TRACE_P(i)
-#define WGP_IN()
-#define WGP_OUT()
-#endif
+// (development tracer, kernel_trace.hpp: workgroups 96 and 100 run on XCCs 0 and 4)
+TBNAV_TRACE_ARRAYS(propose, 4, 96, 100)
 
 // Mixture term of one beam as a function of the distance code it lands on (grid_mapper.cpp:119-121).
 __device__ __forceinline__ double beam_mixture(const ScanC& c, uint16_t code) {
@@ -112,26 +101,13 @@ __device__ inline void llt3(const double A[3][3], double L[3][3]) {
 // Philox4x32-10 keyed by the handle's seed, counter = scan_index * 2^40 + pair index; each counter value
 // yields one Box-Muller pair.  Replaces the host's mt19937_64 draws (particle_filter.cpp:25-34) when
 // reproducibility against the CPU path is not needed; same layout as the host stream.
-__device__ __forceinline__ void philox4x32_10(unsigned long long ctr, unsigned long long key, unsigned int (&out)[4]) {
-  unsigned int c0 = (unsigned int)ctr, c1 = (unsigned int)(ctr >> 32), c2 = 0u, c3 = 0u;
-  unsigned int k0 = (unsigned int)key, k1 = (unsigned int)(key >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned int)p1;
-    const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned int)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 // Box-Muller pair number P of scan `scan` under `seed`: normals 2P and 2P + 1 of the scan's stream (fp64: 53-bit uniforms, log, sqrt,
 // sincospi).  What rbpf_sample_normals stores and what rbpf_propose draws in place: one definition.
 // The uniforms are in (0, 1], not (0, 1): from 2^52 on a double cannot hold the half, the sum rounds to even and the top value gives
 // exactly 1.0 — log 0, rad = -0 and a pair of zeros there; no NaN or infinity for any input (tests/test_noise_restatement.py).
 __device__ __forceinline__ void normal_pair(unsigned long long seed, unsigned long long scan, size_t P, double& a_out, double& b_out) {
   unsigned int r[4];
-  philox4x32_10((scan << 40) + P, seed, r);
+  tbnav::philox4x32_10((scan << 40) + P, seed, r);
   const unsigned long long a = ((unsigned long long)r[0] << 32) | r[1], b = ((unsigned long long)r[2] << 32) | r[3];
   const double u1 = ((double)(a >> 11) + 0.5) * 0x1.0p-53, u2 = ((double)(b >> 11) + 0.5) * 0x1.0p-53;
   const double rad = sqrt(-2.0 * log(u1));
@@ -434,7 +410,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
   if (tid == 0) { sh_def[0] = 0; sh_def[1] = 0; }
 
   // ---- 0. loads, the centre of the samples, the LDS slice of the occupancy bitmap
-  WGP_IN();
+  WG_IN(propose);
   const double th0v = pose[p * 3 + 0], x0v = pose[p * 3 + 1], y0v = pose[p * 3 + 2];
   const double pv0 = prev_pose[p * 3 + 0], pv1 = prev_pose[p * 3 + 1], pv2 = prev_pose[p * 3 + 2];
   // (requested WITH the pose, used much later: the first 64 samples' normals by wave 0, the new pose's three normals and the
@@ -473,7 +449,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
       if (l0 + 1 < n_loc) { if (l0 + 1 < 3 * k) smp[l0 + 1] = b; else sh_zz[l0 + 1 - 3 * k] = b; }
     }
   }
-  TRACE_P(0);
+  TRACE(propose, 0);
   const double th0 = uniform_d(th0v), x0 = uniform_d(x0v), y0 = uniform_d(y0v);
   double mu0[3];
   if (!c.icp_ok) {
@@ -542,7 +518,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
   // (the normals have arrived with the pose: parked in the samples' own LDS slots until wave 0 turns them into samples, so that
   //  they do not hold six registers through the staging)
   if (!dn && c.icp_ok && tid < k) { smp[3 * tid + 0] = zj0; smp[3 * tid + 1] = zj1; smp[3 * tid + 2] = zj2; }
-  TRACE_P(1);
+  TRACE(propose, 1);
   bool staged = false;
   if (ds.mode == 2 && occ_half > 0 && nocc) {
     // query mode: stage the bitmap rows/columns within occ_half cells of the sensor in LDS — every lookup of this
@@ -566,7 +542,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
             st_ids[q] = ds.occ.tab[(tr0 + qi) * ds.occ.TW + tc0 + (q - qi * ntc)];
           }
         __syncthreads();
-        TRACE_P(2);
+        TRACE(propose, 2);
         for (int r = tid; r <= R1 - R0; r += NT) {
           const int row = R0 + r;
           const unsigned int* ids = whole_table ? st_ids + (row >> kTSh) * ds.occ.TW + tc0 : st_ids + ((row >> kTSh) - tr0) * ntc;
@@ -593,7 +569,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     staged = true;
   }
   if (!staged) { if (barrier_or_leave(late_beams())) return; }  // lbeams / sh_mix / sh_def / sh_zz
-  TRACE_P(3);
+  TRACE(propose, 3);
   if (dn && c.icp_ok) { zz0 = sh_zz[0]; zz1 = sh_zz[1]; zz2 = sh_zz[2]; }
   zz0 = uniform_d(zz0); zz1 = uniform_d(zz1); zz2 = uniform_d(zz2); w_old = uniform_d(w_old);  // (arrived long ago; wave-uniform: scalar registers from here on)
 
@@ -652,7 +628,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     }
     if (deferred) atomicAdd(&sh_def[0], 1);
   }
-  TRACE_P(4);
+  TRACE(propose, 4);
   __syncthreads();
   // ---- 2. the lookups the 7 x 7 look did not settle (a beam that ends more than three cells from every obstacle the slice
   //      shows: the first scans of a map, a doorway): the full search, all threads, one inlined copy
@@ -666,7 +642,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     }
     __syncthreads();
   }
-  TRACE_P(5);
+  TRACE(propose, 5);
   __shared__ double sh_pst[kPW];
   if (!c.icp_ok) {
     // weight *= likelihoodFieldModel(scan, T(new pose)) (:171-175): the product per lane, per wave, then over the waves in wave
@@ -697,7 +673,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
       tr.weight_raw[p] = w;
       sens[p * 4 + 0] = Tc[0]; sens[p * 4 + 1] = Tc[1]; sens[p * 4 + 2] = Tc[2]; sens[p * 4 + 3] = Tc[3];  // the sensor transform of the new pose, for the raycast kernel
     }
-    WGP_OUT();
+    WG_OUT(propose);
     return;
   }
   // ---- 3. which beams are stable, the product of their terms, the others listed: every wave over ITS contiguous range of
@@ -731,7 +707,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     if (lane == 0) { sh_cnt[wid] = n; sh_pst[wid] = pst; }
   }
   __syncthreads();
-  TRACE_P(6);
+  TRACE(propose, 6);
   // ---- 4. scan likelihood of every sample: (product over the stable beams) * (its own terms of the unstable ones)
   double* wj = stf;  // [k] likelihoods.at(j) (the sensor transforms are dead once the pairs are through)
   {
@@ -813,7 +789,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     }
   }
   __syncthreads();
-  TRACE_P(7);
+  TRACE(propose, 7);
   // ---- 5. Gaussian proposal (:522-599), new pose (:214-231): wave 0 alone.  The weighted sums are lane-strided partial sums
   //      closed with a butterfly — a fixed order, not the reference's left-to-right one: the results agree to rounding
   //      (asserted at 1e-10 against the oracle) — and every lane of the wave holds them, so nothing goes through LDS again.
@@ -845,7 +821,7 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     for (int r = 0; r < 3; ++r) for (int q = r; q < 3; ++q) su[o++] += (d[r] * d[q]) * w;
   }
   for (int o = 0; o < 6; ++o) su[o] = wave_sum_d(su[o]);
-  TRACE_P(8);
+  TRACE(propose, 8);
   if (lane == 0) {
     double sigma[3][3];
     {
@@ -867,8 +843,8 @@ __global__ __launch_bounds__(NT, TBNAV_PROPOSE_WAVES) void rbpf_propose(ScanC c,
     sensor_transform(c, np[0], np[1], np[2], Ts);
     for (int q = 0; q < 4; ++q) sens[p * 4 + q] = Ts[q];
   }
-  TRACE_P(9);
-  WGP_OUT();
+  TRACE(propose, 9);
+  WG_OUT(propose);
 }
 #define TBNAV_X(NT_, DN_) template __global__ void rbpf_propose<NT_, DN_>(ScanC, const double2* __restrict__, const uint16_t* __restrict__, TilePool, MapT, const int* __restrict__, const int* __restrict__, int, int, int, int, const int* __restrict__, const int4* __restrict__, const double* __restrict__, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, Trace, double* __restrict__, int* __restrict__, const int* __restrict__, const double* __restrict__, NoiseSrc, int* __restrict__);
 TBNAV_PROPOSE_FORMS(TBNAV_X)
@@ -877,71 +853,11 @@ TBNAV_PROPOSE_FORMS(TBNAV_X)
 }  // namespace tbnav_rk
 
 #ifdef TBNAV_PHASE_PROF
-#include <cstdio>
-#include <map>
-#include <vector>
 namespace tbnav_rk {
 void rbpf_prof_print_propose() {
-    unsigned long long tp[2][4][16];
-    if (hipMemcpyFromSymbol(tp, HIP_SYMBOL(g_trace_p), sizeof(tp)) == hipSuccess && tp[0][0][0]) {
-      for (int g = 0; g < 2; ++g) {
-        std::fprintf(stderr, "[rbpf_propose trace of workgroup %d, us; columns: loads requested, centre's sensor transform known, table ids in LDS (barrier), "
-                             "slice staged (barrier), step 1 done (wave 0: samples + odometry likelihoods; others: centre lookups), barrier (+ deferred searches), "
-                             "stable product + unstable list (barrier), pairs / products / weights (barrier), sums, end]\n", g ? 100 : 96);
-        unsigned long long t0 = ~0ull;
-        for (int w = 0; w < 4; ++w) if (tp[g][w][0] && tp[g][w][0] < t0) t0 = tp[g][w][0];
-        for (int w = 0; w < 4; ++w) {
-          std::fprintf(stderr, "  wave %d:", w);
-          for (int i = 0; i < 10; ++i) std::fprintf(stderr, " %6.2f", tp[g][w][i] ? (double)(tp[g][w][i] - t0) * 0.01 : -1.0);
-          std::fprintf(stderr, "\n");
-        }
-      }
-    }
-    {
-      static unsigned long long wgp[4096][3];
-      if (hipMemcpyFromSymbol(wgp, HIP_SYMBOL(g_wgp), sizeof(wgp)) == hipSuccess && wgp[1][0]) {
-        int n = 0;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (int i = 0; i < 4096; ++i) if (wgp[i][0] && wgp[i][1]) { ++n; t0 = std::min(t0, wgp[i][0]); t1 = std::max(t1, wgp[i][1]); }
-        const int nb = 16;
-        const double span = (double)(t1 - t0);
-        int active[nb] = {0}, starts[nb] = {0};
-        double dur[nb] = {0};
-        for (int i = 0; i < 4096; ++i) if (wgp[i][0] && wgp[i][1]) {
-          const int bs = std::min(nb - 1, (int)((double)(wgp[i][0] - t0) / span * nb));
-          ++starts[bs]; dur[bs] += (double)(wgp[i][1] - wgp[i][0]) * 0.01;
-          for (int b = 0; b < nb; ++b) { const double tm = t0 + (b + 0.5) * span / nb; if ((double)wgp[i][0] <= tm && tm < (double)wgp[i][1]) ++active[b]; }
-        }
-        std::fprintf(stderr, "[rbpf_propose workgroups of the last launch] %d recorded, first entry to last exit %.2f us; bins of %.2f us\n  resident at mid-bin:", n, span * 0.01, span * 0.01 / nb);
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5d", active[b]);
-        std::fprintf(stderr, "\n  entered in bin:     ");
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5d", starts[b]);
-        std::fprintf(stderr, "\n  mean residence (us):");
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5.1f", starts[b] ? dur[b] / starts[b] : 0.0);
-        // by XCC and by CU: is a slow workgroup's CU slow as a whole?
-        std::map<unsigned long long, std::vector<double>> by_cu;
-        double xs[16] = {0}; int xn[16] = {0};
-        for (int i = 0; i < 4096; ++i) if (wgp[i][0] && wgp[i][1]) {
-          const unsigned int hw = (unsigned int)wgp[i][2], xcc = (unsigned int)(wgp[i][2] >> 32) & 0xF;
-          const double d = (double)(wgp[i][1] - wgp[i][0]) * 0.01;
-          by_cu[((unsigned long long)xcc << 16) | (hw & 0xFF00u)].push_back(d);
-          xs[xcc] += d; ++xn[xcc];
-        }
-        std::fprintf(stderr, "\n  mean residence by XCC:");
-        for (int x = 0; x < 16; ++x) if (xn[x]) std::fprintf(stderr, " %.1f", xs[x] / xn[x]);
-        double spread_in = 0.0; int ncu = 0; double cu_min = 1e9, cu_max = 0; int n3 = 0, n4 = 0; double d3 = 0, d4 = 0;
-        for (auto& kv : by_cu) {
-          double lo = 1e9, hi = 0, sum = 0;
-          for (double d : kv.second) { lo = std::min(lo, d); hi = std::max(hi, d); sum += d; }
-          spread_in += hi - lo; ++ncu;
-          const double mean = sum / kv.second.size();
-          cu_min = std::min(cu_min, mean); cu_max = std::max(cu_max, mean);
-          if (kv.second.size() <= 3) { ++n3; d3 += mean; } else { ++n4; d4 += mean; }
-        }
-        std::fprintf(stderr, "\n  %d CUs; mean (max - min) inside a CU %.1f us; CU means from %.1f to %.1f us; CUs with <= 3 workgroups: %d, mean %.1f us; with 4+: %d, mean %.1f us\n",
-                     ncu, spread_in / std::max(1, ncu), cu_min, cu_max, n3, n3 ? d3 / n3 : 0.0, n4, n4 ? d4 / n4 : 0.0);
-      }
-    }
+  TBNAV_TRACE_PRINT(propose, "rbpf_propose", 10, "loads requested, centre's sensor transform known, table ids in LDS (barrier), "
+                    "slice staged (barrier), step 1 done (wave 0: samples + odometry likelihoods; others: centre lookups), barrier (+ deferred searches), "
+                    "stable product + unstable list (barrier), pairs / products / weights (barrier), sums, end");
 }
 }  // namespace tbnav_rk
 #endif

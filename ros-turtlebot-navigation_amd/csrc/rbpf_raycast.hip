@@ -2,6 +2,7 @@
 // kernel rbpf_raycast_box (default: LDS counters over the scan's bounding box, end-point cells replayed in beam order, the
 // weights' normalise / selection riding along as workgroup 0) and the beam-ordered rbpf_raycast (scans the box kernel cannot
 // hold; the reference-field mode, whose occupied-set log it writes).  Bit-identical maps.
+#include "kernel_trace.hpp"
 #include "rbpf_device.hpp"
 #include "rbpf_normalize.hpp"
 
@@ -80,21 +81,6 @@ __device__ __forceinline__ bool add_log_odds(const TilePool& P, unsigned int id,
   return was != now;
 }
 
-// Integer wave reductions without LDS round trips: an inclusive scan inside each row of 16 lanes by DPP shifts, then the row
-// totals broadcast down the rows (row_bcast:15 / :31); lane 63 holds the result.  (__shfl_xor is ds_bpermute: six
-// dependent LDS-latency steps per reduction.)
-template <class Op> __device__ __forceinline__ int wave_reduce_dpp(int v, int ident, Op op) {
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x111, 0xf, 0xf, false));  // row_shr:1
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x112, 0xf, 0xf, false));  // row_shr:2
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x114, 0xf, 0xf, false));  // row_shr:4
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x118, 0xf, 0xf, false));  // row_shr:8
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x142, 0xa, 0xf, false));  // row_bcast:15 into rows 1, 3
-  v = op(v, __builtin_amdgcn_update_dpp(ident, v, 0x143, 0xc, 0xf, false));  // row_bcast:31 into rows 2, 3
-  return __builtin_amdgcn_readlane(v, 63);
-}
-__device__ __forceinline__ int wave_min_dpp(int v) { return wave_reduce_dpp(v, 0x7FFFFFFF, [](int a, int b) { return a < b ? a : b; }); }
-__device__ __forceinline__ int wave_max_dpp(int v) { return wave_reduce_dpp(v, (int)0x80000000, [](int a, int b) { return a > b ? a : b; }); }
-__device__ __forceinline__ int wave_sum_dpp(int v) { return wave_reduce_dpp(v, 0, [](int a, int b) { return a + b; }); }
 // n times  x = fl(x + d)  — the updates one cell takes from n beams (grid_mapper.cpp:438-477 adds the same log-odds once per beam) —
 // bit for bit WITHOUT the chain of n dependent adds (13 ns each for one lane: the robot's own cell takes one per beam).  While x
 // stays in one binade it is m * u (u = ulp(x), m a 53-bit integer) and d = kd * ud with ud = u / 2^sh: x + d = (m + q) u + rem ud
@@ -197,26 +183,9 @@ __device__ __forceinline__ bool on_ray_packed(int x0, int y0, int x1, int y1, in
 // vector units are busy 29 us of a 42 us launch (SQ_ACTIVE_INST_VALU); memory traffic is the distinct cells once each way.
 // LDS: tile u32[tile_cap] (rows padded to an even number of columns: pair i = words 2i, 2i+1) |
 // ev u16[Bv][8, or 4 in the four-per-CU form] (slot o's first 8 bytes double as its replayed value) | hot-cell values f64[64] | exy i32[Bv] | ecnt u16[Bv]
-#ifdef TBNAV_PHASE_PROF
-static __device__ unsigned long long g_phase_w[16];
-#endif
-#if defined(TBNAV_PHASE_PROF) && !defined(TBNAV_TRACE_ONLY)
-#define PHASE_STAMP_W(i) do { __syncthreads(); if (threadIdx.x == 0) { const unsigned long long now_ = wall_clock64(); atomicAdd(&g_phase_w[i], now_ - t_prev_); t_prev_ = now_; } } while (0)
-#else
-#define PHASE_STAMP_W(i)
-#endif
-#ifdef TBNAV_PHASE_PROF
-static __device__ unsigned long long g_trace[2][16][16];  // [which][wave][stamp] of TWO workgroups (blockIdx.x == 100: first round of residents; 900: second): 10 ns ticks
-#define TRACE_W(i) do { if ((blockIdx.x == 100 || blockIdx.x == 900) && (threadIdx.x & 63) == 0) g_trace[blockIdx.x == 900][threadIdx.x >> 6][i] = wall_clock64(); } while (0)
-static __device__ unsigned long long g_wg[4096][3];    // [workgroup] entry, exit (10 ns ticks), XCC_ID << 32 | HW_ID — of the LAST launch
-#define WG_IN() do { if (threadIdx.x == 0 && blockIdx.x < 4096) { g_wg[blockIdx.x][0] = wall_clock64(); \
-  g_wg[blockIdx.x][2] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned int)__builtin_amdgcn_s_getreg(63492); } } while (0)
-#define WG_OUT() do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_wg[blockIdx.x][1] = wall_clock64(); } while (0)
-#else
-#define WG_IN()
-#define WG_OUT()
-#define TRACE_W(i)
-#endif
+// (development tracer, kernel_trace.hpp: workgroup 100 is of the first round of residents, 900 of the second)
+TBNAV_TRACE_ARRAYS(raycast_box, 16, 100, 900)
+TBNAV_PHASE_SUMS(raycast_box)
 __global__ __launch_bounds__(kWave) void rbpf_raycast(ScanC c, TilePool P, MapT M, const double2* __restrict__ beams,
                                                      const double* __restrict__ pose, int* __restrict__ trow_occ,
                                                      int* __restrict__ n_occ, int* __restrict__ err, OccLog log,
@@ -429,13 +398,11 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
   __shared__ int robot_cnt;             // beams with a free cell (each adds l_free to the robot's cell once)
   constexpr int nthr = NT, nw = NT / kWave;
   const int p = c.p0 + blockIdx.x - (nz.N > 0 ? 1 : 0), tid_k = threadIdx.x, tid = tid_k, lane = tid & (kWave - 1), wid = tid / kWave;
-#ifdef TBNAV_PHASE_PROF
-  unsigned long long t_prev_ = wall_clock64();
-#endif
+  PHASE_START();
   unsigned int* tab = M.table + (size_t)p * M.TT;
   unsigned int* shed = M.shed + (size_t)p * M.TT;
-  TRACE_W(0);
-  WG_IN();
+  TRACE(raycast_box, 0);
+  WG_IN(raycast_box);
   if (wid == 0) {
     const double x = pose[p * 3 + 1], y = pose[p * 3 + 2];
     int rx0 = 0, ry0 = 0;
@@ -463,7 +430,7 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
     for (int t = tid - kWave; t < kBoxSideMax / kTS + 2; t += nthr - kWave) rc_delta[t] = 0;
   }
   __syncthreads();
-  TRACE_W(1);
+  TRACE(raycast_box, 1);
   // (workgroup-uniform values read from LDS are moved to scalar registers: the kernel has 64 VGPRs to live in)
   auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
   const int rx = uni(srx), ry = uni(sry);
@@ -489,7 +456,7 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
     //  two dependent loads held the whole workgroup up: 1-3 us per particle once the chip is loaded.)
   }
   __syncthreads();
-  TRACE_W(2);
+  TRACE(raycast_box, 2);
   if (bad) { if (tid == 0) atomicOr(&err[0], 1); return; }
   const int minx = uni(bx0), maxx = uni(bx1), maxy = uni(by1);
   const int miny = uni(by0) & ~1;                                   // the box starts on an even column and is an even number of
@@ -578,12 +545,12 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
         record((int)(((old ? old : mine) >> 16) & 0x7FFFu), (b << 1) | 1);
       }
     }
-    TRACE_W(3);
+    TRACE(raycast_box, 3);
     __syncthreads();
-    PHASE_STAMP_W(0);
-    TRACE_W(4);
+    PHASE_STAMP(raycast_box, 0);
+    TRACE(raycast_box, 4);
     // 1. the walk
-    TRACE_W(5);
+    TRACE(raycast_box, 5);
     if (x0 == minx && tq >= 0 && tq < mtn) {
       const unsigned int id = mt_id[tq];
       const int rf = id ? P.ref[id] : 0;
@@ -685,10 +652,10 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
         else atomicAdd(&tile[t], (unsigned int)n_first);
       }
     }
-    TRACE_W(6);
+    TRACE(raycast_box, 6);
     __syncthreads();  // every event is recorded
-    TRACE_W(7);
-    PHASE_STAMP_W(1);
+    TRACE(raycast_box, 7);
+    PHASE_STAMP(raycast_box, 1);
     // 2. requests and marks in one pass.  The band as PAIRS of cells (16 bytes of a map tile's row, two tile words), a thread's
     //    work ITEM a column of kSl pairs: rows j * kSl .. + kSl - 1 of the band, pair column pc — consecutive lanes take consecutive
     //    pair columns, so a wave's request is whole cache lines, and down the column the address moves by one tile row (256 bytes):
@@ -747,10 +714,10 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
       if (robot_cell) ecnt[o] = (unsigned short)(kEv + 1);
       if (robot_cell || ecnt[o] > kEv) { const int i = atomicAdd(&n_ovf, 1); if (i < kWave) ovf[i] = (unsigned short)o; }
     }
-    TRACE_W(8);
+    TRACE(raycast_box, 8);
     __syncthreads();
-    PHASE_STAMP_W(2);
-    TRACE_W(9);
+    PHASE_STAMP(raycast_box, 2);
+    TRACE(raycast_box, 9);
     // C. make the written tiles private to the particle (first write after a resample, or first touch of the area): ONE pop
     //    of a free list for all of them (rbpf_device.hpp: sixteen lists, the workgroup's number names the first to try), then one wave per tile copies 8 KB.  Usually there is nothing to do — and every wave
     //    sees that for itself (one ballot over the at most 64 tiles under the box), without a barrier to agree on it.
@@ -788,7 +755,7 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
         if (nb == ~0ull) bad = 1;
       }
       __syncthreads();
-      TRACE_W(15);
+      TRACE(raycast_box, 15);
       if (bad) { if (tid == 0) atomicOr(&err[3], 8); return; }  // tile pool exhausted (nothing has been written if this is the first band)
       // (tried: every workgroup starting at another tile and another eighth of it — after a resampling hundreds of particles copy
       //  from the same few parents' tiles.  No change: the parents' lines are served by the L2s, tools/rbpf_cow_trace.py)
@@ -833,8 +800,8 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
       }
       __syncthreads();
     }
-    PHASE_STAMP_W(3);
-    TRACE_W(10);
+    PHASE_STAMP(raycast_box, 3);
+    TRACE(raycast_box, 10);
     auto finish_end = [&](int slot, int cx, int cy, double v0o, double vv) {
       *val_at(slot) = vv;
       const bool was = v0o >= c.cut_occ, now = vv >= c.cut_occ;
@@ -909,7 +876,7 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
       ++n_ends;
       finish_end(o, cx, cy, v0o, vv);
     }
-    TRACE_W(11);
+    TRACE(raycast_box, 11);
     // 3b. overflowed slots: one wave per cell.  Lanes test beams q = 64*i + lane against the cell (is it q's end point /
     //     one of q's free cells); the two ballots are the cell's update sequence for those 64 beams, replayed in bit (=
     //     beam) order.  Pre-filter: a Bresenham cell lies within one cell of the line robot -> end point.
@@ -977,10 +944,10 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
         }
       }
     }
-    TRACE_W(12);
+    TRACE(raycast_box, 12);
     __syncthreads();  // every replayed / hot value is in its slot
-    TRACE_W(13);
-    PHASE_STAMP_W(4);
+    TRACE(raycast_box, 13);
+    PHASE_STAMP(raycast_box, 4);
     // 3c. the pairs: a plain cell adds its count, an end-point or hot cell takes the value worked out for it, an untouched one
     //     keeps its own; the pair goes back as one 16-byte store (the tile is private to the particle and nobody else writes
     //     these cells)
@@ -1031,9 +998,9 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
         request_next(i);
       });
     }
-    PHASE_STAMP_W(5);
+    PHASE_STAMP(raycast_box, 5);
   }
-  TRACE_W(14);
+  TRACE(raycast_box, 14);
   __syncthreads();
   // the tile-row counts / occupied count of the particle (this workgroup owns them; nothing waits for the adds)
   int* rc = trow_occ + (size_t)p * M.TW;
@@ -1053,10 +1020,8 @@ __global__ __launch_bounds__(NT, WPS) void rbpf_raycast_box(ScanC c, TilePool P,
     __syncthreads();
     if (tid == 0) { atomicAdd(&touched[0], (unsigned long long)cnt_upd); atomicAdd(&touched[1], (unsigned long long)cnt_dis); }
   }
-#if defined(TBNAV_PHASE_PROF) && !defined(TBNAV_TRACE_ONLY)  // (the sums are contended atomics on ONE address: they distort the very timeline TRACE_ONLY records)
-  if (tid == 0) { atomicAdd(&g_phase_w[15], 1ull); }
-#endif
-  WG_OUT();
+  PHASE_DONE(raycast_box);
+  WG_OUT(raycast_box);
 }
 #define TBNAV_X(NT_, WPS_, C16_, EV_) template __global__ void rbpf_raycast_box<NT_, WPS_, C16_, EV_>(ScanC, TilePool, MapT, const double2* __restrict__, const double* __restrict__, const double* __restrict__, int* __restrict__, int* __restrict__, int* __restrict__, int, unsigned long long* __restrict__, NormArgs, int* __restrict__, int* __restrict__, int, int);
 TBNAV_RAYCAST_BOX_FORMS(TBNAV_X)
@@ -1065,73 +1030,15 @@ TBNAV_RAYCAST_BOX_FORMS(TBNAV_X)
 }  // namespace tbnav_rk
 
 #ifdef TBNAV_PHASE_PROF
-#include <cstdio>
-#include <map>
-#include <vector>
 namespace tbnav_rk {
 void rbpf_prof_print_raycast() {
-    unsigned long long tr[2][16][16];
-    if (hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_trace), sizeof(tr)) == hipSuccess && tr[0][0][0]) {
-      for (int g = 0; g < 2; ++g) {
-        std::fprintf(stderr, "[raycast_box trace of workgroup %d, us since its first stamp; columns: entry, pose barrier, end-point barrier, flags, flag barrier, own events, walk, walk barrier, requests, barrier, tiles private, replay, overflow+hot, barrier, stores, (ring position known: only when tiles are made private)]\n", g ? 900 : 100);
-        unsigned long long t0 = ~0ull;
-        for (int w = 0; w < 16; ++w) if (tr[g][w][0] && tr[g][w][0] < t0) t0 = tr[g][w][0];
-        for (int w = 0; w < 16; ++w) {
-          std::fprintf(stderr, "  wave %2d:", w);
-          for (int i = 0; i < 16; ++i) std::fprintf(stderr, " %5.2f", tr[g][w][i] ? (double)(tr[g][w][i] - t0) * 0.01 : -1.0);
-          std::fprintf(stderr, "\n");
-        }
-      }
-    }
-    {
-      static unsigned long long wg[4096][3];
-      if (hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_wg), sizeof(wg)) == hipSuccess && wg[1][0]) {
-        int n = 0;
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (int i = 0; i < 4096; ++i) if (wg[i][0] && wg[i][1]) { ++n; t0 = std::min(t0, wg[i][0]); t1 = std::max(t1, wg[i][1]); }
-        std::fprintf(stderr, "[raycast_box workgroups of the last launch] %d recorded, first entry to last exit %.2f us\n", n, (double)(t1 - t0) * 0.01);
-        const int nb = 16;
-        const double span = (double)(t1 - t0);
-        int active[nb] = {0}, starts[nb] = {0};
-        double dur_by_start[nb] = {0};
-        for (int i = 0; i < 4096; ++i) if (wg[i][0] && wg[i][1]) {
-          const int bs = std::min(nb - 1, (int)((double)(wg[i][0] - t0) / span * nb));
-          ++starts[bs]; dur_by_start[bs] += (double)(wg[i][1] - wg[i][0]) * 0.01;
-          for (int b = 0; b < nb; ++b) { const double tm = t0 + (b + 0.5) * span / nb; if ((double)wg[i][0] <= tm && tm < (double)wg[i][1]) ++active[b]; }
-        }
-        std::fprintf(stderr, "  time bin (%.2f us each):", span * 0.01 / nb);
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5d", b);
-        std::fprintf(stderr, "\n  resident at mid-bin:    ");
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5d", active[b]);
-        std::fprintf(stderr, "\n  entered in bin:         ");
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5d", starts[b]);
-        std::fprintf(stderr, "\n  mean residence (us):    ");
-        for (int b = 0; b < nb; ++b) std::fprintf(stderr, " %5.1f", starts[b] ? dur_by_start[b] / starts[b] : 0.0);
-        std::map<unsigned long long, int> per_cu, per_xcc;
-        for (int i = 0; i < 4096; ++i) if (wg[i][0] && wg[i][1]) {
-          const unsigned int hw = (unsigned int)wg[i][2], xcc = (unsigned int)(wg[i][2] >> 32) & 0xF;
-          ++per_cu[((unsigned long long)xcc << 16) | (hw & 0xFF00u)];   // cu_id [11:8], sh_id [12], se_id [15:13]
-          ++per_xcc[xcc];
-        }
-        int hist[16] = {0};
-        for (auto& kv : per_cu) ++hist[std::min(15, kv.second)];
-        std::fprintf(stderr, "\n  CUs that ran workgroups: %zu; CUs by number of workgroups run:", per_cu.size());
-        for (int k = 1; k < 16; ++k) if (hist[k]) std::fprintf(stderr, " %d:%d", k, hist[k]);
-        std::fprintf(stderr, "\n  workgroups per XCC:");
-        for (auto& kv : per_xcc) std::fprintf(stderr, " %d", kv.second);
-        double xs[16] = {0}; int xn[16] = {0};
-        for (int i = 0; i < 4096; ++i) if (wg[i][0] && wg[i][1]) { const unsigned int xcc = (unsigned int)(wg[i][2] >> 32) & 0xF; xs[xcc] += (double)(wg[i][1] - wg[i][0]) * 0.01; ++xn[xcc]; }
-        std::fprintf(stderr, "\n  mean residence by XCC (us):");
-        for (int x = 0; x < 16; ++x) if (xn[x]) std::fprintf(stderr, " %.1f", xs[x] / xn[x]);
-        std::fprintf(stderr, "\n");
-      }
-    }
-    unsigned long long pw[16];
-    if (hipMemcpyFromSymbol(pw, HIP_SYMBOL(g_phase_w), sizeof(pw)) == hipSuccess && pw[15])
-      std::fprintf(stderr, "[raycast_box phases, 10 ns ticks per workgroup] set-up + flags %.1f | events + walk %.1f | requests + marks %.1f | "
-                           "private tiles %.1f | end-point replay + hot cells %.1f | pairs %.1f | (unused) %.1f\n",
-                   (double)pw[0] / pw[15], (double)pw[1] / pw[15], (double)pw[2] / pw[15], (double)pw[3] / pw[15], (double)pw[4] / pw[15],
-                   (double)pw[5] / pw[15], (double)pw[14] / pw[15]);
+  TBNAV_TRACE_PRINT(raycast_box, "raycast_box", 16, "entry, pose barrier, end-point barrier, flags, flag barrier, own events, walk, walk barrier, requests, barrier, tiles private, replay, overflow+hot, barrier, stores, (ring position known: only when tiles are made private)");
+  unsigned long long pw[16];
+  if (TBNAV_PHASE_SUMS_READ(raycast_box, pw))
+    std::fprintf(stderr, "[raycast_box phases, 10 ns ticks per workgroup] set-up + flags %.1f | events + walk %.1f | requests + marks %.1f | "
+                         "private tiles %.1f | end-point replay + hot cells %.1f | pairs %.1f | (unused) %.1f\n",
+                 (double)pw[0] / pw[15], (double)pw[1] / pw[15], (double)pw[2] / pw[15], (double)pw[3] / pw[15], (double)pw[4] / pw[15],
+                 (double)pw[5] / pw[15], (double)pw[14] / pw[15]);
 }
 }  // namespace tbnav_rk
 #endif

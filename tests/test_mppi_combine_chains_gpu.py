@@ -1,5 +1,5 @@
 """The straight-line form of mppi_combine<KEEP, 0> (csrc/mppi_softmin.hip: 16-byte record loads, no predicates, and its six wave
-sums side by side on full-mask DPP moves whose lanes below 63 hold no prefix sums — csrc/common.hpp, wave_sums_dpp) against the
+sums side by side on full-mask DPP moves whose lanes below 63 hold no prefix sums — csrc/wave.hpp, wave_sums_dpp) against the
 general form of the same kernel template, bit for bit, on the records of real ticks.
 
 tbnav_mppi_debug_combine_general runs the last tick's combine once more through mppi_combine<KEEP, 1> with one group — the text the

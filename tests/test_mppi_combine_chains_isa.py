@@ -1,5 +1,5 @@
 """The straight-line form of mppi_combine<KEEP, 0> (csrc/mppi_softmin.hip, combine_steps<KEEP, 0, true>: the K = 1024 and K = 2048
-ticks) reduces its six wave sums side by side and without zeroed `old` operands (csrc/common.hpp, wave_sums_dpp).  One wave handles
+ticks) reduces its six wave sums side by side and without zeroed `old` operands (csrc/wave.hpp, wave_sums_dpp).  One wave handles
 one time step and has its SIMD to itself, so every instruction it issues is paid for; six whole wave_sum_dpp one after the other
 cost 84 `v_mov_b32 vN, 0` and 27 `s_nop` more.  The listing is the one the library ships: csrc/Makefile's flags for the
 file (tools/makefile_flags.py), hipcc cross-compiles without a GPU.  Looked at: the block between the `sched_barrier` that closes

@@ -1,4 +1,4 @@
-"""mppi_rollout_fused issues no vector instruction whose result nothing can read (csrc/mppi_rollout.hip, csrc/common.hpp), in the
+"""mppi_rollout_fused issues no vector instruction whose result nothing can read (csrc/mppi_rollout.hip, csrc/wave.hpp), in the
 listing the library ships (csrc/Makefile's flags for the file, tools/makefile_flags.py; hipcc cross-compiles without a GPU):
 
   * small_sincos's full-range evaluation stays behind its wave-uniform branch: between the kernel's entry and s_barrier, outside
