@@ -13,75 +13,65 @@
 
 namespace tbnav_nk {
 
-constexpr int kFmTile = 32;                     // cells per side of a workgroup's output tile: one tile of the filter's pool
-constexpr int kFmThreads = 256;                 // four waves; a wave's 64 lanes are two rows of 32 consecutive iy
-constexpr int kFmRows = 3 * kFmTile;            // staged rows: the tile's and one tile of halo either side (TBNAV_NAV_MAX_REACH)
-constexpr int kFmWords = 3;                     // u32 per staged row: the tile's columns and one tile either side
-constexpr int kFmOwn = kFmTile * kFmTile / kFmThreads;
-constexpr int kFmRowStep = kFmThreads / kFmTile;
-static_assert(TBNAV_NAV_MAX_REACH <= kFmTile, "the search never leaves the 3 x 3 tiles staged");
-static_assert(kFmTile == tbnav_rk::kTS, "an output tile is a tile of the filter's pool");
+constexpr int kOccRows = 3 * kTile;             // staged rows: the output tile's (a tile of the filter's pool) and one tile of halo either side (TBNAV_NAV_MAX_REACH)
+constexpr int kOccWords = 3;                    // u32 per staged row: the tile's columns and one tile either side
+static_assert(TBNAV_NAV_MAX_REACH <= kTile, "the search never leaves the 3 x 3 tiles staged");
 
 struct FromMapArgs {
   const unsigned int* bm;      // TilePool::bm
-  const unsigned int* table;   // [N][TT] the particles' tile tables
-  const int* best;             // where the particle's index is on the device (rbpf_argmax), or null: `particle`
-  int particle;
-  int TW, TT;                  // tiles per side, per map
-  int side;                    // cells per side of the map (and of the output grid)
+  ParticleRef p;               // side: cells per side of the map (and of the output grid)
   int reach;                   // R
   int n_tab;                   // R*R + 1 table entries; tab[n_tab] is the open value
 };
 
 // One workgroup per 32 x 32 output tile.  Rows are ix (the slow index), bits within a row iy — the tiles' own layout and the output's.
 template <class OUT>
-__global__ __launch_bounds__(kFmThreads) void nav_cost_from_occ(FromMapArgs a, const OUT* __restrict__ tab, OUT* __restrict__ out) {
-  __shared__ unsigned int s_occ[kFmRows * kFmWords];
+__global__ __launch_bounds__(kThreads) void nav_cost_from_occ(FromMapArgs a, const OUT* __restrict__ tab, OUT* __restrict__ out) {
+  __shared__ unsigned int s_occ[kOccRows * kOccWords];
   __shared__ OUT s_tab[kInflEntries];
   const int tid = threadIdx.x, tile_x = blockIdx.y, tile_y = blockIdx.x;
-  const int p = a.best ? *a.best : a.particle;
-  const unsigned int* __restrict__ tab_p = a.table + (size_t)p * a.TT;
+  const unsigned int* __restrict__ tab_p = particle_row(a.p);
   // the occupancy rows of the 3 x 3 tiles round this one: id 0 (nobody has written the tile) and tiles outside the map read as
   // empty, and a ragged last tile is cut at the map's side
   int any = 0;
-  for (int i = tid; i < kFmRows * kFmWords; i += kFmThreads) {
-    const int lr = i / kFmWords, wc = i - lr * kFmWords;
-    const int gx = (tile_x - 1) * kFmTile + lr, ty = tile_y - 1 + wc;
+  for (int i = tid; i < kOccRows * kOccWords; i += kThreads) {
+    const int lr = i / kOccWords, wc = i - lr * kOccWords;
+    const int gx = (tile_x - 1) * kTile + lr, ty = tile_y - 1 + wc;
     unsigned int w = 0u;
-    if (gx >= 0 && gx < a.side && ty >= 0 && ty < a.TW) {
-      const unsigned int id = tab_p[(gx >> 5) * a.TW + ty];
-      if (id != 0u) w = a.bm[(size_t)id * kFmTile + (gx & (kFmTile - 1))];
-      const int inside = a.side - ty * kFmTile;   // columns of this tile that are cells of the map (>= 1)
-      if (inside < kFmTile) w &= (1u << inside) - 1u;
+    if (gx >= 0 && gx < a.p.side && ty >= 0 && ty < a.p.TW) {
+      const unsigned int id = tab_p[(gx >> 5) * a.p.TW + ty];
+      if (id != 0u) w = a.bm[(size_t)id * kTile + (gx & (kTile - 1))];
+      const int inside = a.p.side - ty * kTile;   // columns of this tile that are cells of the map (>= 1)
+      if (inside < kTile) w &= (1u << inside) - 1u;
     }
     s_occ[i] = w;
     any |= w != 0u;
   }
-  for (int i = tid; i <= a.n_tab; i += kFmThreads) s_tab[i] = tab[i];
+  for (int i = tid; i <= a.n_tab; i += kThreads) s_tab[i] = tab[i];
   any = __syncthreads_or(any);   // (also: the staging is complete)
 
-  const int ly = tid & (kFmTile - 1), iy = tile_y * kFmTile + ly;
-  const int lx0 = tid >> 5, ix0 = tile_x * kFmTile + lx0;
-  if (iy >= a.side) return;
+  const int ly = tid & (kTile - 1), iy = tile_y * kTile + ly;
+  const int lx0 = tid >> 5, ix0 = tile_x * kTile + lx0;
+  if (iy >= a.p.side) return;
   const OUT open = s_tab[a.n_tab];
   if (!any) {   // nothing occupied within reach of any cell of this tile: in a room, most tiles
 #pragma unroll
-    for (int j = 0; j < kFmOwn; ++j) {
-      const int ix = ix0 + j * kFmRowStep;
-      if (ix < a.side) out[(size_t)ix * a.side + iy] = open;
+    for (int j = 0; j < kOwn; ++j) {
+      const int ix = ix0 + j * kRowStep;
+      if (ix < a.p.side) out[(size_t)ix * a.p.side + iy] = open;
     }
     return;
   }
   const unsigned long long low33 = (1ull << 33) - 1ull;
   const int R = a.reach, c_max = a.n_tab - 1;
-  for (int j = 0; j < kFmOwn; ++j) {
-    const int lx = lx0 + j * kFmRowStep, ix = ix0 + j * kFmRowStep;
-    if (ix >= a.side) break;
+  for (int j = 0; j < kOwn; ++j) {
+    const int lx = lx0 + j * kRowStep, ix = ix0 + j * kRowStep;
+    if (ix >= a.p.side) break;
     int best = 1 << 20;
     // rows at distance dr = 0, 1, .. R either side; in each the nearest set bit left and right of this column, out to 32 columns
     for (int dr = 0; dr <= R && dr * dr < best; ++dr) {
       for (int s = 0; s < (dr == 0 ? 1 : 2); ++s) {
-        const unsigned int* row = s_occ + (kFmTile + lx + (s ? dr : -dr)) * kFmWords;   // rows 0 .. 95: dr <= 32
+        const unsigned int* row = s_occ + (kTile + lx + (s ? dr : -dr)) * kOccWords;   // rows 0 .. 95: dr <= 32
         const unsigned int w0 = row[0], w1 = row[1], w2 = row[2];
         // the cell is bit 32 + ly of the row's 96.  left: bit k <-> column offset k - 32; right: bit k <-> column offset k
         const unsigned long long left = ((((unsigned long long)w1 << 32) | w0) >> ly) & low33;
@@ -98,7 +88,7 @@ __global__ __launch_bounds__(kFmThreads) void nav_cost_from_occ(FromMapArgs a, c
         }
       }
     }
-    out[(size_t)ix * a.side + iy] = best <= c_max ? s_tab[best] : open;
+    out[(size_t)ix * a.p.side + iy] = best <= c_max ? s_tab[best] : open;
   }
 }
 
@@ -133,26 +123,16 @@ float infl_field(double d, double r_robot, double r_inflate) {
   return (float)(d <= r_robot ? 1.0 : (d >= r_inflate ? 0.0 : t * t));
 }
 
-FromMapArgs from_map_args(const tbnav_rbpf* pf, int32_t particle, int reach) {
-  return FromMapArgs{pf->pool.bm, pf->d_table[pf->cur], particle == TBNAV_NAV_BEST_PARTICLE ? pf->d_best : nullptr, particle,
-                     pf->TW, pf->TT, pf->xsize, reach, reach * reach + 1};
-}
 // the arg-max of the weights where the best particle is asked for, then the kernel, on the filter's stream (its device is current);
 // d_tab holds n_tab + 1 values when the kernel runs (the caller has enqueued their copy on the same stream)
 template <class OUT>
 int from_map_enqueue(tbnav_rbpf* pf, int32_t particle, int reach, const OUT* d_tab, OUT* d_out) {
-  if (particle == TBNAV_NAV_BEST_PARTICLE) {
-    const StatePtrs sp = state_ptrs(pf->d_state[pf->cur], pf->N);
-    hipLaunchKernelGGL(rbpf_argmax, dim3(1), dim3(256), 0, pf->stream, pf->N, sp.weight, sp.pose, pf->d_best, pf->d_best_pose);
-    TBNAV_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL((nav_cost_from_occ<OUT>), dim3(pf->TW, pf->TW), dim3(kFmThreads), 0, pf->stream, from_map_args(pf, particle, reach),
-                     d_tab, d_out);
+  const int rc = enqueue_best(pf, particle);
+  if (rc != TBNAV_OK) return rc;
+  const FromMapArgs a{pf->pool.bm, particle_ref(pf, particle), reach, reach * reach + 1};
+  hipLaunchKernelGGL((nav_cost_from_occ<OUT>), dim3(pf->TW, pf->TW), dim3(kThreads), 0, pf->stream, a, d_tab, d_out);
   TBNAV_HIP(hipGetLastError());
   return TBNAV_OK;
-}
-bool particle_ok(const tbnav_rbpf* pf, int32_t particle) {
-  return particle == TBNAV_NAV_BEST_PARTICLE || (particle >= 0 && particle < pf->N);
 }
 
 }  // namespace
@@ -183,13 +163,12 @@ int tbnav_nav_set_cost_from_rbpf(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle,
 int tbnav_nav_profile_cost_from_rbpf(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, double r_robot, double r_inflate, double k, int32_t launches,
                                      float* kernel_ms) {
   if (!h || !pf || !particle_ok(pf, particle) || launches < 1) return TBNAV_ERR_INVALID_ARG;
-  if (h->p.nx != pf->xsize || h->p.ny != pf->xsize || pf->ysize != pf->xsize || h->p.xmin != pf->p.xmin || h->p.ymin != pf->p.ymin ||
-      h->p.resolution != pf->p.resolution)
-    return TBNAV_ERR_INVALID_ARG;
+  const int rc_grid = same_grid(h, pf);   // another grid is refused before G7's arguments are looked at, another device after
+  if (rc_grid == TBNAV_ERR_INVALID_ARG) return rc_grid;
   int R = 0;
   const int rc = infl_check(pf->p.resolution, r_robot, r_inflate, k, &R);
   if (rc != TBNAV_OK) return rc;
-  if (h->device != pf->device) return TBNAV_ERR_UNSUPPORTED;
+  if (rc_grid != TBNAV_OK) return rc_grid;
   const int n_tab = R * R + 1;
   tbnav::DeviceGuard guard(pf->device);
   if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
@@ -198,18 +177,17 @@ int tbnav_nav_profile_cost_from_rbpf(tbnav_nav* h, tbnav_rbpf* pf, int32_t parti
   // G9: behind whatever the filter has in flight.  Solves are synchronous, so nothing reads d_cost now; every value the table holds
   // is at most 1 + 63 = TBNAV_NAV_MAX_COST (G2).
   TBNAV_HIP(hipMemcpyAsync(h->d_infl, h->infl.data(), (size_t)n_tab + 1, hipMemcpyHostToDevice, pf->stream));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  if (kernel_ms) { TBNAV_HIP(hipEventCreate(&ev[0])); TBNAV_HIP(hipEventCreate(&ev[1])); TBNAV_HIP(hipEventRecord(ev[0], pf->stream)); }
+  StageTimer timer(kernel_ms != nullptr, 2, pf->stream);
+  TBNAV_HIP(timer.create());
+  TBNAV_HIP(timer.stamp(0));
   int rc_k = TBNAV_OK;
   for (int l = 0; l < launches && rc_k == TBNAV_OK; ++l) rc_k = from_map_enqueue<uint8_t>(pf, particle, R, h->d_infl, h->d_cost);
-  hipError_t e = hipSuccess;
-  if (kernel_ms && rc_k == TBNAV_OK) e = hipEventRecord(ev[1], pf->stream);
+  hipError_t e = rc_k == TBNAV_OK ? timer.stamp(1) : hipSuccess;
   if (e == hipSuccess) e = hipStreamSynchronize(pf->stream);
   if (kernel_ms) {
     float ms = 0.0f;
-    if (e == hipSuccess && rc_k == TBNAV_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e == hipSuccess && rc_k == TBNAV_OK) e = timer.elapsed(0, &ms);
     *kernel_ms = ms / (float)launches;
-    (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]);
   }
   if (rc_k != TBNAV_OK) return rc_k;
   TBNAV_HIP(e);

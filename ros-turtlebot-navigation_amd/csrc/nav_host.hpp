@@ -1,6 +1,8 @@
 // nav_host.hpp — the goal field's handle and what its host files share (nav.hip: create / solve / results / hand-over of the solved
 // field; nav_from_map.hip: the cost grid taken from a filter's occupancy bits on the device, tbnav_nav.h G7-G9; nav_frontier.hip: the
-// frontiers of a particle's map, their clusters, and the solves that start from several goals, G10-G16).
+// frontiers of a particle's map, their clusters, and the solves that start from several goals, G10-G16): the rounds of a tiled fixed
+// point, the handle's allocations and lazy host copies, the optional stage timing, and the filter as the source of a grid.  What the
+// kernels share is nav_tiles.hpp.
 #ifndef TBNAV_NAV_HOST_HPP
 #define TBNAV_NAV_HOST_HPP
 #include <hip/hip_runtime.h>
@@ -9,6 +11,8 @@
 #include <vector>
 
 #include "common.hpp"
+#include "nav_tiles.hpp"
+#include "rbpf_host.hpp"
 #include "tbnav_nav.h"
 
 struct tbnav_nav {
@@ -48,6 +52,7 @@ struct tbnav_nav {
   // a find's seeds are goals only while the grid and the mask it saw are the ones in force: every successful set of either counts
   uint64_t cost_epoch = 0, visited_epoch = 0, found_cost_epoch = 0, found_visited_epoch = 0;
   tbnav_nav_frontier_info finfo{0, 0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<void**> buffers;      // the d_ members that hold an allocation (dev_alloc lists them, destroy walks them)
 };
 
 namespace tbnav_nk {
@@ -100,6 +105,73 @@ int run_rounds(tbnav_nav* h, unsigned* flags, unsigned* d_rec, hipStream_t strea
 // nav.hip: the rounds of nav_relax_tiles from whatever start d_d and d_flags hold (nav_reset / nav_reset_goals have been enqueued on the
 // null stream; the handle's device is current), and what a finished solve leaves in the handle.  h->solved is false while it runs.
 int relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy);
+
+inline bool in_grid(const tbnav_nav* h, int ix, int iy) { return ix >= 0 && ix < h->p.nx && iy >= 0 && iy < h->p.ny; }
+
+// `count` elements on the device into `slot`, a d_ member of the handle (its device is current); what the member held is freed once
+// the new allocation stands
+template <class T>
+hipError_t dev_alloc(tbnav_nav* h, T*& slot, size_t count) {
+  T* p = nullptr;
+  const hipError_t e = hipMalloc((void**)&p, sizeof(T) * count);
+  if (e != hipSuccess) return e;
+  if (slot) (void)hipFree(slot);
+  else h->buffers.push_back((void**)&slot);
+  slot = p;
+  return hipSuccess;
+}
+
+// the lazy host copies: dev[n] into `host` unless `valid` says it is there already
+template <class T>
+int fetch_once(tbnav_nav* h, const T* dev, std::vector<T>& host, bool& valid) {
+  if (valid) return TBNAV_OK;
+  tbnav::DeviceGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  host.resize((size_t)h->n);
+  TBNAV_HIP(hipMemcpy(host.data(), dev, sizeof(T) * (size_t)h->n, hipMemcpyDeviceToHost));
+  valid = true;
+  return TBNAV_OK;
+}
+
+// Optional event timing round the stages of a profile call: `stamps` events on `stream`, stage i lying between stamps i and i + 1.
+// Where no times are asked for (!on) no event exists and every call does nothing.
+struct StageTimer {
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t stream;
+  int n;
+  StageTimer(bool on, int stamps, hipStream_t st) : stream(st), n(on ? stamps : 0) {}
+  ~StageTimer() { for (int i = 0; i < n; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
+  hipError_t create() {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+    return e;
+  }
+  hipError_t stamp(int i) { return n ? hipEventRecord(ev[i], stream) : hipSuccess; }
+  hipError_t elapsed(int i, float* ms) { return n ? hipEventElapsedTime(ms, ev[i], ev[i + 1]) : hipSuccess; }   // (once the stream has been waited for)
+};
+
+// ---- a particle of a filter as the source of a grid (nav_from_map.hip, nav_frontier.hip) ----
+inline bool particle_ok(const tbnav_rbpf* pf, int32_t particle) {
+  return particle == TBNAV_NAV_BEST_PARTICLE || (particle >= 0 && particle < pf->N);
+}
+inline ParticleRef particle_ref(const tbnav_rbpf* pf, int32_t particle) {
+  return ParticleRef{pf->d_table[pf->cur], particle == TBNAV_NAV_BEST_PARTICLE ? pf->d_best : nullptr, particle, pf->TW, pf->TT, pf->xsize};
+}
+// the arg-max of the weights into pf->d_best where the best particle is asked for, on the filter's stream (its device is current)
+inline int enqueue_best(tbnav_rbpf* pf, int32_t particle) {
+  if (particle != TBNAV_NAV_BEST_PARTICLE) return TBNAV_OK;
+  const StatePtrs sp = state_ptrs(pf->d_state[pf->cur], pf->N);
+  hipLaunchKernelGGL(rbpf_argmax, dim3(1), dim3(256), 0, pf->stream, pf->N, sp.weight, sp.pose, pf->d_best, pf->d_best_pose);
+  TBNAV_HIP(hipGetLastError());
+  return TBNAV_OK;
+}
+// G8: the handle and the filter describe one grid (else TBNAV_ERR_INVALID_ARG) on one device (else TBNAV_ERR_UNSUPPORTED)
+inline int same_grid(const tbnav_nav* h, const tbnav_rbpf* pf) {
+  if (h->p.nx != pf->xsize || h->p.ny != pf->xsize || pf->ysize != pf->xsize || h->p.xmin != pf->p.xmin || h->p.ymin != pf->p.ymin ||
+      h->p.resolution != pf->p.resolution)
+    return TBNAV_ERR_INVALID_ARG;
+  return h->device != pf->device ? TBNAV_ERR_UNSUPPORTED : TBNAV_OK;
+}
 }  // namespace tbnav_nk
 
 #endif

@@ -53,14 +53,19 @@ SERPENTINE_N = 96
 SERPENTINE_LONGEST = (48 * 95 + 47 * 2) * 10 * 64
 
 
-def _serpentine():
-    n = SERPENTINE_N
-    c = np.full((n, n), 64, dtype=np.uint8)
+def _serpentine(n=SERPENTINE_N, cost=64):
+    c = np.full((n, n), cost, dtype=np.uint8)
     for k in range(n // 2):
         c[2 * k + 1, :] = 0
         if 2 * k + 1 < n - 1:
-            c[2 * k + 1, n - 1 if k % 2 == 0 else 0] = 64
+            c[2 * k + 1, n - 1 if k % 2 == 0 else 0] = cost
     return c
+
+
+# the same inside ONE tile at cost 3: 16 corridors of 31 moves and 15 gaps of 2, so the farthest of the 527 passable cells is 526
+# straight moves away — more than a visit's sweeps can carry a front, which advances one cell per sweep along a corridor (a row's
+# 32 cells are lanes of one wave): the tile runs into its sweep bound and wakes itself
+SERPENTINE_IN_TILE_LONGEST = (16 * 31 + 15 * 2) * 10 * 3
 
 
 def _room(n=400, seed=5, discs=12):
@@ -104,6 +109,7 @@ def _build():
     add("diagonal_wall_gap", _diagonal_wall(gap=True), (20, 20), starts=[(39, 0), (32, 32), (39, 39)])
     add("enclosed_goal", _enclosed(), (10, 10))
     add("serpentine_96", _serpentine(), (0, 0))
+    add("serpentine_in_tile_32", _serpentine(32, 3), (0, 0))
     add("empty_400", np.ones((400, 400), dtype=np.uint8), (0, 0), starts=[(399, 100), (123, 399)])
     room = _room()
     add("room_400", room, _first_free(room, (350, 380)))

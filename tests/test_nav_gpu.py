@@ -87,6 +87,22 @@ def test_the_serpentine_takes_rounds_far_beyond_its_tiles_per_side(gpu_pkg):
     nav.close()
 
 
+def test_a_serpentine_inside_one_tile_runs_into_the_sweep_bound_and_wakes_itself(gpu_pkg):
+    """One tile, 16 x 31 corridor moves: a row's 32 cells are lanes of one wave that sweep in lockstep, so a sweep advances a front one
+    cell along a corridor, and three visits of 128 sweeps cannot do them; a last round must change nothing.  So rounds >= 5, and
+    each of the first three visits at least ends at the sweep bound, where the tile wakes itself — nobody else could (== with the
+    restatement is asserted by the case test)."""
+    case = nc.CASES["serpentine_in_tile_32"]
+    nav = _nav(gpu_pkg, case["cost"])
+    nav.solve(*case["goal"])
+    info = nav.lastSolve()
+    print("serpentine in one tile: rounds", info["rounds"], "launches", info["launches"], "tile visits", info["tile_visits"])
+    assert info["tiles"] == (1, 1) and info["rounds"] >= 5
+    assert info["tile_visits"] >= info["rounds"] - 1
+    assert int(nav.costToGo()[30, 0]) == nc.SERPENTINE_IN_TILE_LONGEST
+    nav.close()
+
+
 def test_two_solves_and_a_set_cost_in_a_row_equal_fresh_handles(gpu_pkg):
     """Solving again resets what the last solve left: another goal, then a changed cost grid, each against a fresh handle and the
     restatement; set_cost alone leaves the last solution in place."""

@@ -88,6 +88,10 @@ def test_the_serpentines_longest_distance_is_its_closed_form():
     reached = d[d != nr.UNREACHED]
     assert int(reached.max()) == nc.SERPENTINE_LONGEST == int(d[94, 0])
     assert len(reached) == 48 * 96 + 47
+    d = nc.expected("serpentine_in_tile_32")
+    reached = d[d != nr.UNREACHED]
+    assert int(reached.max()) == nc.SERPENTINE_IN_TILE_LONGEST == 15780 == int(d[30, 0])
+    assert len(reached) == 16 * 32 + 15 == int((nc.CASES["serpentine_in_tile_32"]["cost"] != 0).sum())
 
 
 @pytest.mark.parametrize("name", nc.PATH_TIE_CASES)
