@@ -218,6 +218,60 @@
  *  W8. Test hook tbnav_icp_search_wide_scores: stateless, the wide stage alone whatever `when` says, with the handle's search and
  *      wide parameters (the defaults while they are off; the shape when the handle has it on); scores may be NULL, otherwise
  *      [2A+1][2W+1][2W+1].
+ *  MAP SEARCH (an addition to the search, tbnav_icp_search_map; csrc/icp_search_map.hip; restated in
+ *  tests/icp_search_map_restatement.py, reproduced exactly).  The search above scores a window of poses against a table of THE
+ *  PREVIOUS SCAN: it repairs one slipped scan, not a pose that has drifted over many scans, a robot that was picked up, or a filter
+ *  restarted in a map it already holds, where the previous scan is as wrong as the guess.  The map search forms the table from the
+ *  occupied cells of a filter particle's MAP (tbnav_rbpf.h) instead, on the device, and runs everything behind the table unchanged.
+ *  M1. Handles: an ICP handle h and a filter handle pf, on one device (else TBNAV_ERR_UNSUPPORTED; a member of a sharded group is
+ *      TBNAV_ERR_UNSUPPORTED too).  The search parameters are h's (the defaults while its search is off, as for the other
+ *      stateless entries); their resolution must equal the filter's as doubles, else TBNAV_ERR_INVALID_ARG (a filter's map
+ *      is always square: tbnav_rbpf_create refuses another).  Order: arguments, parameters and particles are looked
+ *      at first (INVALID_ARG), then device and group (UNSUPPORTED), then the guesses (M3, OUT_OF_WORLD).  The beam geometry and Trs that form the cloud are h's own (item 1): making them the filter's is the
+ *      caller's business.  particle is a slot of the filter or TBNAV_ICP_MAP_BEST_PARTICLE (-1): the arg-max of the weights found
+ *      on the device by tbnav_rbpf_best_state's rule (strict >, the first wins), as tbnav_nav.h G8 does.  Anything rejected
+ *      changes nothing: neither the filter, nor h's parameters, stored scan or last records.
+ *  M2. Occupied: a map cell is occupied when its bit in the particle's tiles is set (G8's definition, whatever distance-field mode
+ *      the filter runs in).  The cell (ci, cj) of a world position is G1's: ci = (int)floor((x - xmin) * inv), inv = 1.0 / resolution.
+ *  M3. Frame: T_init = (theta0, x0, y0) is the robot's guessed pose in the WORLD.  (cx, cy) = M2's cell of (x0, y0); a guess that
+ *      is not finite (any of the three) or whose cell is outside the map is TBNAV_ERR_OUT_OF_WORLD.  h2 = n / 2 with S1's n.  The
+ *      table's origin is o = (xmin + (double)cx * resolution, ymin + (double)cy * resolution).  Table cell [iy][ix] IS map cell
+ *      (cx - h2 + ix, cy - h2 + iy); cells outside the map are not occupied.  E' = (double)h2 * resolution takes the place of S1's E
+ *      in S5: with a half_extent that is not a whole number of cells the table's cells would otherwise not be the map's.
+ *  M4. Table: table[iy][ix] = the maximum of stamp[my - (cy - h2 + iy) + k][mx - (cx - h2 + ix) + k] over the occupied map cells
+ *      (mx, my) with both offsets in -k..k, 0 where there is none; stamp is S3's.  This is S4's table of the occupied cells'
+ *      centres.  tgt_points = the number of occupied cells inside the n x n window itself.  (S3's stamp depends on ox^2 + oy^2 only
+ *      and never rises with it: the maximum is the stamp at the least squared distance.  The host checks that property for the
+ *      parameters in force and answers TBNAV_ERR_UNSUPPORTED should it ever fail.)
+ *  M5. Scoring, selection, result: S5-S7 run unchanged on that table with the local guess (theta0, (x0 - o.x), (y0 - o.y)) (two
+ *      fp64 subtractions on the host) and E := E'.  S7's T is formed from the WORLD T_init: x0 + (double)(ix - wl) * resolution
+ *      already is the world pose.  accepted reads tgt_points > 0 where S7 reads "at least one target point".
+ *  M6. Shape and wide stage: F1-F6 and W1-W8 apply as they stand, "the table" being M4's.  W1's limits are unchanged (n <= 176 with
+ *      the wide stage on); `when` keeps its meaning.
+ *  M7. Batch: one scan, n >= 1 pairs (particle_i, T_init_i), independent, each equal to the single call bit for bit: several
+ *      hypotheses against one particle's map, or every particle against its own.  One bad pair rejects the call before any launch.
+ *  M8. Ordering and state: the table kernel runs behind whatever the filter handle has in flight (an event between the two
+ *      streams, no host synchronisation) and the scoring behind the table; the call returns with the result on the host.  The
+ *      filter is only read.  h's stored scan (tbnav_icp_step) is neither read nor written.  tbnav_icp_last_search,
+ *      _last_search_shape and _last_search_wide report this search (of a batch: the last pair's).
+ *  M9. Known limits.  Accuracy is one cell and one angle step: there is no refinement against the map behind it (the filter's own
+ *      hill-climb, tbnav_rbpf_set_scan_matching, is the local method that exists).  Points further than E' from the guess's cell
+ *      add nothing, as in the scan search.  Unknown cells and free cells both score 0: there is no free-space penalty.
+ *      min_quality = 0.5 was set for scan pairs; over a WIDE window against a map it does not separate a true match from a wrong
+ *      room (tests/icp_search_map_cases.py, BEHAVIOUR: the restatement on maps drawn by the oracle's GridMapper from 12 / 20 scans
+ *      of the two rooms of tests/rbpf_cases.py: true matches at +-48 cells and +-45 steps 0.872 and 0.984, a scan of the other room
+ *      0.557, ACCEPTED; at +-14 cells the other room is 0.402, rejected): a caller who searches wide against a map should raise
+ *      min_quality.  The other side of the same coin, from the same table: the table stands round the GUESS's cell, so a guess
+ *      2.5 m off in a 6 x 5 m room leaves two walls outside it; the pose is found to the cell and REJECTED at 0.417, because quality
+ *      divides by all valid points.  A caller far off should look at at_edge and the pose, or search again from info->T.
+ *      The default is unchanged.  The map search is not wired into
+ *      tbnav_icp_step / _match nor into bmapping::ParticleFilter::SLAM: a caller composes it.
+ *  KERNEL (csrc/icp_search_map.hip): icp_search_table_from_occ, one workgroup of 256 threads per (32 x 32 tile of the table, pair):
+ *  the occupancy words of the tile's map rows and 8 either side, read through the particle's tile table (tile id 0, tiles outside
+ *  the map and a ragged last tile read as empty) and funnel-shifted to the table's origin; per cell the nearest set bit by rows
+ *  outwards (clz / ffs, stopping when dr^2 reaches the best) and one look into a value-by-squared-distance table; the tile
+ *  transposed through LDS and written, border of wl zero cells included, in icp_search_table's padded layout.  Integers only, no
+ *  atomic but the count of tgt_points.
  *  KERNELS (csrc/icp_search_wide.hip): icp_search_wide_score, one workgroup of 256 threads per (translation tile, angle, pair):
  *  a tile is up to 33 x 33 translations; the base cells are shifted by the tile's first offset, so the workgroup needs the table
  *  with tile - 1 zero cells on its high side only (side <= 208, read from the first stage's padded table in global memory);
@@ -246,6 +300,7 @@
 
 #include <stdint.h>
 
+#include "tbnav_rbpf.h"
 #include "tbnav_status.h"
 
 #ifdef __cplusplus
@@ -463,6 +518,26 @@ int tbnav_icp_last_search_wide(const tbnav_icp* h, tbnav_icp_search_wide_info* i
 /* test hook (W8), stateless: the wide stage alone; scores [2A+1][2W+1][2W+1] or NULL.  info is required. */
 int tbnav_icp_search_wide_scores(tbnav_icp* h, const float* target_scan, const float* source_scan, int32_t n_beams,
                                  const double T_init[3], double T_out[3], tbnav_icp_search_info* info, uint32_t* scores);
+
+/* ---- the search against a filter's map (M1-M9 of the CORRELATIVE SEARCH section's MAP SEARCH) ---- */
+#define TBNAV_ICP_MAP_BEST_PARTICLE (-1)
+/* the search of one scan against particle's map from the world guess T_init (M1-M6): info->T is the world pose.  info is required. */
+int tbnav_icp_search_map(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T_init[3],
+                         tbnav_icp_search_info* info);
+/* M7: one scan, n pairs (particles[i], T_init[i]): T_init [n][3], infos [n] */
+int tbnav_icp_search_map_batch(tbnav_icp* h, tbnav_rbpf* pf, const float* scan, int32_t n_beams, int32_t n, const int32_t* particles,
+                               const double* T_init, tbnav_icp_search_info* infos);
+/* test hook: the table (M4) of one pair, [n][n], and tgt_points; TBNAV_ERR_HIP should the kernel have left a byte of the padded
+ * table's border unwritten or not zero */
+int tbnav_icp_search_map_table(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const double T_init[3], uint8_t* table, uint32_t* tgt_points);
+/* test hook: tbnav_icp_search_map and the first stage's whole score volume [na][nl][nl]; ignores the wide stage */
+int tbnav_icp_search_map_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T_init[3],
+                                tbnav_icp_search_info* info, uint32_t* scores);
+/* test hook (as W8): the wide stage alone against the map; scores [2A+1][2W+1][2W+1] or NULL */
+int tbnav_icp_search_map_wide_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                     const double T_init[3], tbnav_icp_search_info* info, uint32_t* scores);
+/* the table kernel's name as a profiler prints it; "" until the route has run on this handle */
+int tbnav_icp_last_map_kernel(const tbnav_icp* h, char* kernel, int32_t kernel_cap);
 
 #ifdef __cplusplus
 }

@@ -181,6 +181,7 @@ class IcpSearchWideInfo(C.Structure):
 
 ICP_SEARCH_WIDE_MAX_LIN, ICP_SEARCH_WIDE_MAX_ANG, ICP_SEARCH_WIDE_MAX_TABLE = 64, 180, 176
 ICP_WIDE_ON_REJECT, ICP_WIDE_ON_REJECT_OR_EDGE, ICP_WIDE_ALWAYS = 0, 1, 2
+ICP_MAP_BEST_PARTICLE = -1
 
 
 _lib = None
@@ -415,6 +416,12 @@ def lib() -> C.CDLL:
         "tbnav_icp_get_search_wide": (C.c_int, [vp, C.POINTER(i32), C.POINTER(IcpSearchWideParams)]),
         "tbnav_icp_last_search_wide": (C.c_int, [vp, C.POINTER(IcpSearchWideInfo)]),
         "tbnav_icp_search_wide_scores": (C.c_int, [vp, vp, vp, i32, dp, dp, C.POINTER(IcpSearchInfo), vp]),
+        "tbnav_icp_search_map": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpSearchInfo)]),
+        "tbnav_icp_search_map_batch": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
+        "tbnav_icp_search_map_table": (C.c_int, [vp, vp, i32, dp, vp, C.POINTER(C.c_uint32)]),
+        "tbnav_icp_search_map_scores": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpSearchInfo), vp]),
+        "tbnav_icp_search_map_wide_scores": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpSearchInfo), vp]),
+        "tbnav_icp_last_map_kernel": (C.c_int, [vp, C.c_char_p, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -101,7 +101,10 @@ struct IcpSearch {
   DevBuf d_wsel;                    // SearchSel [escalated pairs] results
   DevBuf d_wshape;                  // ShapeRec [escalated pairs][tiles]: F3's integers per tile
   DevBuf d_wscores;                 // uint32_t: the wide test hook's score volume
-  std::vector<unsigned char> h_in, h_sel, h_shape, h_win, h_wsel, h_wshape;
+  DevBuf d_map_in;                  // the map search (icp_search_map.hip): the value-by-d2 table, then the chunk's MapPairs
+  hipEvent_t map_ev = nullptr;      // ... "the filter's stream has come this far", created at the first map search
+  bool map_ran = false;             // ... tbnav_icp_last_map_kernel
+  std::vector<unsigned char> h_in, h_sel, h_shape, h_win, h_wsel, h_wshape, h_map;
 };
 
 }  // namespace tbnav_icpdev
@@ -134,17 +137,20 @@ struct tbnav_icp {
 
 namespace tbnav_icpdev {
 
+struct MapSource;   // icp_search_device.hpp
+
 // icp.hip
 int ensure_table(tbnav_icp* h, int n_beams);
 
 // icp_search.hip: the search of h->h_pairs[0, n_pairs) from h->h_init (scans already in d_scans / d_stored, the beam table
 // built) with parameters sp -> h->h_sinfo[0, n_pairs).  scores (n_pairs == 1 only): the whole score volume, or null.
 // shp: the shape of the score volume (F1-F6) behind the selection -> h->h_sshape and the shaped T in h->h_sinfo, or null.
+// map: the tables come from a filter particle's occupancy bits (MAP SEARCH, M1-M9; icp_search_device.hpp) instead of target scans.
 // wp: the wide second stage (W1-W8) for the pairs W3 names -> h->h_sinfo holds the OUTCOME (W5) and h->h_swide the first
 // stage's record, or null; wide_scores (n_pairs == 1 only): the wide stage's score volume, or null.
 int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
                  const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp = nullptr,
-                 uint32_t* wide_scores = nullptr);
+                 uint32_t* wide_scores = nullptr, const MapSource* map = nullptr);
 void search_free(tbnav_icp* h);
 
 }  // namespace tbnav_icpdev

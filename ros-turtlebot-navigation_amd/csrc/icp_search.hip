@@ -19,7 +19,10 @@
 // icp_search_device.hpp's scoring front, shared with that kernel.  On the host search_pairs walks the chunks in named steps
 // (pack_chunk, reserve_chunk, launch_table, score_pass, launch_shape) and search_finish forms S7's record, as shape_finish
 // forms F4 / F5's; every device buffer is a DevBuf (icp_device.hpp).  The wide second stage (W1-W8) is icp_search_wide.hip's:
-// search_pairs collects the pairs W3 names behind a chunk's synchronisation and hands them to wide_stage.
+// search_pairs collects the pairs W3 names behind a chunk's synchronisation and hands them to wide_stage.  The tables have one of
+// two sources: target scans (launch_table, here) or the occupancy bits of a filter particle's map (MAP SEARCH, M1-M9:
+// launch_table_from_occ, icp_search_map.hip, which writes the same padded layout); search_pairs is told which by its MapSource and
+// shares everything else between them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -332,8 +335,8 @@ int score_pass(tbnav_icp* h, int n, int n_beams, const SearchConst& sc, const Se
 }
 
 // h_in <- pairs [first, first + n) of h->h_pairs with their guesses h->h_init, then (at the offset returned, 16-byte aligned)
-// their rotations (cos, sin of theta_a in double, glibc): one upload
-size_t pack_chunk(tbnav_icp* h, int first, int n, const SearchConst& sc, const tbnav_icp_search_params& sp) {
+// their rotations (cos, sin of theta_a in double, glibc): one upload.  map (M5): the translation is the local guess, the angle stays
+size_t pack_chunk(tbnav_icp* h, int first, int n, const SearchConst& sc, const tbnav_icp_search_params& sp, const MapSource* map) {
   IcpSearch& S = h->search;
   const size_t rot_at = (sizeof(SearchPair) * (size_t)n + 15) & ~(size_t)15;
   S.h_in.resize(rot_at + sizeof(double2) * (size_t)n * sc.na);
@@ -343,6 +346,7 @@ size_t pack_chunk(tbnav_icp* h, int first, int n, const SearchConst& sc, const t
     const IcpPair& pr = h->h_pairs[(size_t)(first + i)];
     const std::array<double, 3>& T = h->h_init[(size_t)(first + i)];
     hp[i].tgt = pr.tgt; hp[i].src = pr.src; hp[i].x0 = T[1]; hp[i].y0 = T[2];
+    if (map) { hp[i].x0 = map->local[(size_t)(first + i)].x; hp[i].y0 = map->local[(size_t)(first + i)].y; }
     for (int ia = 0; ia < sc.na; ++ia) {
       const double th = T[0] + (double)(ia - sc.wa) * sp.ang_step;
       hr[(size_t)i * sc.na + ia] = make_double2(std::cos(th), std::sin(th));
@@ -376,22 +380,29 @@ void search_finish(const SearchSel& s, const SearchConst& sc, const tbnav_icp_se
   o.reserved = 0;
 }
 
+SearchConst search_const(const tbnav_icp_search_params& p) { return make_const(p); }
+bool search_params_ok(const tbnav_icp_search_params& p) { return params_ok(p); }
+
 void search_free(tbnav_icp* h) {
   IcpSearch& S = h->search;
   (void)hipFree(S.d_stamp);
   for (DevBuf* b : {&S.d_tables, &S.d_in, &S.d_rec, &S.d_sel, &S.d_tgt_points, &S.d_scores, &S.d_shape, &S.d_win, &S.d_wrec, &S.d_wsel,
-                    &S.d_wshape, &S.d_wscores}) b->release();
+                    &S.d_wshape, &S.d_wscores, &S.d_map_in}) b->release();
+  if (S.map_ev) (void)hipEventDestroy(S.map_ev);
   S = IcpSearch{};
 }
 
 int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_params& sp, uint32_t* scores,
-                 const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp, uint32_t* wide_scores) {
+                 const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp, uint32_t* wide_scores,
+                 const MapSource* map) {
   if (!params_ok(sp) || (shp && !shape_params_ok(*shp)) || n_beams <= 0 || n_beams > TBNAV_ICP_MAX_BEAMS || (scores && n_pairs != 1)) return TBNAV_ERR_INVALID_ARG;
   if ((wp && !wide_params_ok(*wp, sp)) || (wide_scores && (!wp || n_pairs != 1))) return TBNAV_ERR_INVALID_ARG;
   const bool first_stage = !(wp && wp->when == TBNAV_ICP_WIDE_ALWAYS);   // W2
   IcpSearch& S = h->search;
-  const SearchConst sc = make_const(sp);
-  if (int rc = ensure_stamp(h, sp)) return rc;
+  SearchConst sc = make_const(sp);
+  if (map) sc.E = map->E;                                                // M3: E' in S1's place
+  if (!map)
+    if (int rc = ensure_stamp(h, sp)) return rc;
   h->h_sinfo.assign((size_t)n_pairs, tbnav_icp_search_info{});
   h->h_sshape.assign((size_t)n_pairs, tbnav_icp_search_shape{});
   h->h_swide.assign((size_t)n_pairs, tbnav_icp_search_wide_info{});
@@ -401,12 +412,12 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
     if (int rc = S.d_scores.reserve(sizeof(uint32_t) * vol)) return rc;
   for (int first = 0; first < n_pairs; first += kChunk) {
     const int n = n_pairs - first < kChunk ? n_pairs - first : kChunk;
-    const size_t rot_at = pack_chunk(h, first, n, sc, sp);
+    const size_t rot_at = pack_chunk(h, first, n, sc, sp, map);
     if (int rc = reserve_chunk(S, n, sc, S.h_in.size(), shp != nullptr)) return rc;
     TBNAV_HIP(hipMemcpyAsync(S.d_in.ptr, S.h_in.data(), S.h_in.size(), hipMemcpyHostToDevice, h->stream));
     const SearchPair* d_pairs = S.d_in.as<SearchPair>();
     const double2* d_rot = reinterpret_cast<const double2*>(S.d_in.as<unsigned char>() + rot_at);
-    if (int rc = launch_table(h, n, n_beams, sc, d_pairs)) return rc;
+    if (int rc = map ? launch_table_from_occ(h, first, n, sc, *map) : launch_table(h, n, n_beams, sc, d_pairs)) return rc;
     esc.clear();
     if (first_stage) {
       if (int rc = score_pass(h, n, n_beams, sc, d_pairs, d_rot, scores ? S.d_scores.as<uint32_t>() : nullptr, 0)) return rc;

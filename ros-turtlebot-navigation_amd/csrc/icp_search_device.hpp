@@ -1,7 +1,8 @@
 // icp_search_device.hpp — what the correlative search's kernels (icp_search.hip) and the kernel that measures the shape of
 // its score volume (icp_search_shape.hip) share: the by-value constants, the per-pair input and result, the cell of a
 // coordinate, the names of the wave reductions they use (wave.hpp) and the scoring front (load_table, base_cells, slow_read: what icp_search_score and
-// icp_search_shape do before they score, and how either reads a table byte for a point of the slow list).
+// icp_search_shape do before they score, and how either reads a table byte for a point of the slow list), and what the search against
+// a filter's map (icp_search_map.hip) hands to search_pairs in place of target scans (MapPair, MapSource).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,5 +118,27 @@ bool wide_params_ok(const tbnav_icp_search_wide_params& wp, const tbnav_icp_sear
 int wide_stage(tbnav_icp* h, int first, const std::vector<int>& esc, int n_beams, const tbnav_icp_search_params& sp,
                const SearchConst& sc, const SearchPair* d_pairs, const tbnav_icp_search_wide_params& wp, uint32_t* scores,
                const tbnav_icp_search_shape_params* shp);
+
+// icp_search_map.hip (MAP SEARCH, M1-M9): a particle's map in place of a target scan.  One MapPair per pair goes to the device;
+// MapSource is what search_pairs needs to know of the route: E' (M3) for SearchConst::E, the local guesses for SearchPair::x0 / y0
+// (h->h_init keeps the WORLD T_init for search_finish, shape_finish and the wide stage's angles), and the table's source.
+constexpr int kMapValues = (2 * TBNAV_ICP_SEARCH_MAX_STAMP * TBNAV_ICP_SEARCH_MAX_STAMP + 1 + 15) & ~15;   // 144 bytes: whole uint4s
+struct MapPair {
+  int32_t particle;   // a slot, or TBNAV_ICP_MAP_BEST_PARTICLE: the filter's arg-max, on the device
+  int32_t ox, oy;     // the map cell of table cell [0][0]: (cx - h2, cy - h2), anywhere relative to the map
+  int32_t pad;
+};
+struct MapSource {
+  const tbnav_rbpf* pf;
+  double E;                        // E' = (double)h2 * resolution
+  std::vector<MapPair> pairs;      // [n_pairs]
+  std::vector<double2> local;      // [n_pairs] (x0 - o.x, y0 - o.y)
+  uint8_t value[kMapValues];       // S3's stamp by d2 = ox^2 + oy^2, 0 .. 2k^2 (M4)
+};
+// icp_search.hip: S1's limits, and the constants of parameters that keep them
+bool search_params_ok(const tbnav_icp_search_params& p);
+SearchConst search_const(const tbnav_icp_search_params& p);
+// icp_search_table_from_occ over the pairs [first, first + n) of map -> d_tables, d_tgt_points (launch_table's layout), on h->stream
+int launch_table_from_occ(tbnav_icp* h, int first, int n, const SearchConst& sc, const MapSource& map);
 
 }  // namespace tbnav_icpdev

@@ -39,11 +39,18 @@
 // that is metres off is found and a good guess pays nothing.  Off unless asked for.  -DTBNAV_SCAN_ALIGNMENT_SEARCH_WIDE beside
 // -DTBNAV_SCAN_ALIGNMENT_DEVICE_ICP and -DTBNAV_SCAN_ALIGNMENT_SEARCH makes the constructor's search carry wide = true; it only
 // changes a default argument too (without the search it has no effect).
+//
+// searchMap(filter, guess_world, scan) (an addition too; tbnav_icp.h, MAP SEARCH M1-M9) scores a window of poses round a guess given
+// in the WORLD against the map of the filter's best particle, on the device, with the search parameters useDeviceICP was given (the
+// defaults without any): for a pose that has drifted over many scans, a robot that was picked up, a filter restarted in a map it
+// already holds, where the previous scan is as wrong as the guess.  It needs useDeviceICP (std::logic_error otherwise), a filter on
+// one GPU (std::runtime_error for one over several) whose cells are the search's; it is not wired into pclICPWrapper or SLAM.
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
 #include <functional>
 #include <iostream>
+#include <memory>
 #include <vector>
 
 #include "bmapping/sensor_model.hpp"
@@ -109,6 +116,16 @@ struct ICPSearch {
   ICPWideWhen wide_when = ICPWideWhen::OnReject;  ///< when it runs
 };
 
+class ParticleFilter;   // bmapping/particle_filter.hpp
+
+/// (addition) what ScanAlignment::searchMap returns: tbnav_icp_search_info's T, quality, accepted and at_edge
+struct MapSearchResult {
+  Transform2D T;          ///< the best pose of the window, in the world (the guess's where nothing scored)
+  double quality = 0.0;   ///< score / (255 * points), 0..1
+  bool accepted = false;  ///< quality >= min_quality, with points in the scan and occupied cells in the window
+  bool at_edge = false;   ///< the choice sits on the border of its window: the truth may lie outside it
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
@@ -136,6 +153,11 @@ class ScanAlignment {
   /// (addition) the same with the correlative search in front of every alignment; throws std::invalid_argument for
   /// parameters outside their limits
   void useDeviceICP(int device, ICPMetric metric, const ICPSearch& search);
+
+  /// (addition) the correlative search of `scan` against the map of the filter's best particle from a guess in the world
+  /// (tbnav_icp.h, MAP SEARCH).  Throws std::logic_error without useDeviceICP, std::runtime_error for a filter over several GPUs,
+  /// std::invalid_argument for a guess outside the map (the reference's out-of-world text) or cells that are not the filter's.
+  MapSearchResult searchMap(ParticleFilter& filter, const Transform2D& guess_world, const std::vector<float>& scan);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {
@@ -165,6 +187,7 @@ class ScanAlignment {
   LaserProperties props_;
   Transform2D Trs_;
   Matcher matcher_;
+  std::shared_ptr<void> device_;   // the tbnav_icp handle useDeviceICP made (the matcher holds it too); copies share it
   std::vector<float> prev_scan_;
   bool have_prev_ = false;
   bool warned_ = false;

@@ -77,6 +77,7 @@ class ParticleFilter {
  private:
   friend class planner::GoalField;
   friend class controller::MPPI;
+  friend class ScanAlignment;       // searchMap: the best particle's map as the search's target
   tbnav_rbpf* h_ = nullptr;         // n_gpus == 1
   tbnav_rbpf_group* g_ = nullptr;   // n_gpus > 1
   bool reference_field_ = false;

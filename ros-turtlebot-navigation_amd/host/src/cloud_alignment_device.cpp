@@ -7,6 +7,7 @@
 #include <string>
 
 #include "bmapping/cloud_alignment.hpp"
+#include "bmapping/particle_filter.hpp"
 #include "tbnav_icp.h"
 
 namespace bmapping {
@@ -33,6 +34,7 @@ void ScanAlignment::installDeviceICP(int device, ICPMetric metric, const ICPSear
   }
   // the matcher holds the handle: copies of this object (and of the std::function) share it
   std::shared_ptr<tbnav_icp> h(raw, tbnav_icp_destroy);
+  device_ = h;
   if (metric == ICPMetric::PointToLine) {
     const int mrc = tbnav_icp_set_metric(raw, TBNAV_ICP_METRIC_LINE, 0, 0.0);  // the default window and gap
     if (mrc != TBNAV_OK) throw std::runtime_error(std::string("bmapping::ScanAlignment::useDeviceICP: ") + tbnav_status_string(mrc));
@@ -84,6 +86,31 @@ void ScanAlignment::installDeviceICP(int device, ICPMetric metric, const ICPSear
     T = Transform2D(rigid2d::Vector2D(out[1], out[2]), out[0]);  // :206-217
     return true;
   };
+}
+
+MapSearchResult ScanAlignment::searchMap(ParticleFilter& filter, const Transform2D& guess_world, const std::vector<float>& scan) {
+  if (!device_) throw std::logic_error("bmapping::ScanAlignment::searchMap: useDeviceICP first");
+  if (filter.g_) throw std::runtime_error("bmapping::ScanAlignment::searchMap: a filter over several GPUs is not supported");
+  const auto g = guess_world.displacement();
+  const double tinit[3] = {g.theta, g.x, g.y};
+  tbnav_icp_search_info info{};
+  const int rc = tbnav_icp_search_map(static_cast<tbnav_icp*>(device_.get()), filter.h_, TBNAV_ICP_MAP_BEST_PARTICLE, scan.data(),
+                                      (int32_t)scan.size(), tinit, &info);
+  if (rc != TBNAV_OK) {
+    const std::string text = tbnav_status_string(rc);
+    if (rc == TBNAV_ERR_OUT_OF_WORLD) throw std::invalid_argument(text);  // what the reference throws (grid_mapper.cpp:856)
+    std::string msg = "bmapping::ScanAlignment::searchMap: " + text;
+    if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+    const char* hip = tbnav_last_hip_error();
+    if (hip && *hip) msg += std::string(" [") + hip + "]";
+    throw std::runtime_error(msg);
+  }
+  MapSearchResult out;
+  out.T = Transform2D(rigid2d::Vector2D(info.T[1], info.T[2]), info.T[0]);
+  out.quality = info.quality;
+  out.accepted = info.accepted != 0;
+  out.at_edge = info.at_edge != 0;
+  return out;
 }
 
 }  // namespace bmapping

@@ -18,6 +18,9 @@ wide=True | dict(...) beside search (an addition too) adds the wide second stage
 +-64 cells and +-180 steps, scored only when the first stage is rejected (when="reject", the default), or also when its choice
 sits on the border of its window ("reject_or_edge"), or always and in its place ("always").  The default is off.
 
+searchMap(filter, T_init, scan) (an addition too) searches against the MAP of a particle of an rbpf.ParticleFilter instead of the
+previous scan (the header's MAP SEARCH, M1-M9): for a pose that has drifted over many scans, or a filter restarted in a known map.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -281,6 +284,57 @@ class ScanAlignment:
         tab = np.zeros((n, n), dtype=np.uint8)
         capi.check(self._L.tbnav_icp_search_table(self._h, scan.ctypes.data, scan.size, tab.ctypes.data), "tbnav_icp_search_table")
         return tab
+
+    def searchMap(self, filter, T_init, scan, particle=capi.ICP_MAP_BEST_PARTICLE):
+        """tbnav_icp_search_map (the header's MAP SEARCH, M1-M9): the search of one scan against the map of a particle of `filter`
+        (rbpf.ParticleFilter; particle=-1: its best one, found on the device) from the WORLD guess T_init = (theta, x, y), with the
+        handle's search parameters -> (accepted, T in the world, info dict).  The map never leaves the device."""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        info = capi.IcpSearchInfo()
+        capi.check(self._L.tbnav_icp_search_map(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T_init), C.byref(info)),
+                   "tbnav_icp_search_map")
+        return bool(info.accepted), tuple(info.T), _search_info(info)
+
+    def searchMapBatch(self, filter, T_init, scan, particles):
+        """tbnav_icp_search_map_batch (M7): one scan, n pairs (particles[i], T_init[i]), each equal to the single call
+        -> list of (accepted, T, info dict)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        particles = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
+        n = particles.size
+        T_init = np.ascontiguousarray(T_init, dtype=np.float64).reshape(n, 3)
+        infos = (capi.IcpSearchInfo * max(n, 1))()
+        capi.check(self._L.tbnav_icp_search_map_batch(self._h, filter._h, scan.ctypes.data, scan.size, n, particles.ctypes.data,
+                                                      T_init.ctypes.data, C.cast(infos, C.c_void_p)), "tbnav_icp_search_map_batch")
+        return [(bool(i.accepted), tuple(i.T), _search_info(i)) for i in infos[:n]]
+
+    def searchMapTable(self, filter, T_init, particle=capi.ICP_MAP_BEST_PARTICLE):
+        """test hook: the table (M4) of one pair and tgt_points -> (uint8 [n][n] indexed [iy][ix], int)"""
+        p = self.searchParams()[1]
+        n = 2 * math.ceil(p["half_extent"] / p["resolution"])
+        tab = np.zeros((n, n), dtype=np.uint8)
+        cnt = C.c_uint32()
+        capi.check(self._L.tbnav_icp_search_map_table(self._h, filter._h, int(particle), _d3(T_init), tab.ctypes.data, C.byref(cnt)),
+                   "tbnav_icp_search_map_table")
+        return tab, int(cnt.value)
+
+    def searchMapScores(self, filter, T_init, scan, particle=capi.ICP_MAP_BEST_PARTICLE, wide=False):
+        """test hook: searchMap and the whole score volume -> (accepted, T, info dict, uint32 [na][nl][nl]); wide=True: the wide
+        stage alone (as searchWideScores), its volume [2A+1][2W+1][2W+1]"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        p = self.searchWideParams()[1] if wide else self.searchParams()[1]
+        na, nl = 2 * p["ang_steps"] + 1, 2 * p["lin_cells"] + 1
+        vol = np.zeros((na, nl, nl), dtype=np.uint32)
+        info = capi.IcpSearchInfo()
+        fn = self._L.tbnav_icp_search_map_wide_scores if wide else self._L.tbnav_icp_search_map_scores
+        capi.check(fn(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T_init), C.byref(info), vol.ctypes.data),
+                   "tbnav_icp_search_map_wide_scores" if wide else "tbnav_icp_search_map_scores")
+        return bool(info.accepted), tuple(info.T), _search_info(info), vol
+
+    def lastMapKernel(self) -> str:
+        """the map search's table kernel as a profiler prints it; "" until searchMap has run on this handle"""
+        buf = C.create_string_buffer(64)
+        capi.check(self._L.tbnav_icp_last_map_kernel(self._h, buf, 64), "tbnav_icp_last_map_kernel")
+        return buf.value.decode()
 
     def lastSearch(self) -> dict:
         """the search record of the last pclICP / pclICPWrapper, for a wrapperBatch the last scan's (searched = 0: none ran)"""
