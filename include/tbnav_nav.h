@@ -9,7 +9,7 @@
  * out of a pocket.  Not built: D* Lite's incremental repair (every solve starts afresh), heading-dependent costs.
  *
  * This section is the whole specification; tests/nav_restatement.py restates G1-G6 in Python integers, tests/nav_from_map_restatement.py G7-G8,
- * tests/nav_frontier_restatement.py G10-G16.
+ * tests/nav_frontier_restatement.py G10-G16, tests/nav_gain_restatement.py G17-G20.
  *
  * G1. Grid.  nx, ny in 2 .. TBNAV_NAV_MAX_SIDE; (xmin, ymin), finite, are the world coordinates of the OUTER corner of cell (0, 0);
  *     resolution finite and > 0.  Cell (ix, iy) is at index ix*ny + iy (x is the slow index): the cost field's layout and, for the
@@ -128,9 +128,60 @@
  * nav_reset_goals: a solve's start from the seed words or from an uploaded list, active the tiles that see a goal (nav_reset's rule).  No
  * kernel waits for another workgroup; every loop is bounded by the tile.
  *
- * Not built here: sharded filters and handles on different devices; information gain or any ranking of frontiers other than nearest;
- * clearing along beams without a return (the mapper's behaviour stays the reference's); incremental updates between scans; a time-out for
- * marks.
+ * FRONTIERS RANKED BY WHAT A SCAN FROM THEM WOULD REVEAL (csrc/nav_gain.hip; an option like everything here).  The nearest seed is the
+ * crudest choice there is: a gap into a closed pocket of 50 unknown cells beats a doorway into the unexplored half of the building whenever
+ * it is a step closer.  Below, every seed cell is a viewpoint, its gain the number of unknown cells a scanner of R cells' range would look
+ * at from there, and the solve starts every seed at a handicap that falls with its gain.  Integer rays and a count of distinct cells: the
+ * gain is one number whatever order the work is done in, and the bar stays ==.  tests/nav_gain_restatement.py restates G17-G20.
+ *
+ * G17. Rays (host arithmetic, integers only, no trigonometry).  The range R is in cells, 1 <= R <= TBNAV_NAV_MAX_GAIN_RANGE.  The end
+ *     points are the ring E(R) = {(ex, ey) : R*R - R < ex*ex + ey*ey <= R*R + R}, in ascending (ex, ey); no component exceeds R, so a
+ *     viewpoint's rays stay inside the (2R+1)^2 window round it.  The ray to (ex, ey) has n = max(|ex|, |ey|) steps; step s = 1 .. n is the
+ *     offset (sgn(ex) * ((2*s*|ex| + n) / (2*n)), sgn(ey) * ((2*s*|ey| + n) / (2*n))), integer division: closed form per step, no error
+ *     term carried from step to step.  tbnav_nav_gain_rays returns the ring.  (The rays enter about 95 % of the disc's cells; that is
+ *     the rule, not a defect to repair.)
+ * G18. What a ray sees.  UNKNOWN is G10's class, a tile with id 0 unknown throughout; OCCUPIED is G8's bit.  From the viewpoint v a ray
+ *     walks its steps in order and ENDS, without counting the cell, at the first step that leaves the grid, or enters an OCCUPIED cell,
+ *     or changes both coordinates while BOTH cells orthogonally between the previous cell and this one are OCCUPIED (G3's reason: the
+ *     mapper's walls are only 8-connected; with one of the two occupied the ray goes on — grazing a corner does not block it).  Every
+ *     other cell entered is passed through, and is SEEN if it is UNKNOWN.  gain(v) = the number of DISTINCT seen cells over all rays of
+ *     E(R).  FREE cells, known cells that are neither, and v itself never count.
+ * G19. Find with gain.  tbnav_nav_find_frontiers_gain runs G10-G13 exactly as tbnav_nav_find_frontiers does — results, info, kernels and
+ *     rejections the same — and then, in the same call on the filter's stream with nothing of the filter's between the two, gain(v) for
+ *     every seed cell of that find from the same particle's map.  A cell that is no seed has gain 0 and is no viewpoint.
+ *     tbnav_nav_gain_info.best is the least cell index among those with gain_max, (-1, -1) with no viewpoint; a find that leaves no seed
+ *     sets computed = 1 and viewpoints = 0 (gain_min = gain_max = 0), and launches none of the gain's kernels.  The gain belongs to the
+ *     find that made it: a later plain tbnav_nav_find_frontiers leaves the handle with NO gain.  range_cells outside
+ *     1 .. TBNAV_NAV_MAX_GAIN_RANGE is TBNAV_ERR_INVALID_ARG and changes nothing.  tbnav_nav_get_frontier_gain: uint32 [nx*ny];
+ *     tbnav_nav_frontier_gain_list: one record per cluster in ascending label order — root, the cluster's gain_max and the least cell index
+ *     with it; a cluster that is no seed gets 0 and (-1, -1) — a host loop over the downloaded arrays, like G16.  Both are
+ *     TBNAV_ERR_INVALID_ARG while the handle has no gain.
+ * G20. Ranked solve.  tbnav_nav_solve_frontiers_ranked, 0 <= gain_weight <= TBNAV_NAV_MAX_GAIN_WEIGHT: the start is
+ *     start[seed] = gain_weight * (gain_max - gain(seed)) at every seed and UNREACHED elsewhere, and the fixed point
+ *     d[a] = min(start[a], min over allowed moves a -> b of d[b] + w*cost[b]).  The relaxation only ever lowers values, so it is
+ *     nav_relax_tiles unchanged and the fixed point stays unique.  It cannot overflow: a window holds (2*128+1)^2 - 1 = 66048 cells
+ *     beside the viewpoint, so a start is at most 4096 * 66048 = 270 532 608, and with G4's bound 3 758 096 384 the sum is
+ *     4 028 628 992 < 2^32.  gain_weight = 0, or every gain equal, gives tbnav_nav_solve_frontiers bit for bit.  gain_max reaches the
+ *     start kernel on the device; the seed list never crosses the host.  TBNAV_ERR_INVALID_ARG when the handle has no gain, or the cost
+ *     grid or the visited mask was set again since the find (G15's rule), or the weight is out of range; TBNAV_ERR_UNSUPPORTED when the
+ *     find left no seed; in both cases the last solution stays.  G6 generalised: the walk of a ranked solution stops at the first cell
+ *     that is a seed whose d equals its own start value (with all starts 0 that is d == 0; every solve that is not ranked keeps the
+ *     d == 0 rule).  tbnav_nav_solve_info.goal is (-1, -1).  G5 and the hand-over are untouched.
+ *
+ * The kernels (csrc/nav_gain.hip).  nav_gain_classes: one workgroup per tile, nav_frontier_mark's ballots, writes the dense row-word
+ * bitmaps unk[nx][TW] and occ[nx][TW] (the columns of a ragged last word past the map's side are set in occ: leaving the grid ends a
+ * ray as an occupied cell does, and no cell orthogonally beside a step inside the grid lies outside it).  nav_gain_list: the seed words'
+ * bits as a list of cell indices, a slot counter its one atomic; the order is free, the result is indexed by cell.
+ * nav_frontier_gain<RMAX>, RMAX = 32 for R <= 32 and 128 above: one workgroup per viewpoint stages the window's rows of both bitmaps,
+ * shifted so that bit 0 is the window's first column, into LDS beside a zeroed seen bitmap; lanes take rays, walk them (the quotients of
+ * G17 by carrying the remainder — the same integers) and OR bits into the seen bitmap; a popcount gives gain[cell], and one 64-bit
+ * atomicMax of (gain << 32 | ~cell) gives gain_max and best at once, another of ~gain gain_min.  nav_reset_ranked: G20's start.  Integers
+ * only; no workgroup waits for another; every loop is bounded by R or the tile.
+ *
+ * G21. Not built here: sharded filters and handles on different devices; gain per heading or field of view; the reference mapper's habit
+ * of dropping beams without a return (sensor_model.cpp:43-112), which makes the gain an UPPER bound on what a scan clears; gain at cells
+ * that are not seeds; any utility other than the linear one; clearing along beams without a return (the mapper's behaviour stays the
+ * reference's); incremental updates between scans; a time-out for marks.
  *
  * Not thread-safe; one handle per planner object; the handle owns all device memory.  Bad arguments return before any device call.
  */
@@ -152,6 +203,8 @@ extern "C" {
 #define TBNAV_NAV_MAX_REACH 32 /* G7's R: one tile of halo round a workgroup's tile */
 #define TBNAV_NAV_BEST_PARTICLE (-1)
 #define TBNAV_NAV_MAX_VISIT_RADIUS 64 /* G14, cells */
+#define TBNAV_NAV_MAX_GAIN_RANGE 128  /* G17, cells */
+#define TBNAV_NAV_MAX_GAIN_WEIGHT 4096 /* G20 */
 
 typedef struct tbnav_nav_params {
   int32_t nx, ny;     /* cells along x (slow index) and y, each 2 .. TBNAV_NAV_MAX_SIDE */
@@ -269,6 +322,43 @@ int tbnav_nav_solve_frontiers(tbnav_nav* h);
 /* G16.  labels_host: nx*ny values.  out: room for cap records (may be null when cap is 0: *n is then the number needed). */
 int tbnav_nav_get_frontier_labels(tbnav_nav* h, uint32_t* labels_host);
 int tbnav_nav_frontier_list(tbnav_nav* h, tbnav_nav_frontier* out, int32_t cap, int32_t* n);
+
+/* What the last find with gain left (G19). */
+typedef struct tbnav_nav_gain_info {
+  int32_t computed;       /* 1 while the handle holds the gain of its last find                              */
+  int32_t range_cells;    /* R                                                                               */
+  int32_t rays;           /* |E(R)|                                                                          */
+  int32_t viewpoints;     /* the find's seed cells                                                           */
+  int32_t gain_min;       /* over the viewpoints; 0 with none                                                */
+  int32_t gain_max;
+  int32_t best[2];        /* the least cell index with gain_max; (-1, -1) with no viewpoint                  */
+} tbnav_nav_gain_info;
+
+/* One cluster's gain (G19). */
+typedef struct tbnav_nav_frontier_gain {
+  int32_t root[2];        /* as in tbnav_nav_frontier                                                        */
+  int32_t gain_max;       /* the most over the cluster's cells; 0 where the cluster is no seed               */
+  int32_t best[2];        /* the least cell index of the cluster with it; (-1, -1) where it is no seed       */
+} tbnav_nav_frontier_gain;
+
+/* G17, no device needed.  *n = |E(R)| (may be null).  ends (may be null) receives *n pairs (ex, ey); cap, the room it has in pairs, too
+ * small: TBNAV_ERR_INVALID_ARG with *n set. */
+int tbnav_nav_gain_rays(int32_t range_cells, int32_t* ends, int32_t cap, int32_t* n);
+/* G19.  info and ginfo may be null. */
+int tbnav_nav_find_frontiers_gain(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, int32_t range_cells,
+                                  tbnav_nav_frontier_info* info, tbnav_nav_gain_info* ginfo);
+/* Measurement hook (tools/nav_gain_time.py): tbnav_nav_profile_find_frontiers with, in stage_ms[4], the gain's kernels together. */
+int tbnav_nav_profile_find_frontiers_gain(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, int32_t range_cells,
+                                          tbnav_nav_frontier_info* info, tbnav_nav_gain_info* ginfo, float* stage_ms);
+/* The handle's gain info (computed = 0 where it has none). */
+int tbnav_nav_last_gain(const tbnav_nav* h, tbnav_nav_gain_info* ginfo);
+/* The gain's kernels of the last find with gain, spelled as a profiler prints them and separated by ';'; "" where none ran. */
+int tbnav_nav_last_gain_kernels(const tbnav_nav* h, char* kernels, int32_t kernels_cap);
+/* gain_host: nx*ny values.  out: room for cap records (may be null when cap is 0: *n is then the number needed). */
+int tbnav_nav_get_frontier_gain(tbnav_nav* h, uint32_t* gain_host);
+int tbnav_nav_frontier_gain_list(tbnav_nav* h, tbnav_nav_frontier_gain* out, int32_t cap, int32_t* n);
+/* G20, synchronous like tbnav_nav_solve. */
+int tbnav_nav_solve_frontiers_ranked(tbnav_nav* h, int32_t gain_weight);
 
 #ifdef __cplusplus
 }

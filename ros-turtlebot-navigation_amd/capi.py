@@ -92,6 +92,20 @@ class NavFrontier(C.Structure):
                 ("sum_iy", C.c_int64)]
 
 
+NAV_MAX_GAIN_RANGE, NAV_MAX_GAIN_WEIGHT = 128, 4096
+
+
+class NavGainInfo(C.Structure):
+    """tbnav_nav_gain_info (G19)."""
+    _fields_ = [("computed", C.c_int32), ("range_cells", C.c_int32), ("rays", C.c_int32), ("viewpoints", C.c_int32), ("gain_min", C.c_int32),
+                ("gain_max", C.c_int32), ("best", C.c_int32 * 2)]
+
+
+class NavFrontierGain(C.Structure):
+    """tbnav_nav_frontier_gain (G19)."""
+    _fields_ = [("root", C.c_int32 * 2), ("gain_max", C.c_int32), ("best", C.c_int32 * 2)]
+
+
 class RbpfParams(C.Structure):
     """tbnav_rbpf_params (include/tbnav_rbpf.h)."""
     _fields_ = [
@@ -291,6 +305,15 @@ def lib() -> C.CDLL:
         "tbnav_nav_solve_frontiers": (C.c_int, [vp]),
         "tbnav_nav_get_frontier_labels": (C.c_int, [vp, vp]),
         "tbnav_nav_frontier_list": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
+        "tbnav_nav_gain_rays": (C.c_int, [i32, vp, i32, C.POINTER(i32)]),
+        "tbnav_nav_find_frontiers_gain": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(NavFrontierInfo), C.POINTER(NavGainInfo)]),
+        "tbnav_nav_profile_find_frontiers_gain": (C.c_int, [vp, vp, i32, i32, i32, C.POINTER(NavFrontierInfo), C.POINTER(NavGainInfo),
+                                                            C.POINTER(C.c_float)]),
+        "tbnav_nav_last_gain": (C.c_int, [vp, C.POINTER(NavGainInfo)]),
+        "tbnav_nav_last_gain_kernels": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_nav_get_frontier_gain": (C.c_int, [vp, vp]),
+        "tbnav_nav_frontier_gain_list": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
+        "tbnav_nav_solve_frontiers_ranked": (C.c_int, [vp, i32]),
         # communicators (include/tbnav_comm.h) and the sharded MPPI tick
         "tbnav_comm_unique_id": (C.c_int, [vp]),
         "tbnav_comm_unique_id_ipc": (C.c_int, [vp]),

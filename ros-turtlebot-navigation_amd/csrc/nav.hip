@@ -97,7 +97,7 @@ int tbnav_nk::relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy) {
   if (h->cost_host_valid) h->cost_solved = h->cost;
   else TBNAV_HIP(hipMemcpy(h->d_cost_solved, h->d_cost, (size_t)h->n, hipMemcpyDeviceToDevice));
   h->cost_solved_valid = h->cost_host_valid;
-  h->solved = true;
+  h->solved = true; h->ranked = false;   // (tbnav_nav_solve_frontiers_ranked sets it once this has returned)
   h->info.solved = 1; h->info.goal[0] = goal_ix; h->info.goal[1] = goal_iy;
   h->info.rounds = rounds; h->info.launches = launches; h->info.tile_visits = visits;
   return TBNAV_OK;
@@ -232,6 +232,7 @@ int tbnav_nav_path(tbnav_nav* h, int32_t start_ix, int32_t start_iy, int32_t* ce
   if (!h || !n || cells_cap < 0 || (cells_cap > 0 && !cells) || !h->solved || !in_grid(h, start_ix, start_iy)) return TBNAV_ERR_INVALID_ARG;
   int rc = fetch_once(h, h->d_d, h->d_host, h->d_host_valid);
   if (rc == TBNAV_OK) rc = fetch_once(h, h->d_cost_solved, h->cost_solved, h->cost_solved_valid);
+  if (rc == TBNAV_OK && h->ranked) rc = fetch_once(h, h->d_start, h->start_host, h->start_host_valid);
   if (rc != TBNAV_OK) return rc;
   const int ny = h->p.ny;
   const std::vector<unsigned>& d = h->d_host;
@@ -242,7 +243,8 @@ int tbnav_nav_path(tbnav_nav* h, int32_t start_ix, int32_t start_iy, int32_t* ce
   for (;;) {   // d falls strictly along the walk (G6), so it ends within n cells
     if (len < cells_cap) { cells[2 * len] = ix; cells[2 * len + 1] = iy; }
     ++len;
-    if (d[(size_t)ix * ny + iy] == 0) break;
+    // G6: the goal, or the seed reached; G20: a seed that still holds its own start value (kInf off the seeds, which no walked cell holds)
+    if (h->ranked ? d[(size_t)ix * ny + iy] == h->start_host[(size_t)ix * ny + iy] : d[(size_t)ix * ny + iy] == 0) break;
     unsigned best = kInf;
     int bm = -1;
     for (int m = 0; m < 8; ++m) {

@@ -208,7 +208,6 @@ namespace {
 
 const char kFrontierKernels[] = "nav_frontier_mark;nav_frontier_label;nav_frontier_sizes;nav_frontier_seeds";
 
-size_t mask_words(const tbnav_nav* h) { return (size_t)h->p.nx * h->tiles_y; }
 void visited_host(tbnav_nav* h) { if (h->visited.empty()) h->visited.assign(mask_words(h), 0u); }
 
 // the device side of G10-G16, at the first call that needs it (the handle's device is current)
@@ -227,8 +226,10 @@ int ensure_buffers(tbnav_nav* h) {
   return TBNAV_OK;
 }
 
+}  // namespace
+
 // G13, with the stages' times where they are asked for (ms[4]: mark, label rounds with the host's reads, sizes, seeds)
-int find(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info, float* ms) {
+int tbnav_nk::find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info, float* ms) {
   if (!h || !pf || !particle_ok(pf, particle) || min_cells < 1 || !h->cost_set) return TBNAV_ERR_INVALID_ARG;
   int rc = same_grid(h, pf);
   if (rc != TBNAV_OK) return rc;
@@ -246,6 +247,7 @@ int find(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbna
   StageTimer timer(ms != nullptr, 5, st);
   TBNAV_HIP(timer.create());
   h->finfo.found = 0; h->label_host_valid = false;   // from here on the last find's results are being overwritten
+  h->ginfo = tbnav_nav_gain_info{0, 0, 0, 0, 0, 0, {-1, -1}}; h->gain_rmax = 0; h->gain_host_valid = false;   // (G19: the gain belonged to that find)
   TBNAV_HIP(hipMemsetAsync(h->d_fcount, 0, sizeof(unsigned) * 4, st));
   rc = enqueue_best(pf, particle);
   if (rc != TBNAV_OK) return rc;
@@ -281,6 +283,8 @@ int find(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbna
   return TBNAV_OK;
 }
 
+namespace {
+
 // d_d and d_flags from the goals (the seed bits, or d_goals' n_cells pairs), then the rounds (the handle's device is current)
 int solve_from_goals(tbnav_nav* h, int n_cells, int goal_ix, int goal_iy) {
   h->solved = false; h->d_host_valid = false;   // from here on the last solution is being overwritten
@@ -298,12 +302,12 @@ int solve_from_goals(tbnav_nav* h, int n_cells, int goal_ix, int goal_iy) {
 extern "C" {
 
 int tbnav_nav_find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info) {
-  return find(h, pf, particle, min_cells, info, nullptr);
+  return find_frontiers(h, pf, particle, min_cells, info, nullptr);
 }
 
 int tbnav_nav_profile_find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info, float* stage_ms) {
   if (!stage_ms) return TBNAV_ERR_INVALID_ARG;
-  return find(h, pf, particle, min_cells, info, stage_ms);
+  return find_frontiers(h, pf, particle, min_cells, info, stage_ms);
 }
 
 int tbnav_nav_last_frontiers(const tbnav_nav* h, tbnav_nav_frontier_info* info) {

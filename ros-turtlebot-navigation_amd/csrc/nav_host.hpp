@@ -1,8 +1,8 @@
 // nav_host.hpp — the goal field's handle and what its host files share (nav.hip: create / solve / results / hand-over of the solved
 // field; nav_from_map.hip: the cost grid taken from a filter's occupancy bits on the device, tbnav_nav.h G7-G9; nav_frontier.hip: the
-// frontiers of a particle's map, their clusters, and the solves that start from several goals, G10-G16): the rounds of a tiled fixed
-// point, the handle's allocations and lazy host copies, the optional stage timing, and the filter as the source of a grid.  What the
-// kernels share is nav_tiles.hpp.
+// frontiers of a particle's map, their clusters, and the solves that start from several goals, G10-G16; nav_gain.hip: the seeds'
+// information gain and the ranked solve, G17-G20): the rounds of a tiled fixed point, the handle's allocations and lazy host copies,
+// the optional stage timing, and the filter as the source of a grid.  What the kernels share is nav_tiles.hpp.
 #ifndef TBNAV_NAV_HOST_HPP
 #define TBNAV_NAV_HOST_HPP
 #include <hip/hip_runtime.h>
@@ -52,7 +52,22 @@ struct tbnav_nav {
   // a find's seeds are goals only while the grid and the mask it saw are the ones in force: every successful set of either counts
   uint64_t cost_epoch = 0, visited_epoch = 0, found_cost_epoch = 0, found_visited_epoch = 0;
   tbnav_nav_frontier_info finfo{0, 0, 0, 0, 0, 0, 0, 0, 0};
-  std::vector<void**> buffers;      // the d_ members that hold an allocation (dev_alloc lists them, destroy walks them)
+  // G17-G20 (nav_gain.hip), allocated at the first find with gain or ranked solve
+  unsigned* d_gunk = nullptr;       // [nx][tiles_y] UNKNOWN bits of the particle's map (d_front's layout)
+  unsigned* d_gocc = nullptr;       // [nx][tiles_y] OCCUPIED bits, and the columns of a ragged last word past the map's side
+  unsigned* d_glist = nullptr;      // [glist_cap] the viewpoints' cell indices, in no order
+  int glist_cap = 0;
+  short* d_grays = nullptr;         // [kGainMaxRays][2] E(R) of grays_range
+  int grays_range = 0;
+  unsigned* d_gain = nullptr;       // [nx][ny] G18's gain, 0 off the viewpoints
+  unsigned long long* d_gstat = nullptr;   // [0] max of gain << 32 | ~cell, [1] max of ~gain, [2] (as unsigned) the list's slot counter
+  unsigned* d_start = nullptr;      // [nx][ny] the last ranked solve's start values, UNREACHED off its seeds (G6 generalised walks over it)
+  std::vector<unsigned> gain_host, start_host;   // downloaded at their first use
+  bool gain_host_valid = false, start_host_valid = false;
+  bool ranked = false;              // the last solve was a ranked one: tbnav_nav_path stops by start_host
+  int gain_rmax = 0;                // nav_frontier_gain's instantiation of the last find with gain, 0: none ran
+  tbnav_nav_gain_info ginfo{0, 0, 0, 0, 0, 0, {-1, -1}};
+  std::vector<void**> buffers;     // the d_ members that hold an allocation (dev_alloc lists them, destroy walks them)
 };
 
 namespace tbnav_nk {
@@ -105,7 +120,11 @@ int run_rounds(tbnav_nav* h, unsigned* flags, unsigned* d_rec, hipStream_t strea
 // nav.hip: the rounds of nav_relax_tiles from whatever start d_d and d_flags hold (nav_reset / nav_reset_goals have been enqueued on the
 // null stream; the handle's device is current), and what a finished solve leaves in the handle.  h->solved is false while it runs.
 int relax_from_start(tbnav_nav* h, int goal_ix, int goal_iy);
+// nav_frontier.hip: G10-G13 with the stages' times where they are asked for (ms[4]); the handle's gain, if it had one, is gone afterwards
+int find_frontiers(tbnav_nav* h, tbnav_rbpf* pf, int32_t particle, int32_t min_cells, tbnav_nav_frontier_info* info, float* ms);
 
+// words of a bit mask over the grid in TilePool::bm's layout, [nx][tiles_y]: the frontier, seed and visited bits, the gain's classes
+inline size_t mask_words(const tbnav_nav* h) { return (size_t)h->p.nx * h->tiles_y; }
 inline bool in_grid(const tbnav_nav* h, int ix, int iy) { return ix >= 0 && ix < h->p.nx && iy >= 0 && iy < h->p.ny; }
 
 // `count` elements on the device into `slot`, a d_ member of the handle (its device is current); what the member held is freed once

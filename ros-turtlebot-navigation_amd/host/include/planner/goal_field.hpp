@@ -10,13 +10,17 @@
 // the best particle's map on the device (G7-G9).  A node that EXPLORES has no waypoint to type: it replaces the solve by
 //     nav.findFrontiers(filter);  if (!nav.solveToFrontiers()) { /* nothing left to explore */ }
 // — the goals are the frontiers of the best particle's map, the border between what it has seen to be free and what it has not seen
-// (G10-G16) — and calls nav.markVisited(x, y, radius) where it arrives at a frontier that its scans do not clear.
+// (G10-G16) — and calls nav.markVisited(x, y, radius) where it arrives at a frontier that its scans do not clear.  One that would
+// rather drive a little farther to a frontier with more behind it replaces the two calls by
+//     nav.findFrontiersGain(filter, range_m);  if (!nav.solveToFrontiersRanked(gain_weight)) { /* nothing left */ }
+// (G17-G20: every seed's gain is the unknown cells a scan of that range would look at from it).
 // and links libtbnav_host.so + libtbnav_hip.so.
 #ifndef TBNAV_PLANNER_GOAL_FIELD_HPP
 #define TBNAV_PLANNER_GOAL_FIELD_HPP
 
 #include <array>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "controller/mppi.hpp"
@@ -39,6 +43,20 @@ struct Frontier {
   bool seeds = false;          ///< size >= the find's min_cells: its cells are goals of solveToFrontiers
   std::array<int, 4> box{};    ///< ix_min, iy_min, ix_max, iy_max
   double cx = 0.0, cy = 0.0;   ///< the centroid in world coordinates (the mean of the cells' centres)
+};
+
+/// What the last find with gain left (tbnav_nav.h G19).
+struct GainInfo {
+  bool computed = false;          ///< the handle holds the gain of its last find
+  int range_cells = 0, rays = 0, viewpoints = 0, gain_min = 0, gain_max = 0;
+  std::array<int, 2> best{{-1, -1}};   ///< the least cell index with gain_max; (-1, -1) with no viewpoint
+};
+
+/// One cluster's gain (tbnav_nav.h G19).
+struct FrontierGain {
+  std::array<int, 2> root{};           ///< as in Frontier
+  int gain_max = 0;                    ///< the most over the cluster's cells; 0 where the cluster is no seed
+  std::array<int, 2> best{{-1, -1}};   ///< the least cell index of the cluster with it; (-1, -1) where it is no seed
 };
 
 class GoalField {
@@ -76,7 +94,21 @@ class GoalField {
   /// to explore; the last solution then stays.  Throws std::invalid_argument before any find, or when the cost grid or the visited
   /// mask was set again since.
   bool solveToFrontiers();
-  std::vector<std::uint32_t> costToGo();           ///< G4, [nx][ny]; 0xFFFFFFFF = blocked or unreached
+  /// G17-G19: findFrontiers, and in the same call the gain of every seed cell: the distinct unknown cells that integer rays of
+  /// range_m (rounded to cells, 1 .. 128) see from it in the same particle's map.  One FrontierGain per cluster, in findFrontiers' order.
+  /// Throws like findFrontiers, and std::invalid_argument for a range outside 1 .. 128 cells.
+  std::vector<FrontierGain> findFrontiersGain(bmapping::ParticleFilter& filter, double range_m, int min_cells = 8);
+  GainInfo lastGain() const;                       ///< tbnav_nav_last_gain
+  std::vector<std::uint32_t> frontierGain();       ///< G18, [nx][ny]; 0 where the cell is no seed
+  std::vector<FrontierGain> frontierGainList();    ///< G19, one per cluster in ascending label order
+  std::vector<std::string> lastGainKernels() const;   ///< the gain's kernels of the last find with gain, as a profiler prints them
+  /// findFrontiersGain with events between the stages: microseconds of mark, label, sizes, seeds, gain (a measurement hook).
+  std::array<double, 5> profileFindFrontiersGain(bmapping::ParticleFilter& filter, double range_m, int min_cells = 8);
+  /// G20: solveToFrontiers with every seed starting at gain_weight * (gain_max - its gain), 0 <= gain_weight <= 4096: a seed that sees
+  /// more may be farther by that much.  false where the find left no seed.  Throws std::invalid_argument where the last find had no
+  /// gain, the cost grid or the visited mask was set again since, or the weight is out of range.  path() then ends at the seed reached.
+  bool solveToFrontiersRanked(int gain_weight);
+  std::vector<std::uint32_t> costToGo();          ///< G4, [nx][ny]; 0xFFFFFFFF = blocked or unreached
   std::vector<float> field(double cap);            ///< G5, metres to go capped at `cap`
   /// G6 from the cell of (x, y): (ix, iy) pairs, start and goal included.  Throws std::runtime_error from a blocked or unreached start.
   std::vector<std::array<int, 2>> path(double x, double y);

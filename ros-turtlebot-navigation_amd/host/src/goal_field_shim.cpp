@@ -107,6 +107,71 @@ bool GoalField::solveToFrontiers() {
   check(rc, "solveToFrontiers");
   return true;
 }
+namespace {
+int32_t range_cells_of(double range_m, double resolution) {
+  const double cells = std::rint(range_m / resolution);
+  if (!(cells >= 1.0 && cells <= (double)TBNAV_NAV_MAX_GAIN_RANGE)) throw std::invalid_argument("findFrontiersGain: the range must be 1 .. 128 cells");
+  return (int32_t)cells;
+}
+}  // namespace
+std::vector<FrontierGain> GoalField::findFrontiersGain(bmapping::ParticleFilter& filter, double range_m, int min_cells) {
+  if (filter.g_) throw std::runtime_error("findFrontiersGain: a filter over several GPUs is not supported");
+  check(tbnav_nav_find_frontiers_gain(h_, filter.h_, TBNAV_NAV_BEST_PARTICLE, min_cells, range_cells_of(range_m, resolution_), nullptr, nullptr),
+        "findFrontiersGain");
+  return frontierGainList();
+}
+std::array<double, 5> GoalField::profileFindFrontiersGain(bmapping::ParticleFilter& filter, double range_m, int min_cells) {
+  if (filter.g_) throw std::runtime_error("profileFindFrontiersGain: a filter over several GPUs is not supported");
+  float ms[5] = {0, 0, 0, 0, 0};
+  check(tbnav_nav_profile_find_frontiers_gain(h_, filter.h_, TBNAV_NAV_BEST_PARTICLE, min_cells, range_cells_of(range_m, resolution_), nullptr, nullptr, ms),
+        "profileFindFrontiersGain");
+  return {ms[0] * 1e3, ms[1] * 1e3, ms[2] * 1e3, ms[3] * 1e3, ms[4] * 1e3};
+}
+GainInfo GoalField::lastGain() const {
+  tbnav_nav_gain_info gi{};
+  check(tbnav_nav_last_gain(h_, &gi), "lastGain");
+  GainInfo out;
+  out.computed = gi.computed != 0;
+  out.range_cells = gi.range_cells; out.rays = gi.rays; out.viewpoints = gi.viewpoints; out.gain_min = gi.gain_min; out.gain_max = gi.gain_max;
+  out.best = {gi.best[0], gi.best[1]};
+  return out;
+}
+std::vector<std::uint32_t> GoalField::frontierGain() {
+  std::vector<std::uint32_t> gain((size_t)nx_ * ny_);
+  check(tbnav_nav_get_frontier_gain(h_, gain.data()), "frontierGain");
+  return gain;
+}
+std::vector<FrontierGain> GoalField::frontierGainList() {
+  int32_t n = 0;
+  const int rc = tbnav_nav_frontier_gain_list(h_, nullptr, 0, &n);   // the number first: "buffer too small" with n set
+  if (n <= 0) { check(rc, "frontierGainList"); return {}; }
+  std::vector<tbnav_nav_frontier_gain> recs((size_t)n);
+  check(tbnav_nav_frontier_gain_list(h_, recs.data(), n, &n), "frontierGainList");
+  std::vector<FrontierGain> out((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    out[(size_t)i].root = {recs[(size_t)i].root[0], recs[(size_t)i].root[1]};
+    out[(size_t)i].gain_max = recs[(size_t)i].gain_max;
+    out[(size_t)i].best = {recs[(size_t)i].best[0], recs[(size_t)i].best[1]};
+  }
+  return out;
+}
+std::vector<std::string> GoalField::lastGainKernels() const {
+  char names[160];
+  check(tbnav_nav_last_gain_kernels(h_, names, (int32_t)sizeof names), "lastGainKernels");
+  std::vector<std::string> out;
+  std::string cur;
+  for (const char* c = names; ; ++c) {
+    if (*c == ';' || *c == '\0') { if (!cur.empty()) out.push_back(cur); cur.clear(); if (*c == '\0') break; }
+    else cur += *c;
+  }
+  return out;
+}
+bool GoalField::solveToFrontiersRanked(int gain_weight) {
+  const int rc = tbnav_nav_solve_frontiers_ranked(h_, gain_weight);
+  if (rc == TBNAV_ERR_UNSUPPORTED) return false;   // the find left no seed
+  check(rc, "solveToFrontiersRanked");
+  return true;
+}
 std::vector<std::uint32_t> GoalField::costToGo() {
   std::vector<std::uint32_t> d((size_t)nx_ * ny_);
   check(tbnav_nav_get_cost_to_go(h_, d.data()), "costToGo");

@@ -1,6 +1,6 @@
 """Python mirror of planner::GoalField over the C-ABI of include/tbnav_nav.h (tests / tools plumbing): the exact cost-to-go to a
 goal cell over a cost grid, solved on the device, and its hand-over to an MPPI handle as a cost field.  The header is the
-specification (G1-G16); the shipped host surface for ROS nodes is the C++ class in host/include/planner/goal_field.hpp.
+specification (G1-G21); the shipped host surface for ROS nodes is the C++ class in host/include/planner/goal_field.hpp.
 """
 from __future__ import annotations
 
@@ -37,6 +37,16 @@ def inflation_tables(resolution: float, r_robot: float, r_inflate: float, k: flo
                                             C.byref(n), C.byref(reach)), "tbnav_nav_inflation_tables")
     assert n.value + 1 == cost.size
     return cost, field, reach.value
+
+
+def gain_rays(range_cells: int) -> np.ndarray:
+    """tbnav_nav_gain_rays (tbnav_nav.h G17; no GPU needed): int32 [n][2], the end points (ex, ey) of the rays in ascending order."""
+    L = capi.lib()
+    n = C.c_int32()
+    capi.check(L.tbnav_nav_gain_rays(int(range_cells), None, 0, C.byref(n)), "tbnav_nav_gain_rays")
+    ends = np.empty((n.value, 2), dtype=np.int32)
+    capi.check(L.tbnav_nav_gain_rays(int(range_cells), ends.ctypes.data, n.value, C.byref(n)), "tbnav_nav_gain_rays")
+    return ends
 
 
 class GoalField:
@@ -176,6 +186,64 @@ class GoalField:
         """The kernels a find launches, as a profiler prints them; [] before the first find."""
         name = C.create_string_buffer(160)
         capi.check(self._L.tbnav_nav_last_frontier_kernels(self._h, name, 160), "tbnav_nav_last_frontier_kernels")
+        return [k for k in name.value.decode().split(";") if k]
+
+    # ---- frontiers ranked by what a scan from them would reveal (tbnav_nav.h G17-G20) ----
+    @staticmethod
+    def _gain_info(gi) -> dict:
+        return dict(computed=bool(gi.computed), range_cells=gi.range_cells, rays=gi.rays, viewpoints=gi.viewpoints, gain_min=gi.gain_min,
+                    gain_max=gi.gain_max, best=(gi.best[0], gi.best[1]))
+
+    def findFrontiersGain(self, pf, range_cells: int, min_cells: int = 8, particle=None):
+        """G19: findFrontiers, and in the same call the gain of every seed cell at a range of range_cells: (info, gain info)."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        info, gi = capi.NavFrontierInfo(), capi.NavGainInfo()
+        capi.check(self._L.tbnav_nav_find_frontiers_gain(self._h, pf._h, p, int(min_cells), int(range_cells), C.byref(info), C.byref(gi)),
+                   "tbnav_nav_find_frontiers_gain")
+        return self._frontier_info(info), self._gain_info(gi)
+
+    def profileFindFrontiersGain(self, pf, range_cells: int, min_cells: int = 8, particle=None):
+        """findFrontiersGain with events between its stages: (info, gain info, microseconds of mark / label / sizes / seeds / gain)."""
+        p = capi.NAV_BEST_PARTICLE if particle is None else int(particle)
+        info, gi, ms = capi.NavFrontierInfo(), capi.NavGainInfo(), (C.c_float * 5)()
+        capi.check(self._L.tbnav_nav_profile_find_frontiers_gain(self._h, pf._h, p, int(min_cells), int(range_cells), C.byref(info), C.byref(gi), ms),
+                   "tbnav_nav_profile_find_frontiers_gain")
+        return self._frontier_info(info), self._gain_info(gi), dict(zip(("mark", "label", "sizes", "seeds", "gain"), (v * 1e3 for v in ms)))
+
+    def lastGain(self) -> dict:
+        gi = capi.NavGainInfo()
+        capi.check(self._L.tbnav_nav_last_gain(self._h, C.byref(gi)), "tbnav_nav_last_gain")
+        return self._gain_info(gi)
+
+    def frontierGain(self) -> np.ndarray:
+        """G18: uint32 [nx][ny], the distinct unknown cells the rays from a seed cell see; 0 where the cell is no seed."""
+        gain = np.empty((self.nx, self.ny), dtype=np.uint32)
+        capi.check(self._L.tbnav_nav_get_frontier_gain(self._h, gain.ctypes.data), "tbnav_nav_get_frontier_gain")
+        return gain
+
+    def frontierGainList(self) -> list:
+        """G19: one dict per cluster in ascending label order: root, gain_max, best; 0 and (-1, -1) where the cluster is no seed."""
+        n = C.c_int32(0)
+        rc = self._L.tbnav_nav_frontier_gain_list(self._h, None, 0, C.byref(n))
+        if n.value <= 0:
+            capi.check(rc, "tbnav_nav_frontier_gain_list")
+            return []
+        recs = (capi.NavFrontierGain * n.value)()
+        capi.check(self._L.tbnav_nav_frontier_gain_list(self._h, recs, n.value, C.byref(n)), "tbnav_nav_frontier_gain_list")
+        return [dict(root=(r.root[0], r.root[1]), gain_max=r.gain_max, best=(r.best[0], r.best[1])) for r in recs[:n.value]]
+
+    def solveFrontiersRanked(self, gain_weight: int) -> bool:
+        """G20: every seed starts at gain_weight * (gain_max - its gain).  False where the find left no seed; the last solution stays."""
+        rc = self._L.tbnav_nav_solve_frontiers_ranked(self._h, int(gain_weight))
+        if rc == capi.ERR_UNSUPPORTED:
+            return False
+        capi.check(rc, "tbnav_nav_solve_frontiers_ranked")
+        return True
+
+    def lastGainKernels(self) -> list:
+        """The gain's kernels of the last find with gain, as a profiler prints them; [] where none ran."""
+        name = C.create_string_buffer(160)
+        capi.check(self._L.tbnav_nav_last_gain_kernels(self._h, name, 160), "tbnav_nav_last_gain_kernels")
         return [k for k in name.value.decode().split(";") if k]
 
     def cellOf(self, x: float, y: float) -> tuple:
