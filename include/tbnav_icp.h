@@ -288,6 +288,79 @@
  *  icp_search_shape (csrc/icp_search_shape.hip), one workgroup per pair behind the final icp_search_select and only when the
  *  shape is asked for, scores the chosen angle once more in the same way and reduces the integers of F3; its 64-byte record
  *  comes back in the synchronisation that brings the selection back: no further synchronisation.
+ *  GLOBAL SEARCH (an addition, tbnav_icp_localize_map; csrc/icp_global.hip; restated in tests/icp_global_restatement.py, reproduced
+ *  exactly).  The map search scores a window round a guess: a table of at most 176 / 208 cells a side, +-64 cells and +-180 steps.
+ *  The global search takes NO guess: it scores every heading at every cell of a particle's map, and prunes with an upper bound
+ *  taken from a max-pooled copy of the likelihood map (Olson 2009; Cartographer's fast correlative matcher).  The bound is exact,
+ *  so the result is the exhaustive search's.  All arithmetic is integer but for L3's offsets.
+ *  L1. Handles and parameters.  An ICP handle h and a filter handle pf as in M1: one device, no member of a sharded group, and M1's
+ *      order of the checks (arguments, parameters and the particle: INVALID_ARG; then device, group and the limits below:
+ *      UNSUPPORTED).  The cloud's beam geometry and Trs are h's (item 1); stamp_cells, sigma and resolution are h's search parameters
+ *      (the defaults while its search is off); the resolution must equal the filter's as doubles.  particle is a slot or
+ *      TBNAV_ICP_MAP_BEST_PARTICLE.  side = the map's side <= TBNAV_ICP_GLOBAL_MAX_SIDE = 2048, a larger one is
+ *      TBNAV_ERR_UNSUPPORTED (a candidate's linear index then fits in 32 bits: 720 * 2048^2 < 2^32).
+ *      tbnav_icp_global_params (defaults in brackets): ang_count NA [360, 1..TBNAV_ICP_GLOBAL_MAX_ANG = 720]; ang_step [pi/180,
+ *      finite]; pool_log2 q [3, 1..5], s = 2^q; region[4] = (tx0, ty0, tx1, ty1), inclusive cells [all -1: the whole map], otherwise
+ *      0 <= tx0 <= tx1 < side and likewise for y, w = tx1 - tx0 + 1, h = ty1 - ty0 + 1; min_quality [0.5, finite]; one reserved
+ *      int32 that must be 0.  NULL params are the defaults.  A bad field is TBNAV_ERR_INVALID_ARG.  More than 2^26 blocks (L5) is
+ *      TBNAV_ERR_UNSUPPORTED.  n_beams is 1..TBNAV_ICP_MAX_BEAMS.  Anything rejected changes nothing; the filter is only ever
+ *      read; h's stored scan, its parameters and the last records of the other searches are untouched by any call of this section.
+ *  L2. Likelihood map.  lik(ci, cj), a uint8 for every map cell, is M4's value with the map cell in the table cell's place: the
+ *      maximum of stamp[mj - cj + k][mi - ci + k] (S3's stamp) over the occupied cells (mi, mj) (M2) with both offsets in -k..k, 0
+ *      where there is none.  lik is 0 for every cell outside the map.  The host's check that the stamp never rises with the squared
+ *      distance, and its TBNAV_ERR_UNSUPPORTED, are M4's.  occupied = the number of occupied cells of the map.
+ *  L3. Candidates.  Heading ia in 0..NA-1: theta = (double)ia * ang_step, its cosine and sine (c, s) from the host's glibc, uploaded
+ *      (as in S5).  The robot stands at the CENTRE of map cell (tx, ty) of the region.  For a valid source point (sx, sy) (the
+ *      doubles of its floats) the cell offset is taken once per heading: vx = ((((c * sx) - (s * sy))) * inv) + 0.5,
+ *      vy = ((((s * sx) + (c * sy))) * inv) + 0.5, fp64 with no contraction, inv = 1.0 / resolution; ox = (int)floor(vx),
+ *      oy = (int)floor(vy).  A point with vx or vy not within +-65536 (a NaN included) adds nothing at that heading (S5's guard).
+ *      score(ia, tx, ty) = the sum over the valid points of lik(tx + ox, ty + oy), a uint32.  The offsets do not depend on
+ *      (tx, ty): that is what makes L5's bound exact.
+ *  L4. Result.  The maximum score over all candidates, ties going to the lowest linear index (ia * side + tx) * side + ty.
+ *      T = (theta, xmin + ((double)tx + 0.5) * resolution, ymin + ((double)ty + 0.5) * resolution), theta not wrapped.  points = the
+ *      valid source points; quality = (double)score / (255.0 * (double)points), 0 with no point; accepted = quality >= min_quality
+ *      and points > 0 and occupied > 0.  With points = 0 or occupied = 0 every score is 0: the result is the region's first
+ *      candidate (ia = 0, tx0, ty0) with accepted = 0.
+ *  L5. Blocks and bounds.  Blocks of s x s cells tile the region from (tx0, ty0); the last ones may be ragged.  nbx = ceil(w / s),
+ *      nby = ceil(h / s), blocks = NA * nbx * nby.  pool(i, j) = the maximum over 0 <= a, b < s of lik(i + a, j + b), for any
+ *      integers i, j: the window FORWARD of the cell.  bound(ia, Bx, By) = the sum over the valid points of
+ *      pool(tx0 + Bx * s + ox, ty0 + By * s + oy) (the guarded points of L3 adding nothing).  bound >= the score of every
+ *      candidate of the block; a ragged block's pool reaches past the region, which only raises the bound.
+ *  L6. What the search may skip: a block only if its bound is < a score some candidate has actually attained.  A block whose bound
+ *      EQUALS that score may hold the answer by L4's index rule, so it is refined.  How seeds are chosen, how many rounds run and
+ *      how survivors are listed is the implementation's; the result is L4's whatever they are.  refined_blocks (the blocks whose
+ *      candidates were all scored) and rounds (the refinement launches) are reported.
+ *  L7. Record tbnav_icp_global_info: searched, accepted, T[3], ia, tx, ty, score, points, occupied, quality, blocks, refined_blocks
+ *      (int64 both), rounds.  searched = 0 and everything else 0 before the first call.
+ *  L8. Ordering: M8's.  The kernels run behind whatever the filter's stream has in flight, through an event, with no host
+ *      synchronisation of that stream; the call returns with the record on the host.
+ *  L9. Entries: tbnav_icp_localize_map; tbnav_icp_localize_map_timed (the same call, its stages timed by events); tbnav_icp_last_global; tbnav_icp_last_global_kernels (the last call's kernels by the names a
+ *      profiler prints, ';'-separated, "" before the first call).  Test hooks, stateless (the last record and the kernel names stay):
+ *      tbnav_icp_localize_map_field (lik [side][side] indexed [ci][cj]; pool [side + s - 1][side + s - 1] indexed
+ *      [i + s - 1][j + s - 1] for i, j in -(s - 1)..side - 1: the s - 1 rows and columns before cell 0 included; occupied);
+ *      tbnav_icp_localize_map_bounds (uint32 [NA][nbx][nby]); tbnav_icp_localize_map_scores (EVERY candidate's score,
+ *      uint32 [NA][w][h] indexed [ia][tx - tx0][ty - ty0], computed by the refinement kernel run over all blocks;
+ *      TBNAV_ERR_UNSUPPORTED above 2^24 candidates).
+ *  L10. Not built: a free-space penalty or a restriction to FREE cells (M9's wrong-room finding applies unchanged); several
+ *      hypotheses or a runner-up at a distance (a symmetric building has several equal answers and the index rule picks one);
+ *      sub-cell or sub-step refinement (a caller runs tbnav_icp_search_map or the filter's hill-climb from T); seeding the
+ *      filter's particles from the result; batches of scans; sharded filters; more than one level of pooling in the contract (an
+ *      implementation may use more inside, L6).
+ *  KERNELS (csrc/icp_global.hip).  icp_global_field, one workgroup of 256 threads per 32 x 32 map tile: icp_search_table_from_occ's
+ *  staged rows and nearest-set-bit search (icp_search_device.hpp: occ_row_window, nearest_occ_d2) with the window at the tile itself;
+ *  lik goes into a byte map [P][P], P = side + 2 * 32 rounded up to 64, cell (ci, cj) at [ci + 32][cj + 32], the margin zero, so that
+ *  a gather needs a clamp of its coordinates (one v_med3 each) and no bounds test; occupied is one integer atomic add per tile.
+ *  icp_global_pool: the s x s forward sliding maximum of that map, rows then columns through LDS, into a second map of the same
+ *  layout.  icp_global_offsets, one workgroup per heading: L3's (ox, oy) of the points that can add anything, packed as two int16
+ *  and compacted in no order (a sum of integers has none), with their count; points.  icp_global_bound, one workgroup per (heading,
+ *  4 x 64 blocks): the heading's offsets in LDS, lanes along By (ty is the map's fast index, so a wave's gathers for one point fall
+ *  in one row of the pooled map); it also leaves the largest bound.  icp_global_hist: 1024 bins over 0..the largest bound, from which
+ *  the host takes the least bound that still leaves 16 seeds.  icp_global_list: the blocks with lo <= bound < hi into a list
+ *  through one slot counter (round 1: the seeds; round 2: lo = the best score the seeds attained, hi = the seeds' least bound).
+ *  icp_global_refine, one workgroup per listed block, scores its s^2 candidates against lik and settles maximum and tie with one
+ *  64-bit atomicMax of (score << 32 | ~linear index) per wave; a block whose bound is 0 holds only zeros and is settled by its
+ *  first candidate without a gather.  No workgroup waits for another; every loop is bounded by the points, the tile or s; a round is
+ *  a launch and the host reads one small record per round: at most two rounds.
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
@@ -538,6 +611,60 @@ int tbnav_icp_search_map_wide_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t parti
                                      const double T_init[3], tbnav_icp_search_info* info, uint32_t* scores);
 /* the table kernel's name as a profiler prints it; "" until the route has run on this handle */
 int tbnav_icp_last_map_kernel(const tbnav_icp* h, char* kernel, int32_t kernel_cap);
+
+/* ---- GLOBAL SEARCH: where the robot is in a particle's map, with no guess (L1-L10 of the section of that name) ---- */
+#define TBNAV_ICP_GLOBAL_MAX_SIDE 2048
+#define TBNAV_ICP_GLOBAL_MAX_ANG 720
+#define TBNAV_ICP_GLOBAL_MAX_BLOCKS (1 << 26)
+#define TBNAV_ICP_GLOBAL_MAX_HOOK_SCORES (1 << 24)
+
+typedef struct tbnav_icp_global_params {
+  double ang_step;      /* pi / 180 */
+  double min_quality;   /* 0.5 */
+  int32_t ang_count;    /* 360 */
+  int32_t pool_log2;    /* 3 */
+  int32_t region[4];    /* tx0, ty0, tx1, ty1, inclusive; all -1: the whole map */
+  int32_t reserved;     /* must be 0 */
+} tbnav_icp_global_params;
+
+typedef struct tbnav_icp_global_info {
+  double T[3];          /* L4 */
+  double quality;
+  int64_t blocks;       /* L5 */
+  int64_t refined_blocks;
+  uint32_t score;
+  int32_t points;       /* valid source points */
+  int32_t occupied;     /* occupied cells of the map */
+  int32_t ia, tx, ty;   /* the chosen candidate */
+  int32_t rounds;
+  int32_t accepted;
+  int32_t searched;     /* 0: no global search has run on this handle; all else is 0 then */
+  int32_t reserved;
+} tbnav_icp_global_info;
+
+void tbnav_icp_default_global_params(tbnav_icp_global_params* p);
+/* the pose of one scan in particle's map (L1-L8); params may be NULL (the defaults); info is required */
+int tbnav_icp_localize_map(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                           const tbnav_icp_global_params* params, tbnav_icp_global_info* info);
+/* the same call with its stages timed by events on the handle's stream: stage_ms [TBNAV_ICP_GLOBAL_STAGES] = icp_global_field (with
+ * the map's memset), _pool, _offsets, _bound, _hist, round 1's _list and _refine, round 2's _list and _refine (0 where no second round
+ * ran); NULL: no event is created and the call IS tbnav_icp_localize_map.  The host's reads between the rounds are in no stage. */
+#define TBNAV_ICP_GLOBAL_STAGES 9
+int tbnav_icp_localize_map_timed(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                 const tbnav_icp_global_params* params, tbnav_icp_global_info* info, float* stage_ms);
+/* the record of the last tbnav_icp_localize_map of this handle (searched = 0 when none ran) */
+int tbnav_icp_last_global(const tbnav_icp* h, tbnav_icp_global_info* info);
+/* the last call's kernels as a profiler prints them, ';'-separated; "" before the first call */
+int tbnav_icp_last_global_kernels(const tbnav_icp* h, char* buf, int32_t cap);
+/* test hook (L9): lik [side][side], pool [side + s - 1][side + s - 1], occupied; all three are required */
+int tbnav_icp_localize_map_field(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const tbnav_icp_global_params* params, uint8_t* lik,
+                                 uint8_t* pool, int32_t* occupied);
+/* test hook (L9): the bound volume, uint32 [NA][nbx][nby] */
+int tbnav_icp_localize_map_bounds(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                  const tbnav_icp_global_params* params, uint32_t* bounds);
+/* test hook (L9): every candidate's score, uint32 [NA][w][h] */
+int tbnav_icp_localize_map_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                  const tbnav_icp_global_params* params, uint32_t* scores);
 
 #ifdef __cplusplus
 }

@@ -198,6 +198,23 @@ ICP_WIDE_ON_REJECT, ICP_WIDE_ON_REJECT_OR_EDGE, ICP_WIDE_ALWAYS = 0, 1, 2
 ICP_MAP_BEST_PARTICLE = -1
 
 
+class IcpGlobalParams(C.Structure):
+    """tbnav_icp_global_params (include/tbnav_icp.h, GLOBAL SEARCH, L1)."""
+    _fields_ = [("ang_step", C.c_double), ("min_quality", C.c_double), ("ang_count", C.c_int32), ("pool_log2", C.c_int32),
+                ("region", C.c_int32 * 4), ("reserved", C.c_int32)]
+
+
+class IcpGlobalInfo(C.Structure):
+    """tbnav_icp_global_info (L7)."""
+    _fields_ = [("T", C.c_double * 3), ("quality", C.c_double), ("blocks", C.c_int64), ("refined_blocks", C.c_int64),
+                ("score", C.c_uint32), ("points", C.c_int32), ("occupied", C.c_int32), ("ia", C.c_int32), ("tx", C.c_int32),
+                ("ty", C.c_int32), ("rounds", C.c_int32), ("accepted", C.c_int32), ("searched", C.c_int32), ("reserved", C.c_int32)]
+
+
+ICP_GLOBAL_STAGES = 9
+ICP_GLOBAL_MAX_SIDE, ICP_GLOBAL_MAX_ANG, ICP_GLOBAL_MAX_BLOCKS, ICP_GLOBAL_MAX_HOOK_SCORES = 2048, 720, 1 << 26, 1 << 24
+
+
 _lib = None
 
 
@@ -445,6 +462,14 @@ def lib() -> C.CDLL:
         "tbnav_icp_search_map_scores": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpSearchInfo), vp]),
         "tbnav_icp_search_map_wide_scores": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpSearchInfo), vp]),
         "tbnav_icp_last_map_kernel": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_icp_default_global_params": (None, [C.POINTER(IcpGlobalParams)]),
+        "tbnav_icp_localize_map": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), C.POINTER(IcpGlobalInfo)]),
+        "tbnav_icp_localize_map_timed": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), C.POINTER(IcpGlobalInfo), vp]),
+        "tbnav_icp_last_global": (C.c_int, [vp, C.POINTER(IcpGlobalInfo)]),
+        "tbnav_icp_last_global_kernels": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_icp_localize_map_field": (C.c_int, [vp, vp, i32, C.POINTER(IcpGlobalParams), vp, vp, C.POINTER(i32)]),
+        "tbnav_icp_localize_map_bounds": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
+        "tbnav_icp_localize_map_scores": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

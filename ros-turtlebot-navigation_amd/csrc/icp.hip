@@ -566,6 +566,7 @@ void tbnav_icp_destroy(tbnav_icp* h) {
     (void)hipFree(h->d_table);
     for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out}) b->release();
     search_free(h);
+    global_free(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);
   }
   delete h;

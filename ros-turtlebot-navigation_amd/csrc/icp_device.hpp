@@ -107,6 +107,22 @@ struct IcpSearch {
   std::vector<unsigned char> h_in, h_sel, h_shape, h_win, h_wsel, h_wshape, h_map;
 };
 
+// the global search's state in the handle (tbnav_icp.h, GLOBAL SEARCH; icp_global.hip owns the buffers, grown on demand)
+struct IcpGlobal {
+  tbnav_icp_global_info last{};     // tbnav_icp_last_global
+  const char* kernels = "";         // tbnav_icp_last_global_kernels
+  DevBuf d_lik, d_pool;             // uint8_t [P][P]: L2's map and L5's pooled copy, zero margin included
+  DevBuf d_in;                      // per call: the value-by-d2 table, then the headings' (cos, sin)
+  DevBuf d_scan;                    // float [n_beams]
+  DevBuf d_off;                     // uint32_t [NA][n_beams]: L3's offsets per heading, packed, compacted in no order
+  DevBuf d_cnt;                     // uint32_t [NA]: how many each heading holds
+  DevBuf d_bounds;                  // uint32_t [blocks]
+  DevBuf d_list;                    // uint32_t: the blocks of a round
+  DevBuf d_scores;                  // uint32_t: the test hook's score volume
+  DevBuf d_rec;                     // GlobalRec, then the seeding histogram
+  std::vector<unsigned char> h_in;
+};
+
 }  // namespace tbnav_icpdev
 
 struct tbnav_icp {
@@ -129,6 +145,7 @@ struct tbnav_icp {
   std::vector<tbnav_icpdev::IcpPair> h_pairs;
   std::vector<tbnav_icpdev::IcpOut> h_out;
   tbnav_icpdev::IcpSearch search;
+  tbnav_icpdev::IcpGlobal global;
   std::vector<std::array<double, 3>> h_init;        // T_init of h_pairs, as given (the search starts from the doubles)
   std::vector<tbnav_icp_search_info> h_sinfo;       // the search record of h_pairs (run_pairs)
   std::vector<tbnav_icp_search_shape> h_sshape;     // and the shape record beside it (computed = 0 where the shape did not run)
@@ -152,5 +169,7 @@ int search_pairs(tbnav_icp* h, int n_pairs, int n_beams, const tbnav_icp_search_
                  const tbnav_icp_search_shape_params* shp, const tbnav_icp_search_wide_params* wp = nullptr,
                  uint32_t* wide_scores = nullptr, const MapSource* map = nullptr);
 void search_free(tbnav_icp* h);
+// icp_global.hip
+void global_free(tbnav_icp* h);
 
 }  // namespace tbnav_icpdev

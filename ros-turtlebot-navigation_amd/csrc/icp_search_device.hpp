@@ -2,7 +2,9 @@
 // its score volume (icp_search_shape.hip) share: the by-value constants, the per-pair input and result, the cell of a
 // coordinate, the names of the wave reductions they use (wave.hpp) and the scoring front (load_table, base_cells, slow_read: what icp_search_score and
 // icp_search_shape do before they score, and how either reads a table byte for a point of the slow list), and what the search against
-// a filter's map (icp_search_map.hip) hands to search_pairs in place of target scans (MapPair, MapSource).
+// a filter's map (icp_search_map.hip) hands to search_pairs in place of target scans (MapPair, MapSource), and the nearest occupied
+// cell of a filter's map (occ_row_window, nearest_occ_d2), which that file's table kernel and the global search's field kernel
+// (icp_global.hip) both call.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -135,6 +137,67 @@ struct MapSource {
   std::vector<double2> local;      // [n_pairs] (x0 - o.x, y0 - o.y)
   uint8_t value[kMapValues];       // S3's stamp by d2 = ox^2 + oy^2, 0 .. 2k^2 (M4)
 };
+// ---- the nearest occupied cell of a filter's map, what icp_search_table_from_occ (icp_search_map.hip) and icp_global_field
+// (icp_global.hip) both stand on.  A workgroup stages kOccRows map rows (a tile's 32 and kOccHalo either side) as kOccRows-bit
+// windows of the map's columns; a cell then looks at rows dr = 0 .. k either side of its own. ----
+constexpr int kOccTile = 32;                               // a tile of the filter's pool, and a word of it
+constexpr int kOccHalo = TBNAV_ICP_SEARCH_MAX_STAMP;       // rows and bits staged either side of the tile, whatever k is
+constexpr int kOccRows = kOccTile + 2 * kOccHalo;          // 48 staged rows of 48 bits
+static_assert(kOccRows <= 64 && kOccRows <= kWave, "a staged row is one 64-bit window, and one wave stages them all");
+
+// bits g0 .. g0 + kOccRows - 1 of map row mx (bit b: map column g0 + b), funnel-shifted out of up to three words read through the
+// particle's tile table ids ([TW][TW]; tile id 0, tiles outside the map, rows outside it and the columns of a ragged last tile read as
+// empty).  g0 may be anywhere relative to the map.
+__device__ __forceinline__ unsigned long long occ_row_window(const unsigned int* __restrict__ bm, const unsigned int* __restrict__ ids,
+                                                             int TW, int side, int mx, int g0) {
+  const int w0 = g0 >> 5, o = g0 & 31;                      // (an arithmetic shift: floor for a window that starts left of the map)
+  unsigned int w[3] = {0u, 0u, 0u};
+  if (mx >= 0 && mx < side) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int wy = w0 + j;
+      if (wy < 0 || wy >= TW) continue;
+      const unsigned int id = ids[(mx >> 5) * TW + wy];
+      if (id != 0u) w[j] = bm[(size_t)id * kOccTile + (mx & (kOccTile - 1))];
+      const int inside = side - wy * kOccTile;                // columns of this tile that are cells of the map (>= 1)
+      if (inside < kOccTile) w[j] &= (1u << inside) - 1u;
+    }
+  }
+  unsigned long long win = (((unsigned long long)w[1] << 32) | w[0]) >> o;
+  if (o > 64 - kOccRows) win |= (unsigned long long)w[2] << (64 - o);
+  return win & ((1ull << kOccRows) - 1ull);
+}
+
+// the least dr^2 + dc^2 over the set bits within k rows and k columns of bit c (kOccHalo .. kOccHalo + 31) of staged row
+// kOccHalo + lx, or 1 << 20 where there is none: rows outwards, the nearest set bit left and right of c in each (clz / ffs on the
+// masked window), stopping at the first dr with dr^2 >= the best so far
+__device__ __forceinline__ int nearest_occ_d2(const unsigned long long* s_occ, int lx, int c, int k) {
+  const unsigned int m = (1u << (k + 1)) - 1u;
+  int best = 1 << 20;
+  for (int dr = 0; dr <= k && dr * dr < best; ++dr) {
+    for (int s = 0; s < (dr == 0 ? 1 : 2); ++s) {
+      const unsigned long long row = s_occ[kOccHalo + lx + (s ? dr : -dr)];   // rows 0 .. 47: dr <= k <= kOccHalo
+      const unsigned int left = (unsigned int)(row >> (c - k)) & m;           // bit q: column offset q - k
+      const unsigned int right = (unsigned int)(row >> c) & m;                // bit q: column offset q
+      if (left) {
+        const int dc = k - (31 - __clz((int)left));
+        const int d2 = dr * dr + dc * dc;
+        best = d2 < best ? d2 : best;
+      }
+      if (right) {
+        const int dc = __ffs((int)right) - 1;
+        const int d2 = dr * dr + dc * dc;
+        best = d2 < best ? d2 : best;
+      }
+    }
+  }
+  return best;
+}
+
+// icp_search_map.hip: S3's stamp by d2 = ox^2 + oy^2, 0 .. 2k^2, into value[kMapValues]; TBNAV_ERR_UNSUPPORTED should it ever rise
+// with d2 (M4's nearest-cell form stands on its never rising)
+int map_value_table(const tbnav_icp_search_params& sp, uint8_t* value);
+
 // icp_search.hip: S1's limits, and the constants of parameters that keep them
 bool search_params_ok(const tbnav_icp_search_params& p);
 SearchConst search_const(const tbnav_icp_search_params& p);

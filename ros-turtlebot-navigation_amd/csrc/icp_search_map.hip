@@ -35,13 +35,13 @@ namespace {
 
 using namespace tbnav_icpdev;
 
-constexpr int kTile = tbnav_rk::kTS;                       // 32: a table tile is as large as a tile of the filter's pool, and a word of it
-constexpr int kHalo = TBNAV_ICP_SEARCH_MAX_STAMP;          // rows and bits staged either side of the tile, whatever k is
-constexpr int kRows = kTile + 2 * kHalo;                   // 48 staged rows of 48 bits
+constexpr int kTile = kOccTile;                            // 32: a table tile is as large as a tile of the filter's pool, and a word of it
+constexpr int kHalo = kOccHalo;                            // rows and bits staged either side of the tile, whatever k is
+constexpr int kRows = kOccRows;                            // 48 staged rows of 48 bits
 constexpr int kOutStride = kTile + 4;                      // bytes per transposed row in LDS: 9 dwords, odd, so 32 iy hit 32 banks
 constexpr int kOwn = kTile * kTile / kThreads;             // cells per thread
 constexpr int kRowStep = kThreads / kTile;
-static_assert(kTile == 32 && kRows <= 64 && kRows <= tbnav_icpdev::kWave, "a staged row is one 64-bit window, and wave 0 stages them all");
+static_assert(kTile == tbnav_rk::kTS && kTile == 32, "a table tile is a tile of the filter's pool");
 
 struct OccArgs {
   const unsigned int* bm;      // TilePool::bm
@@ -68,23 +68,7 @@ __global__ __launch_bounds__(kThreads) void icp_search_table_from_occ(OccArgs a,
   if (tid < tbnav_icpdev::kWave) {
     unsigned long long win = 0ull;
     if (tid < kRows) {
-      const int mx = X0 - kHalo + tid, g0 = Y0 - kHalo;
-      const int w0 = g0 >> 5, o = g0 & 31;                      // (an arithmetic shift: floor for a window that starts left of the map)
-      unsigned int w[3] = {0u, 0u, 0u};
-      if (mx >= 0 && mx < a.side) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const int wy = w0 + j;
-          if (wy < 0 || wy >= a.TW) continue;
-          const unsigned int id = ids[(mx >> 5) * a.TW + wy];
-          if (id != 0u) w[j] = a.bm[(size_t)id * kTile + (mx & (kTile - 1))];
-          const int inside = a.side - wy * kTile;                // columns of this tile that are cells of the map (>= 1)
-          if (inside < kTile) w[j] &= (1u << inside) - 1u;
-        }
-      }
-      win = (((unsigned long long)w[1] << 32) | w[0]) >> o;
-      if (o > 64 - kRows) win |= (unsigned long long)w[2] << (64 - o);
-      win &= (1ull << kRows) - 1ull;
+      win = occ_row_window(a.bm, ids, a.TW, a.side, X0 - kHalo + tid, Y0 - kHalo);
       s_occ[tid] = win;
       any = win != 0ull;
     }
@@ -104,29 +88,11 @@ __global__ __launch_bounds__(kThreads) void icp_search_table_from_occ(OccArgs a,
   if (any) {
     const int k = a.k, c_max = 2 * k * k;
     const int ly = tid & (kTile - 1), c = ly + kHalo;          // this thread's bit in a staged row
-    const unsigned int m = (1u << (k + 1)) - 1u;
 #pragma unroll
     for (int j = 0; j < kOwn; ++j) {
       const int lx = (tid >> 5) + j * kRowStep;
       if (tx * kTile + lx >= a.n || ty * kTile + ly >= a.n) continue;   // a ragged table tile: not a cell of the table, never stored
-      int best = 1 << 20;
-      for (int dr = 0; dr <= k && dr * dr < best; ++dr) {
-        for (int s = 0; s < (dr == 0 ? 1 : 2); ++s) {
-          const unsigned long long row = s_occ[kHalo + lx + (s ? dr : -dr)];   // rows 0 .. 47: dr <= k <= kHalo
-          const unsigned int left = (unsigned int)(row >> (c - k)) & m;        // bit q: column offset q - k
-          const unsigned int right = (unsigned int)(row >> c) & m;             // bit q: column offset q
-          if (left) {
-            const int dc = k - (31 - __clz((int)left));
-            const int d2 = dr * dr + dc * dc;
-            best = d2 < best ? d2 : best;
-          }
-          if (right) {
-            const int dc = __ffs((int)right) - 1;
-            const int d2 = dr * dr + dc * dc;
-            best = d2 < best ? d2 : best;
-          }
-        }
-      }
+      const int best = nearest_occ_d2(s_occ, lx, c, k);
       s_out[ly * kOutStride + lx] = best <= c_max ? s_val[best] : (uint8_t)0;
     }
   }
@@ -188,13 +154,7 @@ int map_prepare(const tbnav_icp* h, const tbnav_rbpf* pf, const float* scan, int
     map.pairs[(size_t)i] = MapPair{particles[i], cx - h2, cy - h2, 0};
     map.local[(size_t)i] = make_double2(T[1] - (pf->p.xmin + (double)cx * sp.resolution), T[2] - (pf->p.ymin + (double)cy * sp.resolution));
   }
-  // S3's stamp by d2; M4's nearest-cell form stands on its never rising
-  std::memset(map.value, 0, sizeof map.value);
-  for (int c = 0; c <= 2 * sc.k * sc.k; ++c) {
-    const double d2 = (double)c * (sp.resolution * sp.resolution);
-    map.value[c] = (uint8_t)std::floor(255.0 * std::exp(-(d2 / (2.0 * (sp.sigma * sp.sigma)))) + 0.5);
-    if (c > 0 && map.value[c] > map.value[c - 1]) return TBNAV_ERR_UNSUPPORTED;
-  }
+  if (int rc = map_value_table(sp, map.value)) return rc;
   return TBNAV_OK;
 }
 
@@ -223,6 +183,17 @@ int map_begin(tbnav_icp* h, tbnav_rbpf* pf, const float* scan, int32_t n_beams, 
 }  // namespace
 
 namespace tbnav_icpdev {
+
+int map_value_table(const tbnav_icp_search_params& sp, uint8_t* value) {
+  const int k = sp.stamp_cells;
+  std::memset(value, 0, (size_t)kMapValues);
+  for (int c = 0; c <= 2 * k * k; ++c) {
+    const double d2 = (double)c * (sp.resolution * sp.resolution);
+    value[c] = (uint8_t)std::floor(255.0 * std::exp(-(d2 / (2.0 * (sp.sigma * sp.sigma)))) + 0.5);
+    if (c > 0 && value[c] > value[c - 1]) return TBNAV_ERR_UNSUPPORTED;
+  }
+  return TBNAV_OK;
+}
 
 int launch_table_from_occ(tbnav_icp* h, int first, int n, const SearchConst& sc, const MapSource& map) {
   IcpSearch& S = h->search;

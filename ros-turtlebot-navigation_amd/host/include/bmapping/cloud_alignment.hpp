@@ -45,6 +45,11 @@
 // defaults without any): for a pose that has drifted over many scans, a robot that was picked up, a filter restarted in a map it
 // already holds, where the previous scan is as wrong as the guess.  It needs useDeviceICP (std::logic_error otherwise), a filter on
 // one GPU (std::runtime_error for one over several) whose cells are the search's; it is not wired into pclICPWrapper or SLAM.
+//
+// localizeInMap(filter, scan, ICPGlobal) (an addition too; tbnav_icp.h, GLOBAL SEARCH L1-L10) takes NO guess: every heading at every
+// cell of the map of the filter's best particle is scored on the device, blocks of cells pruned by an exact bound.  Same needs as
+// searchMap; the result is good to one cell and one angle step (searchMap or the filter's hill-climb refine it), and a symmetric
+// building has several equal answers of which the lowest index is returned.
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 
@@ -126,6 +131,27 @@ struct MapSearchResult {
   bool at_edge = false;   ///< the choice sits on the border of its window: the truth may lie outside it
 };
 
+/// (addition) the global search's parameters: tbnav_icp_global_params with its defaults
+struct ICPGlobal {
+  int ang_count = 360;         ///< headings, 1..720
+  double ang_step = 3.14159265358979323846 / 180.0;
+  int pool_log2 = 3;           ///< blocks of 2^pool_log2 cells a side, 1..5
+  int region[4] = {-1, -1, -1, -1};   ///< tx0, ty0, tx1, ty1 inclusive cells; all -1: the whole map
+  double min_quality = 0.5;    ///< acceptance threshold
+};
+
+/// (addition) what ScanAlignment::localizeInMap returns: tbnav_icp_global_info
+struct MapLocalizeResult {
+  Transform2D T;               ///< the best pose, in the world: a heading step and a cell centre
+  double quality = 0.0;        ///< score / (255 * points), 0..1
+  bool accepted = false;       ///< quality >= min_quality, with points in the scan and occupied cells in the map
+  int ia = 0, tx = 0, ty = 0;  ///< the chosen heading and cell
+  unsigned score = 0;
+  int points = 0, occupied = 0;
+  long long blocks = 0, refined_blocks = 0;   ///< all blocks of the search, and those whose candidates were scored
+  int rounds = 0;
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
@@ -158,6 +184,10 @@ class ScanAlignment {
   /// (tbnav_icp.h, MAP SEARCH).  Throws std::logic_error without useDeviceICP, std::runtime_error for a filter over several GPUs,
   /// std::invalid_argument for a guess outside the map (the reference's out-of-world text) or cells that are not the filter's.
   MapSearchResult searchMap(ParticleFilter& filter, const Transform2D& guess_world, const std::vector<float>& scan);
+
+  /// (addition) where `scan` was taken in the map of the filter's best particle, with no guess (tbnav_icp.h, GLOBAL SEARCH).
+  /// Throws as searchMap does; std::invalid_argument for parameters outside their limits.
+  MapLocalizeResult localizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& params = {});
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

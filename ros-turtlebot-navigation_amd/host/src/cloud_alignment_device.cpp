@@ -113,4 +113,36 @@ MapSearchResult ScanAlignment::searchMap(ParticleFilter& filter, const Transform
   return out;
 }
 
+MapLocalizeResult ScanAlignment::localizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& params) {
+  if (!device_) throw std::logic_error("bmapping::ScanAlignment::localizeInMap: useDeviceICP first");
+  if (filter.g_) throw std::runtime_error("bmapping::ScanAlignment::localizeInMap: a filter over several GPUs is not supported");
+  tbnav_icp_global_params gp;
+  tbnav_icp_default_global_params(&gp);
+  gp.ang_count = params.ang_count;
+  gp.ang_step = params.ang_step;
+  gp.pool_log2 = params.pool_log2;
+  for (int i = 0; i < 4; ++i) gp.region[i] = params.region[i];
+  gp.min_quality = params.min_quality;
+  tbnav_icp_global_info info{};
+  const int rc = tbnav_icp_localize_map(static_cast<tbnav_icp*>(device_.get()), filter.h_, TBNAV_ICP_MAP_BEST_PARTICLE, scan.data(),
+                                        (int32_t)scan.size(), &gp, &info);
+  if (rc != TBNAV_OK) {
+    std::string msg = std::string("bmapping::ScanAlignment::localizeInMap: ") + tbnav_status_string(rc);
+    if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+    const char* hip = tbnav_last_hip_error();
+    if (hip && *hip) msg += std::string(" [") + hip + "]";
+    throw std::runtime_error(msg);
+  }
+  MapLocalizeResult out;
+  out.T = Transform2D(rigid2d::Vector2D(info.T[1], info.T[2]), info.T[0]);
+  out.quality = info.quality;
+  out.accepted = info.accepted != 0;
+  out.ia = info.ia; out.tx = info.tx; out.ty = info.ty;
+  out.score = info.score;
+  out.points = info.points; out.occupied = info.occupied;
+  out.blocks = info.blocks; out.refined_blocks = info.refined_blocks;
+  out.rounds = info.rounds;
+  return out;
+}
+
 }  // namespace bmapping

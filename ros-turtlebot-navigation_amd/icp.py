@@ -21,6 +21,10 @@ sits on the border of its window ("reject_or_edge"), or always and in its place 
 searchMap(filter, T_init, scan) (an addition too) searches against the MAP of a particle of an rbpf.ParticleFilter instead of the
 previous scan (the header's MAP SEARCH, M1-M9): for a pose that has drifted over many scans, or a filter restarted in a known map.
 
+localizeMap(filter, scan) (an addition too) takes NO guess: it scores every heading at every cell of the particle's map and prunes
+with the exact bound of a max-pooled copy of the likelihood map (the header's GLOBAL SEARCH, L1-L10): where the robot is in a map
+the filter already holds.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -90,6 +94,27 @@ _WIDE_WHEN = {"reject": capi.ICP_WIDE_ON_REJECT, "reject_or_edge": capi.ICP_WIDE
 def _search_shape(r: "capi.IcpSearchShape") -> dict:
     return dict(S0=r.S0, Sx=r.Sx, Sy=r.Sy, Sxx=r.Sxx, Sxy=r.Sxy, Syy=r.Syy, l1=r.l1, l2=r.l2, ex=r.ex, ey=r.ey, T_raw=tuple(r.T_raw),
                 cells=r.cells, kind=r.kind, computed=r.computed)
+
+
+_GLOBAL_FIELDS = ("ang_count", "ang_step", "pool_log2", "region", "min_quality")
+
+
+def _global_params(kw) -> "capi.IcpGlobalParams":
+    p = capi.IcpGlobalParams()
+    capi.lib().tbnav_icp_default_global_params(C.byref(p))
+    for key, v in kw.items():
+        if key not in _GLOBAL_FIELDS:
+            raise TypeError(f"localizeMap: no parameter {key!r} (one of {_GLOBAL_FIELDS})")
+        if key == "region":
+            p.region[:] = [int(x) for x in v]
+        else:
+            setattr(p, key, v)
+    return p
+
+
+def _global_info(i: "capi.IcpGlobalInfo") -> dict:
+    return dict(T=tuple(i.T), quality=i.quality, blocks=i.blocks, refined_blocks=i.refined_blocks, score=i.score, points=i.points,
+                occupied=i.occupied, ia=i.ia, tx=i.tx, ty=i.ty, rounds=i.rounds, accepted=i.accepted, searched=i.searched)
 
 
 def _search_info(i: "capi.IcpSearchInfo") -> dict:
@@ -335,6 +360,80 @@ class ScanAlignment:
         buf = C.create_string_buffer(64)
         capi.check(self._L.tbnav_icp_last_map_kernel(self._h, buf, 64), "tbnav_icp_last_map_kernel")
         return buf.value.decode()
+
+    def localizeMap(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """tbnav_icp_localize_map (the header's GLOBAL SEARCH, L1-L10): the pose of one scan in the map of a particle of `filter`
+        (particle=-1: its best one), with no guess; params: ang_count, ang_step, pool_log2, region=(tx0, ty0, tx1, ty1), min_quality
+        (tbnav_icp_default_global_params for what is not named) -> (accepted, T in the world, info dict)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        info = capi.IcpGlobalInfo()
+        capi.check(self._L.tbnav_icp_localize_map(self._h, filter._h, int(particle), scan.ctypes.data, scan.size,
+                                                  C.byref(_global_params(params)), C.byref(info)), "tbnav_icp_localize_map")
+        return bool(info.accepted), tuple(info.T), _global_info(info)
+
+    GLOBAL_STAGES = ("field", "pool", "offsets", "bound", "hist", "list_1", "refine_1", "list_2", "refine_2")
+
+    def localizeMapTimed(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """tbnav_icp_localize_map_timed: localizeMap with its stages timed by events -> (accepted, T, info dict, {stage: ms})"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        info = capi.IcpGlobalInfo()
+        ms = np.zeros(capi.ICP_GLOBAL_STAGES, dtype=np.float32)
+        capi.check(self._L.tbnav_icp_localize_map_timed(self._h, filter._h, int(particle), scan.ctypes.data, scan.size,
+                                                        C.byref(_global_params(params)), C.byref(info), ms.ctypes.data),
+                   "tbnav_icp_localize_map_timed")
+        return bool(info.accepted), tuple(info.T), _global_info(info), dict(zip(self.GLOBAL_STAGES, (float(v) for v in ms)))
+
+    def lastGlobal(self) -> dict:
+        """the record of the last localizeMap of this handle (searched = 0: none ran)"""
+        info = capi.IcpGlobalInfo()
+        capi.check(self._L.tbnav_icp_last_global(self._h, C.byref(info)), "tbnav_icp_last_global")
+        return _global_info(info)
+
+    def lastGlobalKernels(self) -> list:
+        """the last localizeMap's kernels as a profiler prints them; [] before the first call"""
+        buf = C.create_string_buffer(256)
+        capi.check(self._L.tbnav_icp_last_global_kernels(self._h, buf, 256), "tbnav_icp_last_global_kernels")
+        return [k for k in buf.value.decode().split(";") if k]
+
+    @staticmethod
+    def _global_shape(filter, p):
+        side, s = filter.xsize, 1 << p.pool_log2
+        whole = all(v == -1 for v in p.region)
+        w = side if whole else p.region[2] - p.region[0] + 1
+        h = side if whole else p.region[3] - p.region[1] + 1
+        return side, s, w, h
+
+    def localizeMapField(self, filter, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """test hook (L9) -> (lik uint8 [side][side] indexed [ci][cj], pool uint8 [side + s - 1][side + s - 1] indexed
+        [i + s - 1][j + s - 1], occupied)"""
+        p = _global_params(params)
+        side, s, _, _ = self._global_shape(filter, p)
+        lik = np.zeros((side, side), dtype=np.uint8)
+        pool = np.zeros((side + s - 1, side + s - 1), dtype=np.uint8)
+        occ = C.c_int32()
+        capi.check(self._L.tbnav_icp_localize_map_field(self._h, filter._h, int(particle), C.byref(p), lik.ctypes.data, pool.ctypes.data,
+                                                        C.byref(occ)), "tbnav_icp_localize_map_field")
+        return lik, pool, int(occ.value)
+
+    def localizeMapBounds(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """test hook (L9) -> the bound volume, uint32 [NA][nbx][nby]"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        p = _global_params(params)
+        _, s, w, h = self._global_shape(filter, p)
+        vol = np.zeros((max(p.ang_count, 1), max(-(-w // s), 1), max(-(-h // s), 1)), dtype=np.uint32)
+        capi.check(self._L.tbnav_icp_localize_map_bounds(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, C.byref(p),
+                                                         vol.ctypes.data), "tbnav_icp_localize_map_bounds")
+        return vol
+
+    def localizeMapScores(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """test hook (L9) -> every candidate's score, uint32 [NA][w][h], by the refinement kernel run over all blocks"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        p = _global_params(params)
+        _, _, w, h = self._global_shape(filter, p)
+        vol = np.zeros((max(p.ang_count, 1), max(w, 1), max(h, 1)), dtype=np.uint32)
+        capi.check(self._L.tbnav_icp_localize_map_scores(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, C.byref(p),
+                                                         vol.ctypes.data), "tbnav_icp_localize_map_scores")
+        return vol
 
     def lastSearch(self) -> dict:
         """the search record of the last pclICP / pclICPWrapper, for a wrapperBatch the last scan's (searched = 0: none ran)"""
