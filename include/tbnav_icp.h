@@ -254,8 +254,8 @@
  *      streams, no host synchronisation) and the scoring behind the table; the call returns with the result on the host.  The
  *      filter is only read.  h's stored scan (tbnav_icp_step) is neither read nor written.  tbnav_icp_last_search,
  *      _last_search_shape and _last_search_wide report this search (of a batch: the last pair's).
- *  M9. Known limits.  Accuracy is one cell and one angle step: there is no refinement against the map behind it (the filter's own
- *      hill-climb, tbnav_rbpf_set_scan_matching, is the local method that exists).  Points further than E' from the guess's cell
+ *  M9. Known limits.  Accuracy is one cell and one angle step: the refinement below one cell against the same map is tbnav_icp_align_map (MAP
+ *      ALIGNMENT, A1-A11 below), which a caller runs from info->T; the search itself does not run it.  Points further than E' from the guess's cell
  *      add nothing, as in the scan search.  Unknown cells and free cells both score 0: there is no free-space penalty.
  *      min_quality = 0.5 was set for scan pairs; over a WIDE window against a map it does not separate a true match from a wrong
  *      room (tests/icp_search_map_cases.py, BEHAVIOUR: the restatement on maps drawn by the oracle's GridMapper from 12 / 20 scans
@@ -343,7 +343,7 @@
  *      TBNAV_ERR_UNSUPPORTED above 2^24 candidates).
  *  L10. Not built: a free-space penalty or a restriction to FREE cells (M9's wrong-room finding applies unchanged); several
  *      hypotheses or a runner-up at a distance (a symmetric building has several equal answers and the index rule picks one);
- *      sub-cell or sub-step refinement (a caller runs tbnav_icp_search_map or the filter's hill-climb from T); seeding the
+ *      sub-cell or sub-step refinement inside this call (a caller runs tbnav_icp_align_map, MAP ALIGNMENT A1-A11, from T); seeding the
  *      filter's particles from the result; batches of scans; sharded filters; more than one level of pooling in the contract (an
  *      implementation may use more inside, L6).
  *  KERNELS (csrc/icp_global.hip).  icp_global_field, one workgroup of 256 threads per 32 x 32 map tile: icp_search_table_from_occ's
@@ -361,6 +361,74 @@
  *  64-bit atomicMax of (score << 32 | ~linear index) per wave; a block whose bound is 0 holds only zeros and is settled by its
  *  first candidate without a gather.  No workgroup waits for another; every loop is bounded by the points, the tile or s; a round is
  *  a launch and the host reads one small record per round: at most two rounds.
+ *  MAP ALIGNMENT (an addition, tbnav_icp_align_map; csrc/icp_align_map.hip; restated in tests/icp_align_map_restatement.py, reproduced
+ *  bit for bit).  It has NO COUNTERPART IN THE REFERENCE: this section is its whole specification.  The map search and the global
+ *  search stop at one cell and one angle step; the ICP above aligns to the PREVIOUS SCAN, which after a relocalisation is as wrong as
+ *  the guess.  This is the local, metric alignment of one scan to a particle's map: the last link of global search -> window search ->
+ *  alignment.  It is opt-in and stateless; no other entry calls it.  A point-to-line step (L3, L4) against a line fitted to the
+ *  occupied cells round the nearest one (the idea of the normal-distributions transform).  What it must not be (CPU prototype, bench
+ *  room, maps rasterised from 12 synthetic scans at 0.05 m, starts within half a cell and half a degree): ICP against the CENTRE of
+ *  the nearest occupied cell ends 34.7 mm off from starts 19.9 mm off, because a wall on a cell border is drawn two cells thick and
+ *  each row of centres is a stable fixed point; Gauss-Newton on the interpolated table M4 has the same band.  Arithmetic is integer,
+ *  or fp64 with every product and sum as parenthesised and no contraction; no transcendental, and no device sqrt or division but the
+ *  correctly rounded fp64 ones.
+ *  A1. Handles, particle, order of the checks.  An ICP handle h and a filter handle pf on one device (else TBNAV_ERR_UNSUPPORTED; a
+ *      member of a sharded group is TBNAV_ERR_UNSUPPORTED too).  Order: arguments, parameters and particles first (INVALID_ARG), then
+ *      device and group (UNSUPPORTED), then the guesses (A3, OUT_OF_WORLD).  particle is a slot or TBNAV_ICP_MAP_BEST_PARTICLE (M1's
+ *      arg-max).  The cloud's beam geometry and Trs are h's (item 1); max_iter, transform_eps and fitness_eps are h's (item 4);
+ *      max_corr_dist and h's search parameters take no part: the grid (xmin, ymin, resolution, side) is the filter's.  n_beams is
+ *      1..TBNAV_ICP_MAX_BEAMS.  Anything rejected changes nothing: not the filter, not h's parameters, its stored scan or any last
+ *      record.  An accepted call reads the filter, leaves h's stored scan and every last record of the searches alone, and changes
+ *      only what tbnav_icp_last_align_map_kernel reports.
+ *  A1a. Parameters (tbnav_icp_align_map_params; defaults in brackets; NULL: the defaults; a bad field is TBNAV_ERR_INVALID_ARG):
+ *      half_cells H [128, 8..TBNAV_ICP_ALIGN_MAP_MAX_HALF = 256]; gate_cells G [10, 1..16]; feature_cells w [2, 1..4]; max_flatness f
+ *      [0.25, finite, 0 <= f < 1]; one reserved int32 that must be 0.
+ *  A2. Occupied and cells: M2 as it stands (the occupancy bit; ci = (int)floor((x - xmin) * inv), inv = 1.0 / resolution).
+ *  A3. Window.  (cx, cy) = A2's cell of (x0, y0) of T_init, a WORLD pose; a T_init that is not finite (any of the three) or whose cell
+ *      is outside the map is TBNAV_ERR_OUT_OF_WORLD.  The window is the 2H x 2H cells (cx - H .. cx + H - 1, cy - H .. cy + H - 1).
+ *      For everything below an occupied cell EXISTS only if it lies inside both the window and the map.  The window stays where
+ *      T_init put it for all iterations.
+ *  A4. Feature of an occupied cell m = (mi, mj), over the occupied cells q (A3) with |qi - mi| <= w and |qj - mj| <= w, m included.
+ *      Integers, d = q - m: n, sx = sum di, sy = sum dj, sxx = sum di*di, sxy = sum di*dj, syy = sum dj*dj; a = n*sxx - sx*sx,
+ *      c = n*syy - sy*sy, b = n*sxy - sx*sy.  Centroid: bx = xmin + (((double)mi + 0.5) + ((double)sx / (double)n)) * resolution, by
+ *      likewise with mj, sy, ymin.  Eigenvalues: hd = 0.5 * (double)(a - c), dd = sqrt((hd*hd) + ((double)b*(double)b)),
+ *      lmin = (0.5 * (double)(a + c)) - dd, lmax = (0.5 * (double)(a + c)) + dd.  The cell HAS A NORMAL when n >= 3 and lmax > 0 and
+ *      lmin <= f * lmax.  Direction: b != 0: v = ((double)b, lmin - (double)a); b == 0: v = (0, 1) when a >= c, else (1, 0);
+ *      l = sqrt((vx*vx) + (vy*vy)); normal = ((float)(vx / l), (float)(vy / l)).  f is a design constant, not a measurement: it keeps
+ *      blobs and the inside of corners from handing out a direction.
+ *  A5. Pairing, each iteration.  A source point goes to a exactly as in item 3, from the float-rounded guess of item 2 held in fp64.
+ *      Its home cell (hi, hj) is A2's cell of the doubles of a (the floor is compared as a double: a point that is not a number has
+ *      no home); a point whose home is outside the window has no pair.  Its target cell is the occupied cell (A3) with |mi - hi| <= G
+ *      and |mj - hj| <= G that minimises the integer D = (mi - hi)^2 + (mj - hj)^2; ties go to the lowest mi, then the lowest mj.
+ *      The pair is kept when D <= G*G and the target cell has a normal (a cell inside the box and outside the disc is the target and
+ *      is dropped).
+ *  A6. Sums, step, composition, stopping: L3 and L4 as they stand with b := the centroid (bx, by) in doubles and n := the doubles of
+ *      the float normal; item 3's fixed summation order (thread t of 256 adds the kept pairs of beams t, t + 256, ... in increasing
+ *      order, then the tree); fewer than 3 kept pairs: TBNAV_ICP_NO_CORRESPONDENCES; L4's two DEGENERATE tests with the same K;
+ *      composition and item 4's rules and their order unchanged.
+ *  A7. Result: tbnav_icp_info as for the other alignments (criterion, iterations, correspondences and mse of the last iteration) and
+ *      ok (1 when converged); T is item 5's, in the WORLD.  On a failure T_out is T_init's three doubles UNCHANGED and ok = 0: this
+ *      differs from item 5, whose failure is (0, 0, 0), because here T is a world pose and the guess is the best pose known.
+ *  A8. Batch: one scan and n >= 1 pairs (particle_i, T_init_i), each equal to the single call bit for bit.  One bad pair rejects the
+ *      call before any launch.
+ *  A9. Ordering: M8's.  The kernel runs behind whatever the filter's stream has in flight, through an event, and only reads the
+ *      filter; the call returns with the result on the host.
+ *  A10. Entries: tbnav_icp_align_map, tbnav_icp_align_map_batch, tbnav_icp_last_align_map_kernel (the kernel's name as a profiler
+ *      prints it, its template argument included; "" until the route has run on this handle).  Test hook tbnav_icp_align_map_pairs:
+ *      iteration 1's pairing for one pair, per BEAM (tbnav_icp_align_map_pair): has_home, the home cell, the target cell or
+ *      (-1, -1) with D = -1 where the box holds no occupied cell, D, has_normal, the centroid's doubles and the normal's floats (of
+ *      the target cell wherever there is one, whatever D is; zero otherwise), kept.  A beam that is no point, or whose home is
+ *      outside the window, holds has_home = 0, target (-1, -1), D = -1 and zeros.
+ *  A11. Not built: a rule that ends the two-state cycles of the line metric before max_iter (some starts run to the iteration limit
+ *      in them); robust weights; a free-space term; use of the log-odds instead of the bits (the map's own rasterisation bias, up to
+ *      about 9 mm at 0.05 m cells in the prototype, stays: no method that reads occupancy bits removes it); use inside
+ *      tbnav_icp_step or bmapping::ParticleFilter::SLAM; sharded filters; seeding particles on the device.
+ *  KERNEL (csrc/icp_align_map.hip): icp_align_map<P>, one workgroup of 256 threads per pair, the whole loop in one launch.  The
+ *  window's bits are staged once into LDS (at most 512 rows of 16 words, a zero word either side of each row: 36 KB) through the
+ *  particle's tile table by occ_row_window; every iteration then works out of LDS and registers: the nearest cell by rows outwards
+ *  (clz / ffs on a masked 64-bit look; it goes on while dr^2 <= the best D, since a row at dr^2 == D can still win A5's tie), the
+ *  feature from the cell's (2w + 1)^2 bits on the fly, and L3 / L4, the tree and the stopping rules from icp_iter_device.hpp, the
+ *  code icp_align runs.
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
@@ -665,6 +733,44 @@ int tbnav_icp_localize_map_bounds(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle
 /* test hook (L9): every candidate's score, uint32 [NA][w][h] */
 int tbnav_icp_localize_map_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
                                   const tbnav_icp_global_params* params, uint32_t* scores);
+
+/* ---- MAP ALIGNMENT: one scan against a particle's map, below one cell (A1-A11 of the section of that name) ---- */
+#define TBNAV_ICP_ALIGN_MAP_MAX_HALF 256
+
+typedef struct tbnav_icp_align_map_params {
+  double max_flatness;    /* 0.25 */
+  int32_t half_cells;     /* 128 */
+  int32_t gate_cells;     /* 10 */
+  int32_t feature_cells;  /* 2 */
+  int32_t reserved;       /* must be 0 */
+} tbnav_icp_align_map_params;
+
+/* the test hook's record of one beam (A10) */
+typedef struct tbnav_icp_align_map_pair {
+  double bx, by;          /* the target cell's centroid (A4) */
+  float nx, ny;           /* its normal; (0, 0) without one */
+  int32_t hi, hj;         /* the home cell */
+  int32_t mi, mj;         /* the target cell, or (-1, -1) */
+  int32_t D;              /* or -1 */
+  int32_t has_home;
+  int32_t has_normal;
+  int32_t kept;
+} tbnav_icp_align_map_pair;
+
+void tbnav_icp_default_align_map_params(tbnav_icp_align_map_params* p);
+/* the alignment of one scan to particle's map from the world guess T_init (A1-A7).  params may be NULL (the defaults); T_out, ok
+ * and info are required.  T_out is the world pose, or T_init unchanged with ok = 0. */
+int tbnav_icp_align_map(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T_init[3],
+                        const tbnav_icp_align_map_params* params, double T_out[3], int32_t* ok, tbnav_icp_info* info);
+/* A8: one scan, n pairs (particles[i], T_init[i]): T_init [n][3], T_out [n][3], ok [n], infos [n] */
+int tbnav_icp_align_map_batch(tbnav_icp* h, tbnav_rbpf* pf, const float* scan, int32_t n_beams, int32_t n, const int32_t* particles,
+                              const double* T_init, const tbnav_icp_align_map_params* params, double* T_out, int32_t* ok,
+                              tbnav_icp_info* infos);
+/* test hook (A10): iteration 1's pairing of one pair, pairs [n_beams] */
+int tbnav_icp_align_map_pairs(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T_init[3],
+                              const tbnav_icp_align_map_params* params, tbnav_icp_align_map_pair* pairs);
+/* the alignment kernel's name as a profiler prints it; "" until the route has run on this handle */
+int tbnav_icp_last_align_map_kernel(const tbnav_icp* h, char* kernel, int32_t kernel_cap);
 
 #ifdef __cplusplus
 }

@@ -211,6 +211,20 @@ class IcpGlobalInfo(C.Structure):
                 ("ty", C.c_int32), ("rounds", C.c_int32), ("accepted", C.c_int32), ("searched", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IcpAlignMapParams(C.Structure):
+    """tbnav_icp_align_map_params (include/tbnav_icp.h, MAP ALIGNMENT, A1a)."""
+    _fields_ = [("max_flatness", C.c_double), ("half_cells", C.c_int32), ("gate_cells", C.c_int32), ("feature_cells", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class IcpAlignMapPair(C.Structure):
+    """tbnav_icp_align_map_pair (A10): the test hook's record of one beam."""
+    _fields_ = [("bx", C.c_double), ("by", C.c_double), ("nx", C.c_float), ("ny", C.c_float), ("hi", C.c_int32), ("hj", C.c_int32),
+                ("mi", C.c_int32), ("mj", C.c_int32), ("D", C.c_int32), ("has_home", C.c_int32), ("has_normal", C.c_int32),
+                ("kept", C.c_int32)]
+
+
+ICP_ALIGN_MAP_MAX_HALF = 256
 ICP_GLOBAL_STAGES = 9
 ICP_GLOBAL_MAX_SIDE, ICP_GLOBAL_MAX_ANG, ICP_GLOBAL_MAX_BLOCKS, ICP_GLOBAL_MAX_HOOK_SCORES = 2048, 720, 1 << 26, 1 << 24
 
@@ -470,6 +484,11 @@ def lib() -> C.CDLL:
         "tbnav_icp_localize_map_field": (C.c_int, [vp, vp, i32, C.POINTER(IcpGlobalParams), vp, vp, C.POINTER(i32)]),
         "tbnav_icp_localize_map_bounds": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
         "tbnav_icp_localize_map_scores": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
+        "tbnav_icp_default_align_map_params": (None, [C.POINTER(IcpAlignMapParams)]),
+        "tbnav_icp_align_map": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpAlignMapParams), dp, C.POINTER(i32), C.POINTER(IcpInfo)]),
+        "tbnav_icp_align_map_batch": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(IcpAlignMapParams), vp, vp, vp]),
+        "tbnav_icp_align_map_pairs": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpAlignMapParams), vp]),
+        "tbnav_icp_last_align_map_kernel": (C.c_int, [vp, C.c_char_p, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -16,6 +16,8 @@
 // rotation.  LineMetric is the header's POINT-TO-LINE METRIC (an addition; the reference has no such metric): the target's
 // normals as a second float2 array in LDS beside the cloud, computed by the workgroup before the loop, ten sums, and a 3x3
 // Gauss-Newton step solved by every thread from the totals.
+// The line metric's sums and step, the tree and the composition with the stopping rules are icp_iter_device.hpp's, which
+// icp_align_map (icp_align_map.hip, the alignment to a filter's map) calls too.
 // Compiled with -ffp-contract=off (csrc/Makefile): every fp64 / fp32 expression keeps the restatement's rounding.
 #include <hip/hip_runtime.h>
 
@@ -28,6 +30,7 @@
 
 #include "common.hpp"
 #include "icp_device.hpp"
+#include "icp_iter_device.hpp"
 #include "tbnav_icp.h"
 
 namespace {
@@ -116,42 +119,18 @@ struct PointMetric {
 // the point-to-line metric (tbnav_icp.h, POINT-TO-LINE METRIC; no counterpart in the reference): H00, H01, H02, H11, H12,
 // H22, g0, g1, g2, Sr and the 3x3 Gauss-Newton step (theta eliminated last)
 struct LineMetric {
-  static constexpr int kSums = 10;
+  static constexpr int kSums = kLineSums;
   static constexpr bool kNormals = true;
   static constexpr int kMaxBeams = TBNAV_ICP_LINE_MAX_BEAMS;
   using Params = IcpLine;
   static __device__ __forceinline__ bool add(double (&sum)[kSums], float2 a, float2 b, float2 nf, float) {
     if (!(nf.x == nf.x)) return false;  // the nearest target has no normal
-    const double ax = a.x, ay = a.y, nx = nf.x, ny = nf.y;
-    const double ex = ax - (double)b.x, ey = ay - (double)b.y;
-    const double r = (nx * ex) + (ny * ey);
-    const double jj = (ax * ny) - (ay * nx);
-    sum[0] += jj * jj; sum[1] += jj * nx; sum[2] += jj * ny;
-    sum[3] += nx * nx; sum[4] += nx * ny; sum[5] += ny * ny;
-    sum[6] += jj * r; sum[7] += nx * r; sum[8] += ny * r;
-    sum[9] += r * r;
+    line_add(sum, (double)a.x, (double)a.y, (double)b.x, (double)b.y, (double)nf.x, (double)nf.y);   // (icp_iter_device.hpp)
     return true;
   }
   static __device__ __forceinline__ bool step(const double* tot, int n, const Params& ln, double& c, double& s, double& tix,
                                               double& tiy, double& mse) {
-    const double H00 = tot[0], H01 = tot[1], H02 = tot[2], H11 = tot[3], H12 = tot[4], H22 = tot[5];
-    const double g0 = tot[6], g1 = tot[7], g2 = tot[8];
-    mse = tot[9] / (double)n;
-    const double tr = H11 + H22;
-    const double det = (H11 * H22) - (H12 * H12);
-    if (!(det > ln.min_cond * (tr * tr))) return false;
-    const double v1 = ((H22 * H01) - (H12 * H02)) / det;
-    const double v2 = ((H11 * H02) - (H12 * H01)) / det;
-    const double dth = H00 - ((H01 * v1) + (H02 * v2));
-    if (!(dth > ln.min_cond * H00)) return false;
-    const double th = -(g0 - ((v1 * g1) + (v2 * g2))) / dth;
-    const double w1 = g1 + (H01 * th), w2 = g2 + (H02 * th);
-    tix = -((H22 * w1) - (H12 * w2)) / det;
-    tiy = -((H11 * w2) - (H12 * w1)) / det;
-    const double u = 0.5 * th;
-    const double q = 1.0 + (u * u);
-    c = (1.0 - (u * u)) / q; s = th / q;
-    return true;
+    return line_step(tot, n, ln.min_cond, c, s, tix, tiy, mse);
   }
 };
 
@@ -165,11 +144,7 @@ __global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ 
   const int n4 = (n_beams + 3) & ~3;           // the LDS cloud is padded to whole float4 pairs of points with NaN
   float2* tgt = reinterpret_cast<float2*>(lds_dyn);  // [n4]
   float2* nrm = tgt + n4;                            // [n4], M::kNormals only (NaN: no normal)
-  __shared__ double red_a[NS][kThreads / 2];  // s = 128 partials
-  __shared__ double red_b[NS][kThreads / 4];  // s = 64 partials
-  __shared__ int cnt_a[kThreads / 2], cnt_b[kThreads / 4];
-  __shared__ double tot[NS];
-  __shared__ int tot_n;
+  __shared__ TreeLds<NS> tree;                // the partials of s = 128 and 64, and the totals (icp_iter_device.hpp)
 
   const int t = threadIdx.x;
   const IcpPair pr = pairs[blockIdx.x];
@@ -194,8 +169,8 @@ __global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ 
     __syncthreads();
   }
 
-  double R00 = pr.c, R01 = -pr.s, R10 = pr.s, R11 = pr.c, tx = pr.x, ty = pr.y;
-  double prev = DBL_MAX, mse = 0.0;
+  IcpState st{pr.c, -pr.s, pr.s, pr.c, pr.x, pr.y, DBL_MAX};
+  double mse = 0.0;
   int iter = 0, n = 0, crit = TBNAV_ICP_NOT_RUN;
   while (true) {
     ++iter;
@@ -208,8 +183,8 @@ __global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ 
     int bi[P][C];
 #pragma unroll
     for (int j = 0; j < P; ++j) {
-      a[j].x = (float)(((R00 * (double)src[j].x) + (R01 * (double)src[j].y)) + tx);
-      a[j].y = (float)(((R10 * (double)src[j].x) + (R11 * (double)src[j].y)) + ty);
+      a[j].x = (float)(((st.R00 * (double)src[j].x) + (st.R01 * (double)src[j].y)) + st.tx);
+      a[j].y = (float)(((st.R10 * (double)src[j].x) + (st.R11 * (double)src[j].y)) + st.ty);
 #pragma unroll
       for (int c = 0; c < C; ++c) { best[j][c] = __builtin_huge_valf(); bi[j][c] = 0x7fffffff; }
     }
@@ -250,64 +225,20 @@ __global__ __launch_bounds__(kThreads) void icp_align(const float* __restrict__ 
         if (M::add(sum, a[j], b, nf, best[j][0])) ++cnt;
       }
     }
-    // tree: t += t + s for s = 128, 64 (LDS), 32 .. 1 (wave 0, shuffles)
-    if (t >= kThreads / 2) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) red_a[q][t - kThreads / 2] = sum[q];
-      cnt_a[t - kThreads / 2] = cnt;
-    }
-    __syncthreads();
-    if (t < kThreads / 2) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_a[q][t];
-      cnt += cnt_a[t];
-      if (t >= kThreads / 4) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) red_b[q][t - kThreads / 4] = sum[q];
-        cnt_b[t - kThreads / 4] = cnt;
-      }
-    }
-    __syncthreads();
-    if (t < kWave) {
-#pragma unroll
-      for (int q = 0; q < NS; ++q) sum[q] = sum[q] + red_b[q][t];
-      cnt += cnt_b[t];
-#pragma unroll
-      for (int s = kWave / 2; s > 0; s >>= 1) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) sum[q] = sum[q] + __shfl_down(sum[q], s, kWave);
-        cnt += __shfl_down(cnt, s, kWave);
-      }
-      if (t == 0) {
-#pragma unroll
-        for (int q = 0; q < NS; ++q) tot[q] = sum[q];
-        tot_n = cnt;
-      }
-    }
-    __syncthreads();
-    // every thread: R_inc and the criteria from the totals (wave-uniform from here to the loop's end).  The next writes of
-    // red_a / red_b / tot come after the next iteration's first / second barrier, which every thread reaches only after it
-    // has read what it needs here.
-    n = tot_n;
+    // the tree; then every thread: R_inc and the criteria from the totals (wave-uniform from here to the loop's end)
+    tree_totals(tree, sum, cnt, t);
+    n = tree.tot_n;
     if (n < 3) { crit = TBNAV_ICP_NO_CORRESPONDENCES; mse = 0.0; break; }
     // step() assigns all four or returns false.  The zeros are never read, but left undefined on the degenerate path they
     // cost most instantiations registers (8-10 VGPRs at P = 2, which is a workgroup per CU in a batch of the line metric)
     double c = 0.0, s = 0.0, tix = 0.0, tiy = 0.0;
-    if (!M::step(tot, n, mp, c, s, tix, tiy, mse)) { crit = TBNAV_ICP_DEGENERATE; break; }
-    const double n00 = (c * R00) - (s * R10), n01 = (c * R01) - (s * R11);
-    const double n10 = (s * R00) + (c * R10), n11 = (s * R01) + (c * R11);
-    const double ntx = ((c * tx) - (s * ty)) + tix, nty = ((s * tx) + (c * ty)) + tiy;
-    R00 = n00; R01 = n01; R10 = n10; R11 = n11; tx = ntx; ty = nty;
-    if (iter >= k.max_iter) { crit = TBNAV_ICP_ITERATIONS; break; }
-    if (c >= k.rot_thresh && ((tix * tix) + (tiy * tiy)) <= k.trans_thresh) { crit = TBNAV_ICP_TRANSFORM; break; }
-    const double dm = fabs(mse - prev);
-    if (dm < 1e-12) { crit = TBNAV_ICP_ABS_MSE; break; }
-    if (dm / prev < k.fitness_eps) { crit = TBNAV_ICP_REL_MSE; break; }
-    prev = mse;
+    if (!M::step(tree.tot, n, mp, c, s, tix, tiy, mse)) { crit = TBNAV_ICP_DEGENERATE; break; }
+    crit = advance(st, c, s, tix, tiy, mse, iter, k);
+    if (crit != TBNAV_ICP_NOT_RUN) break;
   }
   if (t == 0) {
     IcpOut o;
-    o.R00 = R00; o.R10 = R10; o.tx = tx; o.ty = ty; o.mse = mse;
+    o.R00 = st.R00; o.R10 = st.R10; o.tx = st.tx; o.ty = st.ty; o.mse = mse;
     o.iterations = iter; o.correspondences = n; o.criterion = crit; o.pad = 0;
     out[blockIdx.x] = o;
   }
@@ -564,7 +495,7 @@ void tbnav_icp_destroy(tbnav_icp* h) {
     DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->d_table);
-    for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out}) b->release();
+    for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out, &h->d_align_in, &h->d_align_rec}) b->release();
     search_free(h);
     global_free(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -48,7 +48,7 @@
 //
 // localizeInMap(filter, scan, ICPGlobal) (an addition too; tbnav_icp.h, GLOBAL SEARCH L1-L10) takes NO guess: every heading at every
 // cell of the map of the filter's best particle is scored on the device, blocks of cells pruned by an exact bound.  Same needs as
-// searchMap; the result is good to one cell and one angle step (searchMap or the filter's hill-climb refine it), and a symmetric
+// searchMap; the result is good to one cell and one angle step (alignToMap refines it below a cell; relocalizeInMap is the two in a row), and a symmetric
 // building has several equal answers of which the lowest index is returned.
 #ifndef TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
 #define TBNAV_BMAPPING_CLOUD_ALIGNMENT_HPP
@@ -152,6 +152,30 @@ struct MapLocalizeResult {
   int rounds = 0;
 };
 
+/// (addition) the map alignment's parameters: tbnav_icp_align_map_params with its defaults
+struct ICPAlignMap {
+  int half_cells = 128;        ///< the window +-half_cells round the guess's cell, 8..256
+  int gate_cells = 10;         ///< a point pairs with an occupied cell at most this far from its own, 1..16
+  int feature_cells = 2;       ///< the line of a cell is fitted over +-feature_cells, 1..4
+  double max_flatness = 0.25;  ///< lmin / lmax above which a cell hands out no direction, 0 <= f < 1
+};
+
+/// (addition) what ScanAlignment::alignToMap returns: tbnav_icp_align_map's T, ok and tbnav_icp_info
+struct MapAlignResult {
+  Transform2D T;               ///< the aligned pose in the world; the guess unchanged when ok is false
+  bool ok = false;             ///< converged (ITERATIONS, TRANSFORM, ABS_MSE or REL_MSE)
+  int iterations = 0, correspondences = 0, criterion = 0;
+  double mse = 0.0;
+};
+
+/// (addition) what ScanAlignment::relocalizeInMap returns: both records; aligned is false when the search was not accepted
+struct MapRelocalizeResult {
+  MapLocalizeResult found;
+  MapAlignResult fine;
+  bool aligned = false;
+  Transform2D T;               ///< fine.T when aligned and fine.ok, else found.T
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
@@ -188,6 +212,14 @@ class ScanAlignment {
   /// (addition) where `scan` was taken in the map of the filter's best particle, with no guess (tbnav_icp.h, GLOBAL SEARCH).
   /// Throws as searchMap does; std::invalid_argument for parameters outside their limits.
   MapLocalizeResult localizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& params = {});
+
+  /// (addition) `scan` aligned to the map of the filter's best particle from a guess in the world, below one cell (tbnav_icp.h, MAP
+  /// ALIGNMENT A1-A11).  Throws as searchMap does; std::invalid_argument for parameters outside their limits.
+  MapAlignResult alignToMap(ParticleFilter& filter, const Transform2D& guess_world, const std::vector<float>& scan,
+                            const ICPAlignMap& params = {});
+  /// (addition) localizeInMap, then alignToMap from its pose when it is accepted
+  MapRelocalizeResult relocalizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
+                                      const ICPAlignMap& align = {});
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

@@ -145,4 +145,50 @@ MapLocalizeResult ScanAlignment::localizeInMap(ParticleFilter& filter, const std
   return out;
 }
 
+MapAlignResult ScanAlignment::alignToMap(ParticleFilter& filter, const Transform2D& guess_world, const std::vector<float>& scan,
+                                         const ICPAlignMap& params) {
+  if (!device_) throw std::logic_error("bmapping::ScanAlignment::alignToMap: useDeviceICP first");
+  if (filter.g_) throw std::runtime_error("bmapping::ScanAlignment::alignToMap: a filter over several GPUs is not supported");
+  tbnav_icp_align_map_params ap;
+  tbnav_icp_default_align_map_params(&ap);
+  ap.half_cells = params.half_cells;
+  ap.gate_cells = params.gate_cells;
+  ap.feature_cells = params.feature_cells;
+  ap.max_flatness = params.max_flatness;
+  const auto g = guess_world.displacement();
+  const double tinit[3] = {g.theta, g.x, g.y};
+  double out[3] = {0.0, 0.0, 0.0};
+  int32_t ok = 0;
+  tbnav_icp_info info{};
+  const int rc = tbnav_icp_align_map(static_cast<tbnav_icp*>(device_.get()), filter.h_, TBNAV_ICP_MAP_BEST_PARTICLE, scan.data(),
+                                     (int32_t)scan.size(), tinit, &ap, out, &ok, &info);
+  if (rc != TBNAV_OK) {
+    const std::string text = tbnav_status_string(rc);
+    if (rc == TBNAV_ERR_OUT_OF_WORLD) throw std::invalid_argument(text);  // what the reference throws (grid_mapper.cpp:856)
+    std::string msg = "bmapping::ScanAlignment::alignToMap: " + text;
+    if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+    const char* hip = tbnav_last_hip_error();
+    if (hip && *hip) msg += std::string(" [") + hip + "]";
+    throw std::runtime_error(msg);
+  }
+  MapAlignResult r;
+  r.T = ok ? Transform2D(rigid2d::Vector2D(out[1], out[2]), out[0]) : guess_world;
+  r.ok = ok != 0;
+  r.iterations = info.iterations; r.correspondences = info.correspondences; r.criterion = info.criterion;
+  r.mse = info.mse;
+  return r;
+}
+
+MapRelocalizeResult ScanAlignment::relocalizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global,
+                                                   const ICPAlignMap& align) {
+  MapRelocalizeResult r;
+  r.found = localizeInMap(filter, scan, global);
+  r.T = r.found.T;
+  if (!r.found.accepted) return r;
+  r.fine = alignToMap(filter, r.found.T, scan, align);
+  r.aligned = true;
+  if (r.fine.ok) r.T = r.fine.T;
+  return r;
+}
+
 }  // namespace bmapping

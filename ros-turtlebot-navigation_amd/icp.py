@@ -25,6 +25,9 @@ localizeMap(filter, scan) (an addition too) takes NO guess: it scores every head
 with the exact bound of a max-pooled copy of the likelihood map (the header's GLOBAL SEARCH, L1-L10): where the robot is in a map
 the filter already holds.
 
+alignMap(filter, T_init, scan) (an addition too) aligns one scan to the particle's map BELOW one cell (the header's MAP ALIGNMENT,
+A1-A11): a point-to-line step against lines fitted to the occupied cells; relocalizeMap(filter, scan) is localizeMap followed by it.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -109,6 +112,20 @@ def _global_params(kw) -> "capi.IcpGlobalParams":
             p.region[:] = [int(x) for x in v]
         else:
             setattr(p, key, v)
+    return p
+
+
+_ALIGN_MAP_FIELDS = ("half_cells", "gate_cells", "feature_cells", "max_flatness", "reserved")
+_ALIGN_MAP_PAIR = np.dtype([(f, np.dtype(t)) for f, t in capi.IcpAlignMapPair._fields_])
+
+
+def _align_map_params(kw) -> "capi.IcpAlignMapParams":
+    p = capi.IcpAlignMapParams()
+    capi.lib().tbnav_icp_default_align_map_params(C.byref(p))
+    for key, v in kw.items():
+        if key not in _ALIGN_MAP_FIELDS:
+            raise TypeError(f"alignMap: no parameter {key!r} (one of {_ALIGN_MAP_FIELDS})")
+        setattr(p, key, v)
     return p
 
 
@@ -434,6 +451,58 @@ class ScanAlignment:
         capi.check(self._L.tbnav_icp_localize_map_scores(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, C.byref(p),
                                                          vol.ctypes.data), "tbnav_icp_localize_map_scores")
         return vol
+
+    def alignMap(self, filter, T_init, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """tbnav_icp_align_map (the header's MAP ALIGNMENT, A1-A11): the alignment of one scan to the map of a particle of
+        `filter` (particle=-1: its best one) from the WORLD guess T_init, below one cell; params: half_cells, gate_cells,
+        feature_cells, max_flatness (tbnav_icp_default_align_map_params for what is not named)
+        -> (ok, T in the world, info dict); on a failure T is T_init unchanged."""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        out, ok, info = (C.c_double * 3)(), C.c_int32(), capi.IcpInfo()
+        capi.check(self._L.tbnav_icp_align_map(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T_init),
+                                               C.byref(_align_map_params(params)), out, C.byref(ok), C.byref(info)), "tbnav_icp_align_map")
+        return bool(ok.value), tuple(out), _info(info)
+
+    def alignMapBatch(self, filter, T_init, scan, particles, **params):
+        """tbnav_icp_align_map_batch (A8): one scan, n pairs (particles[i], T_init[i]), each equal to the single call
+        -> list of (ok, T, info dict)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        particles = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
+        n = particles.size
+        T_init = np.ascontiguousarray(T_init, dtype=np.float64).reshape(n, 3)
+        T = np.zeros((max(n, 1), 3), dtype=np.float64)
+        ok = np.zeros(max(n, 1), dtype=np.int32)
+        infos = (capi.IcpInfo * max(n, 1))()
+        capi.check(self._L.tbnav_icp_align_map_batch(self._h, filter._h, scan.ctypes.data, scan.size, n, particles.ctypes.data,
+                                                     T_init.ctypes.data, C.byref(_align_map_params(params)), T.ctypes.data, ok.ctypes.data,
+                                                     C.cast(infos, C.c_void_p)), "tbnav_icp_align_map_batch")
+        return [(bool(ok[i]), tuple(float(v) for v in T[i]), _info(infos[i])) for i in range(n)]
+
+    def alignMapPairs(self, filter, T_init, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """test hook (A10): iteration 1's pairing, per beam -> dict of arrays [n_beams]: has_home, hi, hj, mi, mj, D, has_normal,
+        kept (int32), bx, by (float64), nx, ny (float32)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        recs = (capi.IcpAlignMapPair * scan.size)()
+        capi.check(self._L.tbnav_icp_align_map_pairs(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T_init),
+                                                     C.byref(_align_map_params(params)), C.cast(recs, C.c_void_p)), "tbnav_icp_align_map_pairs")
+        a = np.frombuffer(recs, dtype=_ALIGN_MAP_PAIR).copy()
+        return {f: np.ascontiguousarray(a[f]) for f in _ALIGN_MAP_PAIR.names}
+
+    def lastAlignMapKernel(self) -> str:
+        """the map alignment's kernel as a profiler prints it; "" until alignMap has run on this handle"""
+        buf = C.create_string_buffer(64)
+        capi.check(self._L.tbnav_icp_last_align_map_kernel(self._h, buf, 64), "tbnav_icp_last_align_map_kernel")
+        return buf.value.decode()
+
+    def relocalizeMap(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, localize=None, **params):
+        """localizeMap, then alignMap from its T when it is accepted: where the robot is in the particle's map, with no guess and
+        below one cell.  localize: dict of localizeMap's parameters; params: alignMap's
+        -> (ok, T in the world, dict(localize=localizeMap's record, align=alignMap's info or None when the search was rejected))"""
+        acc, T, ginfo = self.localizeMap(filter, scan, particle, **(localize or {}))
+        if not acc:
+            return False, T, dict(localize=ginfo, align=None)
+        ok, Ta, info = self.alignMap(filter, T, scan, particle, **params)
+        return ok, Ta, dict(localize=ginfo, align=info)
 
     def lastSearch(self) -> dict:
         """the search record of the last pclICP / pclICPWrapper, for a wrapperBatch the last scan's (searched = 0: none ran)"""
