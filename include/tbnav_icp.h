@@ -256,7 +256,8 @@
  *      _last_search_shape and _last_search_wide report this search (of a batch: the last pair's).
  *  M9. Known limits.  Accuracy is one cell and one angle step: the refinement below one cell against the same map is tbnav_icp_align_map (MAP
  *      ALIGNMENT, A1-A11 below), which a caller runs from info->T; the search itself does not run it.  Points further than E' from the guess's cell
- *      add nothing, as in the scan search.  Unknown cells and free cells both score 0: there is no free-space penalty.
+ *      add nothing, as in the scan search.  Unknown cells and free cells both score 0: the search has no free-space penalty; whether a
+ *      beam passes through a wall or ends in space the map knows to be free is asked by tbnav_icp_verify_map (MAP CHECK, V1-V10 below).
  *      min_quality = 0.5 was set for scan pairs; over a WIDE window against a map it does not separate a true match from a wrong
  *      room (tests/icp_search_map_cases.py, BEHAVIOUR: the restatement on maps drawn by the oracle's GridMapper from 12 / 20 scans
  *      of the two rooms of tests/rbpf_cases.py: true matches at +-48 cells and +-45 steps 0.872 and 0.984, a scan of the other room
@@ -341,7 +342,8 @@
  *      tbnav_icp_localize_map_bounds (uint32 [NA][nbx][nby]); tbnav_icp_localize_map_scores (EVERY candidate's score,
  *      uint32 [NA][w][h] indexed [ia][tx - tx0][ty - ty0], computed by the refinement kernel run over all blocks;
  *      TBNAV_ERR_UNSUPPORTED above 2^24 candidates).
- *  L10. Not built: a free-space penalty or a restriction to FREE cells (M9's wrong-room finding applies unchanged); several
+ *  L10. Not built: a free-space penalty or a restriction to FREE cells inside the search (M9's wrong-room finding applies unchanged; a
+ *      caller checks the pose it gets with tbnav_icp_verify_map, MAP CHECK V1-V10, which refuses that wrong room); several
  *      hypotheses or a runner-up at a distance (a symmetric building has several equal answers and the index rule picks one);
  *      sub-cell or sub-step refinement inside this call (a caller runs tbnav_icp_align_map, MAP ALIGNMENT A1-A11, from T); seeding the
  *      filter's particles from the result; batches of scans; sharded filters; more than one level of pooling in the contract (an
@@ -420,7 +422,8 @@
  *      the target cell wherever there is one, whatever D is; zero otherwise), kept.  A beam that is no point, or whose home is
  *      outside the window, holds has_home = 0, target (-1, -1), D = -1 and zeros.
  *  A11. Not built: a rule that ends the two-state cycles of the line metric before max_iter (some starts run to the iteration limit
- *      in them); robust weights; a free-space term; use of the log-odds instead of the bits (the map's own rasterisation bias, up to
+ *      in them); robust weights; a free-space term in the metric (the check of the aligned pose against walls and free space is
+ *      tbnav_icp_verify_map, MAP CHECK V1-V10); use of the log-odds instead of the bits (the map's own rasterisation bias, up to
  *      about 9 mm at 0.05 m cells in the prototype, stays: no method that reads occupancy bits removes it); use inside
  *      tbnav_icp_step or bmapping::ParticleFilter::SLAM; sharded filters; seeding particles on the device.
  *  KERNEL (csrc/icp_align_map.hip): icp_align_map<P>, one workgroup of 256 threads per pair, the whole loop in one launch.  The
@@ -429,6 +432,66 @@
  *  (clz / ffs on a masked 64-bit look; it goes on while dr^2 <= the best D, since a row at dr^2 == D can still win A5's tie), the
  *  feature from the cell's (2w + 1)^2 bits on the fly, and L3 / L4, the tree and the stopping rules from icp_iter_device.hpp, the
  *  code icp_align runs.
+ *
+ * MAP CHECK (an addition, no counterpart in the reference; csrc/icp_verify_map.hip; restated in tests/icp_verify_map_restatement.py and
+ * reproduced bit for bit).  The searches and the alignment above score one thing: an occupied cell near a scan's end point.  This
+ * entry asks what they do not: does a beam pass through a wall the map holds, and does it end in space the map knows to be empty?
+ * It is stateless and opt-in, takes one scan and n (particle, world pose) pairs, walks every beam through that particle's map and
+ * returns integer counts and an accept flag per pair.  Everything is integer arithmetic, or fp64 as parenthesised with no
+ * contraction.
+ *  V1. Handles, particle, order of checks, ordering: A1 and A9 as they stand.  h and pf on one device, a member of a sharded group
+ *      refused; arguments, parameters and particles first (TBNAV_ERR_INVALID_ARG), then a device mismatch or a sharded group
+ *      (TBNAV_ERR_UNSUPPORTED), then the poses: one that is not finite (any of the three), or whose sensor cell (V3) lies outside the
+ *      map, is TBNAV_ERR_OUT_OF_WORLD.  particle is a slot or TBNAV_ICP_MAP_BEST_PARTICLE.  The kernel runs behind the filter's
+ *      stream through an event and only reads the filter.  A rejected call changes nothing; an accepted call changes only what
+ *      tbnav_icp_last_verify_map_kernel reports.
+ *  V1a. Parameters (tbnav_icp_verify_map_params; defaults in brackets; NULL: the defaults; a bad field is TBNAV_ERR_INVALID_ARG):
+ *      half_cells H [96, 8..TBNAV_ICP_VERIFY_MAP_MAX_HALF = 128]; slack_cells k [2, 0..8]; max_through_q10 [102, 0..1024];
+ *      max_missing_q10 [102, 0..1024]; min_hit_q10 [512, 0..1024]; one reserved int32 that must be 0.  The three thresholds are
+ *      design constants placed inside the gap the behaviour table of tests/icp_verify_map_cases.py shows.
+ *  V2. Classes of a map cell.  OCCUPIED is M2's bit.  UNKNOWN and FREE are G10's (tbnav_nav.h): half_lo <= l <= half_hi, and
+ *      l <= free_cut, on the cell's log-odds l with the cuts the filter handle holds.  A tile with id 0 is UNKNOWN throughout.  A
+ *      known cell that is none of these is OTHER.  OCCUPIED wins where a cell is both (which the cuts exclude).
+ *  V3. Cells.  A beam's end point is A5's point a of iteration 1: item 3's transform from the float-rounded pose of item 2, held in
+ *      fp64.  Its end cell e is A2's cell of those doubles.  The sensor cell s is A2's cell of the cloud-frame point a zero range
+ *      would give — Trs's translation as item 1 forms it, ((float)Trs.x, (float)Trs.y) — sent through the same transform.  The
+ *      window is A3's, 2H x 2H round s.  A beam that is no point (item 1's range rules; a range that is not a number) has class NONE
+ *      and takes no part.  A point whose end cell lies outside the window or the map (the floors compared as doubles) is OUTSIDE and
+ *      is not walked.
+ *  V4. Walk.  d = e - s, n = max(|di|, |dj|).  Step t = 1 .. n enters s + G17's closed-form offset for (di, dj):
+ *      (sgn(di) * ((2*t*|di| + n) / (2*n)), sgn(dj) * ((2*t*|dj| + n) / (2*n))), integer division.  A step is BLOCKED when the cell
+ *      it enters is OCCUPIED, or when both coordinates change and BOTH cells orthogonally between the previous cell and this one are
+ *      OCCUPIED (G18's rule).  b is the first blocked step, or n + 1 when none is.  s itself is never tested.
+ *  V5. Class of a walked beam, in this order.  (1) THROUGH when b + k < n: the map holds a wall more than k cells in front of where
+ *      the beam ends.  (2) Otherwise D = the least (mi - ei)^2 + (mj - ej)^2 over the OCCUPIED cells inside the window and the map
+ *      with |mi - ei| <= k and |mj - ej| <= k; HIT when such a cell exists and D <= k*k.  (3) Otherwise by e's class: FREE ->
+ *      MISSING (the map knows this space to be empty and the scan sees a surface there), UNKNOWN -> UNSEEN, OTHER -> UNDECIDED.
+ *      n = 0 is legal; such a beam is never THROUGH.
+ *  V6. Path counts, over the steps t = 1 .. min(b, n) - 1 (the cells entered before the blocking step and before the end cell):
+ *      free_cells those that are FREE, unknown_cells those that are UNKNOWN, summed per beam with no attempt at distinct cells (G18
+ *      counts distinct cells; this is another quantity).
+ *  V7. Record (tbnav_icp_verify_map_info): points, outside, walked = points - outside; hit, through, missing, unseen, undecided
+ *      (they sum to walked); int64 free_cells and unknown_cells; sensor_cell; sensor_class (0 UNKNOWN, 1 FREE, 2 OCCUPIED, 3 OTHER;
+ *      reported, no part of accepted); accepted = 1 when all four hold as integers: walked >= 1, through * 1024 <=
+ *      max_through_q10 * walked, missing * 1024 <= max_missing_q10 * walked, hit * 1024 >= min_hit_q10 * walked.
+ *  V8. Batch: one scan and n >= 1 pairs (particle_i, T_i), each equal to the single call bit for bit.  One bad pair rejects the
+ *      call before any launch.
+ *  V9. Entries: tbnav_icp_default_verify_map_params, tbnav_icp_verify_map, tbnav_icp_verify_map_batch,
+ *      tbnav_icp_last_verify_map_kernel.  Test hook tbnav_icp_verify_map_beams: per BEAM (tbnav_icp_verify_map_beam) cls, e, n, b
+ *      (-1 where nothing blocked), D (-1 where the box is empty or the beam is THROUGH, for which no look is made), free_cells,
+ *      unknown_cells.  All zeros with cls = NONE for a beam that is no point; all zeros but cls for one that is OUTSIDE (its end
+ *      cell need not be an int).
+ *  V10. Not built: a comparison with the expected range for beams without a return (the reference's mapper drops them,
+ *      sensor_model.cpp:43-112); weights by range; use inside tbnav_icp_step, the searches' own acceptance, or
+ *      bmapping::ParticleFilter::SLAM; several hypotheses out of the global search; sharded filters; the mirror pose of a symmetric
+ *      map, which this check cannot break (no method that reads the map can).
+ *  KERNEL (csrc/icp_verify_map.hip): icp_verify_map<P>, one workgroup of 256 threads per pair, thread t keeping beams t, t + 256, ...
+ *  Three bitmaps of the window are staged into LDS, each row with a zero word either side (3 x 256 x 10 words = 30 KB at H = 128):
+ *  OCCUPIED through occ_row_window; FREE and UNKNOWN from the log-odds read through the tile table — a wave64 reads two 32-cell
+ *  words, classifies them against the cuts and packs them with ballots; a tile with id 0 is written all-UNKNOWN without a read — and
+ *  then shifted to the window's origin.  Lanes step their rays out of LDS with G17's quotients by a carried remainder (the same
+ *  integers), look D up by rows outwards (clz / ffs on a masked 64-bit look) and reduce the counts with wave sums and a small LDS
+ *  tree.  No atomics; every loop is bounded by H, k or P.
  *
  * KERNEL: one workgroup of 256 threads per pair, the whole iteration loop in one launch; target cloud as float2 in LDS,
  * source points in registers, no global traffic inside the loop (csrc/icp.hip).  Limits: n_beams <= 4096 (32 KB of LDS),
@@ -771,6 +834,63 @@ int tbnav_icp_align_map_pairs(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, co
                               const tbnav_icp_align_map_params* params, tbnav_icp_align_map_pair* pairs);
 /* the alignment kernel's name as a profiler prints it; "" until the route has run on this handle */
 int tbnav_icp_last_align_map_kernel(const tbnav_icp* h, char* kernel, int32_t kernel_cap);
+
+/* ---- MAP CHECK: a pose against the walls and the free space of a particle's map (V1-V12 of the section of that name) ---- */
+#define TBNAV_ICP_VERIFY_MAP_MAX_HALF 128
+#define TBNAV_ICP_VERIFY_MAP_MAX_SLACK 8
+
+/* the class of a beam (V3, V5) */
+typedef enum tbnav_icp_verify_class {
+  TBNAV_ICP_VERIFY_NONE = 0,       /* no point */
+  TBNAV_ICP_VERIFY_OUTSIDE = 1,    /* the end cell outside the window or the map: not walked */
+  TBNAV_ICP_VERIFY_HIT = 2,
+  TBNAV_ICP_VERIFY_THROUGH = 3,
+  TBNAV_ICP_VERIFY_MISSING = 4,
+  TBNAV_ICP_VERIFY_UNSEEN = 5,
+  TBNAV_ICP_VERIFY_UNDECIDED = 6
+} tbnav_icp_verify_class;
+
+typedef struct tbnav_icp_verify_map_params {
+  int32_t half_cells;       /* 96 */
+  int32_t slack_cells;      /* 2 */
+  int32_t max_through_q10;  /* 102 */
+  int32_t max_missing_q10;  /* 102 */
+  int32_t min_hit_q10;      /* 512 */
+  int32_t reserved;         /* must be 0 */
+} tbnav_icp_verify_map_params;
+
+/* V7 */
+typedef struct tbnav_icp_verify_map_info {
+  int64_t free_cells, unknown_cells;                     /* V6, summed over the walked beams */
+  int32_t points, outside, walked;                       /* walked = points - outside */
+  int32_t hit, through, missing, unseen, undecided;      /* sum to walked */
+  int32_t sensor_cell[2];
+  int32_t sensor_class;                                  /* 0 UNKNOWN, 1 FREE, 2 OCCUPIED, 3 OTHER */
+  int32_t accepted;
+} tbnav_icp_verify_map_info;
+
+/* the test hook's record of one beam (V9); all zero for a beam that is no point, all zero but cls for one that is OUTSIDE */
+typedef struct tbnav_icp_verify_map_beam {
+  int32_t cls;              /* tbnav_icp_verify_class */
+  int32_t e[2];             /* the end cell */
+  int32_t n;                /* steps */
+  int32_t b;                /* the first blocked step, or -1 */
+  int32_t D;                /* V5's least D, or -1 where the box is empty or the beam is THROUGH */
+  int32_t free_cells, unknown_cells;   /* V6 */
+} tbnav_icp_verify_map_beam;
+
+void tbnav_icp_default_verify_map_params(tbnav_icp_verify_map_params* p);
+/* the check of the world pose T against particle's map with one scan (V1-V7).  params may be NULL (the defaults); info is required. */
+int tbnav_icp_verify_map(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T[3],
+                         const tbnav_icp_verify_map_params* params, tbnav_icp_verify_map_info* info);
+/* V8: one scan, n pairs (particles[i], T[i]): T [n][3], infos [n] */
+int tbnav_icp_verify_map_batch(tbnav_icp* h, tbnav_rbpf* pf, const float* scan, int32_t n_beams, int32_t n, const int32_t* particles,
+                               const double* T, const tbnav_icp_verify_map_params* params, tbnav_icp_verify_map_info* infos);
+/* test hook (V9): the record of every beam of one pair, beams [n_beams]; info may be NULL */
+int tbnav_icp_verify_map_beams(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const double T[3],
+                               const tbnav_icp_verify_map_params* params, tbnav_icp_verify_map_info* info, tbnav_icp_verify_map_beam* beams);
+/* the check's kernel as a profiler prints it; "" until the route has run on this handle */
+int tbnav_icp_last_verify_map_kernel(const tbnav_icp* h, char* kernel, int32_t kernel_cap);
 
 #ifdef __cplusplus
 }

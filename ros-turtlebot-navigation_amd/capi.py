@@ -224,6 +224,27 @@ class IcpAlignMapPair(C.Structure):
                 ("kept", C.c_int32)]
 
 
+class IcpVerifyMapParams(C.Structure):
+    """tbnav_icp_verify_map_params (include/tbnav_icp.h, MAP CHECK, V1a)."""
+    _fields_ = [("half_cells", C.c_int32), ("slack_cells", C.c_int32), ("max_through_q10", C.c_int32), ("max_missing_q10", C.c_int32),
+                ("min_hit_q10", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IcpVerifyMapInfo(C.Structure):
+    """tbnav_icp_verify_map_info (V7)."""
+    _fields_ = [("free_cells", C.c_int64), ("unknown_cells", C.c_int64), ("points", C.c_int32), ("outside", C.c_int32), ("walked", C.c_int32),
+                ("hit", C.c_int32), ("through", C.c_int32), ("missing", C.c_int32), ("unseen", C.c_int32), ("undecided", C.c_int32),
+                ("sensor_cell", C.c_int32 * 2), ("sensor_class", C.c_int32), ("accepted", C.c_int32)]
+
+
+class IcpVerifyMapBeam(C.Structure):
+    """tbnav_icp_verify_map_beam (V9): the test hook's record of one beam."""
+    _fields_ = [("cls", C.c_int32), ("e", C.c_int32 * 2), ("n", C.c_int32), ("b", C.c_int32), ("D", C.c_int32), ("free_cells", C.c_int32),
+                ("unknown_cells", C.c_int32)]
+
+
+ICP_VERIFY_NONE, ICP_VERIFY_OUTSIDE, ICP_VERIFY_HIT, ICP_VERIFY_THROUGH, ICP_VERIFY_MISSING, ICP_VERIFY_UNSEEN, ICP_VERIFY_UNDECIDED = range(7)
+ICP_VERIFY_MAP_MAX_HALF, ICP_VERIFY_MAP_MAX_SLACK = 128, 8
 ICP_ALIGN_MAP_MAX_HALF = 256
 ICP_GLOBAL_STAGES = 9
 ICP_GLOBAL_MAX_SIDE, ICP_GLOBAL_MAX_ANG, ICP_GLOBAL_MAX_BLOCKS, ICP_GLOBAL_MAX_HOOK_SCORES = 2048, 720, 1 << 26, 1 << 24
@@ -489,6 +510,11 @@ def lib() -> C.CDLL:
         "tbnav_icp_align_map_batch": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(IcpAlignMapParams), vp, vp, vp]),
         "tbnav_icp_align_map_pairs": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpAlignMapParams), vp]),
         "tbnav_icp_last_align_map_kernel": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_icp_default_verify_map_params": (None, [C.POINTER(IcpVerifyMapParams)]),
+        "tbnav_icp_verify_map": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpVerifyMapParams), C.POINTER(IcpVerifyMapInfo)]),
+        "tbnav_icp_verify_map_batch": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(IcpVerifyMapParams), vp]),
+        "tbnav_icp_verify_map_beams": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpVerifyMapParams), C.POINTER(IcpVerifyMapInfo), vp]),
+        "tbnav_icp_last_verify_map_kernel": (C.c_int, [vp, C.c_char_p, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -495,7 +495,7 @@ void tbnav_icp_destroy(tbnav_icp* h) {
     DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->d_table);
-    for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out, &h->d_align_in, &h->d_align_rec}) b->release();
+    for (DevBuf* b : {&h->d_stored, &h->d_scans, &h->d_pairs, &h->d_out, &h->d_align_in, &h->d_align_rec, &h->d_verify_in, &h->d_verify_out, &h->d_verify_rec}) b->release();
     search_free(h);
     global_free(h);
     if (h->stream) (void)hipStreamDestroy(h->stream);

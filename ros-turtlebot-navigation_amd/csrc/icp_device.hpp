@@ -148,6 +148,8 @@ struct tbnav_icp {
   tbnav_icpdev::IcpGlobal global;
   tbnav_icpdev::DevBuf d_align_in, d_align_rec;     // the map alignment (icp_align_map.hip): its pairs; the test hook's pairing record
   int align_map_p = 0;                              // ... the P of its last launch, 0: none yet (tbnav_icp_last_align_map_kernel)
+  tbnav_icpdev::DevBuf d_verify_in, d_verify_out, d_verify_rec;   // the map check (icp_verify_map.hip): its pairs, their records; the test hook's per-beam record
+  int verify_map_p = 0;                             // ... the P of its last launch, 0: none yet (tbnav_icp_last_verify_map_kernel)
   std::vector<std::array<double, 3>> h_init;       // T_init of h_pairs, as given (the search starts from the doubles)
   std::vector<tbnav_icp_search_info> h_sinfo;       // the search record of h_pairs (run_pairs)
   std::vector<tbnav_icp_search_shape> h_sshape;     // and the shape record beside it (computed = 0 where the shape did not run)

@@ -176,6 +176,35 @@ struct MapRelocalizeResult {
   Transform2D T;               ///< fine.T when aligned and fine.ok, else found.T
 };
 
+/// (addition) the map check's parameters: tbnav_icp_verify_map_params with its defaults
+struct ICPVerifyMap {
+  int half_cells = 96;         ///< the window +-half_cells round the sensor's cell, 8..128
+  int slack_cells = 2;         ///< k: a wall within k cells of a beam's end explains it, 0..8
+  int max_through_q10 = 102;   ///< accepted while through * 1024 <= this * walked, 0..1024
+  int max_missing_q10 = 102;   ///< ... and missing * 1024 <= this * walked
+  int min_hit_q10 = 512;       ///< ... and hit * 1024 >= this * walked
+};
+
+/// (addition) what ScanAlignment::verifyInMap returns: tbnav_icp_verify_map_info
+struct MapVerifyResult {
+  bool accepted = false;       ///< the map does not contradict the pose (tbnav_icp.h, MAP CHECK V7)
+  int points = 0, outside = 0, walked = 0;
+  int hit = 0, through = 0, missing = 0, unseen = 0, undecided = 0;   ///< they sum to walked
+  long long free_cells = 0, unknown_cells = 0;
+  int sensor_cell[2] = {0, 0};
+  int sensor_class = 0;        ///< 0 unknown, 1 free, 2 occupied, 3 known and neither
+};
+
+/// (addition) what ScanAlignment::relocalizeInMapChecked returns: all three records.  aligned: the alignment ran; checked: the check ran
+/// (at fine.T when the alignment converged, else at found.T); verified: it ran and accepts the pose
+struct MapRelocalizeCheckedResult {
+  MapLocalizeResult found;
+  MapAlignResult fine;
+  MapVerifyResult check;
+  bool aligned = false, checked = false, verified = false;
+  Transform2D T;               ///< the pose that was checked, or found.T when none was
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
@@ -220,6 +249,16 @@ class ScanAlignment {
   /// (addition) localizeInMap, then alignToMap from its pose when it is accepted
   MapRelocalizeResult relocalizeInMap(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
                                       const ICPAlignMap& align = {});
+
+  /// (addition) the pose `pose_world` checked against the walls and the free space of the map of the filter's best particle with
+  /// `scan` (tbnav_icp.h, MAP CHECK V1-V10).  Throws as alignToMap does.
+  MapVerifyResult verifyInMap(ParticleFilter& filter, const Transform2D& pose_world, const std::vector<float>& scan,
+                              const ICPVerifyMap& params = {});
+  /// (addition) localizeInMap; alignToMap from its pose when it is accepted or even_if_rejected is set; then verifyInMap at the aligned
+  /// pose, or at the found pose when the alignment did not converge.  relocalizeInMap itself is untouched.
+  MapRelocalizeCheckedResult relocalizeInMapChecked(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
+                                                    const ICPAlignMap& align = {}, const ICPVerifyMap& verify = {},
+                                                    bool even_if_rejected = false);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

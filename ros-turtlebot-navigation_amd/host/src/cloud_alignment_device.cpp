@@ -191,4 +191,54 @@ MapRelocalizeResult ScanAlignment::relocalizeInMap(ParticleFilter& filter, const
   return r;
 }
 
+MapVerifyResult ScanAlignment::verifyInMap(ParticleFilter& filter, const Transform2D& pose_world, const std::vector<float>& scan,
+                                           const ICPVerifyMap& params) {
+  if (!device_) throw std::logic_error("bmapping::ScanAlignment::verifyInMap: useDeviceICP first");
+  if (filter.g_) throw std::runtime_error("bmapping::ScanAlignment::verifyInMap: a filter over several GPUs is not supported");
+  tbnav_icp_verify_map_params vp;
+  tbnav_icp_default_verify_map_params(&vp);
+  vp.half_cells = params.half_cells;
+  vp.slack_cells = params.slack_cells;
+  vp.max_through_q10 = params.max_through_q10;
+  vp.max_missing_q10 = params.max_missing_q10;
+  vp.min_hit_q10 = params.min_hit_q10;
+  const auto g = pose_world.displacement();
+  const double T[3] = {g.theta, g.x, g.y};
+  tbnav_icp_verify_map_info info{};
+  const int rc = tbnav_icp_verify_map(static_cast<tbnav_icp*>(device_.get()), filter.h_, TBNAV_ICP_MAP_BEST_PARTICLE, scan.data(),
+                                      (int32_t)scan.size(), T, &vp, &info);
+  if (rc != TBNAV_OK) {
+    const std::string text = tbnav_status_string(rc);
+    if (rc == TBNAV_ERR_OUT_OF_WORLD) throw std::invalid_argument(text);  // what the reference throws (grid_mapper.cpp:856)
+    std::string msg = "bmapping::ScanAlignment::verifyInMap: " + text;
+    if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+    const char* hip = tbnav_last_hip_error();
+    if (hip && *hip) msg += std::string(" [") + hip + "]";
+    throw std::runtime_error(msg);
+  }
+  MapVerifyResult r;
+  r.accepted = info.accepted != 0;
+  r.points = info.points; r.outside = info.outside; r.walked = info.walked;
+  r.hit = info.hit; r.through = info.through; r.missing = info.missing; r.unseen = info.unseen; r.undecided = info.undecided;
+  r.free_cells = info.free_cells; r.unknown_cells = info.unknown_cells;
+  r.sensor_cell[0] = info.sensor_cell[0]; r.sensor_cell[1] = info.sensor_cell[1];
+  r.sensor_class = info.sensor_class;
+  return r;
+}
+
+MapRelocalizeCheckedResult ScanAlignment::relocalizeInMapChecked(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global,
+                                                                 const ICPAlignMap& align, const ICPVerifyMap& verify, bool even_if_rejected) {
+  MapRelocalizeCheckedResult r;
+  r.found = localizeInMap(filter, scan, global);
+  r.T = r.found.T;
+  if (!r.found.accepted && !even_if_rejected) return r;
+  r.fine = alignToMap(filter, r.found.T, scan, align);
+  r.aligned = true;
+  if (r.fine.ok) r.T = r.fine.T;
+  r.check = verifyInMap(filter, r.T, scan, verify);
+  r.checked = true;
+  r.verified = r.check.accepted;
+  return r;
+}
+
 }  // namespace bmapping

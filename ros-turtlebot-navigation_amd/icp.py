@@ -28,6 +28,10 @@ the filter already holds.
 alignMap(filter, T_init, scan) (an addition too) aligns one scan to the particle's map BELOW one cell (the header's MAP ALIGNMENT,
 A1-A11): a point-to-line step against lines fitted to the occupied cells; relocalizeMap(filter, scan) is localizeMap followed by it.
 
+verifyMap(filter, T, scan) (an addition too) asks whether the particle's map CONTRADICTS a pose (the header's MAP CHECK, V1-V10):
+every beam is walked through the map, and the beams that pass through a wall the map holds or end in space it knows to be free are
+counted against thresholds; relocalizeMapChecked(filter, scan) is localizeMap, alignMap and this check in a row.
+
 metric="line" (an addition with no counterpart in the reference, which only runs PCL's point-to-point ICP) aligns with the
 point-to-line metric of the header's POINT-TO-LINE METRIC section; the default stays "point".
 """
@@ -127,6 +131,28 @@ def _align_map_params(kw) -> "capi.IcpAlignMapParams":
             raise TypeError(f"alignMap: no parameter {key!r} (one of {_ALIGN_MAP_FIELDS})")
         setattr(p, key, v)
     return p
+
+
+_VERIFY_MAP_FIELDS = ("half_cells", "slack_cells", "max_through_q10", "max_missing_q10", "min_hit_q10", "reserved")
+_VERIFY_MAP_BEAM = np.dtype([("cls", np.int32), ("ei", np.int32), ("ej", np.int32), ("n", np.int32), ("b", np.int32), ("D", np.int32),
+                             ("free_cells", np.int32), ("unknown_cells", np.int32)])
+assert _VERIFY_MAP_BEAM.itemsize == C.sizeof(capi.IcpVerifyMapBeam)
+
+
+def _verify_map_params(kw) -> "capi.IcpVerifyMapParams":
+    p = capi.IcpVerifyMapParams()
+    capi.lib().tbnav_icp_default_verify_map_params(C.byref(p))
+    for key, v in kw.items():
+        if key not in _VERIFY_MAP_FIELDS:
+            raise TypeError(f"verifyMap: no parameter {key!r} (one of {_VERIFY_MAP_FIELDS})")
+        setattr(p, key, v)
+    return p
+
+
+def _verify_map_info(i: "capi.IcpVerifyMapInfo") -> dict:
+    return dict(points=i.points, outside=i.outside, walked=i.walked, hit=i.hit, through=i.through, missing=i.missing, unseen=i.unseen,
+                undecided=i.undecided, free_cells=i.free_cells, unknown_cells=i.unknown_cells, sensor_cell=tuple(i.sensor_cell),
+                sensor_class=i.sensor_class, accepted=i.accepted)
 
 
 def _global_info(i: "capi.IcpGlobalInfo") -> dict:
@@ -503,6 +529,61 @@ class ScanAlignment:
             return False, T, dict(localize=ginfo, align=None)
         ok, Ta, info = self.alignMap(filter, T, scan, particle, **params)
         return ok, Ta, dict(localize=ginfo, align=info)
+
+    def verifyMap(self, filter, T, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """tbnav_icp_verify_map (the header's MAP CHECK, V1-V10): the WORLD pose T checked against the walls and the free space of
+        the map of a particle of `filter` (particle=-1: its best one) with one scan; params: half_cells, slack_cells,
+        max_through_q10, max_missing_q10, min_hit_q10 (tbnav_icp_default_verify_map_params for what is not named)
+        -> dict of V7's record: points, outside, walked, hit, through, missing, unseen, undecided, free_cells, unknown_cells,
+        sensor_cell, sensor_class, accepted"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        info = capi.IcpVerifyMapInfo()
+        capi.check(self._L.tbnav_icp_verify_map(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T),
+                                                C.byref(_verify_map_params(params)), C.byref(info)), "tbnav_icp_verify_map")
+        return _verify_map_info(info)
+
+    def verifyMapBatch(self, filter, T, scan, particles, **params):
+        """tbnav_icp_verify_map_batch (V8): one scan, n pairs (particles[i], T[i]), each equal to the single call -> list of dicts"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        particles = np.ascontiguousarray(particles, dtype=np.int32).reshape(-1)
+        n = particles.size
+        T = np.ascontiguousarray(T, dtype=np.float64).reshape(n, 3)
+        infos = (capi.IcpVerifyMapInfo * max(n, 1))()
+        capi.check(self._L.tbnav_icp_verify_map_batch(self._h, filter._h, scan.ctypes.data, scan.size, n, particles.ctypes.data, T.ctypes.data,
+                                                      C.byref(_verify_map_params(params)), C.cast(infos, C.c_void_p)), "tbnav_icp_verify_map_batch")
+        return [_verify_map_info(infos[i]) for i in range(n)]
+
+    def verifyMapBeams(self, filter, T, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
+        """test hook (V9): the record of every beam -> (verifyMap's dict, dict of int32 arrays [n_beams]: cls, ei, ej, n, b, D,
+        free_cells, unknown_cells)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        info = capi.IcpVerifyMapInfo()
+        recs = (capi.IcpVerifyMapBeam * scan.size)()
+        capi.check(self._L.tbnav_icp_verify_map_beams(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, _d3(T),
+                                                      C.byref(_verify_map_params(params)), C.byref(info), C.cast(recs, C.c_void_p)),
+                   "tbnav_icp_verify_map_beams")
+        a = np.frombuffer(recs, dtype=_VERIFY_MAP_BEAM).copy()
+        return _verify_map_info(info), {f: np.ascontiguousarray(a[f]) for f in _VERIFY_MAP_BEAM.names}
+
+    def lastVerifyMapKernel(self) -> str:
+        """the map check's kernel as a profiler prints it; "" until verifyMap has run on this handle"""
+        buf = C.create_string_buffer(64)
+        capi.check(self._L.tbnav_icp_last_verify_map_kernel(self._h, buf, 64), "tbnav_icp_last_verify_map_kernel")
+        return buf.value.decode()
+
+    def relocalizeMapChecked(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, localize=None, align=None, even_if_rejected=False, **params):
+        """localizeMap; when it is accepted (or even_if_rejected) alignMap from the pose it found; then verifyMap at the aligned
+        pose, or at the found pose when the alignment did not converge.  localize, align: dicts of those calls' parameters; params:
+        verifyMap's.  relocalizeMap itself is untouched.
+        -> (verified, T in the world, dict(localize=localizeMap's record, align=alignMap's info or None, aligned=bool,
+        verify=verifyMap's record or None)); verified: the search was accepted (or even_if_rejected) and the check accepts the pose"""
+        acc, T, ginfo = self.localizeMap(filter, scan, particle, **(localize or {}))
+        if not acc and not even_if_rejected:
+            return False, T, dict(localize=ginfo, align=None, aligned=False, verify=None)
+        ok, Ta, info = self.alignMap(filter, T, scan, particle, **(align or {}))
+        Tv = Ta if ok else T
+        rec = self.verifyMap(filter, Tv, scan, particle, **params)
+        return bool(rec["accepted"]), Tv, dict(localize=ginfo, align=info, aligned=ok, verify=rec)
 
     def lastSearch(self) -> dict:
         """the search record of the last pclICP / pclICPWrapper, for a wrapperBatch the last scan's (searched = 0: none ran)"""
