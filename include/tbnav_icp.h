@@ -343,8 +343,8 @@
  *      uint32 [NA][w][h] indexed [ia][tx - tx0][ty - ty0], computed by the refinement kernel run over all blocks;
  *      TBNAV_ERR_UNSUPPORTED above 2^24 candidates).
  *  L10. Not built: a free-space penalty or a restriction to FREE cells inside the search (M9's wrong-room finding applies unchanged; a
- *      caller checks the pose it gets with tbnav_icp_verify_map, MAP CHECK V1-V10, which refuses that wrong room); several
- *      hypotheses or a runner-up at a distance (a symmetric building has several equal answers and the index rule picks one);
+ *      caller checks the pose it gets with tbnav_icp_verify_map, MAP CHECK V1-V10, which refuses that wrong room); (several
+ *      hypotheses, for a symmetric building that has several equal answers, are tbnav_icp_localize_map_hyp, HYPOTHESES H1-H10);
  *      sub-cell or sub-step refinement inside this call (a caller runs tbnav_icp_align_map, MAP ALIGNMENT A1-A11, from T); seeding the
  *      filter's particles from the result; batches of scans; sharded filters; more than one level of pooling in the contract (an
  *      implementation may use more inside, L6).
@@ -363,6 +363,57 @@
  *  64-bit atomicMax of (score << 32 | ~linear index) per wave; a block whose bound is 0 holds only zeros and is settled by its
  *  first candidate without a gather.  No workgroup waits for another; every loop is bounded by the points, the tile or s; a round is
  *  a launch and the host reads one small record per round: at most two rounds.
+ *  HYPOTHESES (an addition, tbnav_icp_localize_map_hyp; csrc/icp_hyp.hip behind csrc/icp_global.hip; restated in
+ *  tests/icp_hyp_restatement.py, reproduced exactly).  The global search returns ONE pose, the maximum, ties going to the lowest index;
+ *  a symmetric building has several equal answers, and score alone cannot choose between a true pose and a wrong room (M9).  This entry
+ *  returns the global search's separated peaks: every candidate at or above a floor that no candidate of its window beats, in order.
+ *  A caller aligns and checks each of them (tbnav_icp_align_map_batch, tbnav_icp_verify_map_batch) and learns which survive, and
+ *  whether more than one does.  It is opt-in; no other entry calls it and no other entry's record is touched.  Integers only.
+ *  H1. Handles, parameters, checks.  The handles, tbnav_icp_global_params, the particle and the order of the checks are L1's, unchanged.
+ *      tbnav_icp_hyp_params (defaults in brackets): max_hyp K [8, 1..TBNAV_ICP_HYP_MAX = 64]; floor_q10 f [768, 1..1024]; sep_cells
+ *      [8, 0..64]; sep_steps [10, 0..TBNAV_ICP_GLOBAL_MAX_ANG]; wrap [1, 0 | 1]; one reserved int32 that must be 0.  NULL is the
+ *      defaults; a bad field is TBNAV_ERR_INVALID_ARG.  Bins: Ba = sep_steps + 1, B = sep_cells + 1, bins = ceil(NA / Ba) *
+ *      ceil(w / B) * ceil(h / B); more than TBNAV_ICP_HYP_MAX_BINS = 2^22 bins is TBNAV_ERR_UNSUPPORTED (behind L1's own limits).
+ *      Anything rejected changes nothing.
+ *  H2. Scores and the floor.  Candidates, scores and the linear index are L3 / L4's.  key(c) = (score << 32) | ~index: a greater key is
+ *      a higher score, then a lower index.  best = L4's maximum score; the floor t = (best * f + 1023) >> 10 in 64-bit integers.  With
+ *      best = 0 (no valid point, or an empty map) the result is empty (n = 0), not an error; floor_score, floor_blocks, candidates and
+ *      n_peaks are 0 then.
+ *  H3. Window.  c' lies in c's window when |tx' - tx| <= sep_cells, |ty' - ty| <= sep_cells and d(ia', ia) <= sep_steps;
+ *      d = |ia' - ia| when wrap = 0, and min(|ia' - ia|, NA - |ia' - ia|) when wrap = 1.  The relation is symmetric.  Only the region's
+ *      candidates exist.
+ *  H4. Peak: a candidate with score >= t whose key is the greatest among all candidates in its window.  A candidate with a greater key
+ *      has score >= its score >= t, so only candidates at or above the floor can suppress one; a suppressor need not be a peak itself.
+ *      No two peaks lie in each other's window.  A plateau of equal scores has one peak per window-connected run: the lowest index.
+ *      L4's result is always a peak.
+ *  H5. Result: the peaks in descending key order, the first n = min(K, n_peaks) of them; hypothesis 0 is L4's answer.  Per hypothesis
+ *      (tbnav_icp_hypothesis): T[3] (L4's formula), quality, score, ia, tx, ty, accepted (L4's rule with gp.min_quality).
+ *  H6. What may be skipped, and the limits.  A block may be skipped only if its bound is < t.  How best is found, how blocks are listed
+ *      and how peaks are found is the implementation's.  More than TBNAV_ICP_HYP_MAX_REFINE = 2^18 blocks with bound >= t, or (looked
+ *      at second) more than TBNAV_ICP_HYP_MAX_CANDIDATES = 2^20 candidates with score >= t, is TBNAV_ERR_UNSUPPORTED with nothing
+ *      changed.  Both are functions of L5's bound volume and L3's score volume alone.
+ *  H7. Record tbnav_icp_hyp_info: searched, n, n_peaks, best_score, floor_score, points, occupied, blocks, floor_blocks (bound >= t),
+ *      refined_blocks (the distinct blocks whose candidates were all scored: floor_blocks <= refined_blocks <= blocks), candidates
+ *      (score >= t), rounds (the scoring launches).  All 0 before the first call.
+ *  H8. Ordering: L8's.
+ *  H9. Entries: tbnav_icp_default_hyp_params; tbnav_icp_localize_map_hyp (cap < 1 is INVALID_ARG; otherwise the call fills
+ *      min(cap, n) hypotheses and reports n); tbnav_icp_last_hyp; tbnav_icp_last_hyp_kernels (';'-separated names as a profiler prints
+ *      them, "" before the first call).  Test hook, stateless: tbnav_icp_localize_map_hyp_candidates, every candidate with score >= t
+ *      in ascending index order as (index uint32, score uint32, peak uint8) and their count (the host sorts: the device's order is
+ *      free).
+ *  H10. Not built: a floor relative to anything but the best score; sub-cell refinement inside the call; batches of scans; sharded
+ *      filters; seeding the filter's particles from the survivors.
+ *  KERNELS (csrc/icp_hyp.hip), behind the global search's own (which find best) and one more icp_global_list with lo = t:
+ *  icp_hyp_collect, one workgroup per listed block in icp_global_refine's shape (the heading's offsets in LDS, lanes over the block's
+ *  cells): every candidate with score >= t is appended to a list of keys, one integer atomic add per wave (ballot, count, the lanes
+ *  take consecutive slots), and folded into its bin of Ba x B x B candidates with a 64-bit atomicMax.  icp_hyp_knock, one lane per
+ *  listed candidate: for every bin that can hold a candidate of its window (3 x 3 spatial bins times the angular bins its headings
+ *  fall in, modulo NA with wrap) it reads the bin's winner and, when that lies inside the window with a lesser key, clears the winner's
+ *  alive flag.  A bin is no wider than a window's half extent + 1, so a peak is its bin's winner, and every candidate of a winner's
+ *  window lies in those bins: the alive winners are exactly H4's peaks.  Winners compared only with winners would NOT be: a
+ *  neighbouring bin's winner can lie outside the window while a lesser member lies inside and still beats the candidate.
+ *  icp_hyp_select, one workgroup: flags, counts and compacts the peaks and leaves the first K in key order.  One read-back for all
+ *  three; no workgroup waits for another.
  *  MAP ALIGNMENT (an addition, tbnav_icp_align_map; csrc/icp_align_map.hip; restated in tests/icp_align_map_restatement.py, reproduced
  *  bit for bit).  It has NO COUNTERPART IN THE REFERENCE: this section is its whole specification.  The map search and the global
  *  search stop at one cell and one angle step; the ICP above aligns to the PREVIOUS SCAN, which after a relocalisation is as wrong as
@@ -423,7 +474,7 @@
  *      outside the window, holds has_home = 0, target (-1, -1), D = -1 and zeros.
  *  A11. Not built: a rule that ends the two-state cycles of the line metric before max_iter (some starts run to the iteration limit
  *      in them); robust weights; a free-space term in the metric (the check of the aligned pose against walls and free space is
- *      tbnav_icp_verify_map, MAP CHECK V1-V10); use of the log-odds instead of the bits (the map's own rasterisation bias, up to
+ *      tbnav_icp_verify_map, MAP CHECK V1-V10; the global search's rival poses to start from are HYPOTHESES H1-H10); use of the log-odds instead of the bits (the map's own rasterisation bias, up to
  *      about 9 mm at 0.05 m cells in the prototype, stays: no method that reads occupancy bits removes it); use inside
  *      tbnav_icp_step or bmapping::ParticleFilter::SLAM; sharded filters; seeding particles on the device.
  *  KERNEL (csrc/icp_align_map.hip): icp_align_map<P>, one workgroup of 256 threads per pair, the whole loop in one launch.  The
@@ -483,7 +534,8 @@
  *      cell need not be an int).
  *  V10. Not built: a comparison with the expected range for beams without a return (the reference's mapper drops them,
  *      sensor_model.cpp:43-112); weights by range; use inside tbnav_icp_step, the searches' own acceptance, or
- *      bmapping::ParticleFilter::SLAM; several hypotheses out of the global search; sharded filters; the mirror pose of a symmetric
+ *      bmapping::ParticleFilter::SLAM (several hypotheses out of the global search are tbnav_icp_localize_map_hyp, HYPOTHESES H1-H10, and
+ *      this check's batch takes them); sharded filters; the mirror pose of a symmetric
  *      map, which this check cannot break (no method that reads the map can).
  *  KERNEL (csrc/icp_verify_map.hip): icp_verify_map<P>, one workgroup of 256 threads per pair, thread t keeping beams t, t + 256, ...
  *  Three bitmaps of the window are staged into LDS, each row with a zero word either side (3 x 256 x 10 words = 30 KB at H = 128):
@@ -796,6 +848,60 @@ int tbnav_icp_localize_map_bounds(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle
 /* test hook (L9): every candidate's score, uint32 [NA][w][h] */
 int tbnav_icp_localize_map_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
                                   const tbnav_icp_global_params* params, uint32_t* scores);
+
+/* ---- HYPOTHESES: the global search's separated peaks (H1-H10 of the section of that name) ---- */
+#define TBNAV_ICP_HYP_MAX 64
+#define TBNAV_ICP_HYP_MAX_BINS (1 << 22)
+#define TBNAV_ICP_HYP_MAX_REFINE (1 << 18)
+#define TBNAV_ICP_HYP_MAX_CANDIDATES (1 << 20)
+
+typedef struct tbnav_icp_hyp_params {
+  int32_t max_hyp;      /* 8 */
+  int32_t floor_q10;    /* 768 */
+  int32_t sep_cells;    /* 8 */
+  int32_t sep_steps;    /* 10 */
+  int32_t wrap;         /* 1 */
+  int32_t reserved;     /* must be 0 */
+} tbnav_icp_hyp_params;
+
+/* H5 */
+typedef struct tbnav_icp_hypothesis {
+  double T[3];
+  double quality;
+  uint32_t score;
+  int32_t ia, tx, ty;
+  int32_t accepted;
+  int32_t reserved;
+} tbnav_icp_hypothesis;
+
+/* H7 */
+typedef struct tbnav_icp_hyp_info {
+  int64_t blocks;
+  int64_t floor_blocks;
+  int64_t refined_blocks;
+  int64_t candidates;
+  uint32_t best_score, floor_score;
+  int32_t points, occupied;
+  int32_t n, n_peaks;
+  int32_t rounds;
+  int32_t searched;     /* 0: no call has run on this handle; all else is 0 then */
+} tbnav_icp_hyp_info;
+
+void tbnav_icp_default_hyp_params(tbnav_icp_hyp_params* p);
+/* the separated peaks of one scan in particle's map (H1-H8): hyps [cap] receives min(cap, info->n) of them.  gparams and hparams may
+ * be NULL (the defaults); hyps and info are required, cap >= 1. */
+int tbnav_icp_localize_map_hyp(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                               const tbnav_icp_global_params* gparams, const tbnav_icp_hyp_params* hparams, tbnav_icp_hypothesis* hyps,
+                               int32_t cap, tbnav_icp_hyp_info* info);
+/* the record of the last tbnav_icp_localize_map_hyp of this handle (searched = 0 when none ran) */
+int tbnav_icp_last_hyp(const tbnav_icp* h, tbnav_icp_hyp_info* info);
+/* the last call's kernels as a profiler prints them, ';'-separated; "" before the first call */
+int tbnav_icp_last_hyp_kernels(const tbnav_icp* h, char* buf, int32_t cap);
+/* test hook (H9), stateless: the candidates with score >= t in ascending index order, the first min(cap, *count) of them into
+ * index / score / peak [cap] (each may be NULL when cap is 0); count is required */
+int tbnav_icp_localize_map_hyp_candidates(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                          const tbnav_icp_global_params* gparams, const tbnav_icp_hyp_params* hparams, uint32_t* index,
+                                          uint32_t* score, uint8_t* peak, int64_t cap, int64_t* count);
 
 /* ---- MAP ALIGNMENT: one scan against a particle's map, below one cell (A1-A11 of the section of that name) ---- */
 #define TBNAV_ICP_ALIGN_MAP_MAX_HALF 256

@@ -211,6 +211,28 @@ class IcpGlobalInfo(C.Structure):
                 ("ty", C.c_int32), ("rounds", C.c_int32), ("accepted", C.c_int32), ("searched", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IcpHypParams(C.Structure):
+    """tbnav_icp_hyp_params (include/tbnav_icp.h, HYPOTHESES, H1)."""
+    _fields_ = [("max_hyp", C.c_int32), ("floor_q10", C.c_int32), ("sep_cells", C.c_int32), ("sep_steps", C.c_int32), ("wrap", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class IcpHypothesis(C.Structure):
+    """tbnav_icp_hypothesis (H5)."""
+    _fields_ = [("T", C.c_double * 3), ("quality", C.c_double), ("score", C.c_uint32), ("ia", C.c_int32), ("tx", C.c_int32), ("ty", C.c_int32),
+                ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class IcpHypInfo(C.Structure):
+    """tbnav_icp_hyp_info (H7)."""
+    _fields_ = [("blocks", C.c_int64), ("floor_blocks", C.c_int64), ("refined_blocks", C.c_int64), ("candidates", C.c_int64),
+                ("best_score", C.c_uint32), ("floor_score", C.c_uint32), ("points", C.c_int32), ("occupied", C.c_int32), ("n", C.c_int32),
+                ("n_peaks", C.c_int32), ("rounds", C.c_int32), ("searched", C.c_int32)]
+
+
+ICP_HYP_MAX, ICP_HYP_MAX_BINS, ICP_HYP_MAX_REFINE, ICP_HYP_MAX_CANDIDATES = 64, 1 << 22, 1 << 18, 1 << 20
+
+
 class IcpAlignMapParams(C.Structure):
     """tbnav_icp_align_map_params (include/tbnav_icp.h, MAP ALIGNMENT, A1a)."""
     _fields_ = [("max_flatness", C.c_double), ("half_cells", C.c_int32), ("gate_cells", C.c_int32), ("feature_cells", C.c_int32),
@@ -505,6 +527,13 @@ def lib() -> C.CDLL:
         "tbnav_icp_localize_map_field": (C.c_int, [vp, vp, i32, C.POINTER(IcpGlobalParams), vp, vp, C.POINTER(i32)]),
         "tbnav_icp_localize_map_bounds": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
         "tbnav_icp_localize_map_scores": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), vp]),
+        "tbnav_icp_default_hyp_params": (None, [C.POINTER(IcpHypParams)]),
+        "tbnav_icp_localize_map_hyp": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), C.POINTER(IcpHypParams), vp, i32,
+                                                 C.POINTER(IcpHypInfo)]),
+        "tbnav_icp_last_hyp": (C.c_int, [vp, C.POINTER(IcpHypInfo)]),
+        "tbnav_icp_last_hyp_kernels": (C.c_int, [vp, C.c_char_p, i32]),
+        "tbnav_icp_localize_map_hyp_candidates": (C.c_int, [vp, vp, i32, vp, i32, C.POINTER(IcpGlobalParams), C.POINTER(IcpHypParams), vp, vp, vp,
+                                                            C.c_int64, C.POINTER(C.c_int64)]),
         "tbnav_icp_default_align_map_params": (None, [C.POINTER(IcpAlignMapParams)]),
         "tbnav_icp_align_map": (C.c_int, [vp, vp, i32, vp, i32, dp, C.POINTER(IcpAlignMapParams), dp, C.POINTER(i32), C.POINTER(IcpInfo)]),
         "tbnav_icp_align_map_batch": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, C.POINTER(IcpAlignMapParams), vp, vp, vp]),

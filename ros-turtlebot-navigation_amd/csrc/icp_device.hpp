@@ -123,6 +123,18 @@ struct IcpGlobal {
   std::vector<unsigned char> h_in;
 };
 
+// the hypotheses' state in the handle (tbnav_icp.h, HYPOTHESES; icp_global.hip owns the buffers, grown on demand, icp_hyp.hip fills them)
+struct IcpHyp {
+  tbnav_icp_hyp_info last{};        // tbnav_icp_last_hyp
+  const char* kernels = "";         // tbnav_icp_last_hyp_kernels
+  DevBuf d_cands;                   // uint64 [cand_cap]: the keys of the candidates with score >= t, in no order
+  DevBuf d_flags;                   // uint8 [cand_cap]: 1 where the candidate is a peak
+  DevBuf d_peaks;                   // uint64 [cand_cap]: the peaks' keys, compacted
+  DevBuf d_bins;                    // uint64 [bins]: each bin's greatest key
+  DevBuf d_alive;                   // uint8 [bins]: 0 where the bin's winner was knocked
+  DevBuf d_rec;                     // HypRec
+};
+
 }  // namespace tbnav_icpdev
 
 struct tbnav_icp {
@@ -146,6 +158,7 @@ struct tbnav_icp {
   std::vector<tbnav_icpdev::IcpOut> h_out;
   tbnav_icpdev::IcpSearch search;
   tbnav_icpdev::IcpGlobal global;
+  tbnav_icpdev::IcpHyp hyp;
   tbnav_icpdev::DevBuf d_align_in, d_align_rec;     // the map alignment (icp_align_map.hip): its pairs; the test hook's pairing record
   int align_map_p = 0;                              // ... the P of its last launch, 0: none yet (tbnav_icp_last_align_map_kernel)
   tbnav_icpdev::DevBuf d_verify_in, d_verify_out, d_verify_rec;   // the map check (icp_verify_map.hip): its pairs, their records; the test hook's per-beam record

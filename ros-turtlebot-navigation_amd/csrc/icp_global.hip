@@ -11,8 +11,11 @@
 //   icp_global_list     the blocks with lo <= bound < hi, through one slot counter
 //   icp_global_refine   one workgroup per listed block: its candidates' scores, one 64-bit atomicMax of (score << 32 | ~index) per wave
 // No workgroup waits for another; every loop is bounded by the points, the tile or s.
+// The host half of HYPOTHESES (H1-H10, tbnav_icp_localize_map_hyp) lives here too, behind the same prepare and run: it lists the blocks
+// whose bound reaches the floor with icp_global_list and hands them to icp_hyp.hip's kernels (icp_global_device.hpp: hyp_enqueue).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +23,7 @@
 
 #include "common.hpp"
 #include "icp_device.hpp"
+#include "icp_global_device.hpp"
 #include "icp_search_device.hpp"
 #include "nav_host.hpp"
 #include "tbnav_icp.h"
@@ -29,30 +33,13 @@ namespace {
 using namespace tbnav_icpdev;
 
 constexpr int kLanes = tbnav_icpdev::kWave;
-constexpr int kMargin = 32;          // zero cells before cell 0 of the byte maps: the largest s, so pool(-s, .) is stored too
+constexpr int kMargin = kGlobalMargin;   // zero cells before cell 0 of the byte maps (icp_global_device.hpp)
 constexpr int kHistBins = 1024;
 constexpr int kSeeds = 16;           // round 1 refines at least this many blocks, those with the largest bounds
 constexpr int kPoolI = 32, kPoolJ = 64, kPoolMaxS = 32;
 constexpr int kBoundBx = kThreads / kLanes;   // 4 x 64 blocks per workgroup of icp_global_bound
 static_assert(kOccTile == tbnav_rk::kTS, "a field tile is a tile of the filter's pool");
 static_assert(kMargin >= kPoolMaxS && (1 << 5) == kPoolMaxS, "q <= 5");
-
-// what the host reads: one record, then the histogram
-struct GlobalRec {
-  unsigned long long key;   // max of score << 32 | ~linear index
-  uint32_t maxb;            // the largest bound
-  uint32_t points;          // valid source points
-  uint32_t occupied;
-  uint32_t nlist;           // icp_global_list's slot counter
-  uint32_t pad[2];
-};
-static_assert(sizeof(GlobalRec) == 32, "the histogram behind it stays aligned");
-
-// the byte maps: cell (ci, cj) at [(ci + kMargin) * P + cj + kMargin]; a coordinate clamped to -kMargin .. side reads what the
-// unclamped one would: zero outside the map (lik), zero outside -(s - 1) .. side - 1 (pool)
-__device__ __forceinline__ int clamp_cell(int v, int side) { return min(max(v, -kMargin), side); }
-__device__ __forceinline__ int off_x(uint32_t o) { return (int)(short)(o & 0xffffu); }
-__device__ __forceinline__ int off_y(uint32_t o) { return (int)(short)(o >> 16); }
 
 struct FieldArgs {
   const unsigned int* bm;      // TilePool::bm
@@ -160,13 +147,6 @@ __global__ __launch_bounds__(kThreads) void icp_global_offsets(const float* __re
     if (ia == 0) rec->points = s_valid;
   }
 }
-
-struct SearchArgs {
-  int side, P, s, q;
-  int tx0, ty0, w, h;        // the region
-  int nbx, nby;
-  int n_beams;
-};
 
 // blockIdx.x: the tile of blocks, tile_x * tiles_y + tile_y; blockIdx.y: the heading.  A wave is one Bx, its lanes 64 By.
 __global__ __launch_bounds__(kThreads) void icp_global_bound(SearchArgs a, int tiles_y, const uint8_t* __restrict__ pool,
@@ -327,6 +307,7 @@ struct Run {
   long long refined = 0;
   int rounds = 0;
   float* ms = nullptr;      // tbnav_icp_localize_map_timed: the stages' times, or null
+  uint32_t hist[kHistBins] = {};   // a full search's seeding histogram, for the hypotheses behind it
 };
 
 // Optional event timing of a timed call's stages: stage i lies between stamps i and i + 1 (stamps 5 / 6 and 8 / 9 have the host's
@@ -455,7 +436,7 @@ int run(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32
                      rec, d_hist);
   TBNAV_HIP(hipGetLastError());
   TBNAV_HIP(st.stamp(5));
-  uint32_t hist[kHistBins];
+  uint32_t* hist = out.hist;
   if (int rc = read_rec(h, &out.rec, hist)) return rc;
   // round 1, the seeds: every block of the highest bins that together hold kSeeds blocks
   const int shift = hist_shift(out.rec.maxb);
@@ -491,6 +472,107 @@ int run(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32
 
 const char* const kAllKernels =
     "icp_global_field;icp_global_pool;icp_global_offsets;icp_global_bound;icp_global_hist;icp_global_list;icp_global_refine";
+const char* const kHypKernels =
+    "icp_global_field;icp_global_pool;icp_global_offsets;icp_global_bound;icp_global_hist;icp_global_list;icp_global_refine;"
+    "icp_hyp_collect;icp_hyp_knock;icp_hyp_select";
+
+// ---- HYPOTHESES (H1-H10): the global search above, then icp_hyp.hip's launches behind one more list ----
+bool hyp_params_ok(const tbnav_icp_hyp_params& p) {
+  return p.max_hyp >= 1 && p.max_hyp <= TBNAV_ICP_HYP_MAX && p.floor_q10 >= 1 && p.floor_q10 <= 1024 && p.sep_cells >= 0 && p.sep_cells <= 64 &&
+         p.sep_steps >= 0 && p.sep_steps <= TBNAV_ICP_GLOBAL_MAX_ANG && (p.wrap == 0 || p.wrap == 1) && p.reserved == 0;
+}
+
+struct HypOut {
+  tbnav_icp_hyp_info info{};
+  std::vector<unsigned long long> keys;      // the first n peaks, in order
+  std::vector<unsigned long long> cands;     // the hook's: every candidate's key, and its peak flag
+  std::vector<uint8_t> flags;
+  const char* kernels = kAllKernels;
+};
+
+// H1-H7 for one call; nothing of the handle but its buffers is changed
+int hyp_run(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams, const tbnav_icp_global_params* gparams,
+            const tbnav_icp_hyp_params* hparams, bool want_cands, Plan& pl, HypOut& out) {
+  tbnav_icp_hyp_params hp;
+  if (hparams) hp = *hparams; else tbnav_icp_default_hyp_params(&hp);
+  if (!hyp_params_ok(hp)) return TBNAV_ERR_INVALID_ARG;
+  if (int rc = prepare(h, pf, particle, true, scan, n_beams, gparams, pl)) return rc;
+  const SearchArgs& a = pl.a;
+  HypArgs ha{};
+  ha.NA = pl.NA; ha.Ba = hp.sep_steps + 1; ha.B = hp.sep_cells + 1;
+  ha.nba = (pl.NA + ha.Ba - 1) / ha.Ba; ha.nbbx = (a.w + ha.B - 1) / ha.B; ha.nbby = (a.h + ha.B - 1) / ha.B;
+  ha.sep_cells = hp.sep_cells; ha.sep_steps = hp.sep_steps; ha.wrap = hp.wrap; ha.K = hp.max_hyp;
+  const long long bins = (long long)ha.nba * ha.nbbx * ha.nbby;
+  if (bins > (long long)TBNAV_ICP_HYP_MAX_BINS) return TBNAV_ERR_UNSUPPORTED;
+  DeviceGuard guard(h->device);
+  if (!guard.ok) return TBNAV_ERR_NO_DEVICE;
+  Run r;
+  if (int rc = run(h, pf, particle, scan, n_beams, pl, kFull, r)) return rc;
+  tbnav_icp_hyp_info& info = out.info;
+  info.searched = 1;
+  info.best_score = (uint32_t)(r.rec.key >> 32);
+  info.points = (int32_t)r.rec.points;
+  info.occupied = (int32_t)r.rec.occupied;
+  info.blocks = pl.blocks;
+  info.refined_blocks = r.refined;
+  info.rounds = r.rounds;
+  if (info.best_score == 0u) return TBNAV_OK;                        // H2: empty
+  const unsigned long long t = ((unsigned long long)info.best_score * (unsigned long long)hp.floor_q10 + 1023ull) >> 10;
+  ha.t = (uint32_t)t;
+  // the histogram's bins from t's upwards hold every block with bound >= t: what the list and the launch are sized by
+  const int shift = hist_shift(r.rec.maxb);
+  long long ub = 0;
+  for (int b = (int)(t >> shift); b < kHistBins; ++b) ub += r.hist[b];
+  if (ub < 1) ub = 1;
+  ha.list_cap = (uint32_t)(ub < (long long)TBNAV_ICP_HYP_MAX_REFINE ? ub : (long long)TBNAV_ICP_HYP_MAX_REFINE);
+  const unsigned long long cc = (unsigned long long)ha.list_cap * (unsigned long long)(a.s * a.s);
+  ha.cand_cap = (uint32_t)(cc < (unsigned long long)TBNAV_ICP_HYP_MAX_CANDIDATES ? cc : (unsigned long long)TBNAV_ICP_HYP_MAX_CANDIDATES);
+  IcpGlobal& G = h->global;
+  IcpHyp& Y = h->hyp;
+  if (int rc = G.d_list.reserve(sizeof(uint32_t) * (size_t)ha.list_cap)) return rc;
+  if (int rc = Y.d_cands.reserve(sizeof(unsigned long long) * (size_t)ha.cand_cap)) return rc;
+  if (int rc = Y.d_peaks.reserve(sizeof(unsigned long long) * (size_t)ha.cand_cap)) return rc;
+  if (int rc = Y.d_flags.reserve((size_t)ha.cand_cap)) return rc;
+  if (int rc = Y.d_bins.reserve(sizeof(unsigned long long) * (size_t)bins)) return rc;
+  if (int rc = Y.d_alive.reserve((size_t)bins)) return rc;
+  if (int rc = Y.d_rec.reserve(sizeof(HypRec))) return rc;
+  GlobalRec* rec = G.d_rec.as<GlobalRec>();
+  TBNAV_HIP(hipMemsetAsync(&rec->nlist, 0, sizeof(uint32_t), h->stream));
+  const long long want = (pl.blocks + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(icp_global_list, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(kThreads), 0, h->stream, G.d_bounds.as<uint32_t>(),
+                     pl.blocks, t, 1ull << 32, G.d_list.as<uint32_t>(), ha.list_cap, rec);
+  TBNAV_HIP(hipGetLastError());
+  const int threads = a.s * a.s >= kThreads ? kThreads : (a.s * a.s > kLanes ? a.s * a.s : kLanes);
+  if (int rc = hyp_enqueue(h->stream, a, ha, threads, G.d_lik.as<uint8_t>(), G.d_off.as<uint32_t>(), G.d_cnt.as<uint32_t>(),
+                           G.d_list.as<uint32_t>(), rec, Y.d_cands.as<unsigned long long>(), Y.d_flags.as<uint8_t>(),
+                           Y.d_peaks.as<unsigned long long>(), Y.d_bins.as<unsigned long long>(), Y.d_alive.as<uint8_t>(), Y.d_rec.as<HypRec>()))
+    return rc;
+  HypRec hr;
+  GlobalRec gr;
+  TBNAV_HIP(hipMemcpyAsync(&gr, rec, sizeof gr, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipMemcpyAsync(&hr, Y.d_rec.ptr, sizeof hr, hipMemcpyDeviceToHost, h->stream));
+  TBNAV_HIP(hipStreamSynchronize(h->stream));
+  if (gr.nlist > (uint32_t)TBNAV_ICP_HYP_MAX_REFINE) return TBNAV_ERR_UNSUPPORTED;          // H6, in this order
+  if (hr.ncand > (uint32_t)TBNAV_ICP_HYP_MAX_CANDIDATES) return TBNAV_ERR_UNSUPPORTED;
+  if (gr.nlist > ha.list_cap || hr.ncand > ha.cand_cap || hr.npeaks > hr.ncand) return TBNAV_ERR_HIP;   // (the sizes above hold them)
+  info.floor_score = ha.t;
+  info.floor_blocks = gr.nlist;
+  // the blocks the rounds refined and the floor's blocks are both "every block with a bound of at least ...": one holds the other
+  if (info.floor_blocks > info.refined_blocks) info.refined_blocks = info.floor_blocks;
+  info.rounds = r.rounds + 1;
+  info.candidates = hr.ncand;
+  info.n_peaks = (int32_t)hr.npeaks;
+  info.n = info.n_peaks < hp.max_hyp ? info.n_peaks : hp.max_hyp;
+  out.keys.assign(hr.keys, hr.keys + info.n);
+  out.kernels = kHypKernels;
+  if (want_cands) {
+    out.cands.resize(hr.ncand);
+    out.flags.resize(hr.ncand);
+    TBNAV_HIP(hipMemcpy(out.cands.data(), Y.d_cands.ptr, sizeof(unsigned long long) * (size_t)hr.ncand, hipMemcpyDeviceToHost));
+    TBNAV_HIP(hipMemcpy(out.flags.data(), Y.d_flags.ptr, (size_t)hr.ncand, hipMemcpyDeviceToHost));
+  }
+  return TBNAV_OK;
+}
 
 }  // namespace
 
@@ -499,6 +581,8 @@ namespace tbnav_icpdev {
 void global_free(tbnav_icp* h) {
   IcpGlobal& G = h->global;
   for (DevBuf* b : {&G.d_lik, &G.d_pool, &G.d_in, &G.d_scan, &G.d_off, &G.d_cnt, &G.d_bounds, &G.d_list, &G.d_scores, &G.d_rec}) b->release();
+  IcpHyp& Y = h->hyp;
+  for (DevBuf* b : {&Y.d_cands, &Y.d_flags, &Y.d_peaks, &Y.d_bins, &Y.d_alive, &Y.d_rec}) b->release();
 }
 
 }  // namespace tbnav_icpdev
@@ -618,6 +702,76 @@ int tbnav_icp_localize_map_scores(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle
   Run r;
   if (int rc = run(h, pf, particle, scan, n_beams, pl, kScores, r)) return rc;
   TBNAV_HIP(hipMemcpy(scores, h->global.d_scores.ptr, sizeof(uint32_t) * (size_t)cands, hipMemcpyDeviceToHost));
+  return TBNAV_OK;
+}
+
+void tbnav_icp_default_hyp_params(tbnav_icp_hyp_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->max_hyp = 8;
+  p->floor_q10 = 768;
+  p->sep_cells = 8;
+  p->sep_steps = 10;
+  p->wrap = 1;
+}
+
+int tbnav_icp_localize_map_hyp(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                               const tbnav_icp_global_params* gparams, const tbnav_icp_hyp_params* hparams, tbnav_icp_hypothesis* hyps,
+                               int32_t cap, tbnav_icp_hyp_info* info) {
+  if (!hyps || !info || cap < 1) return TBNAV_ERR_INVALID_ARG;
+  Plan pl;
+  HypOut out;
+  if (int rc = hyp_run(h, pf, particle, scan, n_beams, gparams, hparams, false, pl, out)) return rc;
+  const uint32_t side = (uint32_t)pl.a.side;
+  for (int i = 0; i < out.info.n && i < cap; ++i) {
+    tbnav_icp_hypothesis y{};
+    const uint32_t lin = ~(uint32_t)out.keys[i];
+    y.score = (uint32_t)(out.keys[i] >> 32);
+    y.ia = (int32_t)(lin / (side * side));
+    y.tx = (int32_t)((lin / side) % side);
+    y.ty = (int32_t)(lin % side);
+    y.T[0] = (double)y.ia * pl.gp.ang_step;
+    y.T[1] = pf->p.xmin + ((double)y.tx + 0.5) * pl.sp.resolution;
+    y.T[2] = pf->p.ymin + ((double)y.ty + 0.5) * pl.sp.resolution;
+    y.quality = out.info.points > 0 ? (double)y.score / (255.0 * (double)out.info.points) : 0.0;
+    y.accepted = y.quality >= pl.gp.min_quality && out.info.points > 0 && out.info.occupied > 0;
+    hyps[i] = y;
+  }
+  *info = out.info;
+  h->hyp.last = out.info;
+  h->hyp.kernels = out.kernels;
+  return TBNAV_OK;
+}
+
+int tbnav_icp_last_hyp(const tbnav_icp* h, tbnav_icp_hyp_info* info) {
+  if (!h || !info) return TBNAV_ERR_INVALID_ARG;
+  *info = h->hyp.last;
+  return TBNAV_OK;
+}
+
+int tbnav_icp_last_hyp_kernels(const tbnav_icp* h, char* buf, int32_t cap) {
+  if (!h || !buf || cap <= 0) return TBNAV_ERR_INVALID_ARG;
+  std::snprintf(buf, (size_t)cap, "%s", h->hyp.kernels);
+  return TBNAV_OK;
+}
+
+int tbnav_icp_localize_map_hyp_candidates(tbnav_icp* h, tbnav_rbpf* pf, int32_t particle, const float* scan, int32_t n_beams,
+                                          const tbnav_icp_global_params* gparams, const tbnav_icp_hyp_params* hparams, uint32_t* index,
+                                          uint32_t* score, uint8_t* peak, int64_t cap, int64_t* count) {
+  if (!count || cap < 0 || (cap > 0 && (!index || !score || !peak))) return TBNAV_ERR_INVALID_ARG;
+  Plan pl;
+  HypOut out;
+  if (int rc = hyp_run(h, pf, particle, scan, n_beams, gparams, hparams, true, pl, out)) return rc;
+  const size_t n = out.cands.size();
+  std::vector<uint32_t> order(n);
+  for (size_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
+  std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return (uint32_t)~out.cands[x] < (uint32_t)~out.cands[y]; });
+  for (size_t i = 0; i < n && (int64_t)i < cap; ++i) {
+    index[i] = ~(uint32_t)out.cands[order[i]];
+    score[i] = (uint32_t)(out.cands[order[i]] >> 32);
+    peak[i] = out.flags[order[i]];
+  }
+  *count = (int64_t)n;
   return TBNAV_OK;
 }
 

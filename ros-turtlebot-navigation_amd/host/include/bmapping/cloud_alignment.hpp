@@ -205,6 +205,50 @@ struct MapRelocalizeCheckedResult {
   Transform2D T;               ///< the pose that was checked, or found.T when none was
 };
 
+/// (addition) the hypotheses' parameters: tbnav_icp_hyp_params with its defaults (tbnav_icp.h, HYPOTHESES H1)
+struct ICPHypotheses {
+  int max_hyp = 8;             ///< K: how many peaks come back, 1..64
+  int floor_q10 = 768;         ///< a peak scores at least this share of the best score, in 1/1024, 1..1024
+  int sep_cells = 8;           ///< no two peaks within this many cells of each other in x and y ..., 0..64
+  int sep_steps = 10;          ///< ... and this many heading steps, 0..720
+  bool wrap = true;            ///< headings NA - 1 and 0 are neighbours
+};
+
+/// (addition) what ScanAlignment::localizeInMapHypotheses returns: tbnav_icp_hypothesis per peak, best first, and tbnav_icp_hyp_info
+struct MapHypothesis {
+  Transform2D T;               ///< a heading step and a cell centre, in the world
+  double quality = 0.0;
+  bool accepted = false;       ///< quality >= min_quality, with points in the scan and occupied cells in the map
+  int ia = 0, tx = 0, ty = 0;
+  unsigned score = 0;
+};
+struct MapHypothesesResult {
+  std::vector<MapHypothesis> hypotheses;   ///< the first min(max_hyp, n_peaks) peaks in descending score, then ascending index
+  int n_peaks = 0;
+  unsigned best_score = 0, floor_score = 0;
+  int points = 0, occupied = 0;
+  long long blocks = 0, floor_blocks = 0, refined_blocks = 0, candidates = 0;
+  int rounds = 0;
+};
+
+/// (addition) one hypothesis through ScanAlignment::relocalizeInMapHypotheses.  aligned / checked: the alignment / the check ran on it
+/// (the check at fine.T when the alignment converged, else at found.T); verified: it ran and accepts the pose
+struct MapHypothesisChecked {
+  MapHypothesis found;
+  MapAlignResult fine;
+  MapVerifyResult check;
+  bool aligned = false, checked = false, verified = false;
+  Transform2D T;               ///< the pose that was checked, or found.T when none was
+};
+struct MapRelocalizeHypothesesResult {
+  MapHypothesesResult found;
+  std::vector<MapHypothesisChecked> hypotheses;
+  int verified_count = 0;
+  int best = -1;               ///< the lowest index verified, -1 when none is
+  bool ambiguous = false;      ///< verified_count > 1: the map holds more than one pose that explains the scan
+  Transform2D T;               ///< best's pose, or hypothesis 0's when none is verified (the identity when there is no hypothesis)
+};
+
 class ScanAlignment {
  public:
   /// matcher(T_out, T_init, previous_scan, current_scan) -> converged
@@ -259,6 +303,16 @@ class ScanAlignment {
   MapRelocalizeCheckedResult relocalizeInMapChecked(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
                                                     const ICPAlignMap& align = {}, const ICPVerifyMap& verify = {},
                                                     bool even_if_rejected = false);
+
+  /// (addition) the global search's separated peaks, best first (tbnav_icp.h, HYPOTHESES H1-H10).  Throws as localizeInMap does.
+  MapHypothesesResult localizeInMapHypotheses(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
+                                              const ICPHypotheses& hyp = {});
+  /// (addition) localizeInMapHypotheses, ONE tbnav_icp_align_map_batch from the hypotheses that are accepted (all of them when
+  /// even_if_rejected) and ONE tbnav_icp_verify_map_batch of each at its aligned pose, or at its found pose where the alignment did not
+  /// converge: three synchronous calls whatever max_hyp is.  relocalizeInMap and relocalizeInMapChecked are untouched.
+  MapRelocalizeHypothesesResult relocalizeInMapHypotheses(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global = {},
+                                                          const ICPHypotheses& hyp = {}, const ICPAlignMap& align = {},
+                                                          const ICPVerifyMap& verify = {}, bool even_if_rejected = false);
 
   bool pclICPWrapper(Transform2D& T, const Transform2D& T_init, const std::vector<float>& scan) {
     if (!have_prev_) {

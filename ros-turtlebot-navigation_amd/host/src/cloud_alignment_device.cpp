@@ -241,4 +241,136 @@ MapRelocalizeCheckedResult ScanAlignment::relocalizeInMapChecked(ParticleFilter&
   return r;
 }
 
+namespace {
+[[noreturn]] void throw_status(const char* where, int rc) {
+  const std::string text = tbnav_status_string(rc);
+  if (rc == TBNAV_ERR_OUT_OF_WORLD) throw std::invalid_argument(text);  // what the reference throws (grid_mapper.cpp:856)
+  std::string msg = std::string("bmapping::ScanAlignment::") + where + ": " + text;
+  if (rc == TBNAV_ERR_INVALID_ARG) throw std::invalid_argument(msg);
+  const char* hip = tbnav_last_hip_error();
+  if (hip && *hip) msg += std::string(" [") + hip + "]";
+  throw std::runtime_error(msg);
+}
+}  // namespace
+
+MapHypothesesResult ScanAlignment::localizeInMapHypotheses(ParticleFilter& filter, const std::vector<float>& scan, const ICPGlobal& global,
+                                                           const ICPHypotheses& hyp) {
+  if (!device_) throw std::logic_error("bmapping::ScanAlignment::localizeInMapHypotheses: useDeviceICP first");
+  if (filter.g_) throw std::runtime_error("bmapping::ScanAlignment::localizeInMapHypotheses: a filter over several GPUs is not supported");
+  tbnav_icp_global_params gp;
+  tbnav_icp_default_global_params(&gp);
+  gp.ang_count = global.ang_count;
+  gp.ang_step = global.ang_step;
+  gp.pool_log2 = global.pool_log2;
+  for (int i = 0; i < 4; ++i) gp.region[i] = global.region[i];
+  gp.min_quality = global.min_quality;
+  tbnav_icp_hyp_params hp;
+  tbnav_icp_default_hyp_params(&hp);
+  hp.max_hyp = hyp.max_hyp;
+  hp.floor_q10 = hyp.floor_q10;
+  hp.sep_cells = hyp.sep_cells;
+  hp.sep_steps = hyp.sep_steps;
+  hp.wrap = hyp.wrap ? 1 : 0;
+  std::vector<tbnav_icp_hypothesis> ys(TBNAV_ICP_HYP_MAX);
+  tbnav_icp_hyp_info info{};
+  const int rc = tbnav_icp_localize_map_hyp(static_cast<tbnav_icp*>(device_.get()), filter.h_, TBNAV_ICP_MAP_BEST_PARTICLE, scan.data(),
+                                            (int32_t)scan.size(), &gp, &hp, ys.data(), (int32_t)ys.size(), &info);
+  if (rc != TBNAV_OK) throw_status("localizeInMapHypotheses", rc);
+  MapHypothesesResult out;
+  for (int i = 0; i < info.n; ++i) {
+    MapHypothesis y;
+    y.T = Transform2D(rigid2d::Vector2D(ys[i].T[1], ys[i].T[2]), ys[i].T[0]);
+    y.quality = ys[i].quality;
+    y.accepted = ys[i].accepted != 0;
+    y.ia = ys[i].ia; y.tx = ys[i].tx; y.ty = ys[i].ty;
+    y.score = ys[i].score;
+    out.hypotheses.push_back(y);
+  }
+  out.n_peaks = info.n_peaks;
+  out.best_score = info.best_score; out.floor_score = info.floor_score;
+  out.points = info.points; out.occupied = info.occupied;
+  out.blocks = info.blocks; out.floor_blocks = info.floor_blocks; out.refined_blocks = info.refined_blocks; out.candidates = info.candidates;
+  out.rounds = info.rounds;
+  return out;
+}
+
+MapRelocalizeHypothesesResult ScanAlignment::relocalizeInMapHypotheses(ParticleFilter& filter, const std::vector<float>& scan,
+                                                                       const ICPGlobal& global, const ICPHypotheses& hyp,
+                                                                       const ICPAlignMap& align, const ICPVerifyMap& verify,
+                                                                       bool even_if_rejected) {
+  MapRelocalizeHypothesesResult r;
+  r.found = localizeInMapHypotheses(filter, scan, global, hyp);
+  std::vector<int> take;
+  for (size_t i = 0; i < r.found.hypotheses.size(); ++i) {
+    MapHypothesisChecked c;
+    c.found = r.found.hypotheses[i];
+    c.T = c.found.T;
+    r.hypotheses.push_back(c);
+    if (c.found.accepted || even_if_rejected) take.push_back((int)i);
+  }
+  if (!r.hypotheses.empty()) r.T = r.hypotheses[0].T;
+  if (take.empty()) return r;
+  tbnav_icp* h = static_cast<tbnav_icp*>(device_.get());
+  const int32_t n = (int32_t)take.size();
+  const std::vector<int32_t> particles((size_t)n, TBNAV_ICP_MAP_BEST_PARTICLE);
+  std::vector<double> tinit((size_t)n * 3), tout((size_t)n * 3);
+  for (int32_t k = 0; k < n; ++k) {
+    const auto g = r.hypotheses[take[k]].found.T.displacement();
+    tinit[3 * k] = g.theta; tinit[3 * k + 1] = g.x; tinit[3 * k + 2] = g.y;
+  }
+  tbnav_icp_align_map_params ap;
+  tbnav_icp_default_align_map_params(&ap);
+  ap.half_cells = align.half_cells;
+  ap.gate_cells = align.gate_cells;
+  ap.feature_cells = align.feature_cells;
+  ap.max_flatness = align.max_flatness;
+  std::vector<int32_t> ok((size_t)n);
+  std::vector<tbnav_icp_info> infos((size_t)n);
+  int rc = tbnav_icp_align_map_batch(h, filter.h_, scan.data(), (int32_t)scan.size(), n, particles.data(), tinit.data(), &ap, tout.data(),
+                                     ok.data(), infos.data());
+  if (rc != TBNAV_OK) throw_status("relocalizeInMapHypotheses", rc);
+  std::vector<double> tcheck((size_t)n * 3);
+  for (int32_t k = 0; k < n; ++k) {
+    MapHypothesisChecked& c = r.hypotheses[take[k]];
+    c.aligned = true;
+    c.fine.ok = ok[k] != 0;
+    c.fine.T = ok[k] ? Transform2D(rigid2d::Vector2D(tout[3 * k + 1], tout[3 * k + 2]), tout[3 * k]) : c.found.T;
+    c.fine.iterations = infos[k].iterations; c.fine.correspondences = infos[k].correspondences; c.fine.criterion = infos[k].criterion;
+    c.fine.mse = infos[k].mse;
+    if (c.fine.ok) c.T = c.fine.T;
+    // the doubles the calls themselves hold, not a round trip through Transform2D
+    for (int j = 0; j < 3; ++j) tcheck[3 * k + j] = ok[k] ? tout[3 * k + j] : tinit[3 * k + j];
+  }
+  tbnav_icp_verify_map_params vp;
+  tbnav_icp_default_verify_map_params(&vp);
+  vp.half_cells = verify.half_cells;
+  vp.slack_cells = verify.slack_cells;
+  vp.max_through_q10 = verify.max_through_q10;
+  vp.max_missing_q10 = verify.max_missing_q10;
+  vp.min_hit_q10 = verify.min_hit_q10;
+  std::vector<tbnav_icp_verify_map_info> checks((size_t)n);
+  rc = tbnav_icp_verify_map_batch(h, filter.h_, scan.data(), (int32_t)scan.size(), n, particles.data(), tcheck.data(), &vp, checks.data());
+  if (rc != TBNAV_OK) throw_status("relocalizeInMapHypotheses", rc);
+  for (int32_t k = 0; k < n; ++k) {
+    MapHypothesisChecked& c = r.hypotheses[take[k]];
+    const tbnav_icp_verify_map_info& info = checks[k];
+    c.checked = true;
+    c.check.accepted = info.accepted != 0;
+    c.check.points = info.points; c.check.outside = info.outside; c.check.walked = info.walked;
+    c.check.hit = info.hit; c.check.through = info.through; c.check.missing = info.missing; c.check.unseen = info.unseen;
+    c.check.undecided = info.undecided;
+    c.check.free_cells = info.free_cells; c.check.unknown_cells = info.unknown_cells;
+    c.check.sensor_cell[0] = info.sensor_cell[0]; c.check.sensor_cell[1] = info.sensor_cell[1];
+    c.check.sensor_class = info.sensor_class;
+    c.verified = c.check.accepted;
+    if (c.verified) {
+      if (r.best < 0) r.best = take[k];
+      ++r.verified_count;
+    }
+  }
+  r.ambiguous = r.verified_count > 1;
+  if (r.best >= 0) r.T = r.hypotheses[r.best].T;
+  return r;
+}
+
 }  // namespace bmapping

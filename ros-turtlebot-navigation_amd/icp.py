@@ -119,6 +119,29 @@ def _global_params(kw) -> "capi.IcpGlobalParams":
     return p
 
 
+_HYP_FIELDS = ("max_hyp", "floor_q10", "sep_cells", "sep_steps", "wrap", "reserved")
+
+
+def _hyp_params(kw) -> "capi.IcpHypParams":
+    p = capi.IcpHypParams()
+    capi.lib().tbnav_icp_default_hyp_params(C.byref(p))
+    for key, v in (kw or {}).items():
+        if key not in _HYP_FIELDS:
+            raise TypeError(f"localizeMapHypotheses: no parameter {key!r} (one of {_HYP_FIELDS})")
+        setattr(p, key, int(v))
+    return p
+
+
+def _hyp_info(i: "capi.IcpHypInfo") -> dict:
+    return dict(searched=i.searched, n=i.n, n_peaks=i.n_peaks, best_score=i.best_score, floor_score=i.floor_score, points=i.points,
+                occupied=i.occupied, blocks=i.blocks, floor_blocks=i.floor_blocks, refined_blocks=i.refined_blocks, candidates=i.candidates,
+                rounds=i.rounds)
+
+
+def _hypothesis(y: "capi.IcpHypothesis") -> dict:
+    return dict(T=tuple(y.T), quality=y.quality, score=y.score, ia=y.ia, tx=y.tx, ty=y.ty, accepted=y.accepted)
+
+
 _ALIGN_MAP_FIELDS = ("half_cells", "gate_cells", "feature_cells", "max_flatness", "reserved")
 _ALIGN_MAP_PAIR = np.dtype([(f, np.dtype(t)) for f, t in capi.IcpAlignMapPair._fields_])
 
@@ -477,6 +500,73 @@ class ScanAlignment:
         capi.check(self._L.tbnav_icp_localize_map_scores(self._h, filter._h, int(particle), scan.ctypes.data, scan.size, C.byref(p),
                                                          vol.ctypes.data), "tbnav_icp_localize_map_scores")
         return vol
+
+    def localizeMapHypotheses(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, hyp=None, cap=None, **params):
+        """tbnav_icp_localize_map_hyp (the header's HYPOTHESES, H1-H10): the global search's separated peaks, best first.  hyp: dict of
+        max_hyp, floor_q10, sep_cells, sep_steps, wrap (tbnav_icp_default_hyp_params for what is not named); cap: how many records to
+        take (default: max_hyp); params: localizeMap's -> (list of dicts T, quality, score, ia, tx, ty, accepted; info dict)"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        hp = _hyp_params(hyp)
+        cap = int(hp.max_hyp if cap is None else cap)
+        hyps = (capi.IcpHypothesis * max(cap, 1))()
+        info = capi.IcpHypInfo()
+        capi.check(self._L.tbnav_icp_localize_map_hyp(self._h, filter._h, int(particle), scan.ctypes.data, scan.size,
+                                                      C.byref(_global_params(params)), C.byref(hp), C.cast(hyps, C.c_void_p), cap,
+                                                      C.byref(info)), "tbnav_icp_localize_map_hyp")
+        return [_hypothesis(hyps[i]) for i in range(min(cap, info.n))], _hyp_info(info)
+
+    def lastHyp(self) -> dict:
+        """the record of the last localizeMapHypotheses of this handle (searched = 0: none ran)"""
+        info = capi.IcpHypInfo()
+        capi.check(self._L.tbnav_icp_last_hyp(self._h, C.byref(info)), "tbnav_icp_last_hyp")
+        return _hyp_info(info)
+
+    def lastHypKernels(self) -> list:
+        """the last localizeMapHypotheses' kernels as a profiler prints them; [] before the first call"""
+        buf = C.create_string_buffer(512)
+        capi.check(self._L.tbnav_icp_last_hyp_kernels(self._h, buf, 512), "tbnav_icp_last_hyp_kernels")
+        return [k for k in buf.value.decode().split(";") if k]
+
+    def localizeMapHypCandidates(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, hyp=None, **params):
+        """test hook (H9): every candidate with score >= the floor, in ascending index order
+        -> (index uint32 [m], score uint32 [m], peak uint8 [m])"""
+        scan = np.ascontiguousarray(scan, dtype=np.float32)
+        gp, hp = _global_params(params), _hyp_params(hyp)
+        count = C.c_int64()
+        args = (self._h, filter._h, int(particle), scan.ctypes.data, scan.size, C.byref(gp), C.byref(hp))
+        capi.check(self._L.tbnav_icp_localize_map_hyp_candidates(*args, None, None, None, 0, C.byref(count)), "tbnav_icp_localize_map_hyp_candidates")
+        m = int(count.value)
+        index, score, peak = np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint8)
+        capi.check(self._L.tbnav_icp_localize_map_hyp_candidates(*args, index.ctypes.data, score.ctypes.data, peak.ctypes.data, m, C.byref(count)),
+                   "tbnav_icp_localize_map_hyp_candidates")
+        assert int(count.value) == m
+        return index[:m], score[:m], peak[:m]
+
+    def relocalizeMapHypotheses(self, filter, scan, particle=capi.ICP_MAP_BEST_PARTICLE, localize=None, hyp=None, align=None, verify=None,
+                                even_if_rejected=False):
+        """localizeMapHypotheses, then ONE alignMapBatch from the hypotheses with accepted = 1 (all of them when even_if_rejected) and ONE
+        verifyMapBatch of each of those at its aligned pose, or at its found pose where the alignment did not converge: three synchronous
+        calls whatever the number of hypotheses.  localize, hyp, align, verify: dicts of those calls' parameters.
+        -> dict(hypotheses=[dict(found=the hypothesis, fine=alignMap's (ok, T, info) or None, check=verifyMap's record or None, T, verified)],
+        info=the search's record, verified_count, best (the lowest index verified, -1: none), ambiguous (verified_count > 1),
+        T (best's, or hypothesis 0's when none is verified, or None when there is no hypothesis))"""
+        hyps, info = self.localizeMapHypotheses(filter, scan, particle, hyp=hyp, **(localize or {}))
+        out = [dict(found=y, fine=None, check=None, T=y["T"], verified=False) for y in hyps]
+        take = [i for i, y in enumerate(hyps) if y["accepted"] or even_if_rejected]
+        if take:
+            parts = [int(particle)] * len(take)
+            fine = self.alignMapBatch(filter, [hyps[i]["T"] for i in take], scan, parts, **(align or {}))
+            for i, f in zip(take, fine):
+                out[i]["fine"] = f
+                out[i]["T"] = f[1] if f[0] else hyps[i]["T"]
+            recs = self.verifyMapBatch(filter, [out[i]["T"] for i in take], scan, parts, **(verify or {}))
+            for i, rec in zip(take, recs):
+                out[i]["check"] = rec
+                out[i]["verified"] = bool(rec["accepted"])
+        ver = [i for i, o in enumerate(out) if o["verified"]]
+        best = ver[0] if ver else -1
+        T = out[best]["T"] if ver else (out[0]["T"] if out else None)
+        return dict(hypotheses=out, info=info, verified_count=len(ver), best=best, ambiguous=len(ver) > 1, T=T)
 
     def alignMap(self, filter, T_init, scan, particle=capi.ICP_MAP_BEST_PARTICLE, **params):
         """tbnav_icp_align_map (the header's MAP ALIGNMENT, A1-A11): the alignment of one scan to the map of a particle of
